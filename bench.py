@@ -9,10 +9,20 @@
            then HT decode of every block + inverse DWT/RCT/DC shift back to pixels.  Inputs are resident
            in HBM before the timed region.  N>1: weak scaling, every rank codes its own frame per step
            and the compressed streams are gathered to rank 0 over RCCL (dist.gather_streams).
-  prints : ONE JSON line (rank 0) with the roofline of the dominant kernel (level-0 5-3 DWT, timed with
-           HIP events on the library's own stream) and a CPU baseline (the C oracle, 1 thread).
+  prints : ONE JSON line (rank 0): metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step) and the
+           workload's configuration.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+      A plain run sets up, runs W warm-up steps, times exactly K steps, writes the last step's outputs if --dump-outputs
+      is given, and prints the line.  --full adds everything else the benchmark measures and checks: the CPU baseline
+      (the C oracle), the short records of the other configurations (C3, C5, C1 on the GPU, C4, closed loop, host
+      boundary), the level-0 DWT kernel timed with HIP events inside the timed region, the one-frame roofline pass and
+      its rotating-buffer repeat, the checks of what was timed (lossless round trip, sha256 of the decoded blocks,
+      gathered streams) and, at N > 1, the scaling records.
+      --dump-outputs DIR: after the timed steps, rank 0 writes what the last step computed for each frame in flight
+      (at most 8) as DIR/<name>.npy in float32 / float64: the compressed stream, its offsets, lengths and bit-plane
+      counts, the decoded blocks and the pixels back; the large arrays as a fixed, seeded sample, with whole-array
+      checksums beside them (64 MB at most in all).  The inputs are seeded: the same arguments give the same inputs.
       N > 1 and no WORLD_SIZE in the environment: this process -- before it has touched the GPU -- starts
       `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` as a CHILD process
       (one rank per GPU over RCCL), passes rank 0's JSON line through and exits with the child's status.  Under
@@ -35,7 +45,6 @@ import bench_host   # noqa: E402  (the pinned-host-memory boundary, the closed-l
 W, H, C, TILE, NRES, CB, PREC = 3840, 2160, 3, 512, 6, 64, 8
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 SEED = 0x4A324B30              # "J2K0" 
-MIN_TIMED_S = 1.0              # floor of the timed region, whatever --steps says (round 4: 0.1 s -- box-to-box spread of 5 % on 0.09 s of samples)
 # sha256 of the int32 `decoded` buffer (every code-block of frame 0 as HTDecoder.Decode returns it, job order) -- what the
 # block decoder must have produced in the timed region; tests/test_bench_digest.py recomputes it with the oracle on CPU
 DECODED_SHA256 = "76eab55b1f63e2eb3644d138c6d655d4b16975c46310378f3f9f1bc509de7d5e"
@@ -65,6 +74,53 @@ def synth_frame(np, index):
     yy, xx = np.mgrid[0:H, 0:W]
     base = np.stack([xx * 255 // W, yy * 255 // H, (xx + yy) * 127 // max(W, H)])
     return np.clip(base + rng.integers(-16, 17, size=(C, H, W)), 0, 255).astype(np.int32)
+
+
+DUMP_MAX_FRAMES = 8            # --dump-outputs: frames in flight written (the first ones)
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: elements kept of each large array, at most
+DUMP_BUDGET = 60 << 20         # --dump-outputs: bytes of .npy payload in all (below the 64 MB cap)
+
+
+def dump_outputs(dirname, frames, n):
+    """--dump-outputs: the arrays a caller of the timed path receives for each frame in `frames` (dicts of device tensors from the
+    last step: stream, offs, lens, numbps, decoded, pixels), as DIR/frame<f>_<name>.npy.  Small arrays are written whole (float64
+    where int32 / int64 values need it); the stream, the decoded blocks and the pixels as a sample at fixed seeded positions (the
+    same for every frame and run), with frame<f>_checksums.npy holding, per array, the element count and the int64 sum and
+    position-weighted sum of ALL its elements (each split into exact 32-bit halves).  Returns (files, bytes)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    frames = frames[:DUMP_MAX_FRAMES]
+    small = (n + 1) * 8 + n * 8 + n * 4 + 3 * 5 * 8
+    k = max(4096, min(DUMP_SAMPLE, (DUMP_BUDGET // max(len(frames), 1) - small) // 20))
+    files, nbytes = 0, 0
+
+    def save(name, a):
+        nonlocal files, nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        files, nbytes = files + 1, nbytes + a.nbytes
+
+    def halves(v):
+        v = int(v) & 0xFFFFFFFFFFFFFFFF
+        return [float(v >> 32), float(v & 0xFFFFFFFF)]
+
+    for f, fr in enumerate(frames):
+        total = int(fr["offs"][n].item())
+        sums = []
+        for j, (name, t, dt) in enumerate((("stream", fr["stream"][:total], np.float32), ("decoded", fr["decoded"], np.float64),
+                            ("pixels", fr["pixels"].reshape(-1), np.float32 if fr["pixels"].dtype == torch.uint8 else np.float64))):
+            x = t.reshape(-1).to(torch.int64)
+            w = torch.arange(x.numel(), dtype=torch.int64, device=x.device) % 65521 + 1
+            sums.append([float(x.numel())] + halves(x.sum().item()) + halves((x * w).sum().item()))
+            idx = np.sort(np.random.default_rng([SEED, j, x.numel()]).integers(0, max(x.numel(), 1), size=min(k, x.numel())))
+            save("frame%d_%s" % (f, name), x[torch.from_numpy(idx).to(x.device)].cpu().numpy().astype(dt))
+            del x, w
+        save("frame%d_offsets" % f, fr["offs"][:n + 1].cpu().numpy().astype(np.float64))
+        save("frame%d_lengths" % f, fr["lens"][:n].cpu().numpy().astype(np.float64))
+        save("frame%d_numbps" % f, fr["numbps"][:n].cpu().numpy().astype(np.float32))
+        save("frame%d_checksums" % f, np.array(sums, np.float64))
+    assert nbytes <= 64 << 20, "--dump-outputs: %d bytes exceed 64 MB" % nbytes
+    return files, nbytes
 
 
 def cpu_baseline(budget_s=10.0):
@@ -159,8 +215,14 @@ def run(state):
     ap.add_argument("--no-other-configs", action="store_true", help="default C2 run at N = 1: do not append the short C3 / C5 / c1gpu records")
     ap.add_argument("--cpu-baseline-s", type=float, default=0.0, help="seconds per leg of the CPU baseline (0: the configuration's default)")
     ap.add_argument("--cpu-baseline-1t", action="store_true", help="CPU baseline: the one-thread leg only")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (exactly this many in the C2 headline run)")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baseline, the other configurations' records, the kernel "
+                         "timings and roofline passes, the checks of what was timed, the scaling records at N > 1 (off: a lean run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="C2 headline: after the timed steps write what the last step computed as DIR/<name>.npy (float32 / float64, "
+                         "large arrays as a fixed seeded sample with whole-array checksums; 64 MB at most)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", type=int, default=-1, help="--config c3|c5: replay each frame's plan calls as one HIP graph (1), launch them one by one (0); -1: the configuration's default")
     ap.add_argument("--io", choices=["planes", "rgba8", "host"], default=os.environ.get("J2K_BENCH_IO", "rgba8"),
@@ -191,10 +253,14 @@ def run(state):
         args.gpus = int(ws) if ws else 1
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if ws is not None and int(ws) != args.gpus:
         print("bench.py: WORLD_SIZE=%s but --gpus %d: launch with --nproc-per-node %d, or drop the launcher and let --gpus start the ranks"
               % (ws, args.gpus, args.gpus), file=sys.stderr)
         raise SystemExit(2)
+    if args.dump_outputs and (args.shard == "tiles" or args.config != "c2" or args.io == "host"):
+        raise SystemExit("bench.py: --dump-outputs is implemented for the C2 headline run (--config c2, --shard frames, --io rgba8|planes)")
     if ws is None and args.gpus > 1:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
     state["skip_teardown"] = False
@@ -248,9 +314,9 @@ def run(state):
     others = None
     solo = int(os.environ.get("WORLD_SIZE", "1")) == 1
     plain = solo and not any(os.environ.get(k, "0") not in ("0", "") for k in ("J2K_BENCH_PEER_REHEARSAL", "J2K_BENCH_ROOT_REHEARSAL"))
-    if plain and not args.no_other_configs and not args.no_cpu_baseline and args.io == "rgba8":
+    if args.full and plain and not args.no_other_configs and not args.no_cpu_baseline and args.io == "rgba8":
         others = other_configs_summary()
-    if solo and not args.no_cpu_baseline:
+    if args.full and solo and not args.no_cpu_baseline:
         cpu_base = cpu_baseline(args.cpu_baseline_s or 10.0)
 
     import numpy as np
@@ -657,21 +723,10 @@ def run(state):
     for _ in range(args.warmup):
         step()
     barrier()
-    # The timed region lasts at least MIN_TIMED_S whatever --steps says (a 20-step C2 run is 8 ms: thinner than a record
-    # should be): a few calibration steps, every rank takes the largest step count any rank needs, `steps` in the JSON line
-    # is the number actually timed and `steps_requested` the flag.
+    # exactly --steps timed steps (`steps` and `steps_requested` in the JSON line are both the flag)
     steps_requested = args.steps
-    tc = time.perf_counter()
-    for _ in range(5):
-        step()
-    barrier()
-    need = int(np.ceil(MIN_TIMED_S / max((time.perf_counter() - tc) / 5, 1e-6)))
-    if world > 1:
-        tn = torch.tensor([need], dtype=torch.int64, device=plan.device if os.environ.get("J2K_BENCH_BACKEND", "nccl") == "nccl" else "cpu")
-        dist.all_reduce(tn, op=dist.ReduceOp.MAX)
-        need = int(tn.item())
-    args.steps = max(args.steps, min(need, 20000))
-    timed_profile = os.environ.get("J2K_BENCH_TIMED_PROFILE", "1") != "0"
+    # --full: the level-0 forward dispatches of lane 0 stamp HIP events inside the timed region (avg_launch_us_in_timed_region)
+    timed_profile = args.full and os.environ.get("J2K_BENCH_TIMED_PROFILE", "1") != "0"
     if timed_profile:
         ctx.profile_enable(True)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -684,12 +739,22 @@ def run(state):
     barrier()
     dt = time.perf_counter() - t0
     launches, k_ms = ctx.profile_read() if timed_profile else (0, 0.0)
-    ctx.profile_enable(False)
+    if timed_profile:
+        ctx.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed: its streams are in buffer set (step number - 1) % NSETS at N > 1, set 0 otherwise
+        b_last = (stepno[0] - 1) % NSETS if (multi and root_n <= 1) else 0
+        frames_out = [dict(stream=ln.streams[b_last], offs=ln.offss[b_last], lens=ln.lenss[b_last], numbps=ln.numbpss[b_last],
+                           decoded=ln.decoded[:int(info.decoded_elems)], pixels=ln.back_pix if args.io == "rgba8" else ln.back)
+                      for ln in lanes if ln.codes]
+        nf, nb_ = dump_outputs(args.dump_outputs, frames_out, n)
+        print("bench.py: wrote %d arrays (%.1f MB) of the last timed step to %s" % (nf, nb_ / 1e6, args.dump_outputs), file=sys.stderr)
     # ---- roofline pass: the same step with ONE frame in flight, so the dominant kernel's duration is its own (with
     #      several frames in flight it shares the chip with the other frames' kernels) ----
     iso_launches, iso_ms = 0, 0.0
     tags = [(0, 0.0)] * 4
-    if rank == 0:
+    rot_tags, rot_n = None, 0
+    if rank == 0 and args.full:
         for _ in range(3):
             lanes[0].code()
         ctx.sync()
@@ -703,7 +768,6 @@ def run(state):
         # ---- the same pass over FOUR buffer sets in rotation (> 1 GB touched between two uses of a line): one lane's ~250 MB fit
         #      the 256 MB Infinity Cache, and FETCH / WRITE_SIZE count fabric requests whether or not the MALL serves them
         #      (MI355X_MICROARCH.md) -- does the solo fraction hold at a footprint that rules the cache out?
-        rot_tags, rot_n = None, 0
         if args.io == "rgba8" and world == 1 and os.environ.get("J2K_BENCH_ROTATE", "1") != "0":
             try:
                 sets = [lanes[0].buffer_set() for _ in range(4)]
@@ -728,8 +792,9 @@ def run(state):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    # ---- correctness of what was timed (outside the timed region) ----
-    nocheck = bool(os.environ.get("J2K_DEV_SKIP"))       # dev experiments that leave kernels out: the line they print is not a result
+    # ---- correctness of what was timed (outside the timed region; --full) ----
+    # J2K_DEV_SKIP: dev experiments that leave kernels out (the line they print is not a result)
+    nocheck = bool(os.environ.get("J2K_DEV_SKIP")) or not args.full
     for ln in lanes:
         if not ln.codes or nocheck:
             continue
@@ -740,17 +805,17 @@ def run(state):
     total_bytes = int(lanes[0].offs[n].item())
     # the block decoder's output of the timed region (it is not what the inverse transform consumed, see config.workload)
     decoded_sha = None
-    if rank == 0 and world == 1 and lanes[0].codes:
+    if rank == 0 and world == 1 and lanes[0].codes and args.full:
         import hashlib
         decoded_sha = hashlib.sha256(lanes[0].decoded[:int(info.decoded_elems)].cpu().numpy().tobytes()).hexdigest()
         if DECODED_SHA256 and not DECODED_SHA256.startswith("%") and not nocheck:
             assert decoded_sha == DECODED_SHA256, "decoded blocks differ from the committed digest (tests/test_bench_digest.py)"
-    if pr_mode == "5":                                   # the packs came back through RCCL and were rebuilt: same bytes
+    if pr_mode == "5" and args.full:                     # the packs came back through RCCL and were rebuilt: same bytes
         ln = lanes[0]
         a_s, a_o, a_l, a_n = ln.assembled[0]
         assert torch.equal(a_o[:n + 1], ln.offs[:n + 1]) and torch.equal(a_l[:n], ln.lens[:n]) and torch.equal(a_n[:n], ln.numbps[:n])
         assert torch.equal(a_s[:total_bytes], ln.stream[:total_bytes]), "self-loop stream differs"
-    if world > 1 and rank == 0:
+    if world > 1 and rank == 0 and args.full:
         # what rank 0 assembled for rank 1's frame == that frame coded here, byte for byte (stream, offsets, lengths, bit planes)
         ln = lanes[0]
         fr1 = torch.from_numpy(synth_frame(np, 1)).to(plan.device)     # kept alive until the sync: the calls are asynchronous
@@ -796,8 +861,8 @@ def run(state):
             "config": {"workload": "3840x2160 sRGB 8-bit, 512x512 tiles, 5-3 lossless + HT block coder, 64x64 code-blocks, "
                                    "6 resolutions (BASELINE configs[1]); frames_in_flight independent frames per rank per step, "
                                    "each on its own HIP stream; a step = forward transform + HT block coding + stream compaction, then HT "
-                                   "block decode of that stream (checked against a committed sha256) + inverse transform of the ENCODER's "
-                                   "coefficients back to pixels (checked equal to the input): two halves, not a round trip through the "
+                                   "block decode of that stream (checked against a committed sha256 with --full) + inverse transform of the ENCODER's "
+                                   "coefficients back to pixels (checked equal to the input with --full): two halves, not a round trip through the "
                                    "decoded blocks -- the reference's HT coder codes one row in four (SURVEY fact 3) and its decoder has no "
                                    "packet->plane placement to mirror; N>1 gathers the compressed streams to rank 0 over RCCL (sent without "
                                    "the reference's MEL zero runs, rebuilt byte for byte at rank 0 inside the timed region)",
@@ -809,7 +874,8 @@ def run(state):
                        "parallelism": "frames/rank" if world > 1 else "single GPU", "gather": gather_path,
                        "ranks_seen": world,
                        "gather_check": ("rank 0's rebuilt stream, offsets, lengths and bit-plane counts of rank 1's frame == that frame coded on rank 0, "
-                                        "byte for byte (asserted after the timed region)") if world > 1 else None},
+                                        "byte for byte (asserted after the timed region)") if world > 1 and args.full else None,
+                       "full": args.full},
             "roofline": {"bound": "hbm",
                          "kernel": ("dwt53_fwd_rgba8_wg_kernel (level 0: RGBA8 unpack + DC shift + RCT + 5-3 lifting, fused)" if args.io == "rgba8"
                                     else "dwt53_fwd_kernel<8,3,true,false,false> (level 0: DC shift + RCT + 5-3 lifting, fused)"),
@@ -831,7 +897,7 @@ def run(state):
                          "traffic_source": TRAFFIC[args.io][1],
                          "copy_peak_guide_gbs": COPY_PEAK_GUIDE_GBS,
                          "frac_of_guide_copy_peak": round(achieved / COPY_PEAK_GUIDE_GBS, 4),
-                         "rotating_buffers": rot},
+                         "rotating_buffers": rot} if args.full else None,
             # every kernel of the step, inside the timed region: the HBM bytes one frame's nine kernels move (PMC counters, committed)
             # x the frames coded per second
             "pipeline": {"hbm_bytes_per_frame": PIPELINE_TRAFFIC[0], "source": PIPELINE_TRAFFIC[1],
@@ -844,10 +910,10 @@ def run(state):
         if others is not None:
             out["other_configs"] = others
         state["line"] = out
-    # ---- N > 1: the same command also carries the tile-sharded C4 record and the frames-per-rank C5 record (a
+    # ---- N > 1 with --full: the same command also carries the tile-sharded C4 record and the frames-per-rank C5 record (a
     #      SCALE file then answers "do tiles shard near-linearly?" without flags).  The headline's lanes are torn down first (the
     #      process group stays), each record runs inside the same ranks, and a watchdog prints the headline alone if one of them hangs.
-    if world > 1 and not peer_rehearsal and not args.no_other_configs and os.environ.get("J2K_BENCH_SCALE_RECORDS", "1") != "0":
+    if world > 1 and args.full and not peer_rehearsal and not args.no_other_configs and os.environ.get("J2K_BENCH_SCALE_RECORDS", "1") != "0":
         import copy
         import threading
         bench_extra.teardown(state.get("lanes", []), False, state.get("helper"), state.get("stop_helper"), ok=True, comm=state.get("comm"))

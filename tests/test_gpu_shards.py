@@ -179,7 +179,7 @@ def test_bench_two_rank_control_flow_rehearsal():
     env = dict(os.environ, J2K_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline", "--inflight", "2"]
+           "--no-cpu-baseline", "--inflight", "2", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -198,7 +198,7 @@ def test_bench_two_rank_control_flow_rehearsal():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env2.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
-                          "--inflight", "2"], env=env2, capture_output=True, text=True, timeout=300)
+                          "--inflight", "2", "--full"], env=env2, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["value"] > 0
@@ -251,7 +251,7 @@ def test_bench_rccl_self_loop_rehearsal():
     env = dict(os.environ, J2K_BENCH_PEER_REHEARSAL="5", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--full"],
                          env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -260,7 +260,7 @@ def test_bench_rccl_self_loop_rehearsal():
     # the probe's fall-back: the same run with the probe made to fail goes through torch.distributed's transfers
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env2 = dict(env, J2K_BENCH_PROBE_FAIL="1", MASTER_PORT=str(port))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"],
                          env=env2, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "falling back to torch.distributed" in out.stderr
