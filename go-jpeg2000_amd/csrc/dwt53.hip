@@ -1223,6 +1223,19 @@ hipError_t launch_dwt53_tail_inv(hipStream_t s, const TailPlane *planes, int npl
 // ================================================================================
 template <int NW>
 static hipError_t fwd_wg_go(hipStream_t s, const LevelLaunch &L, const int32_t *src, int32_t *out, int32_t *nxt, int dc) {
+    if (L.ycc.y) {             // an image.YCbCr (j2k_plan_forward_image): no level-1 fusion, nt stores (the plan's checks)
+        if (L.njobs2 > 0 || L.wg_store != 1) return hipErrorInvalidValue;
+#define J2K_YWG(R) hipExtLaunchKernelGGL((dwt53_fwd_ycc_wg_kernel<NW, 1, 6, 1 + R>), dim3(L.njobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
+                                         L.jobs, L.njobs, L.planes, L.ycc, out, nxt, dc)
+        switch (L.ycc.ratio) {
+            case J2K_YCBCR_444: J2K_YWG(J2K_YCBCR_444); break;
+            case J2K_YCBCR_422: J2K_YWG(J2K_YCBCR_422); break;
+            case J2K_YCBCR_420: J2K_YWG(J2K_YCBCR_420); break;
+            default: return hipErrorInvalidValue;
+        }
+#undef J2K_YWG
+        return hipGetLastError();
+    }
     const uint32_t *pix = reinterpret_cast<const uint32_t *>(src);
 #define J2K_WG(FL) hipExtLaunchKernelGGL((dwt53_fwd_rgba8_wg_kernel<NW, FL, 6>), dim3(L.njobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
                                          L.jobs, L.njobs, L.planes, pix, out, nxt, dc, L.pix_stride)

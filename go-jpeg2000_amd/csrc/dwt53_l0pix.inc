@@ -73,6 +73,21 @@ void dwt53_fwd_rgba8_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
     if (job.plane < 0) return;                     // padding entry of the XCD-aware job order (whole workgroup, before any barrier)
 #include "dwt53_l0pix_fwd_body.inc"
 }
+// The same workgroup over an image.YCbCr (encoder.go:178-195, the default branch; j2k_plan_forward_image): SRC = 1 + J2K_YCBCR_444 /
+// 422 / 420 selects the body's second row source, which loads the Y and chroma bytes of a row and converts them in registers to
+// the packed pixels the RGBA8 source would have loaded (J2K_L0_YCC: the RGBA8 kernels above are compiled without it).
+#define J2K_L0_YCC 1
+template <int NW, int NT, int WPE, int SRC>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
+void dwt53_fwd_ycc_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes, const YccSrc ycc,
+                             int32_t *__restrict__ out, int32_t *__restrict__ nxt, int dc_shift) {
+    static_assert(SRC >= 1 + J2K_YCBCR_444 && SRC <= 1 + J2K_YCBCR_420, "YCbCr 4:4:4, 4:2:2, 4:2:0 only");
+    __shared__ v4i slot[NW][6][64];
+    const DwtJob job = jobs[blockIdx.x];
+    if (job.plane < 0) return;
+#include "dwt53_l0pix_fwd_body.inc"
+}
+#undef J2K_L0_YCC
 
 // ================================================================================================================
 // Inverse counterpart: level 0 of ReconstructMultiLevel53 (dwt.go:534-548) = Inverse2D53 (dwt.go:410-429, columns first,

@@ -17,8 +17,43 @@
     const int q = q0 + wv;                         // regular waves: my pair-row
     const bool live = !helper && q < halfH;
     const int64_t y0 = P.src_off[0] / P.src_stride;
+#ifndef J2K_L0_YCC
     const uint32_t *base = pix + y0 * pix_stride + (P.src_off[0] - y0 * P.src_stride) + (active ? c : 0);
     auto rowp = [&](int r) { return reinterpret_cast<const uint4 *>(base + (int64_t)min(max(r, 0), h - 1) * pix_stride); };
+#else
+    // YCbCr source (dwt53_fwd_ycc_wg_kernel, SRC = 1 + ratio; Rect.Min even and >= 0, so Go's offsets are plain shifts of the
+    // frame position): 8 Y bytes and the 4 (4:2:x) or 8 (4:4:4) Cb / Cr bytes of chroma row y >> VS per row, all loads first,
+    // then the colours in registers as the packed pixels hrow takes (image_color.h)
+    constexpr int HS = SRC == 1 + J2K_YCBCR_444 ? 0 : 1, VS = SRC == 1 + J2K_YCBCR_420 ? 1 : 0;
+    const int64_t gx = (P.src_off[0] - y0 * P.src_stride) + (active ? c : 0);      // frame column of my first pixel
+    struct YccRaw { uint2 y, cb, cr; };
+    auto yload = [&](int r) {
+        const int64_t fy = y0 + min(max(r, 0), h - 1), cy = fy >> VS;
+        YccRaw o;
+        o.y = *reinterpret_cast<const uint2 *>(ycc.y + fy * ycc.ystride + gx);
+        if constexpr (HS == 0) {
+            o.cb = *reinterpret_cast<const uint2 *>(ycc.cb + cy * ycc.cstride + gx);
+            o.cr = *reinterpret_cast<const uint2 *>(ycc.cr + cy * ycc.cstride + gx);
+        } else {
+            o.cb = make_uint2(*reinterpret_cast<const uint32_t *>(ycc.cb + cy * ycc.cstride + (gx >> 1)), 0u);
+            o.cr = make_uint2(*reinterpret_cast<const uint32_t *>(ycc.cr + cy * ycc.cstride + (gx >> 1)), 0u);
+        }
+        return o;
+    };
+    auto ycvt = [&](const YccRaw &o, uint4 &a, uint4 &b) {
+        uint32_t px[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int ci = i >> HS;
+            const int Y = (int)(((i < 4 ? o.y.x : o.y.y) >> (8 * (i & 3))) & 0xFF);
+            const int Cb = (int)(((ci < 4 ? o.cb.x : o.cb.y) >> (8 * (ci & 3))) & 0xFF);
+            const int Cr = (int)(((ci < 4 ? o.cr.x : o.cr.y) >> (8 * (ci & 3))) & 0xFF);
+            px[i] = ycbcr_rgba8(Y, Cb, Cr);
+        }
+        a = make_uint4(px[0], px[1], px[2], px[3]);
+        b = make_uint4(px[4], px[5], px[6], px[7]);
+    };
+#endif
 
     // one row, all three components: unpack, RCT on raw bytes, horizontal 5-3 across the wave -> v[k*2] = lo, v[k*2+1] = hi
     auto hrow = [&](const uint4 &a, const uint4 &b, v4i (&v)[6]) {
@@ -69,8 +104,14 @@
     v4i E[6], O[6];
     if (helper) {
         // rows 2*q0-2, 2*q0-1 (pair-row above the band) and 2*(q0+NR) (even row below it)
+#ifndef J2K_L0_YCC
         const uint4 *p0 = rowp(2 * q0 - 2), *p1 = rowp(2 * q0 - 1), *p2 = rowp(2 * (q0 + NR));
         const uint4 a0 = p0[0], b0 = p0[1], a1 = p1[0], b1 = p1[1], a2 = p2[0], b2 = p2[1];
+#else
+        const YccRaw r0 = yload(2 * q0 - 2), r1 = yload(2 * q0 - 1), r2 = yload(2 * (q0 + NR));
+        uint4 a0, b0, a1, b1, a2, b2;
+        ycvt(r0, a0, b0); ycvt(r1, a1, b1); ycvt(r2, a2, b2);
+#endif
         v4i B[6];
         hrow(a2, b2, B);
 #pragma unroll
@@ -78,8 +119,14 @@
         hrow(a0, b0, E);
         hrow(a1, b1, O);
     } else if (live) {
+#ifndef J2K_L0_YCC
         const uint4 *p0 = rowp(2 * q), *p1 = rowp(2 * q + 1);
         const uint4 a0 = p0[0], b0 = p0[1], a1 = p1[0], b1 = p1[1];
+#else
+        const YccRaw r0 = yload(2 * q), r1 = yload(2 * q + 1);
+        uint4 a0, b0, a1, b1;
+        ycvt(r0, a0, b0); ycvt(r1, a1, b1);
+#endif
         hrow(a0, b0, E);
 #pragma unroll
         for (int v = 0; v < 6; v++) slot[wv][v][lane] = E[v];

@@ -215,6 +215,7 @@ extern "C" int j2k_plan_frame_status(j2k_plan *P) {
     HIPCHK(ctx, hipMemsetAsync(P->d_frame_status, 0, sizeof st, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (st == J2K_ERR_CAPACITY) return fail(ctx, st, "frame codec: the output buffer is smaller than the tile-parts (the last entry of d_tile_offs says what they take)");
+    if (st == J2K_ERR_GO_PANIC) return fail(ctx, st, "frame codec: a palette index >= len(Palette) in the image (Go: index out of range)");
     if (st != J2K_OK) return fail(ctx, st, "frame codec: a malformed tile-part or packet (SOT fields, header bits or body bytes running out)");
     return J2K_OK;
 }
@@ -258,6 +259,17 @@ extern "C" int j2k_plan_encode_frame_pixels(j2k_plan *P, int format, const void 
     int r = cl_prepare(P);
     if (r == J2K_OK) r = cl_workspaces(P);
     if (r == J2K_OK) r = j2k_plan_forward_pixels(P, format, d_pix, stride, P->d_cl_coeff);
+    if (r == J2K_OK) r = plan_encode_frame_from_coeff(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, sop, eph, d_out, cap, d_tile_offs);
+    return r;
+}
+
+// the same chain from an image.YCbCr / CMYK / Paletted (j2k_image.cpp): a palette index >= npal is the frame status's J2K_ERR_GO_PANIC
+extern "C" int j2k_plan_encode_frame_image(j2k_plan *P, const j2k_image *d_img, int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+    if (!P || !d_img) return J2K_ERR_INVALID_ARG;
+    if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    int r = cl_prepare(P);
+    if (r == J2K_OK) r = cl_workspaces(P);
+    if (r == J2K_OK) r = plan_forward_image_impl(P, d_img, P->d_cl_coeff, P->d_frame_status);
     if (r == J2K_OK) r = plan_encode_frame_from_coeff(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, sop, eph, d_out, cap, d_tile_offs);
     return r;
 }

@@ -108,9 +108,16 @@ void plan_t2_packets(const j2k_plan *P, int layer, std::vector<j2k_t2_dev_packet
 struct T1Workspace { size_t off_nsyms, off_sym, stride, total; };
 T1Workspace t1_workspace(const j2k_ctx *ctx, size_t n, size_t wpj);
 int ensure(j2k_ctx *ctx, void **p, size_t bytes);
-struct PixIO { int stride = 0, single = 0, triple = 0; };
+struct PixIO { int stride = 0, single = 0, triple = 0; j2k::YccSrc ycc{}; };   // ycc.y: a YCbCr image in place of packed RGBA8 (triple 8)
 int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix = PixIO());
 int plan_encode_private_slots(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps);
 int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int sop, int eph, uint8_t *d_out, size_t cap,
                                  uint64_t *d_tile_offs);
 int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix = PixIO());
+// the default branch of extractImageData (j2k_image.cpp): d_img's planes on the device; status_word non-null = report a palette index
+// >= npal there (the frame codec's status, asynchronous), else synchronise and return J2K_ERR_GO_PANIC before anything is written
+bool plan_rgba8_wg_fusable(const j2k_plan *P);
+int plan_forward_image_impl(j2k_plan *P, const j2k_image *d_img, int32_t *d_coeff, int *status_word);
+int image_device_bytes(const j2k_image *img, uint64_t need[3]);
+size_t image_layout(const j2k_image *img, const uint64_t need[3], size_t off[4]);
+int image_upload(j2k_ctx *ctx, const j2k_image *img, const uint64_t need[3], uint8_t *dev, const size_t off[4], j2k_image *d_img);

@@ -323,20 +323,17 @@ static int ensure_sized(j2k_ctx *ctx, void **p, size_t *cur, size_t need) {
 // image.*.Pix (host) -> H2D at native width (4 x fewer bytes than int32 planes) -> forward transform -> block coder -> tile-parts
 // (reference-mode plan: SOT | SOD | the tile's concatenated block bytes, encoder.createTileHeader of encodeTile's output; closed-loop
 // plan: SOT | SOD | packets) -> D2H at the exact length.  Synchronous; bench.py --io host shows what pipelining adds on top.
-extern "C" int j2k_encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, uint8_t *out, size_t cap,
-                                      size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
-    if (!P || !pix || !out_len) return J2K_ERR_INVALID_ARG;
+// what follows the pixels' H2D copy in the one-call encode (j2k_encode_pixels_host, j2k_encode_image_host): `forward` puts the host
+// image on the device and runs the forward transform into P->d_coeff (after every other buffer is sized)
+template <typename Fwd>
+static int encode_host_tail(j2k_plan *P, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint32_t *lens,
+                            uint8_t *numbps, const Fwd &forward) {
     j2k_ctx *ctx = P->ctx;
-    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
     const PlanSpec &S = P->spec;
-    const int pb = format == J2K_PIX_GRAY8 ? 1 : format == J2K_PIX_GRAY16 ? 2 : (format == J2K_PIX_RGBA8 || format == J2K_PIX_NRGBA8) ? 4 :
-                   (format == J2K_PIX_RGBA64 || format == J2K_PIX_NRGBA64) ? 8 : 0;
-    if (!pb || stride < (size_t)S.W * pb) return fail(ctx, J2K_ERR_INVALID_ARG, "pixel format / stride");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nb = P->blocks.size(), nt = (size_t)P->tile_count;
     const size_t bound = S.closed_loop ? j2k_plan_frame_bound(P) : j2k_plan_tile_parts_bound(P);
     int r;
-    if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, (size_t)S.H * stride)) != J2K_OK) return r;
     if ((r = ensure(ctx, &P->d_coeff, (size_t)P->coeff_elems * 4)) != J2K_OK) return r;
     if (!S.closed_loop && (r = ensure(ctx, &P->d_stream, (size_t)P->bytes_cap)) != J2K_OK) return r;
     const size_t toff_at = (bound + 64 + 15) & ~size_t(15);                                              // the tile-parts, and behind them their offsets / the length word
@@ -345,8 +342,7 @@ extern "C" int j2k_encode_pixels_host(j2k_plan *P, int format, const void *pix, 
     if ((r = ensure(ctx, &P->d_numbps, nb + 16)) != J2K_OK) return r;
     if (!S.closed_loop && (r = ensure(ctx, &P->d_offs, (nb + 1) * 8)) != J2K_OK) return r;
     uint64_t *d_toffs = reinterpret_cast<uint64_t *>((uint8_t *)P->d_host_io + toff_at);
-    HIPCHK(ctx, hipMemcpyAsync(P->d_host_pix, pix, (size_t)S.H * stride, hipMemcpyHostToDevice, ctx->stream));
-    if ((r = j2k_plan_forward_pixels(P, format, P->d_host_pix, stride, (int32_t *)P->d_coeff)) != J2K_OK) return r;
+    if ((r = forward()) != J2K_OK) return r;
     std::vector<uint64_t> toffs(nt + 1, 0);
     if (S.closed_loop) {                                     // (blocks gathered from their coding slots straight into the tile-parts: no dense stream)
         if ((r = plan_encode_frame_from_coeff(P, (int32_t *)P->d_coeff, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps, sop, eph, (uint8_t *)P->d_host_io, bound, d_toffs)) != J2K_OK) return r;
@@ -379,6 +375,51 @@ extern "C" int j2k_encode_pixels_host(j2k_plan *P, int format, const void *pix, 
     if (total > cap || (total && !out)) return fail(ctx, J2K_ERR_CAPACITY, "out too small (*out_len says what the tile-parts take)");
     if (total) HIPCHK(ctx, hipMemcpy(out, P->d_host_io, total, hipMemcpyDeviceToHost));
     return J2K_OK;
+}
+
+extern "C" int j2k_encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, uint8_t *out, size_t cap,
+                                      size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
+    if (!P || !pix || !out_len) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
+    const PlanSpec &S = P->spec;
+    const int pb = format == J2K_PIX_GRAY8 ? 1 : format == J2K_PIX_GRAY16 ? 2 : (format == J2K_PIX_RGBA8 || format == J2K_PIX_NRGBA8) ? 4 :
+                   (format == J2K_PIX_RGBA64 || format == J2K_PIX_NRGBA64) ? 8 : 0;
+    if (!pb || stride < (size_t)S.W * pb) return fail(ctx, J2K_ERR_INVALID_ARG, "pixel format / stride");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int r;
+    if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, (size_t)S.H * stride)) != J2K_OK) return r;
+    return encode_host_tail(P, sop, eph, out, cap, out_len, tile_offs, lens, numbps, [&]() {
+        HIPCHK(ctx, hipMemcpyAsync(P->d_host_pix, pix, (size_t)S.H * stride, hipMemcpyHostToDevice, ctx->stream));
+        return j2k_plan_forward_pixels(P, format, P->d_host_pix, stride, (int32_t *)P->d_coeff);
+    });
+}
+
+// image.YCbCr / CMYK / Paletted in Go memory (encoder.go:178-195): each plane crosses PCIe at its native size -- the bytes the rectangle
+// reaches, e.g. 1.5 B/px for 4:2:0 -- into the plan's pixel buffer (256-byte aligned planes, so a YCbCr image can take the fused
+// level-0 kernel), then j2k_plan_forward_image; a palette index >= npal returns J2K_ERR_GO_PANIC before anything is written.
+extern "C" int j2k_encode_image_host(j2k_plan *P, const j2k_image *img, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len,
+                                     uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
+    if (!P || !img || !out_len) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
+    const PlanSpec &S = P->spec;
+    if (S.C != 3) return fail(ctx, J2K_ERR_INVALID_ARG, "an image.YCbCr / CMYK / Paletted is 3 components (encoder.go:178-195): the plan has another count");
+    int r = j2k_image_validate(img, S.W, S.H);
+    if (r == J2K_ERR_GO_PANIC) return fail(ctx, r, "image: a plane shorter than the rectangle reaches, or an empty palette (Go panics in At)");
+    if (r != J2K_OK) return fail(ctx, r, "image: unknown kind / ratio, a stride shorter than a row, or dims other than the plan's");
+    uint64_t need[3];
+    image_device_bytes(img, need);
+    size_t off[4];
+    const size_t total = image_layout(img, need, off);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, total + 64)) != J2K_OK) return r;
+    return encode_host_tail(P, sop, eph, out, cap, out_len, tile_offs, lens, numbps, [&]() {
+        j2k_image d_img;
+        const int u = image_upload(ctx, img, need, (uint8_t *)P->d_host_pix, off, &d_img);
+        if (u != J2K_OK) return u;
+        return plan_forward_image_impl(P, &d_img, (int32_t *)P->d_coeff, nullptr);
+    });
 }
 
 // closed-loop plans: tile-parts (host) -> H2D -> parse -> block decode -> placement -> inverse transform -> image.*.Pix (host), one

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "../../include/j2kgfx.h"
+#include "image_color.h"
 
 namespace j2k {
 
@@ -60,6 +61,14 @@ struct TailPlane {
 };
 
 // launch wrappers (dwt53.hip, dwt97.hip, mct.hip, ht.hip, t1.hip)
+// A YCbCr image read by the 5-3 level-0 workgroup kernel itself (j2k_plan_forward_image): the planes at the frame's origin
+// (Rect.Min even and >= 0), one chroma stride for Cb and Cr (Go's CStride); ratio J2K_YCBCR_444 / 422 / 420.
+struct YccSrc {
+    const uint8_t *y, *cb, *cr;
+    int64_t ystride, cstride;
+    int32_t ratio, pad_;
+};
+
 struct LevelLaunch {
     const DwtJob *jobs;   // device
     int njobs;
@@ -85,6 +94,7 @@ struct LevelLaunch {
     int pnjobs, pwaves, pmulti;
     hipEvent_t ev_start, ev_stop;   // non-null: the dispatch itself stamps these (hipExtLaunchKernelGGL) -- the kernel's own
                                     // begin / end, without the launch gap an event pair around the launch would include
+    YccSrc ycc;           // ycc.y non-null: level 0 of the workgroup form reads this YCbCr image instead of packed RGBA8
 };
 
 hipError_t launch_dwt53_fwd(hipStream_t s, const LevelLaunch &L, const int32_t *src, int32_t *out,
@@ -112,6 +122,8 @@ hipError_t launch_unpack_pixels(hipStream_t s, const uint8_t *pix, size_t stride
                                 int32_t *planes);
 hipError_t launch_colorspace(hipStream_t s, int cs, int32_t *planes, int ncomp, size_t n, int precision);
 hipError_t launch_pack_pixels(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, uint8_t *pix, size_t stride);
+// image.YCbCr / CMYK / Paletted -> packed RGBA8 (image.hip); *flag = J2K_ERR_GO_PANIC for a palette index >= npal
+hipError_t launch_image_to_rgba8(hipStream_t s, const j2k_image &img, uint32_t *pix, size_t stride_px, int *flag);
 
 // Tier-2 packets on device buffers (t2dev.hip)
 hipError_t launch_t2_fill_cbs(hipStream_t s, long n, const uint64_t *offs, const uint32_t *lens, const uint8_t *numbps, int mb, int ht, j2k_t2_dev_cb *cbs, uint64_t *reset = nullptr);

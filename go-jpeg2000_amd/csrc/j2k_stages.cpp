@@ -53,6 +53,7 @@ int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix
                     if (rgba8 && P->d_fwd_pix_jobs) { L.jobs = P->d_fwd_pix_jobs; L.njobs = P->fwd_pix_njobs; }
                     if (rgba8 && P->d_fwd_wg_jobs) {   // RGBA8: the workgroup form when every plane qualifies
                         L.jobs = P->d_fwd_wg_jobs; L.njobs = P->fwd_wg_njobs; L.wg_waves = P->fwd_wg_waves; L.wg_store = ctx->l0_store;
+                        L.ycc = pix.ycc;                   // (a YCbCr image: plan_rgba8_wg_fusable ruled out the two forms below)
                         if (P->d_mega_fwd_jobs && !P->d_fwd_wg2_jobs) {   // ... only its top bands: the rest runs beside the deep levels
                             L.jobs = P->d_fwd_top_jobs; L.njobs = P->fwd_top_njobs;
                             mega = true;
@@ -401,6 +402,16 @@ static bool pix_fusable(const j2k_plan *P, int bps, int channels, const void *d_
     // triple.  A four-channel frame whose components are all single planes (no colour transform) would lose updates.
     if (inverse && channels == 4 && T0.njobs && !(T1.njobs && S.C - 3 <= 1)) return false;
     return true;
+}
+
+// Would j2k_plan_forward_pixels(J2K_PIX_RGBA8) of an aligned frame take the level-0 workgroup kernel alone -- the RGBA8 form the YCbCr
+// source of dwt53_l0pix_fwd_body.inc replaces: no level-1 fusion, no merged deep launch, the default nt stores?
+bool plan_rgba8_wg_fusable(const j2k_plan *P) {
+    const PlanSpec &S = P->spec;
+    PixIO io;
+    const void *aligned = reinterpret_cast<const void *>(uintptr_t(256));     // (pix_fusable looks at the pointer's alignment only)
+    if (S.C != 3 || !S.mct || !pix_fusable(P, 1, 4, aligned, (size_t)S.W * 4, false, io) || io.triple != 8) return false;
+    return P->d_fwd_wg_jobs && !P->d_fwd_wg2_jobs && !P->d_mega_fwd_jobs && P->ctx->l0_store == 1 && !P->fwd[0][0].njobs;
 }
 
 extern "C" int j2k_plan_forward_rgba8(j2k_plan *P, const void *d_pix, size_t stride, int32_t *d_coeff) {

@@ -58,6 +58,8 @@ SYMBOLS = [
     "j2k_pixels_components", "j2k_pixels_precision", "j2k_extract_image_data", "j2k_create_image",
     "j2k_unpack_pixels", "j2k_pack_pixels", "j2k_plan_forward_rgba8", "j2k_plan_inverse_rgba8",
     "j2k_plan_forward_pixels", "j2k_plan_inverse_pixels", "j2k_plan_pixels_fused",
+    "j2k_image_validate", "j2k_image_to_rgba8", "j2k_extract_image_planar", "j2k_plan_forward_image", "j2k_plan_image_fused",
+    "j2k_plan_encode_frame_image", "j2k_encode_image_host",
     "j2k_tile_part_bound", "j2k_create_tile_header", "j2k_assemble_tiles", "j2k_read_tile_part_header", "j2k_parse_tile_parts",
     "j2k_plan_tile_parts_bound", "j2k_plan_assemble_tiles_device",
     "j2k_t2_packet_sequence", "j2k_t2_packet_bound", "j2k_t2_encode_packet", "j2k_t2_decode_packet", "j2k_t2_encode_packets_device", "j2k_t2_decode_packets_device", "j2k_plan_t2_packets", "j2k_plan_t2_fill_cbs", "j2k_tagtree_shape", "j2k_tcd_init_tile",
@@ -68,6 +70,15 @@ SYMBOLS = [
 ]
 T2_FRESH, T2_WIDE_LEN, T2_SEATED = 1, 2, 4          # j2k_t2_dev_packet.flags (closed-loop mode)
 PIX_GRAY8, PIX_GRAY16, PIX_RGBA8, PIX_RGBA64, PIX_NRGBA8, PIX_NRGBA64 = range(6)
+IMG_YCBCR, IMG_CMYK, IMG_PALETTED = 16, 17, 18       # j2k_image.kind (encoder.go:178-195, the default branch)
+YCBCR_444, YCBCR_422, YCBCR_420, YCBCR_440, YCBCR_411, YCBCR_410 = range(6)   # image.YCbCrSubsampleRatio
+
+
+class Image(C.Structure):
+    """j2k_image: an image.YCbCr / CMYK / Paletted by its planes (host or device pointers, as the call says)"""
+    _fields_ = [("kind", C.c_int32), ("ratio", C.c_int32), ("min_x", C.c_int32), ("min_y", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("plane", C.c_void_p * 3), ("stride", C.c_int64 * 3),
+                ("len", C.c_uint64 * 3), ("palette", C.c_void_p), ("npal", C.c_int32), ("pad_", C.c_int32)]
 
 _lib = None
 

@@ -187,6 +187,56 @@ class FramePlan:
             self.ctx.check(r)
         return bool(r)
 
+    # ---- image.YCbCr / CMYK / Paletted (encoder.go:178-195; j2kgfx.pixels.YCbCr / CMYK / Paletted) ---------------------------
+    def _img(self, img):
+        for a in img.buffers():
+            if hasattr(a, "data_ptr"):
+                self._p(a)                     # (held like any stage input)
+        return img.struct()
+
+    @_stage
+    def forward_image(self, img, coeff=None):
+        """forward_pixels(PIX_RGBA8) of the image's colours: img's planes = torch uint8 tensors on the device"""
+        coeff = coeff if coeff is not None else self.alloc_coeff()
+        s = self._img(img)
+        self.ctx.check(self.ctx.L.j2k_plan_forward_image(self.h, C.byref(s), self._p(coeff)))
+        return coeff
+
+    def image_fused(self, img):
+        """would forward_image read this image in the level-0 kernel (True) or stage it through an RGBA8 frame (False)?"""
+        s = img.struct()
+        r = self.ctx.L.j2k_plan_image_fused(self.h, C.byref(s))
+        if r < 0:
+            self.ctx.check(r)
+        return bool(r)
+
+    @_stage
+    def encode_frame_image(self, img, sop=False, eph=False, out=None, tile_offs=None):
+        """closed-loop plans: encode_frame_pixels(PIX_RGBA8) of the image's colours -> (out uint8, tile_offs int64[tiles + 1])"""
+        t = _torch()
+        out = out if out is not None else self.empty(self.frame_bound(), t.uint8)
+        tile_offs = tile_offs if tile_offs is not None else self.empty(int(self.info.tiles) + 1, t.int64)[:int(self.info.tiles) + 1]
+        s = self._img(img)
+        self.ctx.check(self.ctx.L.j2k_plan_encode_frame_image(self.h, C.byref(s), int(bool(sop)), int(bool(eph)), self._p(out),
+                                                              C.c_size_t(int(out.numel())), self._p(tile_offs)))
+        return out, tile_offs
+
+    def encode_image_host(self, img, sop=False, eph=False, cap=None):
+        """img's planes = numpy uint8 (host) -> dict(bytes, tile_offs, lens, numbps) as encode_pixels_host"""
+        L = self.ctx.L
+        n, nt = int(self.info.blocks), int(self.info.tiles)
+        L.j2k_plan_tile_parts_bound.restype = C.c_size_t
+        cap = int(cap) if cap is not None else max(self.frame_bound(), int(L.j2k_plan_tile_parts_bound(self.h))) + 64
+        out = np.zeros(max(cap, 1), np.uint8)
+        toffs = np.zeros(nt + 1, np.uint64); lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
+        olen = C.c_size_t(0)
+        s = img.struct()
+        st = L.j2k_encode_image_host(self.h, C.byref(s), int(bool(sop)), int(bool(eph)), out.ctypes.data_as(C.c_void_p), C.c_size_t(cap),
+                                     C.byref(olen), toffs.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p))
+        self.encoded_len = olen.value
+        self.ctx.check(st)
+        return dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
+
     @_stage
     def inverse_pixels(self, coeff, pix):
         """inverse path + createImage for the plan's component count and precision into pix (device uint8 [H, stride])."""

@@ -377,6 +377,58 @@ int j2k_plan_inverse_pixels(j2k_plan *plan, const int32_t *d_coeff, void *d_pix,
  * kernels for these pixels, 0 when it would stage; < 0 on bad arguments.  Launches nothing. */
 int j2k_plan_pixels_fused(const j2k_plan *plan, int format, const void *d_pix, size_t stride, int inverse);
 
+/* ---- the default branch of extractImageData (encoder.go:178-195) for the types Go's decoders return ----------------
+ * Any other image.Image becomes 3 components at precision 8: r>>8, g>>8, b>>8 of img.At(x, y).RGBA(), then the
+ * Options.Precision rescale as for every type.  So an image described here encodes exactly like the packed RGBA8 frame
+ * (J2K_PIX_RGBA8, alpha ignored) of its converted colours, and every call below is that frame's call on the converted
+ * colours.  Colours as Go's image/color (Go >= 1.8), for pixel (x, y) of Rect = [min_x, min_x + width) x [min_y, min_y + height)
+ * and Go's truncating `/`:
+ *   J2K_IMG_YCBCR     plane[0] = Y (yi = (y - min_y) * stride[0] + x - min_x), plane[1] = Cb, plane[2] = Cr at
+ *                     ci = (y / vd - min_y / vd) * stride[k] + x / hd - min_x / hd, (hd, vd) by ratio: 444 (1, 1), 422 (2, 1),
+ *                     420 (2, 2), 440 (1, 2), 411 (4, 1), 410 (4, 2).  color.YCbCr.RGBA(): v = Y * 0x10100 + (91881 Cr',
+ *                     -22554 Cb' - 46802 Cr', 116130 Cb') with Cb' = Cb - 128, Cr' = Cr - 128; the sample = clamp(v, 0, 0xFFFFFF) >> 16.
+ *   J2K_IMG_CMYK      plane[0] = Pix, 4 bytes C, M, Y, K per pixel: w = 0xFFFF - K * 0x101, r = (0xFFFF - C * 0x101) * w / 0xFFFF
+ *                     (uint32; g, b from M, Y), the sample = r >> 8.
+ *   J2K_IMG_PALETTED  plane[0] = Pix, 1 byte per pixel, indexing palette: npal <= 256 entries of Palette[i].RGBA() >> 8 as
+ *                     3 bytes R, G, B (built by the caller).
+ * Go panics -- J2K_ERR_GO_PANIC, nothing written -- when a plane is shorter (len) than the largest offset the rectangle
+ * reaches, when npal == 0 (At returns nil) and when an index >= npal; the last is found on the device. */
+enum { J2K_IMG_YCBCR = 16, J2K_IMG_CMYK = 17, J2K_IMG_PALETTED = 18 };
+enum { J2K_YCBCR_444 = 0, J2K_YCBCR_422 = 1, J2K_YCBCR_420 = 2, J2K_YCBCR_440 = 3, J2K_YCBCR_411 = 4, J2K_YCBCR_410 = 5 };
+typedef struct j2k_image {
+    int32_t kind, ratio;                 /* J2K_IMG_*, J2K_YCBCR_* (YCbCr only) */
+    int32_t min_x, min_y, width, height; /* Rect */
+    const uint8_t *plane[3];             /* YCbCr: Y, Cb, Cr; CMYK / Paletted: Pix (plane[0] only) */
+    int64_t stride[3];                   /* bytes per row of each plane (YCbCr: YStride, CStride, CStride) */
+    uint64_t len[3];                     /* len() of each Go slice */
+    const uint8_t *palette;              /* Paletted: npal x 3 bytes */
+    int32_t npal, pad_;
+} j2k_image;
+/* Host only, no device: J2K_ERR_INVALID_ARG for an unknown kind / ratio, a negative size, a stride shorter than a row or
+ * (width >= 0, height >= 0) dims other than these; J2K_ERR_GO_PANIC for a short plane or npal == 0 (as above). */
+int j2k_image_validate(const j2k_image *img, int width, int height);
+/* An image whose planes and palette are DEVICE memory (the descriptor itself is host memory, as in every call below that takes
+ * d_img) -> packed RGBA8 frame (alpha 255, `stride` bytes per row, 4-byte aligned) on the ctx stream.  Paletted images synchronise
+ * (the index check) and return J2K_ERR_GO_PANIC for an index >= npal. */
+int j2k_image_to_rgba8(j2k_ctx *ctx, const j2k_image *d_img, void *d_pix, size_t stride);
+/* HOST image -> ncomp = 3 planes of width x height int32 (caller-allocated), the mirror of j2k_extract_image_data; the planes
+ * cross PCIe at their native sizes.  target_precision as there (0: 8 bit). */
+int j2k_extract_image_planar(j2k_ctx *ctx, const j2k_image *img, int target_precision, int32_t *const *planes);
+/* j2k_plan_forward_pixels(J2K_PIX_RGBA8) of the converted colours, DEVICE image.  YCbCr 4:4:4 / 4:2:2 / 4:2:0 images are read by
+ * the 5-3 level-0 workgroup kernel itself when j2k_plan_image_fused says so; everything else converts into a staging RGBA8
+ * frame first.  Paletted images synchronise (the index check) and return J2K_ERR_GO_PANIC without touching d_coeff. */
+int j2k_plan_forward_image(j2k_plan *plan, const j2k_image *d_img, int32_t *d_coeff);
+/* 1 when j2k_plan_forward_image would take the fused kernel for this image, 0 when it would stage; < 0 on bad arguments */
+int j2k_plan_image_fused(const j2k_plan *plan, const j2k_image *d_img);
+/* j2k_plan_encode_frame_pixels(J2K_PIX_RGBA8) of the converted colours (closed-loop plans, asynchronous); a paletted index
+ * >= npal is J2K_ERR_GO_PANIC from the next j2k_plan_frame_status, and the tile-parts are then not the image's. */
+int j2k_plan_encode_frame_image(j2k_plan *plan, const j2k_image *d_img, int sop, int eph, uint8_t *d_out, size_t cap,
+                                uint64_t *d_tile_offs);
+/* j2k_encode_pixels_host(J2K_PIX_RGBA8) of the converted colours for a HOST image: the planes cross PCIe at their native
+ * sizes (the bytes the rectangle reaches); outputs as there.  J2K_ERR_GO_PANIC as above with nothing written. */
+int j2k_encode_image_host(j2k_plan *plan, const j2k_image *img, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len,
+                          uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps);
+
 /* ---- decode-side colour conversions to sRGB ---------------------------------
  * getColorConversion(cs)(componentData, precision) (colorspace.go:54-480); the values are the
  * reference's ColorSpace constants (jpeg2000.go:124-197).  Spaces without a conversion (sRGB, gray,
