@@ -554,6 +554,9 @@ __global__ __launch_bounds__(256) void t2_marks_kernel(const T2Chain *__restrict
     const int t = blockIdx.y;
     if (chains[t].skip) return;
     const uint64_t a0 = chains[t].start, a1 = chains[t].end;
+    // a tile-part without a packet area (Psot = 14, or SOD as the stream's last bytes: t2_tile_chain accepts start == end) holds no marker, and
+    // cs[a0] may be the byte behind the caller's buffer: no count is taken, the seed kernel hands the tile to its chain, which reports it
+    if (a0 >= a1) return;
     const uint32_t cap = 2u * (uint32_t)(tile_packet0[t + 1] - tile_packet0[t]);
     uint64_t *m = marks + 2 * (size_t)tile_packet0[t];
     auto found = [&](uint64_t q, uint32_t nx) {
@@ -567,7 +570,7 @@ __global__ __launch_bounds__(256) void t2_marks_kernel(const T2Chain *__restrict
     if (blockIdx.x == 0 && threadIdx.x < 32) {
         const uint64_t q = threadIdx.x < 16 ? a0 + threadIdx.x : (b1 > a0 ? b1 : a0) + (threadIdx.x - 16);
         const bool in = (threadIdx.x < 16 ? q < b0 : q >= b1) && q + 1 < a1;
-        const uint32_t c0 = cs[in ? q : a0], c1 = cs[in ? q + 1 : a0];              // (a1 - a0 >= 1: the chain was checked)
+        const uint32_t c0 = cs[in ? q : a0], c1 = cs[in ? q + 1 : a0];              // (a1 - a0 >= 1: checked above)
         if (in && c0 == 0xFFu && (c1 == 0x91u || c1 == 0x92u)) found(q, c1);
     }
     const uint64_t nvec = (b1 - b0) >> 4;

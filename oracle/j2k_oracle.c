@@ -379,6 +379,8 @@ static double cs_srgb_inverse_gamma(double encoded) {               /* :310-315 
     if (encoded <= 0.04045) return encoded / 12.92;
     return pow((encoded + 0.055) / 1.055, 2.4);
 }
+/* mct.ConvertFloat64ToInt32 (mct.go:137-145) is the same rule as encoder.go:238-242: the pin calls the function orc_preprocess uses */
+void orc_pin_round_half_away(const double *src, int32_t *dst, size_t n) { for (size_t i = 0; i < n; i++) dst[i] = round_half_away(src[i]); }
 double orc_pin_srgb_gamma(double linear) { return cs_srgb_gamma(linear); }
 double orc_pin_srgb_inverse_gamma(double encoded) { return cs_srgb_inverse_gamma(encoded); }
 

@@ -147,6 +147,9 @@ size_t orc_create_tile_header(int tile_idx, const uint8_t *tile_data, size_t len
 double orc_pin_srgb_gamma(double linear);
 double orc_pin_srgb_inverse_gamma(double encoded);
 
+/* mct.ConvertFloat64ToInt32 (mct.go:137-145) by the round_half_away of orc_preprocess, probed by mct_test.go:157-169, 785-808 */
+void orc_pin_round_half_away(const double *src, int32_t *dst, size_t n);
+
 /* ---- pins: internals at the granularity of the reference's own unit tests ------------
  * (internal/entropy/coverage_test.go, t1_test.go; tests/test_oracle_reference_pins.py) */
 void orc_pin_mq_byte_out(uint8_t *buf, size_t buflen, long bp, uint32_t c,

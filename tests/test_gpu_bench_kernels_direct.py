@@ -5,7 +5,7 @@ the oracle at the sizes of BASELINE C2, C4 and C5: forward_rgba8 / forward_pixel
 ReconstructMultiLevel53 + InverseRCT + DC shift (dwt.go:534-548, mct.go:56-66, 113-118) + createImage (decoder.go:417-588)
 on the same coefficients -- no hop through the planar HIP kernels.
 Also a seeded slice of the oracle GPU fuzz (tools/fuzz_gpu.py, tools/fuzz_gpu_tiles.py), which found both real bugs of
-round 2 and was not part of the suite (weak 1b)."""
+round 2 and was not part of the suite (weak 1b), and of the closed-loop fuzzer (tools/fuzz_gpu_closed_loop.py)."""
 import os
 import subprocess
 import sys
@@ -106,10 +106,32 @@ def test_c5_gray16_kernels_direct(oracle):
     assert np.array_equal(out.cpu().numpy(), want_pix)
 
 
-@pytest.mark.parametrize("tool,seed", [("fuzz_gpu.py", 31), ("fuzz_gpu_tiles.py", 32)])
-def test_oracle_fuzz_slice(tool, seed):
-    """12 s of each GPU fuzzer with a fixed seed, in a child process (the tools are scripts): every stage of every random
-    frame / tile against the oracle; a mismatch is an AssertionError there and a non-zero exit here."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", tool), "12", str(seed)], capture_output=True, text=True, timeout=300)
+# The closed-loop fuzzer ends on a frame COUNT (what the slice covers must not depend on the machine's speed).  Seed 33, 600 frames: chosen with
+# `python tools/fuzz_gpu_closed_loop.py 300 33 600 --oracle-only` (the oracle's side alone, no GPU): 600 is the largest round count whose oracle-only
+# run stays under about 20 s on one CPU core (15.4 s; 7 frames in the reference's HT panic domain, 293 with SOP + EPH, 109 with
+# neither, all 18 cells).  The conditions the seed has to meet are asserted below from the tool's own output.
+@pytest.mark.parametrize("tool,seed,frames", [("fuzz_gpu.py", 31, None), ("fuzz_gpu_tiles.py", 32, None), ("fuzz_gpu_closed_loop.py", 33, 600)],
+                         ids=["fuzz_gpu.py-31", "fuzz_gpu_tiles.py-32", "fuzz_gpu_closed_loop.py-33"])
+def test_oracle_fuzz_slice(tool, seed, frames):
+    """12 s of each GPU fuzzer with a fixed seed (the closed-loop one: a fixed number of frames), in a child process (the tools are scripts):
+    every stage of every random frame / tile against the oracle; a mismatch is an AssertionError there and a non-zero exit here."""
+    if frames is None:
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", tool), "12", str(seed)], capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+        assert "fuzz ok" in out.stdout or "ok:" in out.stdout, out.stdout[-500:]
+        return
+    import re
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", tool), "280", str(seed), str(frames)], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
-    assert "fuzz ok" in out.stdout or "ok:" in out.stdout, out.stdout[-500:]
+    last = out.stdout.strip().splitlines()[-1]
+    m = re.match(r"closed-loop fuzz: (\d+) frames clean \((\d+) in the reference's HT panic domain; ", last)
+    assert m, last
+    clean, skipped = int(m.group(1)), int(m.group(2))
+    assert clean + skipped == frames
+    rows = re.findall(r"^frame \d+: components=(\d+) precision=(\d+) coder=(MQ|HT) sop=([01]) eph=([01]) (ok|panic)$", out.stdout, re.M)
+    assert len(rows) == frames and sum(r[5] == "panic" for r in rows) == skipped
+    assert 4 * skipped <= frames                                                                   # at most a quarter is skipped after the status check
+    cells = {(int(r[0]), int(r[1]), r[2]) for r in rows if r[5] == "ok"}
+    assert cells == {(c, p_, k) for c in (1, 3, 4) for p_ in (8, 12, 16) for k in ("MQ", "HT")}    # every cell has a frame that ran
+    assert 3 * sum(r[3] == "1" and r[4] == "1" for r in rows) >= frames                            # SOP + EPH: the packet-parallel parse
+    assert any(r[3] == "0" and r[4] == "0" for r in rows)

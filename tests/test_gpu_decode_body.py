@@ -231,7 +231,7 @@ def test_closed_loop_packets_device_encoder_and_decoder_against_the_restatement(
                 assert gl == 0 and body is None
 
 
-from closed_loop_ref import frame as _frame, oracle_frame as _oracle_frame  # noqa: E402  (shared with the golden digests)
+from closed_loop_ref import check_every_stage as _check_every_stage, frame as _frame, oracle_frame as _oracle_frame  # noqa: E402  (shared with the golden digests)
 
 
 def _rgba(frame):
@@ -284,75 +284,9 @@ def test_closed_loop_every_stage_against_the_oracle_ragged_tiles(env, coder):
     tile-parts, parsed block tables, decoded + placed planes, pixels -- each against the oracle's composition"""
     torch, t2ref, t2, ctx = env
     import oracle as orc
-    from j2kgfx import _lib
-    from j2kgfx.codec import FramePlan
     W, H, tw, th, nres, cb = 301, 211, 128, 96, 4, 32
     frame = _frame(W, H, 3 + coder, noise=30 if coder == 0 else 3)
-    plan = FramePlan(W, H, 3, precision=8, lossless=True, num_resolutions=nres, cb=(cb, cb), tile=(tw, th), coder=coder, ctx=ctx, closed_loop=True)
-    want = _oracle_frame(frame, W, H, tw, th, nres, cb, coder, True, False, orc, t2ref)
-    # job windows
-    blocks = plan.blocks()
-    planes = plan.planes()
-    j = 0
-    for t in sorted(want):
-        jobs = orc.enumerate_blocks(3, want[t]["w"], want[t]["h"], nres, cb, cb, 1)
-        for b in jobs:
-            g = blocks[j]
-            assert (int(planes[g["plane"]][0]), int(planes[g["plane"]][1]), g["band"], g["x0"], g["y0"], g["w"], g["h"]) == \
-                (t, b["comp"], b["band"], b["x0"], b["y0"], b["w"], b["h"])
-            j += 1
-    assert j == len(blocks)
-    # forward + block coder
-    d_frame = torch.from_numpy(frame.astype(np.int32)).to(plan.device)
-    coeff = plan.forward(d_frame)
-    stream, offs, lens, numbps = plan.encode_stream(coeff)
-    cs, toffs = plan.encode_tile_parts(stream, offs, lens, numbps, sop=True, eph=False)
-    plan.frame_status()
-    h_lens, h_nb = lens.cpu().numpy(), numbps.cpu().numpy()
-    h_stream = stream.cpu().numpy()[:int(offs[-1].item())]
-    assert bytes(h_stream) == b"".join(bytes(want[t]["bytes"]) for t in sorted(want))
-    assert np.array_equal(h_lens[:len(blocks)].astype(np.uint32), np.concatenate([want[t]["lens"] for t in sorted(want)]))
-    h_toffs = toffs.cpu().numpy()
-    h_cs = cs.cpu().numpy()
-    for i, t in enumerate(sorted(want)):
-        assert bytes(h_cs[int(h_toffs[i]):int(h_toffs[i + 1])]) == want[t]["part"], t
-    total = int(h_toffs[-1])
-    # parse: the block tables point into the tile-parts
-    offs2, lens2, nb2 = plan.decode_tile_parts(cs, total, tile_offs=None, sop=True, eph=False)
-    plan.frame_status()
-    o2, l2, n2 = offs2.cpu().numpy(), lens2.cpu().numpy(), nb2.cpu().numpy()
-    assert np.array_equal(l2[:len(blocks)], h_lens[:len(blocks)])
-    pos = 0
-    for k in range(len(blocks)):
-        ln = int(l2[k])
-        if ln:
-            assert bytes(h_cs[int(o2[k]):int(o2[k]) + ln]) == bytes(h_stream[pos:pos + ln]), k
-            assert int(n2[k]) == int(h_nb[k])
-        else:
-            assert int(n2[k]) == 0
-        pos += ln
-    # block decode + placement against DecodeCodeBlock for every job of the oracle's list
-    decoded = plan.decode_blocks(cs, offs2, lens2, nb2)
-    placed = plan.place_blocks(decoded)
-    back = plan.inverse(placed)
-    ctx.sync()
-    hp = placed.cpu().numpy()
-    for t in sorted(want):
-        wt = want[t]
-        ref_planes = orc.decode_tile_blocks(wt["bytes"], wt["lens"], wt["numbps"], 3, wt["w"], wt["h"], nres, cb, cb, coder, 1)
-        for c in range(3):
-            row = [r for r in planes if int(r[0]) == t and int(r[1]) == c][0]
-            got = hp[int(row[6]):int(row[6]) + wt["w"] * wt["h"]].reshape(wt["h"], wt["w"])
-            assert np.array_equal(got, ref_planes[c]), (t, c)
-            if coder == 0:
-                assert np.array_equal(got, wt["coeff"][c])        # the MQ coder is lossless: the coefficients come back
-        sub = [orc.reconstruct53(ref_planes[c], wt["w"], wt["h"], nres - 1) for c in range(3)]
-        px = orc.postprocess(sub, 8, True)
-        for c in range(3):
-            assert np.array_equal(back.cpu().numpy()[c, wt["y0"]:wt["y0"] + wt["h"], wt["x0"]:wt["x0"] + wt["w"]], px[c]), (t, c)
-    if coder == 0:
-        assert np.array_equal(back.cpu().numpy(), frame.astype(np.int32))
-    plan.close()
+    _check_every_stage(torch, orc, t2ref, ctx, frame, W, H, tw, th, nres, cb, coder, True, False)
 
 
 def test_closed_loop_4k_sampled_tiles_against_the_oracle(env):
@@ -512,6 +446,25 @@ def test_closed_loop_corrupted_tile_parts_are_reported_not_followed(env, coder):
         assert ((o + l) <= n).all()
         assert int(n2.cpu().numpy()[:int(plan.info.blocks)].max()) <= 31
     assert outcomes["invalid"] > 20 and outcomes["ok"] > 0, outcomes
+    # a last tile-part without a packet area: cut to its 14 header bytes (SOT, SOD), Psot saying so (14) or left open (0: "to the end").  The chain
+    # of that tile is empty (start == end == the stream's length) while the plan has packets for it: reported, and the marker search of the
+    # side-by-side parse must not look at the byte behind the stream (it did: cs[len]).  This pins the STATUS; the stream sits inside a larger
+    # tensor, so no version of the code reads outside an allocation here and the over-read itself is not something this test can see.
+    last = len(h_toffs) - 2
+    n = int(h_toffs[last]) + 14
+    for psot in (14, 0):
+        for given in (True, False):
+            cut = good[:n].copy()
+            cut[n - 8:n - 4] = np.frombuffer(int(psot).to_bytes(4, "big"), np.uint8)
+            assert bytes(cut[n - 14:n - 10]) == b"\xff\x90\x00\x0a" and bytes(cut[n - 2:]) == b"\xff\x93"
+            buf = torch.full((n + 2 * guard,), 0xFF, dtype=torch.uint8, device=plan.device)
+            buf[guard:guard + n] = torch.from_numpy(cut).to(plan.device)
+            t_offs = h_toffs.astype(np.int64).copy()
+            t_offs[-1] = n
+            o2, l2, n2 = plan.decode_tile_parts(buf[guard:], n, tile_offs=torch.from_numpy(t_offs).to(plan.device) if given else None, sop=True, eph=True)
+            with pytest.raises(J2KError) as e:
+                plan.frame_status()
+            assert e.value.status == _lib.ERR_INVALID_ARG, (psot, given)
     # and the intact stream still decodes
     o2, l2, n2 = plan.decode_tile_parts(cs, total, sop=True, eph=True)
     back = plan.inverse(plan.place_blocks(plan.decode_blocks(cs, o2, l2, n2)))

@@ -1,7 +1,7 @@
 """CPU: every NUMERIC vector the reference's own unit tests hold below round-trip level, reproduced by the C oracle
 (oracle/j2k_oracle.c, "pins" section) and -- where it has the function -- by the independent Python restatement
-(oracle/pyref.py).  Source of each vector: internal/entropy/coverage_test.go, t1_test.go, mqc_test.go, ht_test.go of
-mrjoshuak/go-jpeg2000; the vectors are data (inputs + expected outputs), retyped here as Python literals.
+(oracle/pyref.py).  Source of each vector: internal/entropy/coverage_test.go, t1_test.go, mqc_test.go, ht_test.go and
+internal/mct/mct_test.go of mrjoshuak/go-jpeg2000; the vectors are data (inputs + expected outputs), retyped here as Python literals.
 
 VERDICT r1 "missing #4": TestMqByteOutLocal, TestGetSignContextParams, TestT1_GetMRContext(_Detailed),
 TestLutSCCtx/LutSignCtx/LutSC_Values, TestMQEncoder_ByteOut_*, TestT1_CanUseRunLength, ht_test.go:126-147.
@@ -262,6 +262,19 @@ def test_ht_decoder_minimal_data(oracle):
         # ht.go:407): a NON-zero block -- C oracle == pyref
         want = np.array(pyref.HTDecoder(16, 16, tabs).decode(bytes(data)), np.int32).reshape(16, 16)
         assert np.array_equal(out, want)
+
+
+# ---- internal/mct/mct_test.go:157-169 TestConvertFloat64ToInt32 (6 vectors), :785-808 _EdgeCases (the empty slice + 7 vectors) -------
+# by the round_half_away of orc_preprocess / orc_tcd_inverse_dwt (encoder.go:238-242 states mct.go:137-145 again)
+@pytest.mark.parametrize("src,exp", [
+    ([0.4, 0.5, 0.6, -0.4, -0.5, -0.6], [0, 1, 1, 0, -1, -1]),
+    ([], []), ([0.0], [0]), ([0.49999], [0]), ([0.50001], [1]), ([-0.49999], [0]), ([-0.50001], [-1]), ([100.5, -100.5], [101, -101]),
+])
+def test_convert_float64_to_int32(lib, src, exp):
+    s = np.array(src + [0.0], np.float64)                              # (one spare element: an empty array has no address to pass)
+    d = np.full(len(src) + 1, 77, np.int32)
+    lib.orc_pin_round_half_away(s.ctypes.data_as(C.POINTER(C.c_double)), d.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(len(src)))
+    assert d[:len(src)].tolist() == exp and d[len(src)] == 77
 
 
 # ---- ht_test.go:80-92 TestHTEncoderEmptyBlock, :8-77 TestHTEncoderDecoder (only a logged match rate) ---------------------------

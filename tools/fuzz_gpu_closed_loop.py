@@ -1,30 +1,42 @@
 """GPU fuzz, third part (dev tool, run on the GPU box): the CLOSED-LOOP mode (j2k_params.closed_loop; this library's, not the
 reference's) -- random geometries (tiles down to one sample wide, odd sizes, 1..6 resolutions, 4..64 code-blocks), contents and
-precisions, both coders, SOP / EPH on and off.  Every frame: tile-parts == the oracle's composition (preprocess, the job list with
-partitioning windows, the block coder, t2ref.PacketEncoder(len_bits=5) per tile, createTileHeader); parse -> block decode ->
-placement == orc.decode_tile_blocks; MQ frames come back bit-exact; tile-part positions given and found by walking the SOTs.
-    python tools/fuzz_gpu_closed_loop.py [seconds] [seed]"""
+precisions, both coders, SOP / EPH on and off.  Every frame: tile-parts == the oracle's composition (tests/closed_loop_ref.oracle_frame:
+preprocess, the job list with partitioning windows, the block coder, t2ref.PacketEncoder(len_bits=5) per tile, createTileHeader); parse ->
+block decode -> placement == orc.decode_tile_blocks; MQ frames come back bit-exact; tile-part positions given and found by walking the SOTs.
+    python tools/fuzz_gpu_closed_loop.py [seconds] [seed] [frames] [--oracle-only]
+frames: stop after that many frames (clean ones and ones in the reference's HT panic domain together); the time budget ending first is then
+an error (exit status 2) -- what a seeded slice covers does not depend on the machine's speed.
+--oracle-only: the same frames (every random draw is made before the modes part), the oracle's side alone -- no torch.cuda, no product
+library; one line per frame in both modes: the cell (components, precision, coder), the markers, whether the reference's HT encoder panics.
+tests/test_gpu_bench_kernels_direct.py::test_oracle_fuzz_slice runs a seeded slice and states what the seed has to cover."""
 import os
 import sys
 import time
 
 import numpy as np
-import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "go-jpeg2000_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+for p_ in ("go-jpeg2000_amd", "oracle", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, p_))
 import oracle as orc                                     # noqa: E402
 import t2ref                                             # noqa: E402
-from j2kgfx import J2KError, _lib                        # noqa: E402
-from j2kgfx.codec import FramePlan                       # noqa: E402
+from closed_loop_ref import oracle_frame                 # noqa: E402
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+oracle_only = "--oracle-only" in sys.argv[1:]
+if not oracle_only:
+    import torch                                         # noqa: E402
+    from j2kgfx import J2KError, _lib                    # noqa: E402
+    from j2kgfx.codec import FramePlan                   # noqa: E402
+
+budget = float(args[0]) if len(args) > 0 else 120.0
+seed = int(args[1]) if len(args) > 1 else 1
+want_frames = int(args[2]) if len(args) > 2 else 0
 rng = np.random.default_rng(seed)
 t0 = time.time()
 n = npanic = npar_tiles = nser_tiles = nframe_enc = 0
 t_say = t0
-while time.time() - t0 < budget:
+while time.time() - t0 < budget and not (want_frames and n + npanic >= want_frames):
     if time.time() - t_say > 60:
         t_say = time.time(); print("... %d frames, %.0f s" % (n, t_say - t0), flush=True)
     Cn = int(rng.choice([1, 3, 3, 4]))
@@ -55,6 +67,25 @@ while time.time() - t0 < budget:
         frame[:, rng.integers(0, H), rng.integers(0, W)] = top
     frame = frame.astype(np.int32)
     desc = (Cn, W, H, tw, th, nres, cb, coder, prec, kind, sop, eph)
+    # ---- every draw is made: the oracle's side (both modes) -------------------------------------------------------------------------
+    tiles_x = (W + tw - 1) // tw
+    ntiles = tiles_x * ((H + th - 1) // th)
+    try:
+        want = oracle_frame(frame, W, H, tw, th, nres, cb, coder, sop, eph, orc, t2ref, precision=prec)
+        panics = False
+    except ValueError:
+        want, panics = None, True                               # the reference's HT encoder panics on this input
+    print("frame %d: components=%d precision=%d coder=%s sop=%d eph=%d %s" % (n + npanic, Cn, prec, "HT" if coder == 1 else "MQ", sop, eph, "panic" if panics else "ok"), flush=True)
+    ref = None if panics else [(want[tl]["x0"], want[tl]["y0"], want[tl]["w"], want[tl]["h"], want[tl]["bytes"], want[tl]["lens"], want[tl]["numbps"]) for tl in range(ntiles)]
+    if oracle_only:
+        if panics:
+            npanic += 1
+            continue
+        for (x0, y0, w, h, by, ln, nb) in ref:
+            orc.decode_tile_blocks(by, ln, nb, Cn, w, h, nres, cb, cb, coder, 1)
+        n += 1
+        continue
+    # ---- the product ------------------------------------------------------------------------------------------------------------------
     plan = FramePlan(W, H, Cn, precision=prec, lossless=True, num_resolutions=nres, cb=(cb, cb), tile=(tw, th), coder=coder, closed_loop=True)
     d = torch.from_numpy(frame).to(plan.device)
     coeff = plan.forward(d)
@@ -62,47 +93,20 @@ while time.time() - t0 < budget:
         stream, offs, lens, numbps = plan.encode_stream(coeff)
         plan.ctx.sync()
     except J2KError as e:
-        assert e.status == -5 and coder == 1, desc               # the reference's HT encoder panics on this input
+        assert e.status == -5 and coder == 1, desc               # the reference's HT encoder panics on this input ...
+        assert panics, ("the product reports a panic where the oracle does not", desc)
         npanic += 1
         plan.close()
         continue
+    assert not panics, ("oracle panics where the product did not", desc)
     cs, toffs = plan.encode_tile_parts(stream, offs, lens, numbps, sop=sop, eph=eph)
     plan.frame_status()
     h_cs, h_t = cs.cpu().numpy(), toffs.cpu().numpy()
     total = int(h_t[-1])
     planes = plan.planes()
-    tiles_x = (W + tw - 1) // tw
-    ntiles = tiles_x * ((H + th - 1) // th)
-    levels = nres - 1 if nres - 1 > 0 else 5
-    nres_jobs = nres if nres > 0 else 6
-    panics = False
-    ref = []
+    nres_jobs = nres
     for tl in range(ntiles):
-        x0, y0 = (tl % tiles_x) * tw, (tl // tiles_x) * th
-        w, h = min(tw, W - x0), min(th, H - y0)
-        crop = [np.ascontiguousarray(frame[c, y0:y0 + h, x0:x0 + w]) for c in range(Cn)]
-        want_c = orc.preprocess(crop, w, h, prec, True, nres)
-        try:
-            by, ln, nb = orc.encode_tile_blocks(want_c, w, h, nres_jobs, cb, cb, coder, windows=1)
-        except ValueError:
-            panics = True
-            break
-        jobs = orc.enumerate_blocks(Cn, w, h, nres_jobs, cb, cb, 1)
-        enc = t2ref.PacketEncoder(len_bits=5)
-        pos, j = 0, 0
-        while j < len(jobs):
-            k, blocks = j, []
-            while k < len(jobs) and jobs[k]["comp"] == jobs[j]["comp"] and jobs[k]["res"] == jobs[j]["res"]:
-                l_, n_ = int(ln[k]), int(nb[k])
-                blocks.append(t2ref.CodeBlock(bytes(by[pos:pos + l_]), 1 if l_ == 0 else 0, max(31 - n_, 0), 0 if n_ == 0 else (1 if coder == 1 else 3 * n_ - 2)))
-                pos += l_
-                k += 1
-            enc.encode_packet(t2ref.Precinct([blocks]), 0, sop, eph)
-            j = k
-        part = orc.create_tile_header(tl, bytes(enc.out))
-        assert bytes(h_cs[int(h_t[tl]):int(h_t[tl + 1])]) == part, ("tile-part", desc, tl)
-        ref.append((x0, y0, w, h, by, ln, nb))
-    assert not panics, ("oracle panics where the product did not", desc)
+        assert bytes(h_cs[int(h_t[tl]):int(h_t[tl + 1])]) == want[tl]["part"], ("tile-part", desc, tl)
     if Cn == 3 and prec == 8:
         # the one-call frame encoder (blocks gathered from their coding slots straight into the tile-parts) == the stage calls
         pix = np.full((H, W, 4), 255, np.uint8)
@@ -144,5 +148,11 @@ while time.time() - t0 < budget:
                 assert torch.equal(got_px, want_px), ("frame decoder", desc)
     plan.close()
     n += 1
+if want_frames and n + npanic < want_frames:
+    print("closed-loop fuzz: the time budget of %.0f s ended after %d of %d frames, seed %d" % (budget, n + npanic, want_frames, seed))
+    sys.exit(2)
+if oracle_only:
+    print("closed-loop fuzz, the oracle's side alone: %d frames (%d in the reference's HT panic domain) in %.1f s, seed %d" % (n + npanic, npanic, time.time() - t0, seed))
+    sys.exit(0)
 print("closed-loop fuzz: %d frames clean (%d in the reference's HT panic domain; SOP + EPH frames: %d tiles parsed packet-parallel, %d fell back to the tile chain; %d frames also through the one-call frame encoder) in %.0f s, seed %d"
       % (n, npanic, npar_tiles, nser_tiles, nframe_enc, time.time() - t0, seed))
