@@ -104,6 +104,8 @@ def test_forward_image_equals_forward_pixels(W, H, tile, lossless, pix_fuse):
             assert fused                                     # 4:2:0, 4:2:2, 4:4:4 at 4K, 512 tiles, aligned planes
         if not lossless or pix_fuse == 0 or tile == 0:
             assert not fused
+        if (W, tile, lossless, pix_fuse) == (1000, 256, True, 1):
+            assert not fused                                 # no plane 384 columns wide: level 0 is not the workgroup kernel's (pick_cpl)
         ref_c = plan.forward_pixels(2, _dev(ref.rgba8_frame(want)))
         got = plan.forward_image(dimg)
         plan.ctx.sync()

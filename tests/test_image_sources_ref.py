@@ -125,3 +125,82 @@ def test_header_and_binding_declare_the_new_entries(lib):
     assert "typedef struct j2k_image" in txt and "J2K_IMG_YCBCR = 16" in txt
     import ctypes as C
     assert C.sizeof(lib.Image) == 112
+
+
+# ---- image_color.h itself, on the host: the header the staged kernel (image.hip) and the fused 5-3 level-0 kernel share ----------------
+HOST_TABLES = r"""
+#include <stddef.h>
+#include "image_color.h"
+extern "C" void ycc_table(uint32_t *out) {          // entry i: Y = i & 255, Cb = (i >> 8) & 255, Cr = i >> 16
+    for (uint32_t i = 0; i < (1u << 24); i++) out[i] = j2k::ycbcr_rgba8((int)(i & 255), (int)((i >> 8) & 255), (int)(i >> 16));
+}
+extern "C" void cmyk_table(const uint8_t *pix, size_t n, uint32_t *out) {
+    for (size_t i = 0; i < n; i++) out[i] = j2k::cmyk_rgba8(pix[4 * i], pix[4 * i + 1], pix[4 * i + 2], pix[4 * i + 3]);
+}
+extern "C" int divisors(int ratio) { return j2k::ycc_hdiv(ratio) * 16 + j2k::ycc_vdiv(ratio); }
+"""
+
+
+@pytest.fixture(scope="module")
+def color_lib(tmp_path_factory):
+    import ctypes as C
+    import shutil
+    cxx = next((c for c in (os.environ.get("CXX"), "c++", "g++", "clang++") if c and shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler (CXX, c++, g++, clang++) to compile image_color.h with")
+    d = tmp_path_factory.mktemp("image_color")
+    src, so = d / "tables.cpp", d / "libtables.so"
+    src.write_text(HOST_TABLES)
+    subprocess.check_call([cxx, "-O2", "-shared", "-fPIC", "-D__host__=", "-D__device__=", "-D__forceinline__=inline",
+                           "-I", os.path.join(ROOT, "go-jpeg2000_amd", "csrc"), str(src), "-o", str(so)])
+    return C.CDLL(str(so))
+
+
+def test_image_color_header_every_ycbcr_triple(color_lib):
+    """ycbcr_rgba8 of image_color.h, compiled for the host, on all 2^24 (Y, Cb, Cr) against ycbcr_rgb8 (the table the GPU test
+    test_gpu_image_sources_edges.py::test_every_ycbcr_triple_and_the_grid_stride_tail puts through image.hip)"""
+    import ctypes as C
+    packed = ref.ycbcr_table()[3]
+    got = np.zeros(1 << 24, np.uint32)
+    color_lib.ycc_table(got.ctypes.data_as(C.c_void_p))
+    assert np.array_equal(got, packed)
+    assert int(got[0]) == 0xFF000000 | 135 << 8 and int(got[0x7f7f7f]) == 0xFF000000 | 0x7e | 0x80 << 8 | 0x7d << 16     # the pins above
+
+
+def test_image_color_header_every_cmyk_value_pair(color_lib):
+    """cmyk_rgba8 on the 256 x 256 table in which every channel meets every (value, K) pair, against cmyk_rgb8; the chroma divisors
+    of the six ratios against RATIO_DIV"""
+    import ctypes as C
+    pix, packed = ref.cmyk_table()
+    got = np.zeros(1 << 16, np.uint32)
+    color_lib.cmyk_table(pix.ctypes.data_as(C.c_void_p), C.c_size_t(1 << 16), got.ctypes.data_as(C.c_void_p))
+    assert np.array_equal(got.reshape(256, 256), packed)
+    for ratio, (hd, vd) in ref.RATIO_DIV.items():
+        assert color_lib.divisors(ratio) == hd * 16 + vd
+
+
+def test_ycbcr_layout_restates_the_same_picture():
+    """the layout helper of the GPU edge tests: one picture at Rect.Min (0,0) / (2,4) / (6,2), padded strides, views into larger buffers
+    and re-randomised pad bytes is one set of colours by the restatement; random_ycbcr's layout is its default"""
+    rng = np.random.default_rng(11)
+    W, H = 24, 7
+    for ratio in (0, 1, 2):
+        cw, ch = ref.chroma_dims(ratio, (0, 0, W, H))
+        content = tuple(rng.integers(0, 256, size=s, dtype=np.uint8) for s in ((H, W), (ch, cw), (ch, cw)))
+        want = ref.ycbcr_image_rgb(content[0].reshape(-1), content[1].reshape(-1), content[2].reshape(-1), W, cw, ratio, (0, 0, W, H))
+        for mn, ypad, cpad, offs, cpad2 in [((0, 0), 0, 0, (0, 0, 0), None), ((2, 4), 8, 4, (16, 4, 8), None), ((6, 2), 16, 0, (0, 8, 0), None),
+                                            ((0, 2), 0, 4, (0, 0, 0), 8)]:
+            rect = (mn[0], mn[1], mn[0] + W, mn[1] + H)
+            assert ref.chroma_dims(ratio, rect) == (cw, ch)
+            cs2 = None if cpad2 is None else cw + cpad2
+            bufs, spans, ys, cs = ref.ycbcr_layout(rng, ratio, rect, W + ypad, cw + cpad, offs, 5, cs2, content)
+            planes = [b[s0:s1] for b, (s0, s1) in zip(bufs, spans)]
+            assert [p.size for p in planes] == [H * ys, ch * cs, ch * (cs2 or cs)] and all(b.size == s1 + 5 for b, (_, s1) in zip(bufs, spans))
+            assert np.array_equal(ref.ycbcr_image_rgb(*planes, ys, cs, ratio, rect, cs2), want)
+            before = [p.copy() for p in planes]
+            for p, st, row in zip(planes, (ys, cs, cs2 or cs), (W, cw, cw)):
+                ref.rerandomise_pad(rng, p, st, row)
+            assert np.array_equal(ref.ycbcr_image_rgb(*planes, ys, cs, ratio, rect, cs2), want)
+            assert (ypad == 0) == np.array_equal(before[0], planes[0])          # the pad bytes did change, where there are any
+            assert all(np.array_equal(b.reshape(-1, st)[:, :row], p.reshape(-1, st)[:, :row])
+                       for b, p, st, row in zip(before, planes, (ys, cs, cs2 or cs), (W, cw, cw)))
