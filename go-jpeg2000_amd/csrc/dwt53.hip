@@ -719,10 +719,12 @@ template <int CPL, int NC, bool VEC, bool PIX>
 __global__ __launch_bounds__(256) void dwt53_inv_kernel(const DwtJob *__restrict__ jobs, int njobs,
                                                         const DwtPlane *__restrict__ planes,
                                                         const int32_t *__restrict__ coef, const int32_t *__restrict__ prev,
-                                                        int32_t *__restrict__ dst, int dc_shift, int final_level, int pix_stride) {
+                                                        int32_t *__restrict__ dst, int dc_shift, int final_level, int pix_stride,
+                                                        const int *__restrict__ guard) {
     constexpr int H = CPL / 2;
     constexpr int PUB = 2 * NC * CPL * 64;   // ints one wavefront publishes: {s row, d row} x NC x (lo|hi) x 64 lanes
     __shared__ int sh[4 * PUB];
+    if (guard && *guard) return;             // (the frame decoder: a stream that was refused leaves the caller's frame alone)
     const int wv = threadIdx.x >> 6;
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + wv));
     const int lane = threadIdx.x & 63;
@@ -1287,12 +1289,12 @@ static hipError_t inv_go(hipStream_t s, const LevelLaunch &L, const int32_t *coe
     const int blocks = (L.njobs + 3) / 4;
     if constexpr (CPL == 8 && (NC == 3 || NC == 1) && VEC) {
         if (L.pix_stride > 0) {
-            hipExtLaunchKernelGGL((dwt53_inv_kernel<CPL, NC, VEC, true>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0, L.jobs, L.njobs, L.planes, coef, prev, dst, dc, fin, L.pix_stride);
+            hipExtLaunchKernelGGL((dwt53_inv_kernel<CPL, NC, VEC, true>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0, L.jobs, L.njobs, L.planes, coef, prev, dst, dc, fin, L.pix_stride, L.guard);
             return hipGetLastError();
         }
     }
     if (L.pix_stride > 0) return hipErrorInvalidValue;
-    hipExtLaunchKernelGGL((dwt53_inv_kernel<CPL, NC, VEC, false>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0, L.jobs, L.njobs, L.planes, coef, prev, dst, dc, fin, 0);
+    hipExtLaunchKernelGGL((dwt53_inv_kernel<CPL, NC, VEC, false>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0, L.jobs, L.njobs, L.planes, coef, prev, dst, dc, fin, 0, L.guard);
     return hipGetLastError();
 }
 
@@ -1352,7 +1354,7 @@ hipError_t launch_dwt53_inv(hipStream_t s, const LevelLaunch &L, const int32_t *
         if (L.pix_stride <= 0 || L.ncomp != 3 || !final_level) return hipErrorInvalidValue;
         uint32_t *pix = reinterpret_cast<uint32_t *>(dst);
 #define J2K_INVWG(NW, WPE) hipExtLaunchKernelGGL((dwt53_inv_rgba8_wg_kernel<NW, WPE>), dim3(L.njobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
-                                             L.jobs, L.njobs, L.planes, coef, prev, pix, dc_shift, L.pix_stride)
+                                             L.jobs, L.njobs, L.planes, coef, prev, pix, dc_shift, L.pix_stride, L.guard)
         const int wpe = L.wg_store;    // (inverse: occupancy variant, J2K_L0_INV_WPE: 5 = everything in registers, 6 / 7 = odd row parked in LDS)
         if (L.wg_waves == 4) { if (wpe == 5) J2K_INVWG(4, 5); else if (wpe == 7) J2K_INVWG(4, 7); else J2K_INVWG(4, 6); }
         else if (L.wg_waves == 8) { if (wpe == 5) J2K_INVWG(8, 5); else if (wpe == 7) J2K_INVWG(8, 7); else J2K_INVWG(8, 6); }
@@ -1363,7 +1365,7 @@ hipError_t launch_dwt53_inv(hipStream_t s, const LevelLaunch &L, const int32_t *
     if (L.pwaves > 0 && L.pnjobs > 0 && (L.ncomp == 1 || L.pix_stride <= 0 || L.pix_src == 4)) {     // planes in workgroup form (dwt53_plane_wg.inc)
         if (L.pix_stride > 0 && !final_level) return hipErrorInvalidValue;
 #define J2K_PWG(NW, NC, DST, MULTI, WPE) hipExtLaunchKernelGGL((dwt53_inv_plane_wg_kernel<NW, NC, DST, MULTI, WPE>), dim3(L.pnjobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
-                                                 L.pjobs, L.pnjobs, L.planes, coef, prev, (void *)dst, dc_shift, final_level, L.pix_stride, (int64_t)L.comp_elems)
+                                                 L.pjobs, L.pnjobs, L.planes, coef, prev, (void *)dst, dc_shift, final_level, L.pix_stride, (int64_t)L.comp_elems, L.guard)
 #define J2K_PWGM(NW, NC, DST, WPE) do { if (L.pmulti) J2K_PWG(NW, NC, DST, true, WPE); else J2K_PWG(NW, NC, DST, false, WPE); } while (0)
         if (L.pix_stride > 0 && L.pix_src != 1) {
             if (L.pwaves != 4 || L.comp_elems <= 0) return hipErrorInvalidValue;

@@ -252,8 +252,9 @@ template <int NW, int WPE, bool PARK = (WPE > 5)>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void dwt53_inv_rgba8_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                                const int32_t *__restrict__ coef, const int32_t *__restrict__ prev, uint32_t *__restrict__ pix,
-                               int dc_shift, int pix_stride) {
+                               int dc_shift, int pix_stride, const int *__restrict__ guard) {
     __shared__ v4i slot[NW][PARK ? 8 : 6][64];        // (PARK: two more vectors per wave for the pixel-row staging)
+    if (guard && *guard) return;             // (the frame decoder: a stream that was refused leaves the caller's frame alone)
     const DwtJob job = jobs[blockIdx.x];
     if (job.plane < 0) return;
     dwt53_inv_rgba8_wg_body<NW, PARK>(slot, job, planes, coef, prev, pix, dc_shift, pix_stride);

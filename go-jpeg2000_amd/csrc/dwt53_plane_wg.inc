@@ -238,7 +238,8 @@ template <int NW, int NC, int DST, bool MULTI, int WPE>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void dwt53_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                                const int32_t *__restrict__ coef, const int32_t *__restrict__ prev, void *__restrict__ dst,
-                               int dc_shift, int final_level, int pix_stride, int64_t comp_elems) {
+                               int dc_shift, int final_level, int pix_stride, int64_t comp_elems, const int *__restrict__ guard) {
+    if (guard && *guard) return;             // (the frame decoder: a stream that was refused leaves the caller's frame alone)
     static_assert(NC == 1 || (NC == 3 && (DST == 0 || DST == 4)), "pixel triples: RGBA64 here, RGBA8 in dwt53_l0pix.inc");
     constexpr int NR = NW - 1;
     constexpr int NV = (MULTI ? 3 : 2) * NC;       // vectors per row: per component L part, H part [, boundary extras {h[-1], l[+4], h[+4], -}]

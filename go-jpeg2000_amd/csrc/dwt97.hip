@@ -560,11 +560,11 @@ hipError_t launch_dwt97_inv(hipStream_t s, const LevelLaunch &L, const void *coe
         if (L.ncomp != 3 || coef_is_f64 || !mct || dst_mode != DST_I32_FRAME) return hipErrorInvalidValue;
 #define J2K_WG97I(NW) hipExtLaunchKernelGGL((dwt97_inv_rgb_wg_kernel<NW, J2K_WG97I_WPE, false>), dim3(L.njobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
                                              L.jobs, L.njobs, L.planes, reinterpret_cast<const int32_t *>(coef), prev,                       \
-                                             reinterpret_cast<int32_t *>(dst), dc_shift, 0)
+                                             reinterpret_cast<int32_t *>(dst), dc_shift, 0, L.guard)
         if (L.pix_stride > 0) {  // straight to packed RGBA8 pixels (j2k_plan_inverse_pixels on a lossy 8-bit plan): eight waves
             if (L.wg_waves != 8) return hipErrorInvalidValue;
             hipExtLaunchKernelGGL((dwt97_inv_rgb_wg_kernel<8, J2K_WG97I_WPE, true>), dim3(L.njobs), dim3(512), 0, s, L.ev_start, L.ev_stop, 0,
-                                  L.jobs, L.njobs, L.planes, reinterpret_cast<const int32_t *>(coef), prev, reinterpret_cast<int32_t *>(dst), dc_shift, L.pix_stride);
+                                  L.jobs, L.njobs, L.planes, reinterpret_cast<const int32_t *>(coef), prev, reinterpret_cast<int32_t *>(dst), dc_shift, L.pix_stride, L.guard);
             return hipGetLastError();
         }
         if (L.wg_waves == 6) J2K_WG97I(6);
@@ -577,7 +577,7 @@ hipError_t launch_dwt97_inv(hipStream_t s, const LevelLaunch &L, const void *coe
     }
     if (L.pwaves == 8 && L.pnjobs > 0 && L.ncomp == 1) {   // single planes in workgroup form: a deeper level, level 0 of one int32 component, the float64 unit calls
 #define J2K_PWG97I(CF, DI) hipLaunchKernelGGL((dwt97_inv_plane_wg_kernel<8, 6, CF, DI>), dim3(L.pnjobs), dim3(512), 0, s, L.pjobs, L.pnjobs, L.planes, \
-                                               coef, prev, dst, dc_shift, dst_mode == DST_F64_FRAME ? 1 : 0, dst_mode == DST_I32_FRAME ? L.pix_stride : 0)
+                                               coef, prev, dst, dc_shift, dst_mode == DST_F64_FRAME ? 1 : 0, dst_mode == DST_I32_FRAME ? L.pix_stride : 0, L.guard)
         if (dst_mode == DST_I32_FRAME) { if (coef_is_f64) J2K_PWG97I(true, true); else J2K_PWG97I(false, true); }
         else { if (coef_is_f64) J2K_PWG97I(true, false); else J2K_PWG97I(false, false); }
 #undef J2K_PWG97I

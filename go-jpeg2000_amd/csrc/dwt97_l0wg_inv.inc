@@ -34,7 +34,9 @@
 template <int NW, int WPE, bool PIX>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void dwt97_inv_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
-                             const int32_t *__restrict__ coef, const double *__restrict__ prev, int32_t *__restrict__ dst, int dc_shift, int pix_stride) {
+                             const int32_t *__restrict__ coef, const double *__restrict__ prev, int32_t *__restrict__ dst, int dc_shift, int pix_stride,
+                             const int *__restrict__ guard) {
+    if (guard && *guard) return;             // (the frame decoder: a stream that was refused leaves the caller's frame alone)
     typedef double v2d __attribute__((ext_vector_type(2)));
     __shared__ v2d slot[NW][4][64];                      // 8 doubles per lane as four 16-byte pieces, lane-contiguous
     __shared__ v2d xslot[3][4][64];                      // d2 of the pair-row above wave 0, per component
@@ -294,7 +296,9 @@ void dwt97_inv_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
 template <int NW, int WPE, bool CF64, bool DSTI32>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void dwt97_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
-                               const void *__restrict__ coef_, const double *__restrict__ prev, void *__restrict__ dst_, int dc_shift, int frame_rows, int pix_stride) {
+                               const void *__restrict__ coef_, const double *__restrict__ prev, void *__restrict__ dst_, int dc_shift, int frame_rows, int pix_stride,
+                               const int *__restrict__ guard) {
+    if (guard && *guard) return;             // (the frame decoder: a stream that was refused leaves the caller's frame alone)
     const int32_t *coef = reinterpret_cast<const int32_t *>(coef_);
     const double *coeff = reinterpret_cast<const double *>(coef_);
     double *dst = reinterpret_cast<double *>(dst_);

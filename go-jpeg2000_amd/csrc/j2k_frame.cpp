@@ -291,12 +291,13 @@ extern "C" int j2k_plan_decode_frame_pixels(j2k_plan *P, const uint8_t *d_cs, si
         r = stage_reserve(ctx, 2, ht_decode_scratch_words(n) * 4 + 256);
         if (r != J2K_OK) return r;
         HIPCHK(ctx, launch_ht_decode(ctx->stream, P->d_djobs, n, d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_coeff_dec, (uint32_t *)ctx->stage[2], 1, P->d_djobs_placed));
-        return j2k_plan_inverse_pixels(P, P->d_cl_coeff_dec, d_pix, stride);
+        return plan_inverse_pixels_impl(P, P->d_cl_coeff_dec, d_pix, stride, P->d_frame_status);
     } else {
         r = j2k_plan_decode_blocks(P, d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, P->d_cl_decoded);
         if (r == J2K_OK) r = j2k_plan_place_blocks(P, P->d_cl_decoded, P->d_cl_coeff);
     }
-    if (r == J2K_OK) r = j2k_plan_inverse_pixels(P, P->d_cl_coeff, d_pix, stride);
+    // (the status word as the guard of the launches that write d_pix: a stream that was refused leaves the caller's frame alone)
+    if (r == J2K_OK) r = plan_inverse_pixels_impl(P, P->d_cl_coeff, d_pix, stride, P->d_frame_status);
     return r;
 }
 

@@ -113,7 +113,9 @@ int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix
 int plan_encode_private_slots(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps);
 int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int sop, int eph, uint8_t *d_out, size_t cap,
                                  uint64_t *d_tile_offs);
-int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix = PixIO());
+// guard (device, or null): the launches that write d_frame write nothing if *guard != 0 -- the frame decoder's status word
+int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix = PixIO(), const int *guard = nullptr);
+int plan_inverse_pixels_impl(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride, const int *guard);
 // the default branch of extractImageData (j2k_image.cpp): d_img's planes on the device; status_word non-null = report a palette index
 // >= npal there (the frame codec's status, asynchronous), else synchronise and return J2K_ERR_GO_PANIC before anything is written
 bool plan_rgba8_wg_fusable(const j2k_plan *P);

@@ -95,6 +95,7 @@ struct LevelLaunch {
     hipEvent_t ev_start, ev_stop;   // non-null: the dispatch itself stamps these (hipExtLaunchKernelGGL) -- the kernel's own
                                     // begin / end, without the launch gap an event pair around the launch would include
     YccSrc ycc;           // ycc.y non-null: level 0 of the workgroup form reads this YCbCr image instead of packed RGBA8
+    const int *guard;     // inverse: non-null = a device word; the launch writes nothing if it is not 0 (the frame decoder's status, j2k_frame.cpp)
 };
 
 hipError_t launch_dwt53_fwd(hipStream_t s, const LevelLaunch &L, const int32_t *src, int32_t *out,
@@ -122,6 +123,8 @@ hipError_t launch_unpack_pixels(hipStream_t s, const uint8_t *pix, size_t stride
                                 int32_t *planes);
 hipError_t launch_colorspace(hipStream_t s, int cs, int32_t *planes, int ncomp, size_t n, int precision);
 hipError_t launch_pack_pixels(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, uint8_t *pix, size_t stride);
+hipError_t launch_pack_pixels_rect(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, int x0, int y0, int rw, int rh, uint8_t *pix,
+                                   size_t stride, const int *guard = nullptr);   // the rectangle (x0, y0, rw, rh) of the frame only
 // image.YCbCr / CMYK / Paletted -> packed RGBA8 (image.hip); *flag = J2K_ERR_GO_PANIC for a palette index >= npal
 hipError_t launch_image_to_rgba8(hipStream_t s, const j2k_image &img, uint32_t *pix, size_t stride_px, int *flag);
 

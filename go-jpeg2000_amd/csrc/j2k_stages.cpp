@@ -104,13 +104,14 @@ int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix
     return J2K_OK;
 }
 
-int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix) {
+int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix, const int *guard) {
     const int pix_stride = pix.stride;
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
     if (((uintptr_t)d_frame & 15) || ((uintptr_t)d_coeff & 15)) return fail(ctx, J2K_ERR_INVALID_ARG, "device pointers must be 16-byte aligned");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const bool mega = P->d_mega_inv_jobs && pix.triple == 8 && pix_stride > 0 && ctx->l0_wg_inv && S.wavelet == W53;
+    // (a guarded call keeps level 0 -- the launch that writes the frame -- apart from the deep levels: same results)
+    const bool mega = P->d_mega_inv_jobs && pix.triple == 8 && pix_stride > 0 && ctx->l0_wg_inv && S.wavelet == W53 && !guard;
     for (int rep_ = 0; mega && rep_ < dev_reps(0x100); rep_++) {
         hipEvent_t e0, e1;
         profile_pair(ctx, 3, e0, e1);
@@ -141,6 +142,7 @@ int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix
             if (!T.njobs) continue;
             if (S.wavelet == W53) {
                 LevelLaunch L = mk(T);
+                if (l == 0) L.guard = guard;
                 if (l == 0 && pix_stride > 0) pix_launch(L, T, pix, cls, S);  // packed frame (j2k_plan_inverse_rgba8 / _pixels)
                 if (l == 0 && cls == 1 && pix.triple == 8 && pix_stride > 0 && P->d_inv_wg_jobs && ctx->l0_wg_inv) {
                     // RGBA8: the workgroup form when every plane qualifies (same job table as the forward: the plane order
@@ -155,6 +157,7 @@ int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix
                 // dst_mode: 0 = f64 scratch (l>0), 1 = f64 frame (unit calls), 2 = int32 frame via int32(v+0.5) (tcd.go:433-435)
                 const int dst_mode = (l > 0) ? 0 : (S.frame_is_f64 ? 1 : 2);
                 LevelLaunch L97 = mk(T);
+                if (l == 0 && pix_stride > 0) L97.guard = guard;   // (the workgroup forms that write pixels; an int32 frame is the staging frame: the pack is guarded)
                 if (l == 0 && cls == 0 && pix.single == 97) L97.pix_stride = pix.stride;      // image.Gray pixels (j2k_plan_inverse_pixels)
                 if (l == 0 && cls == 1 && dst_mode == 2 && P->d_inv97_wg_jobs) {   // the workgroup form when every plane qualifies
                     L97.jobs = P->d_inv97_wg_jobs; L97.njobs = P->inv97_wg_njobs; L97.wg_waves = P->inv97_wg_waves;
@@ -414,6 +417,32 @@ bool plan_rgba8_wg_fusable(const j2k_plan *P) {
     return P->d_fwd_wg_jobs && !P->d_fwd_wg2_jobs && !P->d_mega_fwd_jobs && P->ctx->l0_store == 1 && !P->fwd[0][0].njobs;
 }
 
+// The staged way out of the inverse calls: the int32 staging frame -> the caller's pixels.  A plan that holds every tile packs the frame; a
+// shard (j2k_params.tile_first / tile_count) packs the rows of tiles its inverse transform wrote and nothing else -- the rest of the staging
+// frame is whatever an earlier call of the context left there, and the rest of the caller's frame belongs to other shards.
+static int plan_pack_pixels(j2k_plan *P, const int32_t *d_planes, int ncomp, int precision, void *d_pix, size_t stride, const int *guard = nullptr) {
+    j2k_ctx *ctx = P->ctx;
+    const PlanSpec &S = P->spec;
+    if (P->tile_count == P->tiles_x * P->tiles_y && !guard) return j2k_pack_pixels(ctx, d_planes, ncomp, precision, S.W, S.H, d_pix, stride);
+    int r = j2k_pack_pixels(ctx, d_planes, ncomp, precision, S.W, 0, d_pix, stride);        // (the argument checks; no rows)
+    if (r != J2K_OK) return r;
+    if (P->tile_count == P->tiles_x * P->tiles_y) {
+        HIPCHK(ctx, launch_pack_pixels_rect(ctx->stream, d_planes, ncomp, precision, S.W, S.H, 0, 0, S.W, S.H, (uint8_t *)d_pix, stride, guard));
+        return J2K_OK;
+    }
+    // tiles are numbered row by row: one rectangle per row of tiles the shard reaches (its first and last may be partial)
+    size_t i = 0;
+    while (i < P->groups.size()) {
+        const Group &a = P->groups[i];
+        int x1 = a.x0 + a.w;
+        size_t k = i + 1;
+        for (; k < P->groups.size() && (P->groups[k].tile == a.tile || (P->groups[k].y0 == a.y0 && P->groups[k].x0 >= x1)); k++) x1 = std::max(x1, P->groups[k].x0 + P->groups[k].w);
+        HIPCHK(ctx, launch_pack_pixels_rect(ctx->stream, d_planes, ncomp, precision, S.W, S.H, a.x0, a.y0, x1 - a.x0, a.h, (uint8_t *)d_pix, stride, guard));
+        i = k;
+    }
+    return J2K_OK;
+}
+
 extern "C" int j2k_plan_forward_rgba8(j2k_plan *P, const void *d_pix, size_t stride, int32_t *d_coeff) {
     if (!P || !d_pix || !d_coeff) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
@@ -442,7 +471,7 @@ extern "C" int j2k_plan_inverse_rgba8(j2k_plan *P, const int32_t *d_coeff, void 
     if (r != J2K_OK) return r;
     r = plan_inverse_impl(P, d_coeff, ctx->stage[0]);
     if (r != J2K_OK) return r;
-    return j2k_pack_pixels(ctx, (const int32_t *)ctx->stage[0], 3, 8, S.W, S.H, d_pix, stride);
+    return plan_pack_pixels(P, (const int32_t *)ctx->stage[0], 3, 8, d_pix, stride);
 }
 
 extern "C" int j2k_plan_forward_pixels(j2k_plan *P, int format, const void *d_pix, size_t stride, int32_t *d_coeff) {
@@ -471,18 +500,21 @@ extern "C" int j2k_plan_pixels_fused(const j2k_plan *P, int format, const void *
 }
 
 extern "C" int j2k_plan_inverse_pixels(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride) {
+    return plan_inverse_pixels_impl(P, d_coeff, d_pix, stride, nullptr);
+}
+int plan_inverse_pixels_impl(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride, const int *guard) {
     if (!P || !d_pix || !d_coeff) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
     // decoder.createImage picks the image type from (components, precision): Gray / Gray16, RGBA / RGBA64 (decoder.go:417-588)
     PixIO io;
     if ((S.precision == 8 || S.precision == 16) && pix_fusable(P, S.precision / 8, S.C == 1 ? 1 : 4, d_pix, stride, true, io))
-        return plan_inverse_impl(P, d_coeff, d_pix, io);
+        return plan_inverse_impl(P, d_coeff, d_pix, io, guard);
     int r = stage_reserve(ctx, 0, (size_t)S.W * S.H * S.C * 4 + 64);
     if (r != J2K_OK) return r;
     r = plan_inverse_impl(P, d_coeff, ctx->stage[0]);
     if (r != J2K_OK) return r;
-    return j2k_pack_pixels(ctx, (const int32_t *)ctx->stage[0], S.C, S.precision, S.W, S.H, d_pix, stride);
+    return plan_pack_pixels(P, (const int32_t *)ctx->stage[0], S.C, S.precision, d_pix, stride, guard);
 }
 
 // Workspace of the T1 encoder: [serial-kernel work: wpj * n] [nsyms: n words] [lane order: n + 64 words] [symbol lists: n * stride].  The symbol

@@ -56,14 +56,17 @@ __global__ __launch_bounds__(256) void unpack_pixels_kernel(const uint8_t *__res
     }
 }
 
-// decoder.createImage: ncomp 1 -> Gray (precision <= 8) or Gray16; 3 / 4 -> RGBA (precision <= 8) or RGBA64
-__global__ __launch_bounds__(256) void pack_pixels_kernel(const int32_t *__restrict__ planes, int ncomp, int precision, int w, int h,
-                                                          uint8_t *__restrict__ pix, size_t stride) {
-    const size_t n = (size_t)w * h;
+// decoder.createImage: ncomp 1 -> Gray (precision <= 8) or Gray16; 3 / 4 -> RGBA (precision <= 8) or RGBA64.  The rectangle (x0, y0, rw, rh) of
+// w x h planes: the whole frame, or the rows of tiles that a shard's inverse transform wrote
+__global__ __launch_bounds__(256) void pack_pixels_kernel(const int32_t *__restrict__ planes, int ncomp, int precision, int w, int h, int x0, int y0, int rw,
+                                                          int rh, uint8_t *__restrict__ pix, size_t stride, const int *__restrict__ guard) {
+    if (guard && *guard) return;             // (the frame decoder: a stream that was refused leaves the caller's frame alone)
+    const size_t n = (size_t)w * h, m = (size_t)rw * rh;
     const int max_val = (int)((1u << precision) - 1);
     const bool wide = precision > 8;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const int y = (int)(i / (size_t)w), x = (int)(i - (size_t)y * w);
+    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < m; j += (size_t)gridDim.x * 256) {
+        const int yy = (int)(j / (size_t)rw), y = y0 + yy, x = x0 + (int)(j - (size_t)yy * rw);
+        const size_t i = (size_t)y * w + x;
         uint8_t *row = pix + (size_t)y * stride;
         int v[4];
         for (int c = 0; c < ncomp; c++) {
@@ -99,12 +102,17 @@ hipError_t launch_unpack_pixels(hipStream_t s, const uint8_t *pix, size_t stride
     return hipGetLastError();
 }
 
-hipError_t launch_pack_pixels(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, uint8_t *pix, size_t stride) {
-    const size_t n = (size_t)w * h;
-    if (!n) return hipSuccess;
-    const int blocks = (int)std::min<size_t>((n + 255) / 256, 65536);
-    hipLaunchKernelGGL(pack_pixels_kernel, dim3(blocks), dim3(256), 0, s, planes, ncomp, precision, w, h, pix, stride);
+hipError_t launch_pack_pixels_rect(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, int x0, int y0, int rw, int rh, uint8_t *pix,
+                                   size_t stride, const int *guard) {
+    if (x0 < 0 || y0 < 0 || rw < 0 || rh < 0 || x0 + rw > w || y0 + rh > h) return hipErrorInvalidValue;
+    const size_t m = (size_t)rw * rh;
+    if (!m) return hipSuccess;
+    const int blocks = (int)std::min<size_t>((m + 255) / 256, 65536);
+    hipLaunchKernelGGL(pack_pixels_kernel, dim3(blocks), dim3(256), 0, s, planes, ncomp, precision, w, h, x0, y0, rw, rh, pix, stride, guard);
     return hipGetLastError();
+}
+hipError_t launch_pack_pixels(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, uint8_t *pix, size_t stride) {
+    return launch_pack_pixels_rect(s, planes, ncomp, precision, w, h, 0, 0, w, h, pix, stride);
 }
 
 }  // namespace j2k

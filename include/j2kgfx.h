@@ -370,7 +370,8 @@ int j2k_plan_inverse_rgba8(j2k_plan *plan, const int32_t *d_coeff, void *d_pix, 
  * 16-byte accesses, the level-0 kernels read / write the pixels themselves -- Gray, Gray16, RGBA,
  * RGBA64, NRGBA, NRGBA64 alike (a fourth component is its own plane: encoder.go:152-179), and so do the
  * 9-7 level-0 kernels for image.RGBA and image.Gray on a lossy 8-bit plan (the reference's DefaultOptions); otherwise
- * the pixels pass through an int32 staging frame.  Same results either way. */
+ * the pixels pass through an int32 staging frame.  Same results either way.  On a shard (tile_first /
+ * tile_count) the inverse writes the pixels of the shard's tiles only, either way. */
 int j2k_plan_forward_pixels(j2k_plan *plan, int format, const void *d_pix, size_t stride, int32_t *d_coeff);
 int j2k_plan_inverse_pixels(j2k_plan *plan, const int32_t *d_coeff, void *d_pix, size_t stride);
 /* 1 when that call (inverse != 0: j2k_plan_inverse_pixels, format ignored) would take the fused
@@ -606,6 +607,8 @@ int j2k_t2_decode_packets_device(j2k_ctx *ctx, const j2k_t2_dev_packet *d_packet
  *                               coding slot into its packet in its tile-part (no dense stream in between); on an HT plan the
  *                               block decoder writes only the rows the reference's HT decoder writes (one in four), straight
  *                               into each block's window of coefficient planes the plan zeroed once.
+ *                               j2k_plan_decode_frame_pixels writes nothing into d_pix while the plan's status word is set -- by a
+ *                               tile-part or packet this call refused, or by an earlier call whose status was never read.
  * All of them return J2K_ERR_UNSUPPORTED on a plan without closed_loop. */
 size_t j2k_plan_frame_bound(const j2k_plan *plan);
 int j2k_plan_encode_tile_parts(j2k_plan *plan, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,

@@ -1,6 +1,6 @@
 """The closed-loop frame by the ORACLE (test infrastructure): the reference's own functions composed per tile -- preprocess (DC shift, RCT, 5-3),
 the job list with partitioning windows, the block coder, one packet per (component, resolution) through the restated PacketEncoder with the
-closed-loop flags, createTileHeader.  Used by tests/test_gpu_decode_body.py, tests/test_gpu_closed_loop_formats.py, tests/test_closed_loop_golden.py, tools/fuzz_gpu_closed_loop.py and tests/golden/make_closed_loop_golden.py."""
+closed-loop flags, createTileHeader.  Used by tests/test_gpu_decode_body.py, tests/test_gpu_closed_loop_formats.py, tests/test_gpu_batch_shard_paths.py, tests/test_closed_loop_golden.py, tools/fuzz_gpu_closed_loop.py and tests/golden/make_closed_loop_golden.py."""
 import numpy as np
 
 
@@ -83,6 +83,22 @@ def oracle_frame(frm, W, H, tw, th, nres, cb, coder, sop, eph, orc, t2ref, tiles
             enc.encode_packet(t2ref.Precinct([blocks]), 0, sop, eph)
             j = k
         out[t] = dict(coeff=coeff, bytes=by, lens=lens, numbps=nb, part=orc.create_tile_header(t, bytes(enc.out)), w=w, h=h, x0=x0, y0=y0)
+    return out
+
+
+def oracle_batch(frames, W, H, tw, th, nres, cb, coder, sop, eph, orc, t2ref, **kw):
+    """A batch plan's tile-parts (j2k_params.frame_rows: the tile grid starts again at every frame, the tiles are numbered through the
+    batch) by the oracle: oracle_frame once per frame of `frames` ([components, H, W] each), frame 0's tiles first, every tile-part made
+    again by createTileHeader at index b * tiles_per_frame + t around the packets of tile t of frame b.  Returns a list of oracle_frame's
+    dicts in batch order, each with frame = b, tile = t, index = its number in the batch, and `part` the tile-part at that number."""
+    out = []
+    tiles1 = ((W + tw - 1) // tw) * ((H + th - 1) // th)
+    for b, frm in enumerate(frames):
+        want = oracle_frame(frm, W, H, tw, th, nres, cb, coder, sop, eph, orc, t2ref, **kw)
+        assert sorted(want) == list(range(tiles1))
+        for t in range(tiles1):
+            k = b * tiles1 + t
+            out.append(dict(want[t], frame=b, tile=t, index=k, part=orc.create_tile_header(k, want[t]["part"][14:])))
     return out
 
 

@@ -63,6 +63,36 @@ def test_oracle_composes_the_pinned_tile_parts_and_reads_them_back(case):
     assert at == len(stream)
 
 
+def test_oracle_batch_renumbers_the_tile_parts_and_nothing_else():
+    """closed_loop_ref.oracle_batch (what the batch tests on the GPU compare with): frame b's tile t is tile-part number b * tiles + t of the
+    batch, made by the oracle's createTileHeader around the same packets -- it differs from the part at number t (oracle_frame's) in bytes 4
+    and 5 only, Isot, which hold the number big-endian.  The same frame three times over, so that part k of the batch and part k % tiles of
+    the frame wrap the same packets."""
+    import oracle as orc
+    import t2ref
+    W, H, tw, th, nres, cb = 75, 52, 32, 32, 3, 8
+    frm = ref.frame_n(W, H, 3, 8, 77)
+    one = ref.oracle_frame(frm, W, H, tw, th, nres, cb, 0, True, True, orc, t2ref)
+    tiles = len(one)
+    assert tiles == 6
+    got = ref.oracle_batch([frm, frm, frm], W, H, tw, th, nres, cb, 0, True, True, orc, t2ref)
+    assert [(g["frame"], g["tile"], g["index"]) for g in got] == [(k // tiles, k % tiles, k) for k in range(3 * tiles)]
+    for k, g in enumerate(got):
+        a, b = np.frombuffer(one[k % tiles]["part"], np.uint8), np.frombuffer(g["part"], np.uint8)
+        assert a.size == b.size
+        differ = set(np.nonzero(a != b)[0].tolist())
+        assert differ <= {4, 5}, (k, sorted(differ))
+        assert int.from_bytes(g["part"][4:6], "big") == k
+        assert int.from_bytes(g["part"][6:10], "big") == len(g["part"]) and g["part"][14:] == one[k % tiles]["part"][14:]
+    assert got[0]["part"] == one[0]["part"] and got[tiles + 1]["part"] != one[1]["part"]
+    # the part at index k against the part at index 0 of the SAME packets, as the header function makes them
+    body = one[0]["part"][14:]
+    p0 = orc.create_tile_header(0, body)
+    for k in (1, 255, 256, 0x1234, 0xFFFF):
+        pk = orc.create_tile_header(k, body)
+        assert pk[:4] == p0[:4] and pk[6:] == p0[6:] and pk[4:6] == k.to_bytes(2, "big")
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ALL_CASES, ids=[c["name"] for c in ALL_CASES])
 def test_product_writes_the_pinned_tile_parts(case):
