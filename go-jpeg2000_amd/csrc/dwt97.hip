@@ -16,8 +16,9 @@
 // so a band reads 7 halo rows).  Every sample is read once and written once per level.
 //
 // Bit-exactness vs Go/amd64: compiled with -ffp-contract=off (no FMA), the reference's literal
-// constants, the same operand association; the symmetric-extension edge terms are computed as
-// c*(x+x), which is bitwise equal to the reference's (2*c)*x (scaling by two is exact).
+// constants, the same operand association.  A symmetric-extension edge term is the reference's (2*c)*x (dwt.go:171-197, 230-260)
+// wherever the samples can be arbitrary float64 -- lift97 below; c*(x+x) is the same bits (scaling by two is exact) only until x+x
+// overflows, and tests/test_gpu_lossy97_oracle.py (`overflow`) has |x| > DBL_MAX/2 beside every kind of edge.
 #include "j2k_internal.h"
 #include <hip/hip_ext.h>
 
@@ -51,6 +52,10 @@ __device__ __forceinline__ double dright(double v) { return dshift(v, 0); }   //
 __device__ __forceinline__ int go_int32(double v) { return v < 2147483648.0 ? (int)v : (int)0x80000000; }
 __device__ __forceinline__ int round_half_away(double v) { return v >= 0 ? go_int32(v + 0.5) : go_int32(v - 0.5); }
 
+// the term c * (a + b) of a lifting step; where b is a's own mirror (the symmetric extension at the first / last sample) the reference
+// writes (2 * c) * a, which stays finite for |a| > DBL_MAX / 2 where a + a does not
+__device__ __forceinline__ double lift97(double c, double a, double b, bool mirror) { return mirror ? (2.0 * c) * a : c * (a + b); }
+
 enum { SRC_I32 = 0, SRC_F64 = 1 };
 enum { Q_NONE_ = 0, Q_ENCODER_ = 1, Q_TCD_ = 2 };
 enum { DST_F64_SCRATCH = 0, DST_F64_FRAME = 1, DST_I32_FRAME = 2 };
@@ -72,7 +77,7 @@ __device__ __forceinline__ void hfwd97(const double (&x)[CPL], int c, int w, dou
     for (int j = 0; j < H; j++) {
         const int ce = c + 2 * j;
         const double en = (ce + 2 < w) ? ((j + 1 < H) ? x[2 * j + 2] : e_r) : x[2 * j];
-        d1[j] = x[2 * j + 1] + A97 * (x[2 * j] + en);
+        d1[j] = x[2 * j + 1] + lift97(A97, x[2 * j], en, ce + 2 >= w);
     }
     const double d1_l = dleft(d1[H - 1]);
 #pragma unroll
@@ -81,14 +86,14 @@ __device__ __forceinline__ void hfwd97(const double (&x)[CPL], int c, int w, dou
         double dp = (j > 0) ? d1[j - 1] : d1_l;
         if (ce + 1 >= w) d1[j] = dp;           // no odd partner: mirrors d[n-2]
         if (ce == 0) dp = d1[j];
-        s1[j] = x[2 * j] + B97 * (dp + d1[j]);
+        s1[j] = x[2 * j] + lift97(B97, d1[j], dp, ce == 0 || ce + 1 >= w);
     }
     const double s1_r = dright(s1[0]);
 #pragma unroll
     for (int j = 0; j < H; j++) {
         const int ce = c + 2 * j;
         const double sn = (ce + 2 < w) ? ((j + 1 < H) ? s1[j + 1] : s1_r) : s1[j];
-        d2[j] = d1[j] + G97 * (s1[j] + sn);
+        d2[j] = d1[j] + lift97(G97, s1[j], sn, ce + 2 >= w);
     }
     const double d2_l = dleft(d2[H - 1]);
 #pragma unroll
@@ -97,7 +102,7 @@ __device__ __forceinline__ void hfwd97(const double (&x)[CPL], int c, int w, dou
         double dp = (j > 0) ? d2[j - 1] : d2_l;
         if (ce + 1 >= w) d2[j] = dp;
         if (ce == 0) dp = d2[j];
-        lo[j] = (s1[j] + D97 * (dp + d2[j])) * K97I;
+        lo[j] = (s1[j] + lift97(D97, d2[j], dp, ce == 0 || ce + 1 >= w)) * K97I;
         hi[j] = d2[j] * K97;
     }
 }
@@ -121,14 +126,14 @@ __device__ __forceinline__ void hinv97(const double (&lo)[CPL / 2], const double
         double dp = (j > 0) ? d2[j - 1] : d2_l;
         if (ce + 1 >= w) d2[j] = dp;
         if (ce == 0) dp = d2[j];
-        s1[j] = lo[j] * K97 - D97 * (dp + d2[j]);
+        s1[j] = lo[j] * K97 - lift97(D97, d2[j], dp, ce == 0 || ce + 1 >= w);
     }
     const double s1_r = dright(s1[0]);
 #pragma unroll
     for (int j = 0; j < H; j++) {
         const int ce = c + 2 * j;
         const double sn = (ce + 2 < w) ? ((j + 1 < H) ? s1[j + 1] : s1_r) : s1[j];
-        d1[j] = d2[j] - G97 * (s1[j] + sn);
+        d1[j] = d2[j] - lift97(G97, s1[j], sn, ce + 2 >= w);
     }
     const double d1_l = dleft(d1[H - 1]);
 #pragma unroll
@@ -137,7 +142,7 @@ __device__ __forceinline__ void hinv97(const double (&lo)[CPL / 2], const double
         double dp = (j > 0) ? d1[j - 1] : d1_l;
         if (ce + 1 >= w) d1[j] = dp;
         if (ce == 0) dp = d1[j];
-        e[j] = s1[j] - B97 * (dp + d1[j]);
+        e[j] = s1[j] - lift97(B97, d1[j], dp, ce == 0 || ce + 1 >= w);
     }
     const double e_r = dright(e[0]);
 #pragma unroll
@@ -145,7 +150,7 @@ __device__ __forceinline__ void hinv97(const double (&lo)[CPL / 2], const double
         const int ce = c + 2 * j;
         const double en = (ce + 2 < w) ? ((j + 1 < H) ? e[j + 1] : e_r) : e[j];
         x[2 * j] = e[j];
-        x[2 * j + 1] = d1[j] - A97 * (e[j] + en);
+        x[2 * j + 1] = d1[j] - lift97(A97, e[j], en, ce + 2 >= w);
     }
 }
 
@@ -280,15 +285,15 @@ __global__ __launch_bounds__(256) void dwt97_fwd_kernel(const DwtJob *__restrict
                     const double env = a ? en.hi[k][j] : en.lo[k][j];
                     double d1t, s1t;
                     if (real) {
-                        d1t = o_ex ? ov + A97 * (ev + (en_ex ? env : ev)) : d1p[a][k][j];
-                        s1t = ev + B97 * ((t == 0 ? d1t : d1p[a][k][j]) + d1t);
+                        d1t = o_ex ? ov + lift97(A97, ev, env, !en_ex) : d1p[a][k][j];
+                        s1t = ev + lift97(B97, d1t, d1p[a][k][j], t == 0 || !o_ex);
                     } else {
                         d1t = d1p[a][k][j];
                         s1t = s1p[a][k][j];     // mirror: s1[q+1] := s1[q]
                     }
                     if (t >= 1) {               // finalize pair t-1
-                        const double d2 = prev_o_ex ? d1p[a][k][j] + G97 * (s1p[a][k][j] + s1t) : d2p[a][k][j];
-                        const double s2 = s1p[a][k][j] + D97 * ((t - 1 == 0 ? d2 : d2p[a][k][j]) + d2);
+                        const double d2 = prev_o_ex ? d1p[a][k][j] + lift97(G97, s1p[a][k][j], s1t, !real) : d2p[a][k][j];
+                        const double s2 = s1p[a][k][j] + lift97(D97, d2, d2p[a][k][j], t - 1 == 0 || !prev_o_ex);
                         if (a == 0) { outl[k][j] = s2 * K97I; outl2[k][j] = d2 * K97; }
                         else { outh[k][j] = s2 * K97I; outh2[k][j] = d2 * K97; }
                         d2p[a][k][j] = d2;
@@ -452,16 +457,16 @@ __global__ __launch_bounds__(256) void dwt97_inv_kernel(const DwtJob *__restrict
                     if (real) {
                         const double s2t = (a ? L.hi[k][j] : L.lo[k][j]) * K97;
                         if (hi_ex) d2t = (a ? Hh.hi[k][j] : Hh.lo[k][j]) * K97I;     // else mirrors d2[t-1]
-                        s1t = s2t - D97 * ((t == 0 ? d2t : d2p[a][k][j]) + d2t);
+                        s1t = s2t - lift97(D97, d2t, d2p[a][k][j], t == 0 || !hi_ex);
                     }
                     double d1n = d1p[a][k][j], en_ = ep[a][k][j];
                     if (p1_real) {
-                        if (p1_hi) d1n = d2p[a][k][j] - G97 * (s1p[a][k][j] + (real ? s1t : s1p[a][k][j]));   // d1[t-1]; else mirrors d1[t-2]
-                        en_ = s1p[a][k][j] - B97 * ((t - 1 == 0 ? d1n : d1p[a][k][j]) + d1n);               // e[t-1]
+                        if (p1_hi) d1n = d2p[a][k][j] - lift97(G97, s1p[a][k][j], s1t, !real);   // d1[t-1]; else mirrors d1[t-2]
+                        en_ = s1p[a][k][j] - lift97(B97, d1n, d1p[a][k][j], t - 1 == 0 || !p1_hi);               // e[t-1]
                     }
                     if (p2_real) {
                         const double e_t2 = e2[a][k][j];
-                        const double on = d1p[a][k][j] - A97 * (e_t2 + (p1_real ? en_ : e_t2));             // o[t-2]
+                        const double on = d1p[a][k][j] - lift97(A97, e_t2, en_, !p1_real);             // o[t-2]
                         if (a == 0) { re_lo[k][j] = e_t2; ro_lo[k][j] = on; } else { re_hi[k][j] = e_t2; ro_hi[k][j] = on; }
                     }
                     e2[a][k][j] = ep[a][k][j];

@@ -23,8 +23,10 @@
 //   * v / step for the constant step = 1.0 / Quality is evaluated as q0 = v * r, q = fma(fma(-q0, step, v), r, q0) with
 //     r = RN(1 / step): three instructions instead of the ~14 of the IEEE divide expansion, and -- by Markstein's theorem, r
 //     being the correctly rounded reciprocal and q0 within an ulp of the quotient -- the same correctly rounded result the
-//     reference's division gives (checked against the oracle's true division by tests/test_gpu_dwt97.py on every coefficient
-//     of its frames, and by tests/test_markstein_division.py on 10^7 values per Quality on the CPU).
+//     reference's division gives (checked against the oracle's true division on every coefficient of their frames by
+//     tests/test_gpu_lossy97_oracle.py -- every workgroup width, Quality 1, 2, 3, 75, 100, 101, 4097, 8191, samples inside and
+//     outside the precision -- and tests/test_gpu_dwt97.py, and by tests/test_markstein_division.py on 10^7 values per
+//     Quality on the CPU).
 // Bit-exactness otherwise as dwt97.hip: no contraction (-ffp-contract=off; the two fma above are explicit and exact by
 // construction), the reference's literal constants and operand association.
 // Geometry contract (checked by the plan): int32 source, three components with ICT, every plane 16 <= w <= 512, w % 8 == 0,
@@ -72,6 +74,9 @@ void dwt97_fwd_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
     const int c = lane * 8;
     const bool active = c < w;
     const bool last_lane = c + 8 >= w;
+    // arbitrary float64 samples (the unit calls) can make x + x overflow at a mirrored edge where the reference's (2 * c) * x stays
+    // finite: lift97's second form there; samples that come from int32 are far below that, and keep one form for every position
+    constexpr bool EDGE = (SRC == 1);
     const int q0 = job.prow0;
     const int t = q0 - 2 + wv;                           // my pair-row
     const bool live = t >= 0 && t < halfH;
@@ -140,25 +145,25 @@ void dwt97_fwd_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const double en = (j < 3) ? x[2 * j + 2] : (last_lane ? x[6] : e_r);
-            d1[j] = x[2 * j + 1] + A97 * (x[2 * j] + en);
+            d1[j] = x[2 * j + 1] + lift97(A97, x[2 * j], en, EDGE && j == 3 && last_lane);
         }
         const double d1_l = dleft(d1[3]);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const double dp = (j > 0) ? d1[j - 1] : (lane == 0 ? d1[0] : d1_l);
-            s1[j] = x[2 * j] + B97 * (dp + d1[j]);
+            s1[j] = x[2 * j] + lift97(B97, d1[j], dp, EDGE && j == 0 && lane == 0);
         }
         const double s1_r = dright(s1[0]);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const double sn = (j < 3) ? s1[j + 1] : (last_lane ? s1[3] : s1_r);
-            d2[j] = d1[j] + G97 * (s1[j] + sn);
+            d2[j] = d1[j] + lift97(G97, s1[j], sn, EDGE && j == 3 && last_lane);
         }
         const double d2_l = dleft(d2[3]);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const double dp = (j > 0) ? d2[j - 1] : (lane == 0 ? d2[0] : d2_l);
-            lo[j] = (s1[j] + D97 * (dp + d2[j])) * K97I;
+            lo[j] = (s1[j] + lift97(D97, d2[j], dp, EDGE && j == 0 && lane == 0)) * K97I;
             hi[j] = d2[j] * K97;
         }
     };
@@ -177,6 +182,8 @@ void dwt97_fwd_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
     // wave's "row below".
     double El[4], Eh[4], Ol[4], Oh[4], Nl[4], Nh[4];
     const bool nx = live && t + 1 < halfH && wv < NW - 1;    // the pair-row below exists and a wave holds it
+    // (wave-uniform) the row read from the slot is this wave's own: the mirror above the first pair-row / of a missing odd row, below the last row
+    const bool m_up = EDGE && (t == 0 || !o_ex), m_dn1 = EDGE && !en_ex, m_dn3 = EDGE && t + 1 >= halfH;
     if (live) {
         hrow(2 * t, El, Eh);
         put(wv, El, Eh);
@@ -192,8 +199,8 @@ void dwt97_fwd_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
         get(wv + 1, Nl, Nh);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            Ol[j] = Ol[j] + A97 * (El[j] + Nl[j]);                           // O becomes d1
-            Oh[j] = Oh[j] + A97 * (Eh[j] + Nh[j]);
+            Ol[j] = Ol[j] + lift97(A97, El[j], Nl[j], m_dn1);                // O becomes d1
+            Oh[j] = Oh[j] + lift97(A97, Eh[j], Nh[j], m_dn1);
         }
         if (wv < NW - 1 && o_ex) put(wv + 1, Ol, Oh);
         if (t == 0) put(wv, Ol, Oh);                          // d1[-1] := d1[0]
@@ -206,8 +213,8 @@ void dwt97_fwd_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
         if (!o_ex) get(wv, Ol, Oh);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            El[j] = El[j] + B97 * (Pl[j] + Ol[j]);                           // E becomes s1
-            Eh[j] = Eh[j] + B97 * (Ph[j] + Oh[j]);
+            El[j] = El[j] + lift97(B97, Ol[j], Pl[j], m_up);                 // E becomes s1
+            Eh[j] = Eh[j] + lift97(B97, Oh[j], Ph[j], m_up);
         }
         put(wv, El, Eh);
         if (!nx && wv < NW - 1) put(wv + 1, El, Eh);          // s1 past the end mirrors s1 (dwt.go:189-197)
@@ -218,8 +225,8 @@ void dwt97_fwd_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
         get(wv + 1, Nl, Nh);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            Ol[j] = Ol[j] + G97 * (El[j] + Nl[j]);                           // O becomes d2
-            Oh[j] = Oh[j] + G97 * (Eh[j] + Nh[j]);
+            Ol[j] = Ol[j] + lift97(G97, El[j], Nl[j], m_dn3);                // O becomes d2
+            Oh[j] = Oh[j] + lift97(G97, Eh[j], Nh[j], m_dn3);
         }
         if (wv < NW - 1 && o_ex) put(wv + 1, Ol, Oh);
         if (t == 0) put(wv, Ol, Oh);                          // d2[-1] := d2[0]
@@ -233,8 +240,8 @@ void dwt97_fwd_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
         if (!o_ex) get(wv, Ol, Oh);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            El[j] = (El[j] + D97 * (Pl[j] + Ol[j])) * K97I;
-            Eh[j] = (Eh[j] + D97 * (Ph[j] + Oh[j])) * K97I;
+            El[j] = (El[j] + lift97(D97, Ol[j], Pl[j], m_up)) * K97I;
+            Eh[j] = (Eh[j] + lift97(D97, Oh[j], Ph[j], m_up)) * K97I;
             Ol[j] = Ol[j] * K97;
             Oh[j] = Oh[j] * K97;
         }

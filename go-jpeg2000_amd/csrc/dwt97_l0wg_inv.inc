@@ -319,6 +319,9 @@ void dwt97_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
     const bool nx = live && t + 1 < halfH && wv < NW - 1;
     const int p0 = active ? lane * 4 : 0;
     const bool last_lane = c + 8 >= w;
+    // float64 coefficients (the unit calls) can make x + x overflow at a mirrored edge: the reference's (2 * c) * x there (lift97); wave-uniform
+    // for the rows: the row read from the slot is this wave's own above the first pair-row / for a missing odd row, and below the last pair-row
+    const bool m_up = CF64 && (t == 0 || !hi_ex), m_dn = CF64 && t + 1 >= halfH;
     auto put = [&](int s, const double (&lo)[4], const double (&hi)[4]) {
         slot[s][0][lane] = (v2d){lo[0], lo[1]}; slot[s][1][lane] = (v2d){lo[2], lo[3]};
         slot[s][2][lane] = (v2d){hi[0], hi[1]}; slot[s][3][lane] = (v2d){hi[2], hi[3]};
@@ -367,8 +370,8 @@ void dwt97_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
         if (!hi_ex) get(up, Dl, Dh);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            Sl[j] = Ll[j] * K97 - D97 * (Rl[j] + Dl[j]);
-            Sh[j] = Lh[j] * K97 - D97 * (Rh[j] + Dh[j]);
+            Sl[j] = Ll[j] * K97 - lift97(D97, Dl[j], Rl[j], m_up);
+            Sh[j] = Lh[j] * K97 - lift97(D97, Dh[j], Rh[j], m_up);
         }
         put(wv, Sl, Sh);
         if (!nx && wv < NW - 1) put(wv + 1, Sl, Sh);
@@ -378,8 +381,8 @@ void dwt97_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
         get(slot[dn], Rl, Rh);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            Dl[j] = Dl[j] - G97 * (Sl[j] + Rl[j]);
-            Dh[j] = Dh[j] - G97 * (Sh[j] + Rh[j]);
+            Dl[j] = Dl[j] - lift97(G97, Sl[j], Rl[j], m_dn);
+            Dh[j] = Dh[j] - lift97(G97, Sh[j], Rh[j], m_dn);
         }
         if (hi_ex && wv < NW - 1) put(wv + 1, Dl, Dh);
         if (t == 0) put(wv, Dl, Dh);
@@ -390,8 +393,8 @@ void dwt97_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
         if (!hi_ex) get(slot[wv], Dl, Dh);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            Sl[j] = Sl[j] - B97 * (Rl[j] + Dl[j]);
-            Sh[j] = Sh[j] - B97 * (Rh[j] + Dh[j]);
+            Sl[j] = Sl[j] - lift97(B97, Dl[j], Rl[j], m_up);
+            Sh[j] = Sh[j] - lift97(B97, Dh[j], Rh[j], m_up);
         }
         put(wv, Sl, Sh);
         if (!nx && wv < NW - 1) put(wv + 1, Sl, Sh);
@@ -401,8 +404,8 @@ void dwt97_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
     get(slot[wv + 1], Rl, Rh);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        Dl[j] = Dl[j] - A97 * (Sl[j] + Rl[j]);
-        Dh[j] = Dh[j] - A97 * (Sh[j] + Rh[j]);
+        Dl[j] = Dl[j] - lift97(A97, Sl[j], Rl[j], m_dn);
+        Dh[j] = Dh[j] - lift97(A97, Sh[j], Rh[j], m_dn);
     }
     // dwt.go:212-262 across the wave (w even, a multiple of 8: the edges are lane 0 and the last lane)
     auto hrow_out = [&](const double (&lo)[4], const double (&hi)[4], int ro) {
@@ -413,26 +416,26 @@ void dwt97_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const double dp = (j > 0) ? d[j - 1] : (lane == 0 ? d[0] : d2_l);
-            s_[j] = lo[j] * K97 - D97 * (dp + d[j]);
+            s_[j] = lo[j] * K97 - lift97(D97, d[j], dp, CF64 && j == 0 && lane == 0);
         }
         const double s1_r = dright(s_[0]);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const double sn = (j < 3) ? s_[j + 1] : (last_lane ? s_[3] : s1_r);
-            d[j] = d[j] - G97 * (s_[j] + sn);
+            d[j] = d[j] - lift97(G97, s_[j], sn, CF64 && j == 3 && last_lane);
         }
         const double d1_l = dleft(d[3]);
         {
             double dp = (lane == 0) ? d[0] : d1_l;
 #pragma unroll
-            for (int j = 0; j < 4; j++) { s_[j] = s_[j] - B97 * (dp + d[j]); dp = d[j]; }
+            for (int j = 0; j < 4; j++) { s_[j] = s_[j] - lift97(B97, d[j], dp, CF64 && j == 0 && lane == 0); dp = d[j]; }
         }
         const double e_r = dright(s_[0]);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const double en = (j < 3) ? s_[j + 1] : (last_lane ? s_[3] : e_r);
             x[2 * j] = s_[j];
-            x[2 * j + 1] = d[j] - A97 * (s_[j] + en);
+            x[2 * j + 1] = d[j] - lift97(A97, s_[j], en, CF64 && j == 3 && last_lane);
         }
         if (active) {
             if constexpr (DSTI32) {

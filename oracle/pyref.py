@@ -14,7 +14,7 @@ points than the C oracle where the reference has two equivalent forms:
   * sign context: computed by the branchy rule (t1.go:387-460), not the LUT.
 
 Go semantics: int32 wraparound via _i32(), uint32 via & M32, Go shifts >= width
-give 0 (Python big ints make that explicit), int32(float64) == math.trunc.
+give 0 (Python big ints make that explicit), int32(float64) == math.trunc inside int32 (outside: _trunc32).
 """
 import math
 
@@ -230,7 +230,12 @@ def reconstruct97(d, w, h, levels): _reconstruct(d, w, h, levels, inverse2d97)
 
 
 def _trunc32(v):
-    return _i32(int(math.trunc(v)))
+    """Go's int32(float64) as amd64 runs it (encoder.go:238-242, 270-275): CVTTSD2SL truncates toward zero and gives the "integer
+    indefinite" 0x80000000 for NaN and for whatever does not fit -- not the low 32 bits of a wider integer, which this function
+    returned until tests/lossy97_cases.py's `outrange` frames set it against the C oracle's go_int32"""
+    if v != v or not (-2147483649.0 < v < 2147483648.0):
+        return -(1 << 31)
+    return int(math.trunc(v))
 
 
 def preprocess(planes, w, h, precision, lossless, num_resolutions, quality=0):  # encoder.go:216-281

@@ -4,7 +4,8 @@ Tolerance (north_star: "within a stated PSNR tolerance for 9-7 lossy"): the kern
 with -ffp-contract=off and follow the reference's operation order, so the bar here is the
 strongest one available: float64 results BIT-IDENTICAL to the oracle (np.array_equal), i.e.
 PSNR = inf between GPU and CPU outputs.  The reference's own tests use 1e-10/1e-9 round-trip
-tolerances (internal/dwt/dwt_test.go:48-79,118-150,275-309) -- also asserted."""
+tolerances (internal/dwt/dwt_test.go:48-79,118-150,275-309) -- also asserted.
+Every kernel form, seam shape and the ends of int32 / float64: tests/test_gpu_lossy97_oracle.py."""
 import numpy as np
 import pytest
 
