@@ -5,7 +5,9 @@ Shapes chosen for the boundaries of that kernel: the level it streams from memor
 leave the deep workgroup 1, 2 or 64 pair-rows and the flat ones none, one or a partial band, odd heights at every level
 (missing odd row, mirrored d), a next-level matrix that ends in the middle of a row (odd ceil(h/2)), two to five levels inside
 the launch, RGB tiles incl. ragged edge tiles, a frame that does not qualify (falls back), full-range int32 input
-(wraparound in both directions)."""
+(wraparound in both directions).
+Each J2K_DEEP / J2K_DEEP_MID / J2K_DEEP_MID_INV / J2K_MEGA setting against the oracle itself, inverses on arbitrary coefficients included:
+tests/test_gpu_lossless53_oracle.py."""
 import os
 
 import numpy as np

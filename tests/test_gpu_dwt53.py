@@ -1,7 +1,8 @@
 """GPU parity: 5-3 DWT / RCT / DC shift kernels (through the C ABI) vs the C oracle.
 Mirrors the reference's own tests: internal/dwt/dwt_test.go:8-46,81-116,152-187,
 internal/mct/mct_test.go:8-39,533-598,681-717 -- plus forward-coefficient equality,
-which the reference never asserts."""
+which the reference never asserts.  Every 5-3 kernel form at the seams of its own job tables, the inverses on
+arbitrary coefficients: tests/test_gpu_lossless53_oracle.py (cases: tests/lossless53_cases.py)."""
 import numpy as np
 import pytest
 

@@ -4,7 +4,8 @@ The general (marching) kernels are checked against the oracle in test_gpu_dwt53.
 boundary of the workgroup form -- strips (widths above 512, a last strip narrower than 512, exactly 512), odd and tiny heights,
 bands that end at / one row before the plane's end, every level count, the prefix / final split of every level, full-range
 int32 input (wraparound), packed Gray16 in and out -- is run with the knob at 0, 4 and 8 and must give identical
-coefficients and identical reconstructions; the 0 setting is also compared with the oracle on the smaller shapes."""
+coefficients and identical reconstructions; the 0 setting is also compared with the oracle on the smaller shapes.
+Each setting against the oracle itself, inverses on arbitrary coefficients included: tests/test_gpu_lossless53_oracle.py."""
 import os
 
 import numpy as np
