@@ -315,9 +315,12 @@ __global__ __launch_bounds__(256) void dwt97_fwd_kernel(const DwtJob *__restrict
 // ================================================================================
 // inverse
 // ================================================================================
-template <int CPL, int NC>
+// DEQ: j2k_plan_set_dequantize -- every int32 coefficient times `step` (dwt.Dequantize, dwt.go:517) right after its conversion, before the
+// K97 / K97I scaling; a value from `prev` was multiplied when the coarser level read it.  A template parameter here: as a kernel argument
+// that is always passed, the two SGPRs of `step` raised the SGPR spills of <2, 3> and <4, 1> (docs/KERNEL_NOTES.md)
+template <int CPL, int NC, bool DEQ>
 __device__ __forceinline__ void inv97_load_row(const void *__restrict__ coef, int coef_f64, const double *__restrict__ prev,
-                                               const DwtPlane &P, int ri, int p0, Row97<CPL, NC> &R) {
+                                               const DwtPlane &P, int ri, int p0, double step, Row97<CPL, NC> &R) {
     constexpr int H = CPL / 2;
     const int halfW = (P.w + 1) >> 1;
     const int nL = halfW - p0, nH = (P.w - halfW) - p0;
@@ -340,7 +343,7 @@ __device__ __forceinline__ void inv97_load_row(const void *__restrict__ coef, in
             } else {
                 const double vp = prev[P.nxt_off[k] + (from_prev ? idx : 0)];
                 const int vc = reinterpret_cast<const int32_t *>(coef)[P.src_off[k] + idx];                // tcd.go:429-431
-                v = from_prev ? vp : (double)vc;
+                v = from_prev ? vp : (DEQ ? (double)vc * step : (double)vc);
             }
             if (!ok) v = 0.0;
             if (is_lo) R.lo[k][jj] = v; else R.hi[k][jj] = v;
@@ -391,10 +394,10 @@ __device__ __forceinline__ void inv97_finish_row(void *__restrict__ dst, const D
     }
 }
 
-template <int CPL, int NC>
+template <int CPL, int NC, bool DEQ>
 __global__ __launch_bounds__(256) void dwt97_inv_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                                                         const void *__restrict__ coef, int coef_f64, const double *__restrict__ prev,
-                                                        void *__restrict__ dst, int dc_shift, int dst_mode, int mct) {
+                                                        void *__restrict__ dst, int dc_shift, int dst_mode, int mct, double step) {
     constexpr int H = CPL / 2;
     constexpr int HL = (H >= 2) ? 1 : 2;
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
@@ -417,7 +420,7 @@ __global__ __launch_bounds__(256) void dwt97_inv_kernel(const DwtJob *__restrict
     if (h < 2) {
         if (q0 == 0) {
             Row r0;
-            inv97_load_row<CPL, NC>(coef, coef_f64, prev, P, 0, p0, r0);
+            inv97_load_row<CPL, NC, DEQ>(coef, coef_f64, prev, P, 0, p0, step, r0);
             inv97_finish_row<CPL, NC>(dst, P, 0, c, owned, dc_shift, dst_mode, mct, r0.lo, r0.hi);
         }
         return;
@@ -439,8 +442,8 @@ __global__ __launch_bounds__(256) void dwt97_inv_kernel(const DwtJob *__restrict
         const bool hi_ex = real && (2 * t + 1 < h);
         Row L, Hh;
         if (real) {   // the high row is clamped into the plane (hi_ex discards it when it does not exist)
-            inv97_load_row<CPL, NC>(coef, coef_f64, prev, P, t, p0, L);
-            inv97_load_row<CPL, NC>(coef, coef_f64, prev, P, halfH + min(t, h - halfH - 1), p0, Hh);
+            inv97_load_row<CPL, NC, DEQ>(coef, coef_f64, prev, P, t, p0, step, L);
+            inv97_load_row<CPL, NC, DEQ>(coef, coef_f64, prev, P, halfH + min(t, h - halfH - 1), p0, step, Hh);
         }
         const bool p1_real = (t >= 1) && (t - 1 < halfH);            // pair t-1 exists
         const bool p1_hi = p1_real && (2 * (t - 1) + 1 < h);
@@ -558,18 +561,18 @@ hipError_t launch_dwt97_fwd(hipStream_t s, const LevelLaunch &L, const void *src
 }
 
 hipError_t launch_dwt97_inv(hipStream_t s, const LevelLaunch &L, const void *coef, int coef_is_f64, const double *prev, void *dst,
-                            int dc_shift, int final_level, int dst_mode, int mct) {
+                            int dc_shift, int final_level, int dst_mode, int mct, double step) {
     (void)final_level;
     if (L.njobs <= 0) return hipSuccess;
     if (L.wg_waves > 0) {      // level 0 of an RGB triple, int32 coefficients -> int32 frame with inverse ICT (dwt97_l0wg_inv.inc)
         if (L.ncomp != 3 || coef_is_f64 || !mct || dst_mode != DST_I32_FRAME) return hipErrorInvalidValue;
 #define J2K_WG97I(NW) hipExtLaunchKernelGGL((dwt97_inv_rgb_wg_kernel<NW, J2K_WG97I_WPE, false>), dim3(L.njobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
                                              L.jobs, L.njobs, L.planes, reinterpret_cast<const int32_t *>(coef), prev,                       \
-                                             reinterpret_cast<int32_t *>(dst), dc_shift, 0, L.guard)
+                                             reinterpret_cast<int32_t *>(dst), dc_shift, 0, L.guard, step)
         if (L.pix_stride > 0) {  // straight to packed RGBA8 pixels (j2k_plan_inverse_pixels on a lossy 8-bit plan): eight waves
             if (L.wg_waves != 8) return hipErrorInvalidValue;
             hipExtLaunchKernelGGL((dwt97_inv_rgb_wg_kernel<8, J2K_WG97I_WPE, true>), dim3(L.njobs), dim3(512), 0, s, L.ev_start, L.ev_stop, 0,
-                                  L.jobs, L.njobs, L.planes, reinterpret_cast<const int32_t *>(coef), prev, reinterpret_cast<int32_t *>(dst), dc_shift, L.pix_stride, L.guard);
+                                  L.jobs, L.njobs, L.planes, reinterpret_cast<const int32_t *>(coef), prev, reinterpret_cast<int32_t *>(dst), dc_shift, L.pix_stride, L.guard, step);
             return hipGetLastError();
         }
         if (L.wg_waves == 6) J2K_WG97I(6);
@@ -582,20 +585,59 @@ hipError_t launch_dwt97_inv(hipStream_t s, const LevelLaunch &L, const void *coe
     }
     if (L.pwaves == 8 && L.pnjobs > 0 && L.ncomp == 1) {   // single planes in workgroup form: a deeper level, level 0 of one int32 component, the float64 unit calls
 #define J2K_PWG97I(CF, DI) hipLaunchKernelGGL((dwt97_inv_plane_wg_kernel<8, 6, CF, DI>), dim3(L.pnjobs), dim3(512), 0, s, L.pjobs, L.pnjobs, L.planes, \
-                                               coef, prev, dst, dc_shift, dst_mode == DST_F64_FRAME ? 1 : 0, dst_mode == DST_I32_FRAME ? L.pix_stride : 0, L.guard)
+                                               coef, prev, dst, dc_shift, dst_mode == DST_F64_FRAME ? 1 : 0, dst_mode == DST_I32_FRAME ? L.pix_stride : 0, L.guard, step)
         if (dst_mode == DST_I32_FRAME) { if (coef_is_f64) J2K_PWG97I(true, true); else J2K_PWG97I(false, true); }
         else { if (coef_is_f64) J2K_PWG97I(true, false); else J2K_PWG97I(false, false); }
 #undef J2K_PWG97I
         return hipGetLastError();
     }
     const int blocks = (L.njobs + 3) / 4;
+    const bool deq = step != 1.0 && !coef_is_f64;
+#define J2K_INV97(CPL, NC) do { \
+        if (deq) hipLaunchKernelGGL((dwt97_inv_kernel<CPL, NC, true>), dim3(blocks), dim3(256), 0, s, L.jobs, L.njobs, L.planes, coef, coef_is_f64, prev, dst, dc_shift, dst_mode, mct, step); \
+        else hipLaunchKernelGGL((dwt97_inv_kernel<CPL, NC, false>), dim3(blocks), dim3(256), 0, s, L.jobs, L.njobs, L.planes, coef, coef_is_f64, prev, dst, dc_shift, dst_mode, mct, step); \
+    } while (0)
     if (L.ncomp == 3) {
-        hipLaunchKernelGGL((dwt97_inv_kernel<2, 3>), dim3(blocks), dim3(256), 0, s, L.jobs, L.njobs, L.planes, coef, coef_is_f64, prev, dst, dc_shift, dst_mode, mct);
+        J2K_INV97(2, 3);
     } else if (L.cpl == 4) {
-        hipLaunchKernelGGL((dwt97_inv_kernel<4, 1>), dim3(blocks), dim3(256), 0, s, L.jobs, L.njobs, L.planes, coef, coef_is_f64, prev, dst, dc_shift, dst_mode, mct);
+        J2K_INV97(4, 1);
     } else {
-        hipLaunchKernelGGL((dwt97_inv_kernel<2, 1>), dim3(blocks), dim3(256), 0, s, L.jobs, L.njobs, L.planes, coef, coef_is_f64, prev, dst, dc_shift, dst_mode, mct);
+        J2K_INV97(2, 1);
     }
+#undef J2K_INV97
+    return hipGetLastError();
+}
+
+// ================================================================================
+// dwt.Quantize / dwt.Dequantize (dwt.go:500-520): the unit calls
+// ================================================================================
+// Not the encoder's quantiser (encoder.go:270-275 divides by the step): the product with invStep = 1.0 / stepSize, formed on the
+// host, then Floor / Ceil before Go's int32().
+__global__ __launch_bounds__(256) void quantize97_kernel(const double *__restrict__ src, size_t n, double inv_step, int32_t *__restrict__ dst) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const double v = src[i];
+        const double q = v * inv_step;
+        dst[i] = v >= 0 ? go_int32(floor(q + 0.5)) : go_int32(ceil(q - 0.5));      // (-0.0 >= 0; NaN takes the Ceil branch)
+    }
+}
+
+__global__ __launch_bounds__(256) void dequantize97_kernel(const int32_t *__restrict__ src, size_t n, double step, double *__restrict__ dst) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = (double)src[i] * step;
+}
+
+hipError_t launch_quantize97(hipStream_t s, const double *src, size_t n, double step, int32_t *dst) {
+    if (!n) return hipSuccess;
+    const int blocks = (int)std::min<size_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(quantize97_kernel, dim3(blocks), dim3(256), 0, s, src, n, 1.0 / step, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_dequantize97(hipStream_t s, const int32_t *src, size_t n, double step, double *dst) {
+    if (!n) return hipSuccess;
+    const int blocks = (int)std::min<size_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(dequantize97_kernel, dim3(blocks), dim3(256), 0, s, src, n, step, dst);
     return hipGetLastError();
 }
 

@@ -26,6 +26,11 @@
 //     one (no real image does) redoes that batch of conversions with go_int32.
 // Sources: elements below n_next of the dense matrix are the coarser level's float64 output (`prev`), the rest int32
 // coefficients; n_next = halfW * halfH is a multiple of halfW, so a half-row is one or the other.
+// step (j2k_plan_set_dequantize): every int32 coefficient is multiplied by it right after its conversion and before the K97 / K97I
+// scaling -- dwt.Dequantize (dwt.go:514-520) in front of ReconstructMultiLevel97 -- at its two loads: half_values(false, ...) and the
+// separate high row above the band that wave 0 parks in xslot.  Values from `prev` were multiplied when the coarser level read them.
+// 1.0 = off (x * 1.0 is exact: tcd.ApplyInverseDWT as written); a kernel argument, not a template parameter, because it costs these
+// kernels two SGPRs and nothing else (docs/KERNEL_NOTES.md, the resource tables).
 // Geometry contract (checked by the plan): int32 coefficients and frame, three components with ICT, every plane
 // 16 <= w <= 512, w % 8 == 0, h >= 2, offsets and strides multiples of 4 elements.
 
@@ -35,7 +40,7 @@ template <int NW, int WPE, bool PIX>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void dwt97_inv_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                              const int32_t *__restrict__ coef, const double *__restrict__ prev, int32_t *__restrict__ dst, int dc_shift, int pix_stride,
-                             const int *__restrict__ guard) {
+                             const int *__restrict__ guard, double step) {
     if (guard && *guard) return;             // (the frame decoder: a stream that was refused leaves the caller's frame alone)
     typedef double v2d __attribute__((ext_vector_type(2)));
     __shared__ v2d slot[NW][4][64];                      // 8 doubles per lane as four 16-byte pieces, lane-contiguous
@@ -86,7 +91,7 @@ void dwt97_inv_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
             for (int j = 0; j < 4; j++) v[j] = __hiloint2double(a[2 * j + 1], a[2 * j]);
         } else {
 #pragma unroll
-            for (int j = 0; j < 4; j++) v[j] = (double)a[j];                                               // tcd.go:429-431
+            for (int j = 0; j < 4; j++) v[j] = (double)a[j] * step;                                        // tcd.go:429-431, dwt.go:517
         }
     };
     if (live) {
@@ -105,8 +110,8 @@ void dwt97_inv_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 const v4i a = Xl[k], b = Xh[k];
-                xslot[k][0][lane] = (v2d){(double)a.x * K97I, (double)a.y * K97I}; xslot[k][1][lane] = (v2d){(double)a.z * K97I, (double)a.w * K97I};
-                xslot[k][2][lane] = (v2d){(double)b.x * K97I, (double)b.y * K97I}; xslot[k][3][lane] = (v2d){(double)b.z * K97I, (double)b.w * K97I};
+                xslot[k][0][lane] = (v2d){(double)a.x * step * K97I, (double)a.y * step * K97I}; xslot[k][1][lane] = (v2d){(double)a.z * step * K97I, (double)a.w * step * K97I};
+                xslot[k][2][lane] = (v2d){(double)b.x * step * K97I, (double)b.y * step * K97I}; xslot[k][3][lane] = (v2d){(double)b.z * step * K97I, (double)b.w * step * K97I};
             }
         }
     }
@@ -292,12 +297,12 @@ void dwt97_inv_rgb_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
 // component means 60-odd VGPRs and seven waves per SIMD; planes narrower than 512 columns use the first w / 8 lanes.
 // Round 4: CF64 -- the coefficients are float64 (the unit calls dwt.Inverse2D97 / ReconstructMultiLevel97, dwt.go:453-473, 561-573);
 // DSTI32 -- level 0 of ONE component of an int32 frame: int32(v + 0.5) (tcd.go:433-435) and the DC shift (mct.go:113-118) at the
-// store, rows out_stride apart.
+// store, rows out_stride apart.  step: as above, in load_half's int32 branch only (CF64 has no quantiser and is passed 1.0).
 template <int NW, int WPE, bool CF64, bool DSTI32>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void dwt97_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                                const void *__restrict__ coef_, const double *__restrict__ prev, void *__restrict__ dst_, int dc_shift, int frame_rows, int pix_stride,
-                               const int *__restrict__ guard) {
+                               const int *__restrict__ guard, double step) {
     if (guard && *guard) return;             // (the frame decoder: a stream that was refused leaves the caller's frame alone)
     const int32_t *coef = reinterpret_cast<const int32_t *>(coef_);
     const double *coeff = reinterpret_cast<const double *>(coef_);
@@ -341,7 +346,7 @@ void dwt97_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
             v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
         } else {
             const v4i a = *reinterpret_cast<const v4i *>(coef + P.src_off[0] + idx + p0);
-            v[0] = (double)a.x; v[1] = (double)a.y; v[2] = (double)a.z; v[3] = (double)a.w;
+            v[0] = (double)a.x * step; v[1] = (double)a.y * step; v[2] = (double)a.z * step; v[3] = (double)a.w * step;   // dwt.go:517
         }
     };
     double Dl[4], Dh[4], Sl[4], Sh[4], Rl[4], Rh[4], Ll[4], Lh[4];

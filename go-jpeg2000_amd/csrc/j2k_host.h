@@ -23,7 +23,9 @@ hipError_t launch_ict(hipStream_t s, double *a, double *b, double *c, size_t n, 
 hipError_t launch_dwt97_fwd(hipStream_t s, const LevelLaunch &L, const void *src, int src_is_f64, int32_t *out_i32,
                             double *out_f64, double *nxt, int dc_shift, int quant, double step, int mct);
 hipError_t launch_dwt97_inv(hipStream_t s, const LevelLaunch &L, const void *coef, int coef_is_f64, const double *prev,
-                            void *dst, int dc_shift, int final_level, int dst_mode, int mct);
+                            void *dst, int dc_shift, int final_level, int dst_mode, int mct, double step);
+hipError_t launch_quantize97(hipStream_t s, const double *src, size_t n, double step, int32_t *dst);
+hipError_t launch_dequantize97(hipStream_t s, const int32_t *src, size_t n, double step, double *dst);
 hipError_t launch_ht_encode(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots,
                             uint32_t *lens, uint8_t *numbps, int *fault, uint32_t *maglens = nullptr, const HtUJob *utab = nullptr, int nunique = 0,
                             const int *alias_ids = nullptr);

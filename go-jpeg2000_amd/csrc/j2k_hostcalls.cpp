@@ -75,6 +75,36 @@ extern "C" int j2k_tcd_apply_inverse_dwt(j2k_ctx *c, int32_t *d, int w, int h, i
     return host_dwt(c, d, w, h, levels, W97, true, Q_TCD, false);
 }
 
+// ---- dwt.Quantize / dwt.Dequantize (dwt.go:500-520): slot 0 in, slot 1 out --------------------------
+extern "C" int j2k_quantize(j2k_ctx *ctx, const double *src, size_t n, double step_size, int32_t *dst) {
+    if (!ctx) return J2K_ERR_INVALID_ARG;
+    if (n == 0) return J2K_OK;
+    if (!src || !dst) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_quantize: NULL buffer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int r = stage_reserve(ctx, 0, n * 8);
+    if (r == J2K_OK) r = stage_reserve(ctx, 1, n * 4);
+    if (r != J2K_OK) return r;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->stage[0], src, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, launch_quantize97(ctx->stream, (const double *)ctx->stage[0], n, step_size, (int32_t *)ctx->stage[1]));
+    HIPCHK(ctx, hipMemcpyAsync(dst, ctx->stage[1], n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return J2K_OK;
+}
+extern "C" int j2k_dequantize(j2k_ctx *ctx, const int32_t *src, size_t n, double step_size, double *dst) {
+    if (!ctx) return J2K_ERR_INVALID_ARG;
+    if (n == 0) return J2K_OK;
+    if (!src || !dst) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_dequantize: NULL buffer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int r = stage_reserve(ctx, 0, n * 4);
+    if (r == J2K_OK) r = stage_reserve(ctx, 1, n * 8);
+    if (r != J2K_OK) return r;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->stage[0], src, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, launch_dequantize97(ctx->stream, (const int32_t *)ctx->stage[0], n, step_size, (double *)ctx->stage[1]));
+    HIPCHK(ctx, hipMemcpyAsync(dst, ctx->stage[1], n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return J2K_OK;
+}
+
 // ---- mct ------------------------------------------------------------------------
 static int host_elementwise3(j2k_ctx *ctx, void *a, void *b, void *c, size_t n, size_t esz, int op, int arg) {
     if (!ctx) return J2K_ERR_INVALID_ARG;

@@ -217,4 +217,5 @@ struct j2k_plan {
     uint64_t *d_bigsym_off = nullptr;       // MQ plans with blocks above 64 x 64: where each job's symbol list starts (bytes; n + 1 entries), built at the first encode
     size_t bigsym_total = 0;
     bool dec_coded_rows_only = false;       // j2k_plan_set_decode_coded_rows_only: HT decode leaves the rows the reference's decoder never writes alone
+    bool dequantize = false;                // j2k_plan_set_dequantize: the 9-7 inverse kernels multiply every int32 coefficient by 1.0 / Quality at their load (dwt.go:514-520)
 };

@@ -110,6 +110,8 @@ int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix
     const PlanSpec &S = P->spec;
     if (((uintptr_t)d_frame & 15) || ((uintptr_t)d_coeff & 15)) return fail(ctx, J2K_ERR_INVALID_ARG, "device pointers must be 16-byte aligned");
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    // j2k_plan_set_dequantize: dwt.Dequantize's factor, the double the forward path divides by (encoder.go:269); 1.0 = tcd.ApplyInverseDWT as written
+    const double dq_step = (P->dequantize && S.quant == Q_ENCODER) ? 1.0 / (double)S.quality : 1.0;
     // (a guarded call keeps level 0 -- the launch that writes the frame -- apart from the deep levels: same results)
     const bool mega = P->d_mega_inv_jobs && pix.triple == 8 && pix_stride > 0 && ctx->l0_wg_inv && S.wavelet == W53 && !guard;
     for (int rep_ = 0; mega && rep_ < dev_reps(0x100); rep_++) {
@@ -164,7 +166,7 @@ int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix
                     if (pix.triple == 97) L97.pix_stride = pix.stride;           // packed RGBA8 frame (j2k_plan_inverse_pixels)
                 }
                 HIPCHK(ctx, launch_dwt97_inv(ctx->stream, L97, d_coeff, S.quant == Q_NONE ? 1 : 0, (const double *)prev, dst,
-                                             l == 0 ? S.dc_shift_inv : 0, l == 0, dst_mode, (cls == 1) ? 1 : 0));
+                                             l == 0 ? S.dc_shift_inv : 0, l == 0, dst_mode, (cls == 1) ? 1 : 0, dq_step));
             }
         }
     }
@@ -755,6 +757,13 @@ extern "C" int j2k_plan_compact(j2k_plan *P, const uint8_t *d_slots, const uint3
 extern "C" int j2k_plan_set_decode_coded_rows_only(j2k_plan *P, int on) {
     if (!P) return J2K_ERR_INVALID_ARG;
     P->dec_coded_rows_only = on != 0;
+    return J2K_OK;
+}
+
+extern "C" int j2k_plan_set_dequantize(j2k_plan *P, int on) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    if (P->spec.wavelet != W97 || P->spec.quant != Q_ENCODER) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_set_dequantize: a lossy plan only");
+    P->dequantize = on != 0;
     return J2K_OK;
 }
 

@@ -45,7 +45,7 @@ def _stage(fn):
 class FramePlan:
     def __init__(self, width, height, ncomp, precision=8, lossless=True, quality=0, num_resolutions=6,
                  cb=(64, 64), tile=(0, 0), coder=_lib.CODER_MQ, is_signed=False, tile_first=0, tile_count=0,
-                 ctx=None, track_streams=True, frame_rows=0, closed_loop=False):
+                 ctx=None, track_streams=True, frame_rows=0, closed_loop=False, dequantize=False):
         self.ctx = ctx or default_context()
         self.track_streams = bool(track_streams)
         self._ext_stream = None
@@ -66,6 +66,8 @@ class FramePlan:
         self.device = "cuda:%d" % self.ctx.device
         from .context import register_plan
         register_plan(self)                     # closed by the package's atexit hook if the caller never does
+        if dequantize:
+            self.set_dequantize(True)
 
     def close(self):
         if getattr(self, "h", None):
@@ -171,6 +173,12 @@ class FramePlan:
         """HT coder: decode_blocks leaves the rows the reference's decoder never writes (y % 4 != 0) untouched -- the pooled
         HTDecoder's behaviour; the caller owns a buffer it zeroed once (j2k_plan_set_decode_coded_rows_only)."""
         self.ctx.check(self.ctx.L.j2k_plan_set_decode_coded_rows_only(self.h, int(bool(on))))
+
+    def set_dequantize(self, on=True):
+        """lossy plans: inverse / inverse_rgba8 / inverse_pixels / decode_frame_pixels / decode_pixels_host multiply every int32
+        coefficient by 1.0 / Quality first (dwt.Dequantize, fused into the inverse kernels' loads), so that a lossy frame decodes
+        to the picture; off (the default) is tcd.ApplyInverseDWT as the reference wrote it (j2k_plan_set_dequantize)."""
+        self.ctx.check(self.ctx.L.j2k_plan_set_dequantize(self.h, int(bool(on))))
 
     @_stage
     def forward_pixels(self, fmt, pix, coeff=None):

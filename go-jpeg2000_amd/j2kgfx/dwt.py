@@ -2,6 +2,8 @@
 Go slice; it is transformed in place.  `length`/`width`/`height` as in the reference."""
 import ctypes as C
 
+import numpy as np
+
 from .context import default_context
 from .mct import _f64, _i32
 
@@ -49,6 +51,23 @@ def Forward2D97(data, width, height, ctx=None):          # dwt.go:432-451
 def Inverse2D97(data, width, height, ctx=None):          # dwt.go:454-473
     ctx = ctx or default_context(); _need(data, width * height)
     ctx.check(ctx.L.j2k_inverse2d97(ctx.h, _f64(data), int(width), int(height)))
+
+
+def quantize(data, step_size, ctx=None):                 # dwt.go:500-511 (returns a new []int32; not the encoder's quantiser)
+    ctx = ctx or default_context()
+    out = np.zeros(data.size, np.int32)
+    ctx.check(ctx.L.j2k_quantize(ctx.h, _f64(data), data.size, float(step_size), _i32(out)))
+    return out
+
+
+def dequantize(data, step_size, ctx=None):               # dwt.go:514-520 (returns a new []float64)
+    ctx = ctx or default_context()
+    out = np.zeros(data.size, np.float64)
+    ctx.check(ctx.L.j2k_dequantize(ctx.h, _i32(data), data.size, float(step_size), _f64(out)))
+    return out
+
+
+Quantize, Dequantize = quantize, dequantize
 
 
 def DecomposeMultiLevel53(data, width, height, levels, ctx=None):     # dwt.go:524-531

@@ -119,6 +119,12 @@ int j2k_reconstruct_multilevel53(j2k_ctx *ctx, int32_t *data, int width, int hei
 int j2k_decompose_multilevel97(j2k_ctx *ctx, double *data, int width, int height, int levels);
 int j2k_reconstruct_multilevel97(j2k_ctx *ctx, double *data, int width, int height, int levels);
 
+/* dwt.Quantize (dwt.go:500-511): invStep = 1.0 / step_size, then int32(math.Floor(v*invStep + 0.5)) for v >= 0 (-0.0 included),
+ * int32(math.Ceil(v*invStep - 0.5)) otherwise; int32() as Go converts (out of range and NaN: 0x80000000).  NOT the encoder's
+ * quantiser (encoder.go:270-275 divides and truncates).  dwt.Dequantize (dwt.go:514-520): float64(v) * step_size.  n == 0: no-op. */
+int j2k_quantize(j2k_ctx *ctx, const double *src, size_t n, double step_size, int32_t *dst);
+int j2k_dequantize(j2k_ctx *ctx, const int32_t *src, size_t n, double step_size, double *dst);
+
 /* tcd.TileEncoder.ApplyForwardDWT / TileDecoder.ApplyInverseDWT on one
  * tile-component (internal/tcd/tcd.go:508-534, 416-437): reversible -> 5-3 int32;
  * else int32->f64, 9-7, int32(v +- 0.5) forward / int32(v + 0.5) inverse. */
@@ -266,6 +272,11 @@ int j2k_plan_decode_blocks(j2k_plan *plan, const uint8_t *d_stream, const uint64
  * buffer once, or does not read them), the coded rows are written in full as before.  Three quarters of the decoder's
  * store stream (77 of 103 MB per 4K frame) disappear. */
 int j2k_plan_set_decode_coded_rows_only(j2k_plan *plan, int on);
+/* Lossy plans (lossless = 0) only; J2K_ERR_UNSUPPORTED otherwise.  Default off: tcd.ApplyInverseDWT as the reference
+ * wrote it.  On: the inverse path multiplies every int32 coefficient by 1.0 / Quality first (dwt.Dequantize, dwt.go:514-520),
+ * fused into the load of the inverse kernels.  Applies to every later call on the plan, and to what is captured into a
+ * graph from then on; a graph captured earlier keeps the setting it was captured with. */
+int j2k_plan_set_dequantize(j2k_plan *plan, int on);
 /* job j's offset (in int32 elements) into d_decoded */
 int j2k_plan_get_decoded_offsets(const j2k_plan *plan, uint64_t *offs, size_t cap);
 
