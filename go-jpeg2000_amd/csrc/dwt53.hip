@@ -292,7 +292,11 @@ __device__ __forceinline__ void fwd_load_row_thin(const int32_t *__restrict__ sr
     for (int k = 0; k < NC; k++) hfwd<CPL, true>(X.x[k], c, P.w, R.lo[k], R.hi[k]);
 }
 
-template <int CPL, int NC, bool VEC>
+// MAL (Mallat plans, j2k_params.closed_loop = 2): the level ran on the rectangle [0, w) x [0, h) of the plane, so a sample keeps its row and
+// column there -- the coefficient plane's row stride is the PLANE's width (coef_stride), not w -- and only LL, the low half of the rows
+// above h_{l+1}, goes on to the dense w_{l+1} x h_{l+1} scratch of the next level.  The low and the high half of a lane are stored apart, so
+// no run straddles column w_{l+1}; VEC needs coef_stride % 4 == 0 on top of the prefix rules (the plan builder's check).
+template <int CPL, int NC, bool VEC, bool MAL = false>
 __device__ __forceinline__ void fwd_store_row(int32_t *__restrict__ out, int32_t *__restrict__ nxt, const DwtPlane &P, int ro,
                                               int p0, bool owned, const int (&lo)[NC][CPL / 2], const int (&hi)[NC][CPL / 2]) {
     constexpr int H = CPL / 2;
@@ -300,6 +304,27 @@ __device__ __forceinline__ void fwd_store_row(int32_t *__restrict__ out, int32_t
     const int halfW = (P.w + 1) >> 1;
     const int nL = halfW - p0;             // valid low columns from p0
     const int nH = (P.w - halfW) - p0;     // valid high columns from p0
+    if constexpr (MAL) {
+        const bool to_nxt = P.n_next != 0 && ro < ((P.h + 1) >> 1);
+        const int64_t oL = to_nxt ? (int64_t)ro * halfW + p0 : (int64_t)ro * P.coef_stride + p0;
+        const int64_t oH = (int64_t)ro * P.coef_stride + halfW + p0;
+#pragma unroll
+        for (int k = 0; k < NC; k++) {
+            int32_t *bl = (to_nxt ? nxt + P.nxt_off[k] : out + P.out_off[k]) + oL;
+            int32_t *bh = out + P.out_off[k] + oH;
+            if constexpr (VEC) {
+                store_half<H, true>(bl, lo[k], nL, !to_nxt);
+                store_half<H, true>(bh, hi[k], nH, true);
+            } else {
+#pragma unroll
+                for (int j = 0; j < H; j++) {
+                    if (j < nL) bl[j] = lo[k][j];
+                    if (j < nH) bh[j] = hi[k][j];
+                }
+            }
+        }
+        return;
+    }
     const int idxL = ro * P.w + p0;
     const int idxH = idxL + halfW;
 #pragma unroll
@@ -326,7 +351,7 @@ __device__ __forceinline__ void fwd_store_row(int32_t *__restrict__ out, int32_t
 }
 
 // w < 2 or h < 2: one of the two passes is the identity.  Rare (deepest levels of tiny planes); kept simple.
-template <int CPL, int NC, bool VEC>
+template <int CPL, int NC, bool VEC, bool MAL = false>
 __device__ __forceinline__ void fwd_job_thin(const DwtJob &job, const DwtPlane &P, const int32_t *__restrict__ src,
                                           int32_t *__restrict__ out, int32_t *__restrict__ nxt, int dc_shift, int c, int p0,
                                           bool owned, int64_t pix0, int pix_stride) {
@@ -338,7 +363,7 @@ __device__ __forceinline__ void fwd_job_thin(const DwtJob &job, const DwtPlane &
     int dvp_lo[NC][H], dvp_hi[NC][H];
     fwd_load_row_thin<CPL, NC, VEC>(src, P, 2 * job.prow0, c, dc_shift, ye, pix0, pix_stride);
     if (h < 2) {
-        if (job.prow0 == 0) fwd_store_row<CPL, NC, VEC>(out, nxt, P, 0, p0, owned, ye.lo, ye.hi);
+        if (job.prow0 == 0) fwd_store_row<CPL, NC, VEC, MAL>(out, nxt, P, 0, p0, owned, ye.lo, ye.hi);
         return;
     }
     if (job.prow0 > 0) {
@@ -376,8 +401,8 @@ __device__ __forceinline__ void fwd_job_thin(const DwtJob &job, const DwtPlane &
                 dv_lo[k][j] = dl;
                 dv_hi[k][j] = dh;
             }
-        fwd_store_row<CPL, NC, VEC>(out, nxt, P, pr, p0, owned, sv_lo, sv_hi);
-        if (has_odd) fwd_store_row<CPL, NC, VEC>(out, nxt, P, halfH + pr, p0, owned, dv_lo, dv_hi);
+        fwd_store_row<CPL, NC, VEC, MAL>(out, nxt, P, pr, p0, owned, sv_lo, sv_hi);
+        if (has_odd) fwd_store_row<CPL, NC, VEC, MAL>(out, nxt, P, halfH + pr, p0, owned, dv_lo, dv_hi);
 #pragma unroll
         for (int k = 0; k < NC; k++)
 #pragma unroll
@@ -405,7 +430,7 @@ __device__ __forceinline__ void fwd_job_thin(const DwtJob &job, const DwtPlane &
 // three rows per WORKGROUP (not per wavefront).
 // PF: the loads of pair-row q+1 are issued before the vertical lifting and the stores of pair-row q (software
 // pipelining, one pair-row deep; costs CPL*NC*2 more live registers)
-template <int CPL, int NC, bool VEC, bool PF, bool PIX>
+template <int CPL, int NC, bool VEC, bool PF, bool PIX, bool MAL = false>
 __global__ __launch_bounds__(256) J2K_FWD_ATTR void dwt53_fwd_kernel(const DwtJob *__restrict__ jobs, int njobs,
                                                                      const DwtPlane *__restrict__ planes,
                                                                      const int32_t *__restrict__ src, int32_t *__restrict__ out,
@@ -439,7 +464,7 @@ __global__ __launch_bounds__(256) J2K_FWD_ATTR void dwt53_fwd_kernel(const DwtJo
         pix0 = y0 * pix_stride + (P.src_off[0] - y0 * P.src_stride);
     }
     if (w < 2 || h < 2) {            // never linked
-        fwd_job_thin<CPL, NC, VEC>(job, P, src, out, nxt, dc_shift, c, p0, owned, pix0, PIX ? pix_stride : 0);
+        fwd_job_thin<CPL, NC, VEC, MAL>(job, P, src, out, nxt, dc_shift, c, p0, owned, pix0, PIX ? pix_stride : 0);
         __syncthreads();
         return;
     }
@@ -538,9 +563,9 @@ __global__ __launch_bounds__(256) J2K_FWD_ATTR void dwt53_fwd_kernel(const DwtJo
                     pub_mine[((NC + k) * CPL + H + j) * 64] = dv_hi[k][j];
                 }
         } else {
-            fwd_store_row<CPL, NC, VEC>(out, nxt, P, pr, p0, owned, sv_lo, sv_hi);
+            fwd_store_row<CPL, NC, VEC, MAL>(out, nxt, P, pr, p0, owned, sv_lo, sv_hi);
         }
-        if (has_odd) fwd_store_row<CPL, NC, VEC>(out, nxt, P, halfH + pr, p0, owned, dv_lo, dv_hi);
+        if (has_odd) fwd_store_row<CPL, NC, VEC, MAL>(out, nxt, P, halfH + pr, p0, owned, dv_lo, dv_hi);
 #pragma unroll
         for (int k = 0; k < NC; k++)
 #pragma unroll
@@ -562,7 +587,7 @@ __global__ __launch_bounds__(256) J2K_FWD_ATTR void dwt53_fwd_kernel(const DwtJo
                 sv_lo[k][j] = wadd(ye.lo[k][j], avg2(dvp_lo[k][j], dl));
                 sv_hi[k][j] = wadd(ye.hi[k][j], avg2(dvp_hi[k][j], dh));
             }
-        fwd_store_row<CPL, NC, VEC>(out, nxt, P, pr_end, p0, owned, sv_lo, sv_hi);
+        fwd_store_row<CPL, NC, VEC, MAL>(out, nxt, P, pr_end, p0, owned, sv_lo, sv_hi);
     }
 }
 
@@ -572,12 +597,43 @@ __global__ __launch_bounds__(256) J2K_FWD_ATTR void dwt53_fwd_kernel(const DwtJo
 // Input row `ri` of the level matrix, columns [p0,p0+H) of the L part and of the H part,
 // each element taken from `prev` (output of the coarser inverse level) when its linear
 // index is below n_next, else from the coefficient plane.
-template <int CPL, int NC, bool VEC>
+template <int CPL, int NC, bool VEC, bool MAL = false>
 __device__ __forceinline__ void inv_load_row(const int32_t *__restrict__ coef, const int32_t *__restrict__ prev,
                                              const DwtPlane &P, int ri, int p0, int c, FwdRow<CPL, NC, VEC> &R) {
     constexpr int H = CPL / 2;
     const int halfW = (P.w + 1) >> 1;
     const int nL = halfW - p0, nH = (P.w - halfW) - p0;
+    if constexpr (MAL) {       // the routing of fwd_store_row<MAL>, read back: LL from the coarser level's dense result, the rest from its place in the plane
+        const bool from_prev = P.n_next != 0 && ri < ((P.h + 1) >> 1);
+        const bool in = c < P.w;
+        const int64_t oL = !in ? 0 : (from_prev ? (int64_t)ri * halfW + p0 : (int64_t)ri * P.coef_stride + p0);
+        const int64_t oH = !in ? 0 : (int64_t)ri * P.coef_stride + halfW + p0;
+#pragma unroll
+        for (int k = 0; k < NC; k++) {
+            const int32_t *bl = (from_prev ? prev + P.nxt_off[k] : coef + P.src_off[k]) + oL;
+            const int32_t *bh = coef + P.src_off[k] + oH;
+            if constexpr (VEC) {       // clamped to element 0 past the row end: always a valid address, no branch
+                if constexpr (H == 4) {
+                    int4 a = *reinterpret_cast<const int4 *>(bl), b = *reinterpret_cast<const int4 *>(bh);
+                    R.lo[k][0] = in ? a.x : 0; R.lo[k][1] = in ? a.y : 0; R.lo[k][2] = in ? a.z : 0; R.lo[k][3] = in ? a.w : 0;
+                    R.hi[k][0] = in ? b.x : 0; R.hi[k][1] = in ? b.y : 0; R.hi[k][2] = in ? b.z : 0; R.hi[k][3] = in ? b.w : 0;
+                } else if constexpr (H == 2) {
+                    int2 a = *reinterpret_cast<const int2 *>(bl), b = *reinterpret_cast<const int2 *>(bh);
+                    R.lo[k][0] = in ? a.x : 0; R.lo[k][1] = in ? a.y : 0; R.hi[k][0] = in ? b.x : 0; R.hi[k][1] = in ? b.y : 0;
+                } else {
+                    const int a = bl[0], b = bh[0];
+                    R.lo[k][0] = in ? a : 0; R.hi[k][0] = in ? b : 0;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < H; j++) {
+                    R.lo[k][j] = (in && j < nL) ? bl[j] : 0;
+                    R.hi[k][j] = (in && j < nH) ? bh[j] : 0;
+                }
+            }
+        }
+        return;
+    }
     const int idxL = ri * P.w + p0, idxH = idxL + halfW;
 #pragma unroll
     for (int k = 0; k < NC; k++) {
@@ -715,7 +771,7 @@ __device__ __forceinline__ void inv_compute_xe(int q, int nhigh, const FwdRow<CP
 // s and d rows of its own pair-rows plus d[q0-1] above and s[q1], d[q1] below.  The two rows below are the FIRST rows
 // the band below loads, so a band with J2K_LINK_UP publishes them to LDS and a band with J2K_LINK_DOWN takes them from
 // there at its last pair-row; only d[q0-1] is still read twice (one halo row per band instead of three).
-template <int CPL, int NC, bool VEC, bool PIX>
+template <int CPL, int NC, bool VEC, bool PIX, bool MAL = false>
 __global__ __launch_bounds__(256) void dwt53_inv_kernel(const DwtJob *__restrict__ jobs, int njobs,
                                                         const DwtPlane *__restrict__ planes,
                                                         const int32_t *__restrict__ coef, const int32_t *__restrict__ prev,
@@ -761,7 +817,7 @@ __global__ __launch_bounds__(256) void dwt53_inv_kernel(const DwtJob *__restrict
     if (h < 2) {  // columns untouched; never linked
         if (pr_begin == 0) {
             Row s0;
-            inv_load_row<CPL, NC, VEC>(coef, prev, P, 0, p0, c, s0);
+            inv_load_row<CPL, NC, VEC, MAL>(coef, prev, P, 0, p0, c, s0);
             inv_finish_row<CPL, NC, VEC, PIX>(dst, P, 0, c, owned, s0.lo, s0.hi, dc_shift, fin, pix0, pix_stride);
         }
         __syncthreads();
@@ -774,9 +830,9 @@ __global__ __launch_bounds__(256) void dwt53_inv_kernel(const DwtJob *__restrict
     // only ever combined into values the has_d / has_next selects discard.
     Row s, dcur, dprev;
     int xe_lo[NC][H], xe_hi[NC][H];
-    inv_load_row<CPL, NC, VEC>(coef, prev, P, pr_begin, p0, c, s);
-    inv_load_row<CPL, NC, VEC>(coef, prev, P, halfH + min(pr_begin, nhigh - 1), p0, c, dcur);
-    inv_load_row<CPL, NC, VEC>(coef, prev, P, halfH + max(pr_begin - 1, 0), p0, c, dprev);
+    inv_load_row<CPL, NC, VEC, MAL>(coef, prev, P, pr_begin, p0, c, s);
+    inv_load_row<CPL, NC, VEC, MAL>(coef, prev, P, halfH + min(pr_begin, nhigh - 1), p0, c, dcur);
+    inv_load_row<CPL, NC, VEC, MAL>(coef, prev, P, halfH + max(pr_begin - 1, 0), p0, c, dprev);
     if (link_up) {
 #pragma unroll
         for (int k = 0; k < NC; k++)
@@ -806,8 +862,8 @@ __global__ __launch_bounds__(256) void dwt53_inv_kernel(const DwtJob *__restrict
                     dn.hi[k][j] = pub_below[((NC + k) * CPL + H + j) * 64];
                 }
         } else {
-            inv_load_row<CPL, NC, VEC>(coef, prev, P, min(q + 1, halfH - 1), p0, c, sn);
-            inv_load_row<CPL, NC, VEC>(coef, prev, P, halfH + min(q + 1, nhigh - 1), p0, c, dn);
+            inv_load_row<CPL, NC, VEC, MAL>(coef, prev, P, min(q + 1, halfH - 1), p0, c, sn);
+            inv_load_row<CPL, NC, VEC, MAL>(coef, prev, P, halfH + min(q + 1, nhigh - 1), p0, c, dn);
         }
         inv_compute_xe<CPL, NC, VEC>(q + 1, nhigh, sn, dcur, dn, xn_lo, xn_hi);   // unused when !has_next
         inv_finish_row<CPL, NC, VEC, PIX>(dst, P, 2 * q, c, owned, xe_lo, xe_hi, dc_shift, fin, pix0, pix_stride);
@@ -1278,6 +1334,11 @@ static hipError_t fwd_go(hipStream_t s, const LevelLaunch &L, const int32_t *src
         }
     }
     if (L.pix_stride > 0) return hipErrorInvalidValue;
+    if (L.mallat) {           // a Mallat plan's level: its own instantiation, the prefix kernels are untouched
+        hipExtLaunchKernelGGL((dwt53_fwd_kernel<CPL, NC, VEC, false, false, true>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0,
+                              L.jobs, L.njobs, L.planes, src, out, nxt, dc, 0);
+        return hipGetLastError();
+    }
     if (L.pf) hipExtLaunchKernelGGL((dwt53_fwd_kernel<CPL, NC, VEC, true, false>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0,
                                     L.jobs, L.njobs, L.planes, src, out, nxt, dc, 0);
     else hipExtLaunchKernelGGL((dwt53_fwd_kernel<CPL, NC, VEC, false, false>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0,
@@ -1294,6 +1355,10 @@ static hipError_t inv_go(hipStream_t s, const LevelLaunch &L, const int32_t *coe
         }
     }
     if (L.pix_stride > 0) return hipErrorInvalidValue;
+    if (L.mallat) {
+        hipExtLaunchKernelGGL((dwt53_inv_kernel<CPL, NC, VEC, false, true>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0, L.jobs, L.njobs, L.planes, coef, prev, dst, dc, fin, 0, L.guard);
+        return hipGetLastError();
+    }
     hipExtLaunchKernelGGL((dwt53_inv_kernel<CPL, NC, VEC, false>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0, L.jobs, L.njobs, L.planes, coef, prev, dst, dc, fin, 0, L.guard);
     return hipGetLastError();
 }
@@ -1316,6 +1381,7 @@ static hipError_t inv_go(hipStream_t s, const LevelLaunch &L, const int32_t *coe
     } while (0)
 
 hipError_t launch_dwt53_fwd(hipStream_t s, const LevelLaunch &L, const int32_t *src, int32_t *out, int32_t *nxt, int dc_shift) {
+    if (L.mallat && (L.wg_waves > 0 || L.pnjobs > 0 || L.pix_stride > 0)) return hipErrorInvalidValue;   // Mallat plans have the general kernels only
     if (L.wg_waves > 0) {      // packed RGBA8 level 0, workgroup form (dwt53_l0pix.inc); geometry checked by the plan
         if (L.njobs <= 0 && L.njobs2 <= 0) return hipSuccess;
         if (L.pix_stride <= 0 || L.ncomp != 3) return hipErrorInvalidValue;
@@ -1349,6 +1415,7 @@ hipError_t launch_dwt53_fwd(hipStream_t s, const LevelLaunch &L, const int32_t *
 }
 hipError_t launch_dwt53_inv(hipStream_t s, const LevelLaunch &L, const int32_t *coef, const int32_t *prev, int32_t *dst,
                             int dc_shift, int final_level) {
+    if (L.mallat && (L.wg_waves > 0 || L.pnjobs > 0 || L.pix_stride > 0)) return hipErrorInvalidValue;
     if (L.wg_waves > 0) {      // level 0 straight to a packed RGBA8 frame, workgroup form (dwt53_l0pix.inc)
         if (L.njobs <= 0) return hipSuccess;
         if (L.pix_stride <= 0 || L.ncomp != 3 || !final_level) return hipErrorInvalidValue;

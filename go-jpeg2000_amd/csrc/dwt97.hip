@@ -197,7 +197,8 @@ __device__ __forceinline__ void fwd97_load_row(const void *__restrict__ src, int
     for (int k = 0; k < NC; k++) hfwd97<CPL>(x[k], c, P.w, R.lo[k], R.hi[k]);
 }
 
-template <int CPL, int NC>
+// MAL: a level of a Mallat plan -- the routing of dwt53.hip's fwd_store_row<MAL> (DwtPlane::coef_stride)
+template <int CPL, int NC, bool MAL = false>
 __device__ __forceinline__ void fwd97_store_row(int32_t *__restrict__ out_i32, double *__restrict__ out_f64, double *__restrict__ nxt,
                                                 const DwtPlane &P, int ro, int p0, bool owned, int quant, double step,
                                                 const double (&lo)[NC][CPL / 2], const double (&hi)[NC][CPL / 2]) {
@@ -205,6 +206,24 @@ __device__ __forceinline__ void fwd97_store_row(int32_t *__restrict__ out_i32, d
     if (!owned) return;
     const int halfW = (P.w + 1) >> 1;
     const int nL = halfW - p0, nH = (P.w - halfW) - p0;
+    if constexpr (MAL) {
+        const bool ll = P.n_next != 0 && ro < ((P.h + 1) >> 1);       // this row's low half is LL: the next level's input
+#pragma unroll
+        for (int k = 0; k < NC; k++)
+#pragma unroll
+            for (int j = 0; j < 2 * H; j++) {
+                const bool is_lo = j < H;
+                const int jj = is_lo ? j : j - H;
+                if (jj >= (is_lo ? nL : nH)) continue;
+                const double v = is_lo ? lo[k][jj] : hi[k][jj];
+                const int64_t idx = (int64_t)ro * P.coef_stride + (is_lo ? 0 : halfW) + p0 + jj;
+                if (is_lo && ll) nxt[P.nxt_off[k] + (int64_t)ro * halfW + p0 + jj] = v;
+                else if (quant == Q_NONE_) out_f64[P.out_off[k] + idx] = v;
+                else if (quant == Q_ENCODER_) out_i32[P.out_off[k] + idx] = v >= 0 ? go_int32(v / step + 0.5) : go_int32(v / step - 0.5);
+                else out_i32[P.out_off[k] + idx] = round_half_away(v);
+            }
+        return;
+    }
     const int idxL = ro * P.w + p0, idxH = idxL + halfW;
 #pragma unroll
     for (int k = 0; k < NC; k++)
@@ -222,7 +241,7 @@ __device__ __forceinline__ void fwd97_store_row(int32_t *__restrict__ out_i32, d
         }
 }
 
-template <int CPL, int NC>
+template <int CPL, int NC, bool MAL = false>
 __global__ __launch_bounds__(256) void dwt97_fwd_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                                                         const void *__restrict__ src, int src_f64, int32_t *__restrict__ out_i32,
                                                         double *__restrict__ out_f64, double *__restrict__ nxt, int dc_shift,
@@ -250,7 +269,7 @@ __global__ __launch_bounds__(256) void dwt97_fwd_kernel(const DwtJob *__restrict
         if (q0 == 0) {
             Row r0;
             fwd97_load_row<CPL, NC>(src, src_f64, P, 0, c, dc_shift, mct, r0);
-            fwd97_store_row<CPL, NC>(out_i32, out_f64, nxt, P, 0, p0, owned, quant, step, r0.lo, r0.hi);
+            fwd97_store_row<CPL, NC, MAL>(out_i32, out_f64, nxt, P, 0, p0, owned, quant, step, r0.lo, r0.hi);
         }
         return;
     }
@@ -302,8 +321,8 @@ __global__ __launch_bounds__(256) void dwt97_fwd_kernel(const DwtJob *__restrict
                     s1p[a][k][j] = s1t;
                 }
         if (t >= 1 && t - 1 >= q0) {
-            fwd97_store_row<CPL, NC>(out_i32, out_f64, nxt, P, t - 1, p0, owned, quant, step, outl, outh);
-            if (prev_o_ex) fwd97_store_row<CPL, NC>(out_i32, out_f64, nxt, P, halfH + t - 1, p0, owned, quant, step, outl2, outh2);
+            fwd97_store_row<CPL, NC, MAL>(out_i32, out_f64, nxt, P, t - 1, p0, owned, quant, step, outl, outh);
+            if (prev_o_ex) fwd97_store_row<CPL, NC, MAL>(out_i32, out_f64, nxt, P, halfH + t - 1, p0, owned, quant, step, outl2, outh2);
         }
 #pragma unroll
         for (int k = 0; k < NC; k++)
@@ -318,12 +337,39 @@ __global__ __launch_bounds__(256) void dwt97_fwd_kernel(const DwtJob *__restrict
 // DEQ: j2k_plan_set_dequantize -- every int32 coefficient times `step` (dwt.Dequantize, dwt.go:517) right after its conversion, before the
 // K97 / K97I scaling; a value from `prev` was multiplied when the coarser level read it.  A template parameter here: as a kernel argument
 // that is always passed, the two SGPRs of `step` raised the SGPR spills of <2, 3> and <4, 1> (docs/KERNEL_NOTES.md)
-template <int CPL, int NC, bool DEQ>
+template <int CPL, int NC, bool DEQ, bool MAL = false>
 __device__ __forceinline__ void inv97_load_row(const void *__restrict__ coef, int coef_f64, const double *__restrict__ prev,
                                                const DwtPlane &P, int ri, int p0, double step, Row97<CPL, NC> &R) {
     constexpr int H = CPL / 2;
     const int halfW = (P.w + 1) >> 1;
     const int nL = halfW - p0, nH = (P.w - halfW) - p0;
+    if constexpr (MAL) {
+        const bool ll = P.n_next != 0 && ri < ((P.h + 1) >> 1);       // this row's low half is LL: the coarser level's result
+#pragma unroll
+        for (int k = 0; k < NC; k++)
+#pragma unroll
+            for (int j = 0; j < 2 * H; j++) {
+                const bool is_lo = j < H;
+                const int jj = is_lo ? j : j - H;
+                const bool ok = jj < (is_lo ? nL : nH);
+                const bool from_prev = is_lo && ll;
+                // branch-free as below: an element past the row end reads the row's first one, both sources at an address of their own
+                const int64_t cidx = (int64_t)ri * P.coef_stride + (ok ? (is_lo ? 0 : halfW) + p0 + jj : 0);
+                const int64_t pidx = from_prev ? (int64_t)ri * halfW + (ok ? p0 + jj : 0) : 0;
+                double v;
+                if (coef_f64) {
+                    const double *b = from_prev ? prev + P.nxt_off[k] + pidx : reinterpret_cast<const double *>(coef) + P.src_off[k] + cidx;
+                    v = *b;
+                } else {
+                    const double vp = prev[P.nxt_off[k] + pidx];
+                    const int vc = reinterpret_cast<const int32_t *>(coef)[P.src_off[k] + cidx];
+                    v = from_prev ? vp : (DEQ ? (double)vc * step : (double)vc);
+                }
+                if (!ok) v = 0.0;
+                if (is_lo) R.lo[k][jj] = v; else R.hi[k][jj] = v;
+            }
+        return;
+    }
     const int idxL = ri * P.w + p0, idxH = idxL + halfW;
 #pragma unroll
     for (int k = 0; k < NC; k++)
@@ -394,7 +440,7 @@ __device__ __forceinline__ void inv97_finish_row(void *__restrict__ dst, const D
     }
 }
 
-template <int CPL, int NC, bool DEQ>
+template <int CPL, int NC, bool DEQ, bool MAL = false>
 __global__ __launch_bounds__(256) void dwt97_inv_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                                                         const void *__restrict__ coef, int coef_f64, const double *__restrict__ prev,
                                                         void *__restrict__ dst, int dc_shift, int dst_mode, int mct, double step) {
@@ -420,7 +466,7 @@ __global__ __launch_bounds__(256) void dwt97_inv_kernel(const DwtJob *__restrict
     if (h < 2) {
         if (q0 == 0) {
             Row r0;
-            inv97_load_row<CPL, NC, DEQ>(coef, coef_f64, prev, P, 0, p0, step, r0);
+            inv97_load_row<CPL, NC, DEQ, MAL>(coef, coef_f64, prev, P, 0, p0, step, r0);
             inv97_finish_row<CPL, NC>(dst, P, 0, c, owned, dc_shift, dst_mode, mct, r0.lo, r0.hi);
         }
         return;
@@ -442,8 +488,8 @@ __global__ __launch_bounds__(256) void dwt97_inv_kernel(const DwtJob *__restrict
         const bool hi_ex = real && (2 * t + 1 < h);
         Row L, Hh;
         if (real) {   // the high row is clamped into the plane (hi_ex discards it when it does not exist)
-            inv97_load_row<CPL, NC, DEQ>(coef, coef_f64, prev, P, t, p0, step, L);
-            inv97_load_row<CPL, NC, DEQ>(coef, coef_f64, prev, P, halfH + min(t, h - halfH - 1), p0, step, Hh);
+            inv97_load_row<CPL, NC, DEQ, MAL>(coef, coef_f64, prev, P, t, p0, step, L);
+            inv97_load_row<CPL, NC, DEQ, MAL>(coef, coef_f64, prev, P, halfH + min(t, h - halfH - 1), p0, step, Hh);
         }
         const bool p1_real = (t >= 1) && (t - 1 < halfH);            // pair t-1 exists
         const bool p1_hi = p1_real && (2 * (t - 1) + 1 < h);
@@ -523,6 +569,7 @@ static hipError_t fwd97_wg_go(hipStream_t s, const LevelLaunch &L, const void *s
 hipError_t launch_dwt97_fwd(hipStream_t s, const LevelLaunch &L, const void *src, int src_is_f64, int32_t *out_i32, double *out_f64,
                             double *nxt, int dc_shift, int quant, double step, int mct) {
     if (L.njobs <= 0) return hipSuccess;
+    if (L.mallat && (L.wg_waves > 0 || L.pnjobs > 0 || L.pix_stride > 0)) return hipErrorInvalidValue;   // Mallat plans have the general kernels only
     if (L.wg_waves > 0) {      // level 0 of an int32 RGB triple with ICT, workgroup form (dwt97_l0wg.inc); geometry checked by the plan
         if (L.ncomp != 3 || src_is_f64 || !mct) return hipErrorInvalidValue;
         if (L.wg_waves == 6) return fwd97_wg_go<6>(s, L, src, out_i32, out_f64, nxt, dc_shift, quant, step);
@@ -550,6 +597,12 @@ hipError_t launch_dwt97_fwd(hipStream_t s, const LevelLaunch &L, const void *src
         return hipGetLastError();
     }
     const int blocks = (L.njobs + 3) / 4;
+    if (L.mallat) {            // a Mallat plan's level: its own instantiations, the prefix kernels are untouched
+#define J2K_FWD97M(CPL, NC) hipExtLaunchKernelGGL((dwt97_fwd_kernel<CPL, NC, true>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0, L.jobs, L.njobs, L.planes, src, src_is_f64, out_i32, out_f64, nxt, dc_shift, quant, step, mct)
+        if (L.ncomp == 3) J2K_FWD97M(2, 3); else if (L.cpl == 4) J2K_FWD97M(4, 1); else J2K_FWD97M(2, 1);
+#undef J2K_FWD97M
+        return hipGetLastError();
+    }
     if (L.ncomp == 3) {
         hipExtLaunchKernelGGL((dwt97_fwd_kernel<2, 3>), dim3(blocks), dim3(256), 0, s, L.ev_start, L.ev_stop, 0, L.jobs, L.njobs, L.planes, src, src_is_f64, out_i32, out_f64, nxt, dc_shift, quant, step, mct);
     } else if (L.cpl == 4) {
@@ -564,6 +617,7 @@ hipError_t launch_dwt97_inv(hipStream_t s, const LevelLaunch &L, const void *coe
                             int dc_shift, int final_level, int dst_mode, int mct, double step) {
     (void)final_level;
     if (L.njobs <= 0) return hipSuccess;
+    if (L.mallat && (L.wg_waves > 0 || L.pnjobs > 0 || L.pix_stride > 0)) return hipErrorInvalidValue;
     if (L.wg_waves > 0) {      // level 0 of an RGB triple, int32 coefficients -> int32 frame with inverse ICT (dwt97_l0wg_inv.inc)
         if (L.ncomp != 3 || coef_is_f64 || !mct || dst_mode != DST_I32_FRAME) return hipErrorInvalidValue;
 #define J2K_WG97I(NW) hipExtLaunchKernelGGL((dwt97_inv_rgb_wg_kernel<NW, J2K_WG97I_WPE, false>), dim3(L.njobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
@@ -593,6 +647,15 @@ hipError_t launch_dwt97_inv(hipStream_t s, const LevelLaunch &L, const void *coe
     }
     const int blocks = (L.njobs + 3) / 4;
     const bool deq = step != 1.0 && !coef_is_f64;
+    if (L.mallat) {
+#define J2K_INV97M(CPL, NC) do { \
+        if (deq) hipLaunchKernelGGL((dwt97_inv_kernel<CPL, NC, true, true>), dim3(blocks), dim3(256), 0, s, L.jobs, L.njobs, L.planes, coef, coef_is_f64, prev, dst, dc_shift, dst_mode, mct, step); \
+        else hipLaunchKernelGGL((dwt97_inv_kernel<CPL, NC, false, true>), dim3(blocks), dim3(256), 0, s, L.jobs, L.njobs, L.planes, coef, coef_is_f64, prev, dst, dc_shift, dst_mode, mct, step); \
+    } while (0)
+        if (L.ncomp == 3) J2K_INV97M(2, 3); else if (L.cpl == 4) J2K_INV97M(4, 1); else J2K_INV97M(2, 1);
+#undef J2K_INV97M
+        return hipGetLastError();
+    }
 #define J2K_INV97(CPL, NC) do { \
         if (deq) hipLaunchKernelGGL((dwt97_inv_kernel<CPL, NC, true>), dim3(blocks), dim3(256), 0, s, L.jobs, L.njobs, L.planes, coef, coef_is_f64, prev, dst, dc_shift, dst_mode, mct, step); \
         else hipLaunchKernelGGL((dwt97_inv_kernel<CPL, NC, false>), dim3(blocks), dim3(256), 0, s, L.jobs, L.njobs, L.planes, coef, coef_is_f64, prev, dst, dc_shift, dst_mode, mct, step); \

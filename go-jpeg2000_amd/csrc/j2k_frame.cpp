@@ -301,6 +301,33 @@ extern "C" int j2k_plan_decode_frame_pixels(j2k_plan *P, const uint8_t *d_cs, si
     return r;
 }
 
+// j2k_plan_decode_frame_pixels to a reduced resolution (Mallat plans).  Every packet is parsed as before -- a tile's packets are in component ->
+// resolution order, the later ones cannot be found otherwise -- but the block decoder and the placement run the jobs of the resolutions
+// <= num_resolutions - 1 - reduce only (with the MQ coder that is where the decode time is), and the inverse transform stops at level `reduce`.
+extern "C" int j2k_plan_decode_frame_pixels_reduced(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
+                                                    void *d_pix, size_t stride) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    ReducedTab *R = nullptr;
+    int r = plan_reduced(P, reduce, &R);
+    if (r != J2K_OK) return r;
+    if (reduce == 0) return j2k_plan_decode_frame_pixels(P, d_cs, len, d_tile_offs, sop, eph, d_pix, stride);
+    if (!d_pix) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    r = cl_prepare(P);
+    if (r == J2K_OK) r = cl_workspaces(P);
+    if (r == J2K_OK) r = j2k_plan_decode_tile_parts(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps);
+    if (r != J2K_OK) return r;
+    HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, R->d_offs, R->d_lens, R->d_numbps));
+    const bool ht = P->spec.coder == J2K_CODER_HT;
+    int32_t *coeff = ht ? P->d_cl_coeff_dec : P->d_cl_coeff;
+    // (HT: straight into the windows of the plan's zeroed planes, coded rows only, as the full decode; the windows left out keep what an earlier
+    //  full decode wrote -- no level >= reduce reads them)
+    r = plan_decode_blocks_jobs(P, R->d_djobs, R->njobs, d_cs, R->d_offs, R->d_lens, R->d_numbps, ht ? coeff : P->d_cl_decoded, ht ? R->d_placed : nullptr);
+    if (r == J2K_OK && !ht) HIPCHK(ctx, launch_place_blocks(ctx->stream, R->d_bjobs, R->d_djobs, R->njobs, R->max_block_h, P->d_cl_decoded, coeff));
+    if (r == J2K_OK) r = plan_inverse_pixels_reduced_impl(P, coeff, reduce, d_pix, stride, P->d_frame_status);
+    return r;
+}
+
 extern "C" int j2k_plan_get_decoded_offsets(const j2k_plan *P, uint64_t *offs, size_t cap) {
     if (!P || !offs) return J2K_ERR_INVALID_ARG;
     if (cap < P->dec_off.size()) return J2K_ERR_CAPACITY;

@@ -69,6 +69,10 @@ hipError_t launch_t2_decode_tiles(hipStream_t s, void *chains, int ntiles, const
                                   int ht, int mb, uint64_t *offs, uint32_t *lens, uint8_t *numbps);
 hipError_t launch_t2_blocks(hipStream_t s, long n, const j2k_t2_dev_cb *cbs, int ht, int mb, uint64_t total, uint64_t *offs, uint32_t *lens, uint8_t *numbps, int *status);
 hipError_t launch_place_blocks(hipStream_t s, const BlockJob *src_jobs, const BlockJob *dec_jobs, int njobs, int max_h, const int32_t *decoded, int32_t *coeff, int ystep = 1);
+hipError_t launch_select_blocks(hipStream_t s, const int *ids, int m, const uint64_t *offs, const uint32_t *lens, const uint8_t *numbps, uint64_t *offs_r,
+                                uint32_t *lens_r, uint8_t *numbps_r);
+hipError_t launch_mallat_ll(hipStream_t s, const LLPlane *planes, int nplanes, int max_samples, const int32_t *coef, int32_t *frame, int lossy, double step,
+                            int dc_shift);
 hipError_t launch_scan(hipStream_t s, const uint32_t *lens, int njobs, uint64_t *offs, const uint32_t *mels, uint64_t *toffs);
 size_t pack_header_bytes(size_t n);
 hipError_t launch_pack(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs, const uint64_t *toffs,
@@ -105,6 +109,9 @@ static int upload(j2k_ctx *ctx, T **dptr, const std::vector<T> &v) {
 int build_plan(j2k_ctx *ctx, const j2k::PlanSpec &S, j2k_plan **out);
 int cached_plan(j2k_ctx *ctx, const j2k::PlanSpec &S, j2k_plan **out);
 void plan_t2_packets(const j2k_plan *P, int layer, std::vector<j2k_t2_dev_packet> &out, std::vector<int> *tile_packet0);
+// the tables of a Mallat plan decoded `reduce` resolutions down (made at the first use of that `reduce`, kept in the plan); the refusals of
+// include/j2kgfx.h: J2K_ERR_UNSUPPORTED on any other plan, J2K_ERR_INVALID_ARG for a `reduce` the geometry does not allow
+int plan_reduced(j2k_plan *P, int reduce, j2k::ReducedTab **out);
 
 // ---- stages (j2k_stages.cpp) ----
 struct T1Workspace { size_t off_nsyms, off_sym, stride, total; };
@@ -118,6 +125,11 @@ int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *
 // guard (device, or null): the launches that write d_frame write nothing if *guard != 0 -- the frame decoder's status word
 int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix = PixIO(), const int *guard = nullptr);
 int plan_inverse_pixels_impl(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride, const int *guard);
+int plan_inverse_pixels_reduced_impl(j2k_plan *P, const int32_t *d_coeff, int reduce, void *d_pix, size_t stride, const int *guard);
+// j2k_plan_decode_blocks on a job table of its own (the plan's, or the subset of a reduced-resolution decode); placed != NULL (HT): every block
+// straight into its window of the coefficient planes `d_decoded`, coded rows only
+int plan_decode_blocks_jobs(j2k_plan *P, const j2k::BlockJob *d_djobs, int n, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
+                            const uint8_t *d_numbps, int32_t *d_decoded, const j2k::BlockJob *d_placed);
 // the default branch of extractImageData (j2k_image.cpp): d_img's planes on the device; status_word non-null = report a palette index
 // >= npal there (the frame codec's status, asynchronous), else synchronise and return J2K_ERR_GO_PANIC before anything is written
 bool plan_rgba8_wg_fusable(const j2k_plan *P);

@@ -452,10 +452,22 @@ extern "C" int j2k_encode_image_host(j2k_plan *P, const j2k_image *img, int sop,
     });
 }
 
+static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride);
 // closed-loop plans: tile-parts (host) -> H2D -> parse -> block decode -> placement -> inverse transform -> image.*.Pix (host), one
 // synchronous call.  The pixel format is the plan's: components 1 / 3 / 4, precision <= 8 -> Gray / RGBA, else Gray16 / RGBA64
 // (decoder.createImage, decoder.go:417-588).
 extern "C" int j2k_decode_pixels_host(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, void *pix, size_t stride) {
+    return decode_pixels_host_impl(P, cs, len, sop, eph, -1, pix, stride);
+}
+// ... of a Mallat plan to a reduced resolution: pix holds ceil(H / 2^reduce) rows of `stride` bytes
+extern "C" int j2k_decode_pixels_host_reduced(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    int32_t wr = 0, hr = 0;
+    const int r = j2k_plan_reduced_size(P, reduce, &wr, &hr);     // (J2K_ERR_UNSUPPORTED on any other plan, J2K_ERR_INVALID_ARG for a reduce outside 0 ... levels)
+    if (r != J2K_OK) return r;
+    return decode_pixels_host_impl(P, cs, len, sop, eph, reduce, pix, stride);
+}
+static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride) {
     if (!P || !cs || !pix) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
@@ -463,11 +475,14 @@ extern "C" int j2k_decode_pixels_host(j2k_plan *P, const uint8_t *cs, size_t len
     if (!S.closed_loop) return fail(ctx, J2K_ERR_UNSUPPORTED, "the plan was not made with j2k_params.closed_loop: the reference has no decode body to mirror");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int r;
-    const size_t pixbytes = (size_t)S.H * stride;
+    const size_t rows = reduce > 0 ? (size_t)(((int64_t)S.H + (((int64_t)1 << reduce) - 1)) >> reduce) : (size_t)S.H;
+    const size_t pixbytes = rows * stride;
     if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, pixbytes)) != J2K_OK) return r;
     if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, len + 64)) != J2K_OK) return r;
     HIPCHK(ctx, hipMemcpyAsync(P->d_host_io, cs, len, hipMemcpyHostToDevice, ctx->stream));
-    if ((r = j2k_plan_decode_frame_pixels(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, P->d_host_pix, stride)) != J2K_OK) return r;
+    r = reduce >= 0 ? j2k_plan_decode_frame_pixels_reduced(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, reduce, P->d_host_pix, stride)
+                    : j2k_plan_decode_frame_pixels(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, P->d_host_pix, stride);
+    if (r != J2K_OK) return r;
     HIPCHK(ctx, hipMemcpyAsync(pix, P->d_host_pix, pixbytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return j2k_plan_frame_status(P);

@@ -19,7 +19,9 @@ struct DwtPlane {
     int32_t w, h;         // dims of this level: dense w x h matrix
     int32_t n_next;       // w_{l+1}*h_{l+1}; linear idx < n_next -> nxt, else -> out (0 on the last level)
     int32_t out_stride;   // inverse level 0 only: row stride of the destination frame
-    int32_t pad_;
+    int32_t coef_stride;  // Mallat plans only (the MAL kernels): row stride of the coefficient plane = w of level 0.  They route on row and
+                          // column, not on the linear index: LL (row < h_{l+1}, column < w_{l+1}) <-> nxt as a dense w_{l+1} x h_{l+1}
+                          // matrix while n_next != 0, everything else <-> the plane at row * coef_stride + column
 };
 
 // One wavefront's work: a column strip x a band of pair-rows of one plane.
@@ -60,6 +62,15 @@ struct TailPlane {
     int32_t pad_;
 };
 
+// One tile-component (or MCT triple) of a Mallat plan decoded to its coarsest resolution (reduce = levels): no inverse level runs, the LL
+// rectangle [0, w) x [0, h) of each coefficient plane is the picture (mct.hip: mallat_ll_kernel)
+struct LLPlane {
+    int64_t coef_off[3];  // coefficient plane of comp k (row stride coef_stride)
+    int64_t out_off[3];   // its place in the reduced int32 frame (row stride out_stride)
+    int32_t w, h, coef_stride, out_stride;
+    int32_t nc, pad_;     // 1, or 3 = inverse RCT / ICT on the triple
+};
+
 // launch wrappers (dwt53.hip, dwt97.hip, mct.hip, ht.hip, t1.hip)
 // A YCbCr image read by the 5-3 level-0 workgroup kernel itself (j2k_plan_forward_image): the planes at the frame's origin
 // (Rect.Min even and >= 0), one chroma stride for Cb and Cr (Go's CStride); ratio J2K_YCBCR_444 / 422 / 420.
@@ -96,6 +107,7 @@ struct LevelLaunch {
                                     // begin / end, without the launch gap an event pair around the launch would include
     YccSrc ycc;           // ycc.y non-null: level 0 of the workgroup form reads this YCbCr image instead of packed RGBA8
     const int *guard;     // inverse: non-null = a device word; the launch writes nothing if it is not 0 (the frame decoder's status, j2k_frame.cpp)
+    int mallat;           // 1: a level of a Mallat plan (DwtPlane::coef_stride): the MAL instantiation of the general kernels
 };
 
 hipError_t launch_dwt53_fwd(hipStream_t s, const LevelLaunch &L, const int32_t *src, int32_t *out,

@@ -101,6 +101,7 @@ struct PlanSpec {
     int tile_first = 0, tile_count = 0;
     bool frame_is_f64 = false; // unit 9-7 calls: source/destination "frame" is f64
     bool closed_loop = false;  // j2k_params.closed_loop: code-block windows = the Mallat rectangles of the plane (they partition it)
+    bool mallat = false;       // j2k_params.closed_loop == J2K_CLOSED_LOOP_MALLAT: level l runs on the rectangle [0, w_l) x [0, h_l) of the plane, so those windows are its sub-bands
     bool operator==(const PlanSpec &o) const;
 };
 
@@ -123,6 +124,22 @@ struct LevelTab {
     DwtJob *d_pjobs = nullptr;
     int pnjobs = 0, pwaves = 0, pmulti = 0;
     bool p_pix_only = false;   // the table serves packed-pixel sources only (level 0 of RGB triples: RGBA64); int32 planes keep the general kernels
+    bool mallat = false;       // a level of a Mallat plan: the MAL instantiation of the general kernels (LevelLaunch::mallat)
+};
+
+// A Mallat plan decoded `reduce` resolutions down (j2k_plan_*_reduced): LL_reduce is the frame, W_r x H_r = ceil(W / 2^reduce) x ceil(H / 2^reduce),
+// tile (x0, y0) at (x0 >> reduce, y0 >> reduce)
+struct ReducedTab {
+    bool built = false;
+    int Wr = 0, Hr = 0;
+    LevelTab inv[2];           // the launch of level `reduce`, the final one ([0] single components, [1] MCT triples): out_off / out_stride address the reduced frame
+    LLPlane *d_ll = nullptr;   // reduce == levels: no level runs (mct.hip mallat_ll_kernel)
+    int nll = 0, ll_samples = 0;
+    // the code-block jobs of the resolutions <= num_resolutions - 1 - reduce, in job order, and their share of the frame's block tables
+    int njobs = 0, max_block_h = 0;
+    int *d_ids = nullptr;
+    BlockJob *d_bjobs = nullptr, *d_djobs = nullptr, *d_placed = nullptr;   // windows / dense decoded blocks (the plan's offsets) / HT: the windows as destinations
+    uint64_t *d_offs = nullptr; uint32_t *d_lens = nullptr; uint8_t *d_numbps = nullptr;
 };
 
 }  // namespace j2k
@@ -217,5 +234,6 @@ struct j2k_plan {
     uint64_t *d_bigsym_off = nullptr;       // MQ plans with blocks above 64 x 64: where each job's symbol list starts (bytes; n + 1 entries), built at the first encode
     size_t bigsym_total = 0;
     bool dec_coded_rows_only = false;       // j2k_plan_set_decode_coded_rows_only: HT decode leaves the rows the reference's decoder never writes alone
+    std::vector<j2k::ReducedTab> reduced;   // Mallat plans: [reduce], 1 ... levels
     bool dequantize = false;                // j2k_plan_set_dequantize: the 9-7 inverse kernels multiply every int32 coefficient by 1.0 / Quality at their load (dwt.go:514-520)
 };

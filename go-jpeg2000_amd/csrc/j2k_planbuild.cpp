@@ -10,10 +10,31 @@ bool PlanSpec::operator==(const PlanSpec &o) const {
     return W == o.W && H == o.H && C == o.C && tile_w == o.tile_w && tile_h == o.tile_h && levels == o.levels &&
            frame_h == o.frame_h && wavelet == o.wavelet && precision == o.precision && dc_shift == o.dc_shift && dc_shift_inv == o.dc_shift_inv && mct == o.mct && quant == o.quant && quality == o.quality &&
            num_res_jobs == o.num_res_jobs && cb_w == o.cb_w && cb_h == o.cb_h && coder == o.coder &&
-           tile_first == o.tile_first && tile_count == o.tile_count && frame_is_f64 == o.frame_is_f64 && closed_loop == o.closed_loop;
+           tile_first == o.tile_first && tile_count == o.tile_count && frame_is_f64 == o.frame_is_f64 && closed_loop == o.closed_loop && mallat == o.mallat;
 }
 
 static inline int pick_cpl(int maxw) { return maxw >= 384 ? 8 : (maxw >= 192 ? 4 : 2); }
+
+// Which instantiation of the general kernels a level table is cut for: columns per lane, vector accesses or not, halo lanes per side.  One
+// rule for build_plan's level tables and for plan_reduced's final launch: the job table and the launch must agree on it.
+//   frame_stride > 0: the level reads / writes a frame with this row stride (level 0; the final launch of a reduced decode)
+//   cpl0: the J2K_CPL0 tuning knob (5-3 level 0), 0 = none;  vec_ok: what the caller has ruled out already
+struct LevelRule { int cpl; bool vec; int halo; };
+static LevelRule level_rule(const PlanSpec &S, int cls, const std::vector<DwtPlane> &planes, int maxw, int frame_stride, int cpl0, bool vec_ok) {
+    int cpl = pick_cpl(maxw);
+    if (cpl0 > 0 && S.wavelet == W53) cpl = cpl0;
+    if (S.wavelet == W97) cpl = (cls == 1) ? 2 : (maxw >= 192 ? 4 : 2);   // f64: 2 or 4 columns per lane
+    for (size_t i = 0; i < planes.size() && vec_ok; i++) {
+        const DwtPlane &D = planes[i];
+        if (D.w % cpl) vec_ok = false;
+        if (frame_stride > 0 && (frame_stride % cpl)) vec_ok = false;
+        for (int k = 0; k < 3; k++)
+            if ((D.src_off[k] % 4) || (D.out_off[k] % 4) || (D.nxt_off[k] % 4)) vec_ok = false;
+    }
+    if (S.wavelet == W97) vec_ok = false;        // the 9-7 kernels use scalar accesses
+    else if (!vec_ok) cpl = 2;
+    return LevelRule{cpl, vec_ok, (S.wavelet == W97 && cpl < 4) ? 2 : 1};
+}
 
 extern "C" size_t j2k_block_bound(int coder, int w, int h) {
     size_t n = (size_t)std::max(w, 0) * (size_t)std::max(h, 0);
@@ -59,6 +80,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
     const int L = S.levels;
     const bool triple = S.mct && S.C >= 3;
     const int esz = S.wavelet == W97 ? 8 : 4;
+    const bool mal = S.mallat;          // a Mallat plan: the per-level launches with the MAL kernels for every level, none of the specialised forms
 
     // ---- tile-components, coefficient + scratch offsets -------------------------
     int64_t coef = 0, sa = 0, sb = 0;
@@ -87,7 +109,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
     P->coeff_elems = coef; P->scrA_elems = sa; P->scrB_elems = sb;
 
     // ---- fused LDS tail for the small levels (5-3 only) --------------------------------
-    if (S.wavelet == W53 && ctx->use_tail && L >= 3) {
+    if (S.wavelet == W53 && ctx->use_tail && L >= 3 && !mal) {
         for (int l0 = 1; l0 <= L - 2 && P->tail_l0 < 0; l0++) {
             bool ok = true;
             for (const Group &g : P->groups) {
@@ -123,7 +145,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
     // ---- every level below level 0 in one launch per direction (dwt53_deep.inc) ------------------
     // levels deep_l0 .. L-1, deep_l0 = the level above the first one that fits LDS: it streams from memory in the same workgroups
     int lds_l0 = -1;        // the first level whose input fits the LDS buffers (the tail above needs two such levels, this one)
-    if (S.wavelet == W53) {
+    if (S.wavelet == W53 && !mal) {
         for (int l0 = 1; l0 <= L - 1 && lds_l0 < 0; l0++) {
             bool fits = true;
             for (const Group &g : P->groups) {
@@ -255,6 +277,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                     for (int i = 0; i < l; i++) { w = (w + 1) / 2; h = (h + 1) / 2; }
                     const int wn = (w + 1) / 2, hn = (h + 1) / 2;
                     const int nplanes_here = as_triple ? 1 : g.nc;
+                    if (mal && (g.w % 4)) vec_ok = false;      // rows of the coefficient plane are 16-byte aligned only then
                     for (int k0 = 0; k0 < nplanes_here; k0++) {
                         DwtPlane D{};
                         const int kn = as_triple ? 3 : 1;
@@ -277,6 +300,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                         D.out_stride = S.W;
                         D.w = w; D.h = h;
                         D.n_next = (l == L - 1) ? 0 : wn * hn;
+                        D.coef_stride = mal ? g.w : 0;
                         planes.push_back(D);
                         pw.push_back(w); ph.push_back(h);
                         maxw = std::max(maxw, w);
@@ -284,22 +308,13 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                 }
                 LevelTab &T = (dir == 0 ? P->fwd : P->inv)[cls][l];
                 T.ncomp = cls ? 3 : 1;
+                T.mallat = mal;
                 T.nplanes = (int)planes.size();
                 if (planes.empty()) continue;
-                int cpl = pick_cpl(maxw);
-                if (l == 0 && ctx->cpl0 > 0 && S.wavelet == W53) cpl = ctx->cpl0;   // tuning knob J2K_CPL0
-                if (S.wavelet == W97) cpl = (cls == 1) ? 2 : (maxw >= 192 ? 4 : 2);   // f64: 2 or 4 columns per lane
-                for (size_t i = 0; i < planes.size() && vec_ok; i++) {
-                    const DwtPlane &D = planes[i];
-                    if (D.w % cpl) vec_ok = false;
-                    if (l == 0 && (S.W % cpl)) vec_ok = false;
-                    for (int k = 0; k < 3; k++)
-                        if ((D.src_off[k] % 4) || (D.out_off[k] % 4) || (D.nxt_off[k] % 4)) vec_ok = false;
-                }
-                if (S.wavelet == W97) vec_ok = false;        // the 9-7 kernels use scalar accesses
-                else if (!vec_ok) cpl = 2;
+                const LevelRule rule = level_rule(S, cls, planes, maxw, l == 0 ? S.W : 0, l == 0 ? ctx->cpl0 : 0, vec_ok);   // (cpl0: tuning knob J2K_CPL0)
+                const int cpl = rule.cpl, halo = rule.halo;
+                vec_ok = rule.vec;
                 T.cpl = cpl; T.vec = vec_ok ? 1 : 0;
-                const int halo = (S.wavelet == W97 && cpl < 4) ? 2 : 1;
                 const int band53 = (dir == 1 && ctx->band_prows_inv > 0) ? ctx->band_prows_inv : ctx->band_prows;
                 const int band = (S.wavelet == W97) ? ctx->band_prows_97 : band53;
                 auto build_jobs = [&](int band_) {
@@ -343,7 +358,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                 int r = upload(ctx, &T.d_planes, planes);
                 if (r == J2K_OK) r = upload(ctx, &T.d_jobs, jobs);
                 if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
-                if (S.wavelet == W53 && vec_ok && ctx->plane_wg > 0 && (cls == 0 || ctx->plane_wg3 || l == 0)) {   // both directions; cls 1 = level 0 of RGB triples: int32 planes (J2K_PLANE_WG3) or RGBA64 pixels
+                if (!mal && S.wavelet == W53 && vec_ok && ctx->plane_wg > 0 && (cls == 0 || ctx->plane_wg3 || l == 0)) {   // both directions; cls 1 = level 0 of RGB triples: int32 planes (J2K_PLANE_WG3) or RGBA64 pixels
                     // workgroup form for single-component planes (dwt53_plane_wg.inc): whole 16-byte lanes, at least two rows
                     bool ok = true;
                     int multi = 0;
@@ -382,7 +397,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                         if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
                     }
                 }
-                if (S.wavelet == W97 && cls == 0 && ctx->plane_wg97 > 0) {
+                if (!mal && S.wavelet == W97 && cls == 0 && ctx->plane_wg97 > 0) {
                     // single planes of the 9-7 transform in workgroup form (dwt97_l0wg.inc SRC = 1 / 2, dwt97_l0wg_inv.inc): the deeper
                     // levels (float64 scratch in, int32 coefficients), and since round 4 level 0 of one int32 component (gray frames,
                     // frames without the colour transform) and the float64 unit calls (dwt.go:432-473, 551-573): one job per (plane,
@@ -406,7 +421,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                         if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
                     }
                 }
-                if (dir == 0 && l == 0 && cls == 1 && S.wavelet == W53 && vec_ok && cpl == 8) {
+                if (!mal && dir == 0 && l == 0 && cls == 1 && S.wavelet == W53 && vec_ok && cpl == 8) {
                     // the packed-pixel forward (j2k_plan_forward_rgba8) moves a third of the bytes per row on the read side
                     // and likes shorter bands: its own job table (measured: 3 pair-rows 29.6 us, 5 pair-rows 31.9 us)
                     std::vector<DwtJob> pj = build_jobs(ctx->band_prows_pix);
@@ -528,7 +543,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                         }
                     }
                 }
-                if (dir == 0 && l == 0 && cls == 1 && S.wavelet == W97 && S.mct && !S.frame_is_f64 && ctx->l0_wg97 > 0) {
+                if (!mal && dir == 0 && l == 0 && cls == 1 && S.wavelet == W97 && S.mct && !S.frame_is_f64 && ctx->l0_wg97 > 0) {
                     // workgroup form of the lossy level 0 (dwt97_l0wg.inc): one job per (plane, band of NW - 3 pair-rows,
                     // component); the three components of a band are neighbours in the table and the whole table is dealt
                     // XCD-aware like the 5-3 one, so the rows they share are L2 hits
@@ -554,7 +569,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                         if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
                     }
                 }
-                if (dir == 1 && l == 0 && cls == 1 && S.wavelet == W97 && S.mct && !S.frame_is_f64 && S.quant != Q_NONE && ctx->l0_wg97_inv > 0) {
+                if (!mal && dir == 1 && l == 0 && cls == 1 && S.wavelet == W97 && S.mct && !S.frame_is_f64 && S.quant != Q_NONE && ctx->l0_wg97_inv > 0) {
                     // workgroup form of the lossy inverse level 0 (dwt97_l0wg_inv.inc): one job per (plane, band of NW - 3
                     // pair-rows), all three components in the workgroup; dealt XCD-aware like the forward table
                     bool ok97 = (S.W % 4) == 0;
@@ -700,9 +715,144 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
     return J2K_OK;
 }
 
+// ------------------------------------------------------------------------------
+// Mallat plans, reduced-resolution decode: the tables of one `reduce`
+// ------------------------------------------------------------------------------
+static void free_reduced(ReducedTab &R) {
+    void *rp[] = {R.inv[0].d_planes, R.inv[0].d_jobs, R.inv[1].d_planes, R.inv[1].d_jobs, R.d_ll, R.d_ids, R.d_bjobs, R.d_djobs, R.d_placed, R.d_offs, R.d_lens, R.d_numbps};
+    for (void *p : rp) if (p) (void)hipFree(p);
+    R = ReducedTab();
+}
+
+int plan_reduced(j2k_plan *P, int reduce, ReducedTab **out) {
+    j2k_ctx *ctx = P->ctx;
+    const PlanSpec &S = P->spec;
+    if (!S.mallat) return fail(ctx, J2K_ERR_UNSUPPORTED, "reduced-resolution decode needs a Mallat plan (j2k_params.closed_loop = J2K_CLOSED_LOOP_MALLAT): no other plan's coarser levels are pictures");
+    const int L = S.levels;
+    if (reduce < 0 || reduce > L) return fail(ctx, J2K_ERR_INVALID_ARG, "reduce outside 0 ... decomposition levels");
+    const int fh = S.frame_h > 0 ? S.frame_h : S.H;
+    const int tw = S.tile_w > 0 ? S.tile_w : S.W, th = S.tile_h > 0 ? S.tile_h : fh;
+    const int mask = (int)(((int64_t)1 << reduce) - 1);
+    // a tile's origin must stay a whole sample of the reduced frame, or the reduced tiles would overlap or leave gaps
+    if ((tw < S.W && (tw & mask)) || (th < fh && (th & mask))) return fail(ctx, J2K_ERR_INVALID_ARG, "reduce: the tile size is not a multiple of 2^reduce");
+    if (fh < S.H && (fh & mask)) return fail(ctx, J2K_ERR_INVALID_ARG, "reduce: frame_rows is not a multiple of 2^reduce");
+    *out = nullptr;
+    if (reduce == 0) return J2K_OK;      // exactly the call without it: nothing is built (so nothing stands in the way of a capture)
+    if (P->reduced.empty()) P->reduced.resize((size_t)L + 1);
+    ReducedTab &R = P->reduced[(size_t)reduce];
+    *out = &R;
+    if (R.built) return J2K_OK;
+    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the tables of a `reduce` are made at its first use -- run the call once before j2k_ctx_capture_begin");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    auto shr = [&](int v) { return (int)(((int64_t)v + mask) >> reduce); };      // ceil(v / 2^reduce) = `reduce` times (v + 1) / 2
+    R.Wr = shr(S.W); R.Hr = shr(S.H);
+    int r = J2K_OK;
+    if (reduce == L) {
+        std::vector<LLPlane> ll;
+        for (const Group &g : P->groups) {
+            const int kn = g.nc == 3 ? 3 : 1;
+            for (int k0 = 0; k0 < (g.nc == 3 ? 1 : g.nc); k0++) {
+                LLPlane D{};
+                for (int k = 0; k < kn; k++) {
+                    const int kk = g.nc == 3 ? k : k0;
+                    D.coef_off[k] = g.coef_off[kk];
+                    D.out_off[k] = (int64_t)(g.comp0 + kk) * R.Hr * R.Wr + (int64_t)(g.y0 >> reduce) * R.Wr + (g.x0 >> reduce);
+                }
+                D.w = shr(g.w); D.h = shr(g.h); D.coef_stride = g.w; D.out_stride = R.Wr; D.nc = kn;
+                R.ll_samples = std::max(R.ll_samples, D.w * D.h);
+                ll.push_back(D);
+            }
+        }
+        R.nll = (int)ll.size();
+        r = upload(ctx, &R.d_ll, ll);
+    } else if (reduce > 0) {
+        // level `reduce` as the final launch: its planes grouped as MCT triples, as level 0 groups them; the general kernels, unlinked bands
+        for (int cls = 0; cls < 2 && r == J2K_OK; cls++) {
+            std::vector<DwtPlane> planes;
+            bool vec_ok = !ctx->force_novec;
+            int maxw = 0;
+            for (const Group &g : P->groups) {
+                if ((cls == 1) != (g.nc == 3)) continue;
+                const int w = shr(g.w), h = shr(g.h), wn = (w + 1) / 2, hn = (h + 1) / 2, kn = cls ? 3 : 1;
+                if (g.w % 4) vec_ok = false;
+                for (int k0 = 0; k0 < (cls ? 1 : g.nc); k0++) {
+                    DwtPlane D{};
+                    for (int k = 0; k < kn; k++) {
+                        const int kk = cls ? k : k0;
+                        D.src_off[k] = g.coef_off[kk];
+                        D.nxt_off[k] = ((reduce & 1) ? g.scrB_off : g.scrA_off)[kk];      // X_{reduce + 1}
+                        D.out_off[k] = (int64_t)(g.comp0 + kk) * R.Hr * R.Wr + (int64_t)(g.y0 >> reduce) * R.Wr + (g.x0 >> reduce);
+                    }
+                    D.src_stride = w; D.out_stride = R.Wr; D.w = w; D.h = h;
+                    D.n_next = (reduce == L - 1) ? 0 : wn * hn;
+                    D.coef_stride = g.w;
+                    planes.push_back(D);
+                    maxw = std::max(maxw, w);
+                }
+            }
+            LevelTab &T = R.inv[cls];
+            T.ncomp = cls ? 3 : 1; T.mallat = true; T.nplanes = (int)planes.size();
+            if (planes.empty()) continue;
+            const LevelRule rule = level_rule(S, cls, planes, maxw, R.Wr, 0, vec_ok);
+            const int cpl = rule.cpl, halo = rule.halo;
+            T.cpl = cpl; T.vec = rule.vec ? 1 : 0;
+            const int band = (S.wavelet == W97) ? ctx->band_prows_97 : (ctx->band_prows_inv > 0 ? ctx->band_prows_inv : ctx->band_prows);
+            std::vector<DwtJob> jobs;
+            for (size_t i = 0; i < planes.size(); i++) make_jobs(jobs, (int)i, planes[i].w, planes[i].h, cpl, band, halo);
+            T.njobs = (int)jobs.size();
+            r = upload(ctx, &T.d_planes, planes);
+            if (r == J2K_OK) r = upload(ctx, &T.d_jobs, jobs);
+        }
+    }
+    // the code-block jobs a decode to this resolution needs: resolutions 0 ... num_resolutions - 1 - reduce
+    if (r == J2K_OK && reduce > 0) {
+        const int numRes = S.num_res_jobs > 0 ? S.num_res_jobs : 6;
+        std::vector<int> ids;
+        std::vector<BlockJob> bj, dj, pj;
+        for (size_t j = 0; j < P->blocks.size(); j++) {
+            if (P->block_res[j] > numRes - 1 - reduce) continue;
+            const j2k_block &b = P->blocks[j];
+            const int64_t *d = &P->plane_desc[(size_t)b.plane * 7];      // tile, comp, x0, y0, w, h, coefficient offset
+            BlockJob J{};
+            J.src_off = d[6] + (int64_t)b.y0 * d[4] + b.x0;
+            J.stride = (int32_t)d[4]; J.w = b.w; J.h = b.h; J.band = b.band;
+            J.out_off = (int64_t)P->slot_off[j]; bj.push_back(J);
+            J.out_off = (int64_t)P->dec_off[j]; dj.push_back(J);
+            J.out_off = J.src_off; pj.push_back(J);
+            ids.push_back((int)j);
+            R.max_block_h = std::max(R.max_block_h, b.h);
+        }
+        R.njobs = (int)ids.size();
+        r = upload(ctx, &R.d_ids, ids);
+        if (r == J2K_OK) r = upload(ctx, &R.d_bjobs, bj);
+        if (r == J2K_OK) r = upload(ctx, &R.d_djobs, dj);
+        if (r == J2K_OK && S.coder == J2K_CODER_HT) r = upload(ctx, &R.d_placed, pj);
+        const size_t m = ids.size();
+        auto alloc = [&](void **p, size_t bytes) { if (r == J2K_OK) { hipError_t e = hipMalloc(p, bytes); if (e != hipSuccess) r = fail_hip(ctx, e, "hipMalloc (reduced decode)"); } };
+        alloc((void **)&R.d_offs, (m + 1) * 8 + 16);
+        alloc((void **)&R.d_lens, m * 4 + 16);
+        alloc((void **)&R.d_numbps, m + 16);
+    }
+    if (r != J2K_OK) { free_reduced(R); return r; }      // (a later call starts again from nothing)
+    R.built = true;
+    return J2K_OK;
+}
+
+extern "C" int j2k_plan_reduced_size(const j2k_plan *P, int reduce, int32_t *width, int32_t *height) {
+    if (!P || !width || !height) return J2K_ERR_INVALID_ARG;
+    const PlanSpec &S = P->spec;
+    if (!S.mallat) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "reduced-resolution decode needs a Mallat plan (j2k_params.closed_loop = J2K_CLOSED_LOOP_MALLAT)");
+    if (reduce < 0 || reduce > S.levels) return fail(P->ctx, J2K_ERR_INVALID_ARG, "reduce outside 0 ... decomposition levels");
+    const int64_t m = ((int64_t)1 << reduce) - 1;
+    *width = (int32_t)(((int64_t)S.W + m) >> reduce);          // decoder.go:289-295: (w + 1) / 2 per step
+    *height = (int32_t)(((int64_t)S.H + m) >> reduce);
+    return J2K_OK;
+}
+
 extern "C" void j2k_plan_destroy(j2k_plan *P) {
     if (!P) return;
     if (P->ctx) { (void)hipSetDevice(P->ctx->device); (void)hipStreamSynchronize(P->ctx->stream); }
+    for (ReducedTab &R : P->reduced) free_reduced(R);
     for (int cls = 0; cls < 2; cls++) {
         for (auto &T : P->fwd[cls]) { if (T.d_planes) (void)hipFree(T.d_planes); if (T.d_jobs) (void)hipFree(T.d_jobs); if (T.d_pjobs) (void)hipFree(T.d_pjobs); }
         if (cls == 0 && P->d_bigsym_off) { (void)hipFree(P->d_bigsym_off); P->d_bigsym_off = nullptr; }
@@ -737,6 +887,7 @@ static int spec_from_params(j2k_ctx *ctx, const j2k_params *p, PlanSpec &S) {
     S.coder = p->coder;
     S.tile_first = p->tile_first; S.tile_count = p->tile_count;
     S.closed_loop = p->closed_loop != 0;
+    S.mallat = p->closed_loop == J2K_CLOSED_LOOP_MALLAT;
     if (S.coder != J2K_CODER_MQ && S.coder != J2K_CODER_HT) return fail(ctx, J2K_ERR_INVALID_ARG, "coder");
     if (S.coder == J2K_CODER_MQ && !ctx->counted_mq) { ctx->counted_mq = true; g_mq_ctxs.fetch_add(1, std::memory_order_relaxed); }
     return J2K_OK;

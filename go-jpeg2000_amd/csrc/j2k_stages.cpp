@@ -9,6 +9,7 @@ using namespace j2k;
 static LevelLaunch mk(const LevelTab &T, int pf = 0) {
     LevelLaunch L{T.d_jobs, T.njobs, T.d_planes, T.cpl, T.vec, T.ncomp, pf};
     L.pjobs = T.d_pjobs; L.pnjobs = T.p_pix_only ? 0 : T.pnjobs; L.pwaves = T.pwaves; L.pmulti = T.pmulti;
+    L.mallat = T.mallat ? 1 : 0;
     return L;
 }
 
@@ -171,6 +172,51 @@ int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix
         }
     }
     return J2K_OK;
+}
+
+// A Mallat plan decoded `reduce` (>= 1) resolutions down: the inverse levels L-1 ... reduce only, the launch of level `reduce` as the final one
+// (inverse RCT / ICT, DC shift, int32(v + 0.5) for 9-7) into the reduced int32 frame [C][H_r][W_r]; reduce == L: no level runs.  The windows
+// of the resolutions above are never read.
+static int plan_inverse_reduced_impl(j2k_plan *P, const void *d_coeff, int reduce, int32_t *d_frame) {
+    j2k_ctx *ctx = P->ctx;
+    const PlanSpec &S = P->spec;
+    if (((uintptr_t)d_frame & 15) || ((uintptr_t)d_coeff & 15)) return fail(ctx, J2K_ERR_INVALID_ARG, "device pointers must be 16-byte aligned");
+    ReducedTab *R = nullptr;
+    int r = plan_reduced(P, reduce, &R);
+    if (r != J2K_OK) return r;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const double dq_step = (P->dequantize && S.quant == Q_ENCODER) ? 1.0 / (double)S.quality : 1.0;
+    if (reduce == S.levels) {
+        HIPCHK(ctx, launch_mallat_ll(ctx->stream, R->d_ll, R->nll, R->ll_samples, (const int32_t *)d_coeff, d_frame, S.wavelet == W97 ? 1 : 0, dq_step, S.dc_shift_inv));
+        return J2K_OK;
+    }
+    for (int l = S.levels - 1; l >= reduce; l--) {
+        const bool fin = l == reduce;
+        void *prev = (l & 1) ? P->d_scrB : P->d_scrA;                        // X_{l+1}
+        void *dst = fin ? (void *)d_frame : ((l & 1) ? P->d_scrA : P->d_scrB);  // X_l
+        for (int cls = 0; cls < 2; cls++) {
+            const LevelTab &T = fin ? R->inv[cls] : P->inv[cls][l];
+            if (!T.njobs) continue;
+            LevelLaunch L = mk(T);
+            if (S.wavelet == W53) {
+                profile_pair(ctx, 3, L.ev_start, L.ev_stop);
+                HIPCHK(ctx, launch_dwt53_inv(ctx->stream, L, (const int32_t *)d_coeff, (const int32_t *)prev, (int32_t *)dst, fin ? S.dc_shift_inv : 0, fin));
+            } else {
+                HIPCHK(ctx, launch_dwt97_inv(ctx->stream, L, d_coeff, S.quant == Q_NONE ? 1 : 0, (const double *)prev, dst, fin ? S.dc_shift_inv : 0, fin,
+                                             fin ? 2 : 0, (cls == 1) ? 1 : 0, dq_step));
+            }
+        }
+    }
+    return J2K_OK;
+}
+
+extern "C" int j2k_plan_inverse_reduced(j2k_plan *P, const int32_t *d_coeff, int reduce, int32_t *d_frame) {
+    if (!P || !d_frame || !d_coeff) return J2K_ERR_INVALID_ARG;
+    ReducedTab *R = nullptr;
+    int r = plan_reduced(P, reduce, &R);          // (the refusals come first, reduce = 0 included)
+    if (r != J2K_OK) return r;
+    if (reduce == 0) return plan_inverse_impl(P, d_coeff, d_frame);
+    return plan_inverse_reduced_impl(P, d_coeff, reduce, d_frame);
 }
 
 extern "C" int j2k_plan_forward(j2k_plan *P, const int32_t *d_frame, int32_t *d_coeff) {
@@ -360,6 +406,7 @@ extern "C" int j2k_convert_colorspace(j2k_ctx *ctx, int cs, int32_t *const *plan
 static bool pix_fusable(const j2k_plan *P, int bps, int channels, const void *d_pix, size_t stride, bool inverse, PixIO &io) {
     const PlanSpec &S = P->spec;
     const int prec = 8 * bps, pb = bps * channels;
+    if (S.mallat) return false;        // a Mallat plan has the general kernels only: pixels go through the int32 staging frame
     if (S.wavelet == W97) {
         // the lossy path -- the reference's default (jpeg2000.go:305-316) -- for image.RGBA at 8 bit: the workgroup kernels of level 0 read /
         // write the pixels (dwt97_l0wg.inc SRC 3, dwt97_l0wg_inv.inc PIX)
@@ -443,6 +490,48 @@ static int plan_pack_pixels(j2k_plan *P, const int32_t *d_planes, int ncomp, int
         i = k;
     }
     return J2K_OK;
+}
+
+// plan_pack_pixels for a reduced frame: W_r x H_r, tile (x0, y0, w, h) at (x0 >> reduce, y0 >> reduce), ceil(w / 2^reduce) x ceil(h / 2^reduce)
+static int plan_pack_pixels_reduced(j2k_plan *P, const ReducedTab &R, int reduce, const int32_t *d_planes, void *d_pix, size_t stride, const int *guard) {
+    j2k_ctx *ctx = P->ctx;
+    const PlanSpec &S = P->spec;
+    const bool whole = P->tile_count == P->tiles_x * P->tiles_y;
+    if (whole && !guard) return j2k_pack_pixels(ctx, d_planes, S.C, S.precision, R.Wr, R.Hr, d_pix, stride);
+    int r = j2k_pack_pixels(ctx, d_planes, S.C, S.precision, R.Wr, 0, d_pix, stride);        // (the argument checks; no rows)
+    if (r != J2K_OK) return r;
+    if (whole) {
+        HIPCHK(ctx, launch_pack_pixels_rect(ctx->stream, d_planes, S.C, S.precision, R.Wr, R.Hr, 0, 0, R.Wr, R.Hr, (uint8_t *)d_pix, stride, guard));
+        return J2K_OK;
+    }
+    const int m = (1 << reduce) - 1;
+    int last_tile = -1;
+    for (const Group &g : P->groups) {            // one rectangle per tile of the shard
+        if (g.tile == last_tile) continue;
+        last_tile = g.tile;
+        HIPCHK(ctx, launch_pack_pixels_rect(ctx->stream, d_planes, S.C, S.precision, R.Wr, R.Hr, g.x0 >> reduce, g.y0 >> reduce, (g.w + m) >> reduce, (g.h + m) >> reduce,
+                                            (uint8_t *)d_pix, stride, guard));
+    }
+    return J2K_OK;
+}
+
+int plan_inverse_pixels_reduced_impl(j2k_plan *P, const int32_t *d_coeff, int reduce, void *d_pix, size_t stride, const int *guard) {
+    if (!P || !d_pix || !d_coeff) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    const PlanSpec &S = P->spec;
+    ReducedTab *R = nullptr;
+    int r = plan_reduced(P, reduce, &R);
+    if (r != J2K_OK) return r;
+    if (reduce == 0) return plan_inverse_pixels_impl(P, d_coeff, d_pix, stride, guard);
+    // (a Mallat plan's pixels always go through the int32 staging frame)
+    r = stage_reserve(ctx, 0, (size_t)R->Wr * R->Hr * S.C * 4 + 64);
+    if (r != J2K_OK) return r;
+    r = plan_inverse_reduced_impl(P, d_coeff, reduce, (int32_t *)ctx->stage[0]);
+    if (r != J2K_OK) return r;
+    return plan_pack_pixels_reduced(P, *R, reduce, (const int32_t *)ctx->stage[0], d_pix, stride, guard);
+}
+extern "C" int j2k_plan_inverse_pixels_reduced(j2k_plan *P, const int32_t *d_coeff, int reduce, void *d_pix, size_t stride) {
+    return plan_inverse_pixels_reduced_impl(P, d_coeff, reduce, d_pix, stride, nullptr);
 }
 
 extern "C" int j2k_plan_forward_rgba8(j2k_plan *P, const void *d_pix, size_t stride, int32_t *d_coeff) {
@@ -770,15 +859,19 @@ extern "C" int j2k_plan_set_dequantize(j2k_plan *P, int on) {
 extern "C" int j2k_plan_decode_blocks(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
                                       const uint8_t *d_numbps, int32_t *d_decoded) {
     if (!P || !d_stream || !d_offs || !d_lens || !d_numbps || !d_decoded) return J2K_ERR_INVALID_ARG;
+    return plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_stream, d_offs, d_lens, d_numbps, d_decoded, nullptr);
+}
+
+int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
+                            const uint8_t *d_numbps, int32_t *d_decoded, const BlockJob *d_placed) {
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int n = (int)P->blocks.size();
     if (!n) return J2K_OK;
     if (P->spec.coder == J2K_CODER_HT) {
         int r = stage_reserve(ctx, 2, ht_decode_scratch_words(n) * 4 + 256);
         if (r != J2K_OK) return r;
-        HIPCHK(ctx, launch_ht_decode(ctx->stream, P->d_djobs, n, d_stream, d_offs, d_lens, d_decoded, (uint32_t *)ctx->stage[2],
-                                     P->dec_coded_rows_only ? 1 : 0));
+        HIPCHK(ctx, launch_ht_decode(ctx->stream, d_djobs, n, d_stream, d_offs, d_lens, d_decoded, (uint32_t *)ctx->stage[2],
+                                     (d_placed || P->dec_coded_rows_only) ? 1 : 0, d_placed));
     } else {
         size_t wpj = 0;                                  // the one-block decoder's workspace holds the flags only
         int max_dim = 0;
@@ -796,7 +889,7 @@ extern "C" int j2k_plan_decode_blocks(j2k_plan *P, const uint8_t *d_stream, cons
         int r = stage_reserve(ctx, 2, gen_bytes + 256 + (split ? j2k::t1_dec_split_bytes((size_t)n) : 0));
         if (r != J2K_OK && split) { (void)hipGetLastError(); split = false; r = stage_reserve(ctx, 2, gen_bytes + 256); }
         if (r != J2K_OK) return r;
-        HIPCHK(ctx, launch_t1_decode(ctx->stream, P->d_djobs, n, d_stream, d_offs, d_lens, d_numbps, d_decoded,
+        HIPCHK(ctx, launch_t1_decode(ctx->stream, d_djobs, n, d_stream, d_offs, d_lens, d_numbps, d_decoded,
                                      (uint8_t *)ctx->stage[2], wpj, max_dim, ctx->t1_dec_general,
                                      split ? (uint8_t *)ctx->stage[2] + gen_bytes : nullptr, ctx->t1_dec_lanes, mq_throughput_mode() ? 1 : 0));
     }

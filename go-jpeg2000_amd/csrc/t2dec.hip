@@ -734,6 +734,23 @@ __global__ __launch_bounds__(256) void place_blocks_kernel(const BlockJob *__res
     }
 }
 
+// The block tables of a subset of the plan's jobs (a reduced-resolution decode: the jobs of the resolutions it needs, ids ascending):
+// entry i of the outputs = entry ids[i] of the frame's tables, so the block decoders can run on the subset's own job table
+__global__ __launch_bounds__(256) void select_blocks_kernel(const int *__restrict__ ids, int m, const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
+                                                            const uint8_t *__restrict__ numbps, uint64_t *__restrict__ offs_r, uint32_t *__restrict__ lens_r,
+                                                            uint8_t *__restrict__ numbps_r) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const int j = ids[i];
+    offs_r[i] = offs[j]; lens_r[i] = lens[j]; numbps_r[i] = numbps[j];
+}
+hipError_t launch_select_blocks(hipStream_t s, const int *ids, int m, const uint64_t *offs, const uint32_t *lens, const uint8_t *numbps, uint64_t *offs_r,
+                                uint32_t *lens_r, uint8_t *numbps_r) {
+    if (m <= 0) return hipSuccess;
+    hipLaunchKernelGGL(select_blocks_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, ids, m, offs, lens, numbps, offs_r, lens_r, numbps_r);
+    return hipGetLastError();
+}
+
 size_t t2_chain_bytes() { return sizeof(T2Chain); }
 
 hipError_t launch_t2_tile_chains(hipStream_t s, const uint8_t *cs, uint64_t len, const uint64_t *tile_offs, int ntiles, int tile_first,

@@ -65,9 +65,11 @@ SYMBOLS = [
     "j2k_t2_packet_sequence", "j2k_t2_packet_bound", "j2k_t2_encode_packet", "j2k_t2_decode_packet", "j2k_t2_encode_packets_device", "j2k_t2_decode_packets_device", "j2k_plan_t2_packets", "j2k_plan_t2_fill_cbs", "j2k_tagtree_shape", "j2k_tcd_init_tile",
     "j2k_plan_frame_bound", "j2k_plan_encode_tile_parts", "j2k_plan_decode_tile_parts", "j2k_plan_place_blocks", "j2k_plan_frame_status", "j2k_plan_frame_parallel_tiles",
     "j2k_plan_encode_frame_pixels", "j2k_plan_decode_frame_pixels", "j2k_encode_pixels_host", "j2k_decode_pixels_host",
+    "j2k_plan_reduced_size", "j2k_plan_inverse_reduced", "j2k_plan_inverse_pixels_reduced", "j2k_plan_decode_frame_pixels_reduced", "j2k_decode_pixels_host_reduced",
     "j2k_plan_pack_bound", "j2k_plan_pack_stream", "j2k_plan_unpack_stream", "j2k_plan_unpack_streams",
     "j2k_comm_load_error", "j2k_comm_get_unique_id", "j2k_comm_create", "j2k_comm_destroy", "j2k_comm_last_error", "j2k_comm_stream", "j2k_gather_streams", "j2k_comm_wait",
 ]
+CLOSED_LOOP_MALLAT = 2                               # j2k_params.closed_loop: the closed loop over a Mallat decomposition
 T2_FRESH, T2_WIDE_LEN, T2_SEATED = 1, 2, 4          # j2k_t2_dev_packet.flags (closed-loop mode)
 PIX_GRAY8, PIX_GRAY16, PIX_RGBA8, PIX_RGBA64, PIX_NRGBA8, PIX_NRGBA64 = range(6)
 IMG_YCBCR, IMG_CMYK, IMG_PALETTED = 16, 17, 18       # j2k_image.kind (encoder.go:178-195, the default branch)

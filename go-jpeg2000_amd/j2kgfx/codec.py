@@ -45,7 +45,7 @@ def _stage(fn):
 class FramePlan:
     def __init__(self, width, height, ncomp, precision=8, lossless=True, quality=0, num_resolutions=6,
                  cb=(64, 64), tile=(0, 0), coder=_lib.CODER_MQ, is_signed=False, tile_first=0, tile_count=0,
-                 ctx=None, track_streams=True, frame_rows=0, closed_loop=False, dequantize=False):
+                 ctx=None, track_streams=True, frame_rows=0, closed_loop=False, dequantize=False, mallat=False):
         self.ctx = ctx or default_context()
         self.track_streams = bool(track_streams)
         self._ext_stream = None
@@ -55,7 +55,10 @@ class FramePlan:
                                   num_resolutions=num_resolutions, cb_w=cb[0], cb_h=cb[1], tile_w=tile[0],
                                   tile_h=tile[1], coder=coder, tile_first=tile_first, tile_count=tile_count,
                                   frame_rows=frame_rows,    # frame_rows > 0: a batch of height / frame_rows frames stacked vertically
-                                  closed_loop=int(bool(closed_loop)))   # this library's closed-loop mode (not the reference): windows that partition the plane, readable packets
+                                  # this library's closed-loop mode (not the reference): windows that partition the plane, readable packets;
+                                  # mallat (implies it): level l of the transform on the rectangle [0, w_l) x [0, h_l), so the windows are sub-bands
+                                  closed_loop=_lib.CLOSED_LOOP_MALLAT if mallat else int(bool(closed_loop)))
+        self.mallat = bool(mallat)
         h = C.c_void_p()
         self.ctx.check(L.j2k_plan_create(self.ctx.h, C.byref(self.params), C.byref(h)))
         self.h = h
@@ -135,8 +138,20 @@ class FramePlan:
         self.ctx.check(self.ctx.L.j2k_plan_forward(self.h, self._p(frame), self._p(coeff)))
         return coeff
 
+    def reduced_shape(self, reduce):
+        """Mallat plans: (H_r, W_r) = ceil(H / 2^reduce), ceil(W / 2^reduce) of a decode with reduce=... (j2k_plan_reduced_size)"""
+        w, h = C.c_int32(0), C.c_int32(0)
+        self.ctx.check(self.ctx.L.j2k_plan_reduced_size(self.h, int(reduce), C.byref(w), C.byref(h)))
+        return int(h.value), int(w.value)
+
     @_stage
-    def inverse(self, coeff, frame=None):
+    def inverse(self, coeff, frame=None, reduce=0):
+        """reduce > 0 (Mallat plans): stop at level `reduce`, frame = int32 [C, H_r, W_r] (reduced_shape)"""
+        if reduce:
+            t = _torch()
+            frame = frame if frame is not None else t.empty((self.ncomp,) + self.reduced_shape(reduce), dtype=t.int32, device=self.device)
+            self.ctx.check(self.ctx.L.j2k_plan_inverse_reduced(self.h, self._p(coeff), int(reduce), self._p(frame)))
+            return frame
         frame = frame if frame is not None else self.alloc_frame()
         self.ctx.check(self.ctx.L.j2k_plan_inverse(self.h, self._p(coeff), self._p(frame)))
         return frame
@@ -246,8 +261,11 @@ class FramePlan:
         return dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
 
     @_stage
-    def inverse_pixels(self, coeff, pix):
-        """inverse path + createImage for the plan's component count and precision into pix (device uint8 [H, stride])."""
+    def inverse_pixels(self, coeff, pix, reduce=0):
+        """inverse path + createImage for the plan's component count and precision into pix (device uint8 [H, stride]; reduce > 0: [H_r, stride])."""
+        if reduce:
+            self.ctx.check(self.ctx.L.j2k_plan_inverse_pixels_reduced(self.h, self._p(coeff), int(reduce), self._p(pix), C.c_size_t(int(pix.shape[1]))))
+            return pix
         self.ctx.check(self.ctx.L.j2k_plan_inverse_pixels(self.h, self._p(coeff), self._p(pix), C.c_size_t(int(pix.shape[1]))))
         return pix
 
@@ -339,8 +357,13 @@ class FramePlan:
         return out, tile_offs
 
     @_stage
-    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False):
-        """tile-parts cs[:length] -> pixels into pix (device uint8 [H, stride])"""
+    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0):
+        """tile-parts cs[:length] -> pixels into pix (device uint8 [H, stride]; reduce > 0, Mallat plans: [H_r, stride], and only the
+        code-blocks of the resolutions it needs are decoded)"""
+        if reduce:
+            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_reduced(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
+                                                                           int(bool(sop)), int(bool(eph)), int(reduce), self._p(pix), C.c_size_t(int(pix.shape[1]))))
+            return pix
         self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
                                                                int(bool(sop)), int(bool(eph)), self._p(pix), C.c_size_t(int(pix.shape[1]))))
         return pix
@@ -363,10 +386,14 @@ class FramePlan:
         self.ctx.check(st)
         return dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
 
-    def decode_pixels_host(self, cs, shape, sop=False, eph=False):
-        """closed-loop plans: tile-parts (bytes / numpy uint8) -> numpy uint8 pixels of `shape` = (H, stride)"""
+    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0):
+        """closed-loop plans: tile-parts (bytes / numpy uint8) -> numpy uint8 pixels of `shape` = (H, stride); reduce > 0: (H_r, stride)"""
         cs = np.ascontiguousarray(np.frombuffer(bytes(cs), np.uint8) if not isinstance(cs, np.ndarray) else cs, dtype=np.uint8)
         pix = np.zeros(shape, np.uint8)
+        if reduce:
+            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_reduced(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
+                                                                     int(reduce), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
+            return pix
         self.ctx.check(self.ctx.L.j2k_decode_pixels_host(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
                                                          pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
         return pix

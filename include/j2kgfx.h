@@ -192,8 +192,24 @@ typedef struct {
                                    row -> column, and j2k_plan_encode_tile_parts / j2k_plan_decode_tile_parts write and
                                    read packets with the J2K_T2_* flags below, so that pixels -> tile-parts -> pixels is
                                    a bit-exact round trip with the MQ coder.  Transform, block coders and every byte of
-                                   a code-block are the reference's in both modes */
+                                   a code-block are the reference's in both modes.
+                                   2 (J2K_CLOSED_LOOP_MALLAT): the closed-loop mode with a Mallat decomposition under it, also
+                                   outside reference parity.  In modes 0 and 1 level l+1 of the transform runs on the first
+                                   w_{l+1} h_{l+1} LINEAR elements of the plane (dwt.DecomposeMultiLevel53/97, dwt.go:524-573):
+                                   only level 0 decorrelates the picture and the rectangles above are labels, not sub-bands.
+                                   Here level l is the reference's single-level 2-D transform (Forward2D53 / Forward2D97,
+                                   dwt.go:356-473) on the RECTANGLE [0,w_l) x [0,h_l) of the plane, read as a dense w_l x h_l
+                                   matrix and written back in place (row stride = the plane's width); the inverse walks the
+                                   levels back the same way.  DC shift, RCT / ICT and its rounding, the float64 plane kept
+                                   across all 9-7 levels, the quantiser, int32(v + 0.5), j2k_plan_set_dequantize, the windows,
+                                   job order, block coders, packets, tile-parts, batches and shards are those of mode 1 --
+                                   the windows now ARE the sub-bands of each resolution, streams are smaller, and
+                                   LL_r is a picture: the j2k_plan_*_reduced calls below.  Every level runs as its own
+                                   launch of the general kernels (none of the workgroup / tail / deep forms is built), so
+                                   pixels go through the int32 staging frame and j2k_plan_pixels_fused reports 0.  The
+                                   streams are still not Part-1 conformant: the packet headers are the reference's */
 } j2k_params;
+#define J2K_CLOSED_LOOP_MALLAT 2
 
 typedef struct {
     int64_t tiles;              /* tiles in this shard                                        */
@@ -633,6 +649,27 @@ int j2k_plan_encode_frame_pixels(j2k_plan *plan, int format, const void *d_pix, 
                                  uint8_t *d_out, size_t cap, uint64_t *d_tile_offs);
 int j2k_plan_decode_frame_pixels(j2k_plan *plan, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
                                  void *d_pix, size_t stride);
+
+/* ---- reduced-resolution decode of a Mallat plan (j2k_params.closed_loop = J2K_CLOSED_LOOP_MALLAT): Config.ReduceResolution -------
+ * reduce = r runs the inverse levels L-1 ... r only (L = num_resolutions - 1) and takes LL_r as the frame: inverse RCT / ICT, DC shift
+ * and the pixel pack at ceil(W / 2^r) x ceil(H / 2^r), the reference's output size (decodeTiles, decoder.go:289-295: (w + 1) / 2 per
+ * step; the reference itself decodes no pixels there).  Tile (x0, y0, w, h) lands at (x0 >> r, y0 >> r) with ceil(w / 2^r) x
+ * ceil(h / 2^r) samples.  Explicit calls, not plan state: a captured graph means what it says.
+ *   J2K_ERR_UNSUPPORTED   a plan that is not Mallat
+ *   J2K_ERR_INVALID_ARG   reduce < 0 or > L; a tiled frame whose tile_w or tile_h is not a multiple of 2^r; a batch whose frame_rows
+ *                         is not a multiple of 2^r (the reduced tiles would not cover the reduced frame exactly once)
+ * reduce = 0 is exactly the call without it.  d_frame = [C][H_r][W_r] int32; pixels in the plan's own format, as
+ * j2k_plan_inverse_pixels; a shard writes its own tiles only.  The decode calls parse every packet (a tile's packets are in component ->
+ * resolution order) but decode and place only the code-blocks of the resolutions <= num_resolutions - 1 - r -- with the MQ coder the
+ * block decoder is where the time is -- and, like j2k_plan_decode_frame_pixels, write nothing into d_pix while the plan's status word
+ * is set.  The tables of an r are made at its first use (so: once before j2k_ctx_capture_begin) and kept in the plan. */
+int j2k_plan_reduced_size(const j2k_plan *plan, int reduce, int32_t *width, int32_t *height);
+int j2k_plan_inverse_reduced(j2k_plan *plan, const int32_t *d_coeff, int reduce, int32_t *d_frame);
+int j2k_plan_inverse_pixels_reduced(j2k_plan *plan, const int32_t *d_coeff, int reduce, void *d_pix, size_t stride);
+int j2k_plan_decode_frame_pixels_reduced(j2k_plan *plan, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs,
+                                         int sop, int eph, int reduce, void *d_pix, size_t stride);
+int j2k_decode_pixels_host_reduced(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, int reduce,
+                                   void *pix, size_t stride);
 
 /* The block coder's outputs as those tables.  j2k_plan_t2_packets (host table out): one packet per (tile, component,
  * resolution) of the plan in job order (encoder.go:616-673: tile, component, resolution, band, block row, block column), its
