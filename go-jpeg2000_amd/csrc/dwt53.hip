@@ -1381,17 +1381,23 @@ static hipError_t inv_go(hipStream_t s, const LevelLaunch &L, const int32_t *coe
     } while (0)
 
 hipError_t launch_dwt53_fwd(hipStream_t s, const LevelLaunch &L, const int32_t *src, int32_t *out, int32_t *nxt, int dc_shift) {
-    if (L.mallat && (L.wg_waves > 0 || L.pnjobs > 0 || L.pix_stride > 0)) return hipErrorInvalidValue;   // Mallat plans have the general kernels only
     if (L.wg_waves > 0) {      // packed RGBA8 level 0, workgroup form (dwt53_l0pix.inc); geometry checked by the plan
         if (L.njobs <= 0 && L.njobs2 <= 0) return hipSuccess;
         if (L.pix_stride <= 0 || L.ncomp != 3) return hipErrorInvalidValue;
+        if (L.mallat) {        // a Mallat plan: eight waves, nt stores, RGBA8 pixels, level 0 alone (all the plan builds a table for)
+            if (L.wg_waves != 8 || L.wg_store != 1 || L.njobs2 > 0 || L.ycc.y || L.njobs <= 0) return hipErrorInvalidValue;
+            hipExtLaunchKernelGGL((dwt53_fwd_rgba8_wg_kernel<8, 1, 6, true>), dim3(L.njobs), dim3(8 * 64), 0, s, L.ev_start, L.ev_stop, 0,
+                                  L.jobs, L.njobs, L.planes, reinterpret_cast<const uint32_t *>(src), out, nxt, dc_shift, L.pix_stride);
+            return hipGetLastError();
+        }
         if (L.wg_waves == 4) return fwd_wg_go<4>(s, L, src, out, nxt, dc_shift);
         if (L.wg_waves == 8) return fwd_wg_go<8>(s, L, src, out, nxt, dc_shift);
         return hipErrorInvalidValue;
     }
     if (L.pwaves > 0 && L.pnjobs > 0 && (L.ncomp == 1 || L.pix_stride <= 0 || L.pix_src == 4)) {     // planes in workgroup form (dwt53_plane_wg.inc)
-#define J2K_PWG(NW, NC, SRC, MULTI, WPE) hipExtLaunchKernelGGL((dwt53_fwd_plane_wg_kernel<NW, NC, SRC, MULTI, WPE>), dim3(L.pnjobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
+#define J2K_PWG1(NW, NC, SRC, MULTI, WPE, MAL) hipExtLaunchKernelGGL((dwt53_fwd_plane_wg_kernel<NW, NC, SRC, MULTI, WPE, MAL>), dim3(L.pnjobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
                                                  L.pjobs, L.pnjobs, L.planes, (const void *)src, out, nxt, dc_shift, L.pix_stride, (int64_t)L.comp_elems)
+#define J2K_PWG(NW, NC, SRC, MULTI, WPE) do { if (L.mallat) J2K_PWG1(NW, NC, SRC, MULTI, WPE, true); else J2K_PWG1(NW, NC, SRC, MULTI, WPE, false); } while (0)
 #define J2K_PWGM(NW, NC, SRC, WPE) do { if (L.pmulti) J2K_PWG(NW, NC, SRC, true, WPE); else J2K_PWG(NW, NC, SRC, false, WPE); } while (0)
         if (L.pix_stride > 0 && L.pix_src != 1) {     // Gray8 / a channel of a four-channel pixel / RGBA64 (four waves per workgroup only)
             if (L.pwaves != 4 || L.comp_elems <= 0) return hipErrorInvalidValue;
@@ -1409,17 +1415,24 @@ hipError_t launch_dwt53_fwd(hipStream_t s, const LevelLaunch &L, const int32_t *
 #undef J2K_PWG2
 #undef J2K_PWGM
 #undef J2K_PWG
+#undef J2K_PWG1
         return hipGetLastError();
     }
+    if (L.mallat && L.pix_stride > 0) return hipErrorInvalidValue;   // Mallat plans read packed pixels in the workgroup forms only
     J2K_DISPATCH(fwd_go, s, L, src, out, nxt, dc_shift);
 }
 hipError_t launch_dwt53_inv(hipStream_t s, const LevelLaunch &L, const int32_t *coef, const int32_t *prev, int32_t *dst,
                             int dc_shift, int final_level) {
-    if (L.mallat && (L.wg_waves > 0 || L.pnjobs > 0 || L.pix_stride > 0)) return hipErrorInvalidValue;
     if (L.wg_waves > 0) {      // level 0 straight to a packed RGBA8 frame, workgroup form (dwt53_l0pix.inc)
         if (L.njobs <= 0) return hipSuccess;
         if (L.pix_stride <= 0 || L.ncomp != 3 || !final_level) return hipErrorInvalidValue;
         uint32_t *pix = reinterpret_cast<uint32_t *>(dst);
+        if (L.mallat) {        // a Mallat plan: four waves, everything in registers (all the plan builds a table for)
+            if (L.wg_waves != 4 || L.wg_store != 5) return hipErrorInvalidValue;
+            hipExtLaunchKernelGGL((dwt53_inv_rgba8_wg_kernel<4, 5, false, true>), dim3(L.njobs), dim3(4 * 64), 0, s, L.ev_start, L.ev_stop, 0,
+                                  L.jobs, L.njobs, L.planes, coef, prev, pix, dc_shift, L.pix_stride, L.guard);
+            return hipGetLastError();
+        }
 #define J2K_INVWG(NW, WPE) hipExtLaunchKernelGGL((dwt53_inv_rgba8_wg_kernel<NW, WPE>), dim3(L.njobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
                                              L.jobs, L.njobs, L.planes, coef, prev, pix, dc_shift, L.pix_stride, L.guard)
         const int wpe = L.wg_store;    // (inverse: occupancy variant, J2K_L0_INV_WPE: 5 = everything in registers, 6 / 7 = odd row parked in LDS)
@@ -1431,8 +1444,9 @@ hipError_t launch_dwt53_inv(hipStream_t s, const LevelLaunch &L, const int32_t *
     }
     if (L.pwaves > 0 && L.pnjobs > 0 && (L.ncomp == 1 || L.pix_stride <= 0 || L.pix_src == 4)) {     // planes in workgroup form (dwt53_plane_wg.inc)
         if (L.pix_stride > 0 && !final_level) return hipErrorInvalidValue;
-#define J2K_PWG(NW, NC, DST, MULTI, WPE) hipExtLaunchKernelGGL((dwt53_inv_plane_wg_kernel<NW, NC, DST, MULTI, WPE>), dim3(L.pnjobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
+#define J2K_PWG1(NW, NC, DST, MULTI, WPE, MAL) hipExtLaunchKernelGGL((dwt53_inv_plane_wg_kernel<NW, NC, DST, MULTI, WPE, MAL>), dim3(L.pnjobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
                                                  L.pjobs, L.pnjobs, L.planes, coef, prev, (void *)dst, dc_shift, final_level, L.pix_stride, (int64_t)L.comp_elems, L.guard)
+#define J2K_PWG(NW, NC, DST, MULTI, WPE) do { if (L.mallat) J2K_PWG1(NW, NC, DST, MULTI, WPE, true); else J2K_PWG1(NW, NC, DST, MULTI, WPE, false); } while (0)
 #define J2K_PWGM(NW, NC, DST, WPE) do { if (L.pmulti) J2K_PWG(NW, NC, DST, true, WPE); else J2K_PWG(NW, NC, DST, false, WPE); } while (0)
         if (L.pix_stride > 0 && L.pix_src != 1) {
             if (L.pwaves != 4 || L.comp_elems <= 0) return hipErrorInvalidValue;
@@ -1450,8 +1464,10 @@ hipError_t launch_dwt53_inv(hipStream_t s, const LevelLaunch &L, const int32_t *
 #undef J2K_PWG2
 #undef J2K_PWGM
 #undef J2K_PWG
+#undef J2K_PWG1
         return hipGetLastError();
     }
+    if (L.mallat && L.pix_stride > 0) return hipErrorInvalidValue;   // Mallat plans write packed pixels in the workgroup forms only
     J2K_DISPATCH(inv_go, s, L, coef, prev, dst, dc_shift, final_level);
 }
 

@@ -61,9 +61,11 @@ template <int NW, int NT>
 __device__ __forceinline__ void dwt53_fwd_rgba8_wg_body(v4i (&slot)[NW][6][64], const DwtJob job, const DwtPlane *__restrict__ planes,
                                                         const uint32_t *__restrict__ pix, int32_t *__restrict__ out, int32_t *__restrict__ nxt,
                                                         int dc_shift, int pix_stride) {
+    constexpr bool MAL = false;                    // (the merged launch is not built for Mallat plans)
 #include "dwt53_l0pix_fwd_body.inc"
 }
-template <int NW, int NT, int WPE>
+// MAL: the level 0 of a Mallat plan (the body's store_row)
+template <int NW, int NT, int WPE, bool MAL = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void dwt53_fwd_rgba8_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                                const uint32_t *__restrict__ pix, int32_t *__restrict__ out, int32_t *__restrict__ nxt,
@@ -85,6 +87,7 @@ void dwt53_fwd_ycc_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
     __shared__ v4i slot[NW][6][64];
     const DwtJob job = jobs[blockIdx.x];
     if (job.plane < 0) return;
+    constexpr bool MAL = false;                    // (prefix plans only: plan_rgba8_wg_fusable)
 #include "dwt53_l0pix_fwd_body.inc"
 }
 #undef J2K_L0_YCC
@@ -103,7 +106,9 @@ void dwt53_fwd_ycc_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
 // Coefficients are arbitrary int32 here (a decoder's input): every sum wraps like Go's int32 and the mirror rules are real
 // selects, not the small-value shortcuts of the forward kernel.
 // ================================================================================================================
-template <int NW, bool PARK>
+// MAL: the level 0 of a Mallat plan -- load_row routes as inv_load_row<MAL> does: LL (the low half of a low-pass row, while there is a coarser
+// level) from its dense (w/2) x ceil(h/2) result, every other half-row from the plane at row * coef_stride + column.
+template <int NW, bool PARK, bool MAL = false>
 __device__ __forceinline__ void dwt53_inv_rgba8_wg_body(v4i (&slot)[NW][PARK ? 8 : 6][64], const DwtJob job, const DwtPlane *__restrict__ planes,
                                                         const int32_t *__restrict__ coef, const int32_t *__restrict__ prev, uint32_t *__restrict__ pix,
                                                         int dc_shift, int pix_stride) {
@@ -126,6 +131,16 @@ __device__ __forceinline__ void dwt53_inv_rgba8_wg_body(v4i (&slot)[NW][PARK ? 8
     // row `ro` of the level matrix: v[2k] = L part, v[2k+1] = H part of component k; elements below n_next come from the
     // coarser level's output (prev), the rest from the coefficient plane -- uniform per half-row (n_next % (w/2) == 0)
     auto load_row = [&](int ro, v4i (&v)[6]) {
+        if constexpr (MAL) {
+            const bool ll = P.n_next != 0 && ro < halfH;
+            const int offP = ro * P.coef_stride + lo4, offL = ll ? ro * halfW + lo4 : offP;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                v[2 * k] = *reinterpret_cast<const v4i *>((ll ? prev + P.nxt_off[k] : coef + P.src_off[k]) + offL);
+                v[2 * k + 1] = *reinterpret_cast<const v4i *>(coef + P.src_off[k] + offP + halfW);
+            }
+            return;
+        }
         const int idxL = ro * w + lo4, idxH = idxL + halfW;
         const bool finL = ro * w >= P.n_next, finH = ro * w + halfW >= P.n_next;
 #pragma unroll
@@ -248,7 +263,7 @@ __device__ __forceinline__ void dwt53_inv_rgba8_wg_body(v4i (&slot)[NW][PARK ? 8
         finish_row(2 * q + 1, D);
     }
 }
-template <int NW, int WPE, bool PARK = (WPE > 5)>
+template <int NW, int WPE, bool PARK = (WPE > 5), bool MAL = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void dwt53_inv_rgba8_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                                const int32_t *__restrict__ coef, const int32_t *__restrict__ prev, uint32_t *__restrict__ pix,
@@ -257,7 +272,7 @@ void dwt53_inv_rgba8_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
     if (guard && *guard) return;             // (the frame decoder: a stream that was refused leaves the caller's frame alone)
     const DwtJob job = jobs[blockIdx.x];
     if (job.plane < 0) return;
-    dwt53_inv_rgba8_wg_body<NW, PARK>(slot, job, planes, coef, prev, pix, dc_shift, pix_stride);
+    dwt53_inv_rgba8_wg_body<NW, PARK, MAL>(slot, job, planes, coef, prev, pix, dc_shift, pix_stride);
 }
 
 // ================================================================================================================

@@ -1,8 +1,8 @@
 // dwt53_l0pix_fwd_body.inc -- the statements of one workgroup of the packed-RGBA8 level-0 forward transform (see dwt53_l0pix.inc),
 // included TEXTUALLY by dwt53_fwd_rgba8_wg_kernel (its own static LDS array) and by dwt53_fwd_rgba8_wg_body (dynamic LDS of
 // dwt53_mega_fwd_kernel): as a function call the kernel lost two registers to the inliner's different schedule and spilled.
-// Names it expects in scope: NW, NT (template parameters), slot (v4i [NW][6][64] in LDS), job (DwtJob), planes, pix, out, nxt,
-// dc_shift, pix_stride.
+// Names it expects in scope: NW, NT (template parameters), MAL (a compile-time bool: Mallat routing of the stores, see store_row), slot
+// (v4i [NW][6][64] in LDS), job (DwtJob), planes, pix, out, nxt, dc_shift, pix_stride.
 
     constexpr int NR = NW - 1;                     // regular waves = pair-rows per workgroup
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -79,8 +79,22 @@
     };
     // n_next = (w/2) * h_next is a multiple of w/2, so "this half-row lies past the prefix that feeds level 1" is the same
     // for every lane: wave-uniform branches (a per-lane select would also make the compiler drop the nt flag)
+    // MAL (a Mallat plan, DwtPlane::coef_stride): the routing of fwd_store_row<MAL> -- LL (the low half of a low-pass row, while there is a
+    // next level) to its dense (w/2) x ceil(h/2) scratch, every other half-row to the plane at row * coef_stride + column; uniform as well
     auto store_row = [&](int ro, const v4i (&v)[6], int ysub) {
         if (!active) return;
+        if constexpr (MAL) {
+            const bool ll = P.n_next != 0 && ro < halfH;
+            const int offP = ro * P.coef_stride + lane * 4, offL = ll ? ro * halfW + lane * 4 : offP;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const v4i vl = (k == 0) ? v[0] - ysub : v[2 * k];
+                if (ll) *reinterpret_cast<v4i *>(nxt + P.nxt_off[k] + offL) = vl;
+                else st_final<NT>(reinterpret_cast<v4i *>(out + P.out_off[k] + offL), vl);
+                st_final<NT>(reinterpret_cast<v4i *>(out + P.out_off[k] + offP + halfW), v[2 * k + 1]);
+            }
+            return;
+        }
         const int idxL = ro * w + lane * 4, idxH = idxL + halfW;
         const bool finL = ro * w >= P.n_next, finH = ro * w + halfW >= P.n_next;
 #pragma unroll

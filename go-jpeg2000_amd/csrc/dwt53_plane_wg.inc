@@ -25,9 +25,12 @@ __device__ __forceinline__ v4i wsub4(const v4i &a, const v4i &b) { return (v4i)(
 //   4 = a 16-bit sample of an eight-byte pixel (image.RGBA64 / NRGBA64, high byte first); with NC = 3 channels 0, 1, 2.
 // pix_stride = the frame's row stride in PIXELS, comp_elems = W * H of the frame (src_off = component * comp_elems + y0 * W + x0).
 // MULTI: the plane has more than one 512-column strip.
+// MAL: a level of a Mallat plan (DwtPlane::coef_stride): half-rows are routed as fwd_store_row<MAL> / inv_load_row<MAL> route them -- LL (the
+// low half of a low-pass row, while n_next != 0) <-> the dense (w/2) x ceil(h/2) scratch of the next level, every other half-row <-> the
+// coefficient plane at row * coef_stride + column.  Wave-uniform per half-row like the prefix test; coef_stride % 4 == 0 (the plan's check).
 template <int SRC> struct PixSrc { static constexpr int PB = SRC == 1 ? 2 : SRC == 2 ? 1 : SRC == 3 ? 4 : 8, SB = (SRC == 1 || SRC == 4) ? 2 : 1; };
 __device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xFF) << 8) | ((v >> 8) & 0xFF); }
-template <int NW, int NC, int SRC, bool MULTI, int WPE>
+template <int NW, int NC, int SRC, bool MULTI, int WPE, bool MAL = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void dwt53_fwd_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                                const void *__restrict__ src, int32_t *__restrict__ out, int32_t *__restrict__ nxt, int dc_shift,
@@ -152,6 +155,17 @@ void dwt53_fwd_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
     // n_next = (w/2) * h_next is a multiple of w/2: "this half-row lies past the prefix that feeds the next level" is wave-uniform
     auto store_row = [&](int ro, const v4i (&v)[NV]) {
         if (!active) return;
+        if constexpr (MAL) {
+            const bool ll = P.n_next != 0 && ro < halfH;
+            const int64_t offP = (int64_t)ro * P.coef_stride + (c >> 1), offL = ll ? (int64_t)ro * halfW + (c >> 1) : offP;
+#pragma unroll
+            for (int k = 0; k < NC; k++) {
+                if (ll) *reinterpret_cast<v4i *>(nxt + P.nxt_off[k] + offL) = v[2 * k];
+                else st_final<1>(reinterpret_cast<v4i *>(out + P.out_off[k] + offL), v[2 * k]);
+                st_final<1>(reinterpret_cast<v4i *>(out + P.out_off[k] + offP + halfW), v[2 * k + 1]);
+            }
+            return;
+        }
         const int64_t idxL = (int64_t)ro * w + (c >> 1), idxH = idxL + halfW;
         const bool finL = (int64_t)ro * w >= P.n_next, finH = (int64_t)ro * w + halfW >= P.n_next;
 #pragma unroll
@@ -234,7 +248,7 @@ void dwt53_fwd_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
 // ================================================================================================================
 // NC = 3: level 0 of an RGB triple, inverse RCT (mct.go:56-66) + DC shift to three int32 planes (the planar twin of
 // dwt53_inv_rgba8_wg_kernel).
-template <int NW, int NC, int DST, bool MULTI, int WPE>
+template <int NW, int NC, int DST, bool MULTI, int WPE, bool MAL = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void dwt53_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
                                const int32_t *__restrict__ coef, const int32_t *__restrict__ prev, void *__restrict__ dst,
@@ -263,10 +277,14 @@ void dwt53_inv_plane_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
     // row `ro` of the level matrix; elements below n_next come from prev (uniform per half-row: n_next % (w/2) == 0)
     auto load_row = [&](int ro, v4i (&v)[NV]) {
         const int64_t rowL = (int64_t)ro * w, rowH = rowL + halfW;
+        const bool ll = MAL && P.n_next != 0 && ro < halfH;                 // MAL: bl, bh = where the two half-rows start
+        const int64_t rowP = MAL ? (int64_t)ro * P.coef_stride : 0;
 #pragma unroll
         for (int k = 0; k < NC; k++) {
-            const int32_t *bl = (rowL >= P.n_next ? coef + P.src_off[k] : prev + P.nxt_off[k]) + rowL;
-            const int32_t *bh = (rowH >= P.n_next ? coef + P.src_off[k] : prev + P.nxt_off[k]) + rowH;
+            const int32_t *bl = MAL ? (ll ? prev + P.nxt_off[k] + (int64_t)ro * halfW : coef + P.src_off[k] + rowP)
+                                    : (rowL >= P.n_next ? coef + P.src_off[k] : prev + P.nxt_off[k]) + rowL;
+            const int32_t *bh = MAL ? coef + P.src_off[k] + rowP + halfW
+                                    : (rowH >= P.n_next ? coef + P.src_off[k] : prev + P.nxt_off[k]) + rowH;
             v[2 * k] = *reinterpret_cast<const v4i *>(bl + p4);
             v[2 * k + 1] = *reinterpret_cast<const v4i *>(bh + p4);
             if constexpr (MULTI) {

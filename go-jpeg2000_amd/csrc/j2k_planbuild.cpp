@@ -80,7 +80,11 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
     const int L = S.levels;
     const bool triple = S.mct && S.C >= 3;
     const int esz = S.wavelet == W97 ? 8 : 4;
-    const bool mal = S.mallat;          // a Mallat plan: the per-level launches with the MAL kernels for every level, none of the specialised forms
+    // a Mallat plan: the MAL kernels for every level, one general launch each.  Of the specialised 5-3 forms it has the two that read / write
+    // packed pixels at level 0 -- the RGBA8 workgroup tables (the shapes the launchers have a MAL instantiation for) and the plane-workgroup
+    // table of level 0; not the tail / deep / mega / fused-level launches, not the plane-workgroup form below level 0 (measured: they did not pay,
+    // docs/KERNEL_NOTES.md "§4r, continued"), nothing 9-7
+    const bool mal = S.mallat;
 
     // ---- tile-components, coefficient + scratch offsets -------------------------
     int64_t coef = 0, sa = 0, sb = 0;
@@ -358,8 +362,11 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                 int r = upload(ctx, &T.d_planes, planes);
                 if (r == J2K_OK) r = upload(ctx, &T.d_jobs, jobs);
                 if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
-                if (!mal && S.wavelet == W53 && vec_ok && ctx->plane_wg > 0 && (cls == 0 || ctx->plane_wg3 || l == 0)) {   // both directions; cls 1 = level 0 of RGB triples: int32 planes (J2K_PLANE_WG3) or RGBA64 pixels
+                if ((!mal || l == 0) && S.wavelet == W53 && vec_ok && ctx->plane_wg > 0 && (cls == 0 || ctx->plane_wg3 || l == 0)) {   // both directions; cls 1 = level 0 of RGB triples: int32 planes (J2K_PLANE_WG3) or RGBA64 pixels
                     // workgroup form for single-component planes (dwt53_plane_wg.inc): whole 16-byte lanes, at least two rows
+                    // (a Mallat plan: level 0 only, where the form reads / writes the packed pixels.  vec_ok holds the rule that every tile-component
+                    //  of the table is a multiple of 4 wide, so the rows of its coefficient plane are 16-byte aligned; w % 8 == 0 below makes the
+                    //  half-row at column w / 2 aligned as well)
                     bool ok = true;
                     int multi = 0;
                     for (size_t i = 0; i < planes.size() && ok; i++) {
@@ -421,13 +428,15 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                         if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
                     }
                 }
-                if (!mal && dir == 0 && l == 0 && cls == 1 && S.wavelet == W53 && vec_ok && cpl == 8) {
-                    // the packed-pixel forward (j2k_plan_forward_rgba8) moves a third of the bytes per row on the read side
-                    // and likes shorter bands: its own job table (measured: 3 pair-rows 29.6 us, 5 pair-rows 31.9 us)
-                    std::vector<DwtJob> pj = build_jobs(ctx->band_prows_pix);
-                    P->fwd_pix_njobs = (int)pj.size();
-                    r = upload(ctx, &P->d_fwd_pix_jobs, pj);
-                    if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
+                if (dir == 0 && l == 0 && cls == 1 && S.wavelet == W53 && vec_ok && cpl == 8) {
+                    if (!mal) {     // (the general kernels have no packed-pixel Mallat instantiation)
+                        // the packed-pixel forward (j2k_plan_forward_rgba8) moves a third of the bytes per row on the read side
+                        // and likes shorter bands: its own job table (measured: 3 pair-rows 29.6 us, 5 pair-rows 31.9 us)
+                        std::vector<DwtJob> pj = build_jobs(ctx->band_prows_pix);
+                        P->fwd_pix_njobs = (int)pj.size();
+                        r = upload(ctx, &P->d_fwd_pix_jobs, pj);
+                        if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
+                    }
                     // workgroup form (dwt53_l0pix.inc): one job per workgroup of l0_wg waves = l0_wg - 1 pair-rows of one
                     // plane; its geometry contract: one 512-column strip, whole 16-byte lanes, at least two rows
                     bool wg_ok = ctx->l0_wg > 0;
@@ -474,20 +483,26 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                             }
                             return wj;
                         };
-                        std::vector<DwtJob> wj = wg_table(ctx->l0_wg);
-                        P->fwd_wg_njobs = (int)wj.size();
-                        P->fwd_wg_waves = ctx->l0_wg;
-                        r = upload(ctx, &P->d_fwd_wg_jobs, wj);
-                        if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
+                        // (a Mallat plan: only the shapes its kernels are instantiated for -- forward 8 waves with nt stores, inverse 4 waves
+                        //  with everything in registers, the defaults; any other setting keeps the general Mallat launch and staged pixels)
                         const int invw = ctx->l0_wg_invw > 0 ? ctx->l0_wg_invw : ctx->l0_wg;
-                        std::vector<DwtJob> ij = wg_table(invw, false, ctx->l0_xcd_group);      // (measured: inverse 25.2 -> 24.5 us at groups of 8; the forward table loses 0.5 us with it)
-                        P->inv_wg_njobs = (int)ij.size();
-                        P->inv_wg_waves = invw;
-                        r = upload(ctx, &P->d_inv_wg_jobs, ij);
-                        if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
+                        if (!mal || (ctx->l0_wg == 8 && ctx->l0_store == 1)) {
+                            std::vector<DwtJob> wj = wg_table(ctx->l0_wg);
+                            P->fwd_wg_njobs = (int)wj.size();
+                            P->fwd_wg_waves = ctx->l0_wg;
+                            r = upload(ctx, &P->d_fwd_wg_jobs, wj);
+                            if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
+                        }
+                        if (!mal || (invw == 4 && ctx->l0_inv_wpe == 5)) {
+                            std::vector<DwtJob> ij = wg_table(invw, false, ctx->l0_xcd_group);      // (measured: inverse 25.2 -> 24.5 us at groups of 8; the forward table loses 0.5 us with it)
+                            P->inv_wg_njobs = (int)ij.size();
+                            P->inv_wg_waves = invw;
+                            r = upload(ctx, &P->d_inv_wg_jobs, ij);
+                            if (r != J2K_OK) { j2k_plan_destroy(P); return r; }
+                        }
                         // merged launches (dwt53_mega_*_kernel): every level below 0 + the level-0 bands that neither feed nor
                         // need them, for frames of RGB triples only whose deep launch starts at level 1
-                        if (ctx->mega && P->deep_l0 == 1 && S.C == 3 && planes.size() == P->groups.size() && !P->deep_jobs_host.empty()) {
+                        if (!mal && ctx->mega && P->deep_l0 == 1 && S.C == 3 && planes.size() == P->groups.size() && !P->deep_jobs_host.empty()) {
                             const int order = ctx->mega;       // 1: deep, level-0 bands, flat; 2: deep, flat, level-0 bands
                             for (int d2 = 0; d2 < 2; d2++) {
                                 const int nr_top = (d2 == 0 ? ctx->l0_wg : invw) - 1;
@@ -516,7 +531,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                         }
                         // levels 0 + 1 in one launch (dwt53_fwd_rgba8_wg2_kernel): needs a level 1 (levels >= 2), only RGB
                         // triples in the frame (the level-1 plane table is then three planes per level-0 plane, same order)
-                        if (ctx->l0_fuse > 0 && L >= 2 && S.C == 3 && (P->tail_l0 < 0 || P->tail_l0 >= 2) && (P->deep_l0 < 0 || P->deep_l0 >= 2)) {
+                        if (!mal && ctx->l0_fuse > 0 && L >= 2 && S.C == 3 && (P->tail_l0 < 0 || P->tail_l0 >= 2) && (P->deep_l0 < 0 || P->deep_l0 >= 2)) {
                             auto xcd = [&](std::vector<DwtJob> &v) {
                                 if (!ctx->l0_xcd || v.size() < 64) return;
                                 const size_t chunk = (v.size() + 7) / 8;

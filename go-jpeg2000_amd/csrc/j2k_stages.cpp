@@ -403,10 +403,12 @@ extern "C" int j2k_convert_colorspace(j2k_ctx *ctx, int cs, int32_t *const *plan
 // (RGBA, NRGBA, RGBA64, NRGBA64).  The plan's precision must be the format's own (no rescale: encoder.go:196-210) and unsigned; single
 // components need the workgroup form of dwt53_plane_wg.inc (Gray16 also has a general kernel), 8-bit triples the packed-RGBA8 kernels,
 // 16-bit triples the plane kernels' NC = 3 form.
+// A Mallat plan fuses where a prefix plan of the same parameters would AND the level-0 launch that touches the pixels is a workgroup form:
+// the general kernels have no packed-pixel Mallat instantiation, so RGBA8 without its workgroup table and Gray16 without the plane table
+// keep the int32 staging frame.
 static bool pix_fusable(const j2k_plan *P, int bps, int channels, const void *d_pix, size_t stride, bool inverse, PixIO &io) {
     const PlanSpec &S = P->spec;
     const int prec = 8 * bps, pb = bps * channels;
-    if (S.mallat) return false;        // a Mallat plan has the general kernels only: pixels go through the int32 staging frame
     if (S.wavelet == W97) {
         // the lossy path -- the reference's default (jpeg2000.go:305-316) -- for image.RGBA at 8 bit: the workgroup kernels of level 0 read /
         // write the pixels (dwt97_l0wg.inc SRC 3, dwt97_l0wg_inv.inc PIX)
@@ -440,12 +442,17 @@ static bool pix_fusable(const j2k_plan *P, int bps, int channels, const void *d_
     if (T0.njobs) {
         io.single = channels == 1 ? (bps == 2 ? 1 : 2) : (bps == 2 ? 4 : 3);
         const bool wg = T0.pnjobs > 0 && !T0.p_pix_only;
-        if (io.single == 1 ? !(wg || (T0.vec && T0.cpl == 8)) : !(wg && T0.pwaves == 4)) return false;
+        if (io.single == 1 ? !(wg || (T0.vec && T0.cpl == 8 && !S.mallat)) : !(wg && T0.pwaves == 4)) return false;
         if (io.single == 1 && T1.njobs) return false;
     }
     if (T1.njobs) {
         if (channels != 4 || !S.mct) return false;
-        if (bps == 1) { if (!T1.vec || T1.cpl != 8) return false; io.triple = 8; }
+        if (bps == 1) {
+            if (!T1.vec || T1.cpl != 8) return false;
+            // (Mallat: the table exists only for the shapes the launchers have; the launch takes the store flavour / occupancy variant from the context)
+            if (S.mallat && (inverse ? !(P->d_inv_wg_jobs && P->ctx->l0_wg_inv && P->ctx->l0_inv_wpe == 5) : !(P->d_fwd_wg_jobs && P->ctx->l0_store == 1))) return false;
+            io.triple = 8;
+        }
         else { if (!T1.pnjobs || T1.pwaves != 4) return false; io.triple = 4; }
     }
     if (inverse && channels == 4 && !T1.njobs && S.C != 4) return false;      // three components on their own leave alpha unwritten
@@ -462,6 +469,7 @@ bool plan_rgba8_wg_fusable(const j2k_plan *P) {
     const PlanSpec &S = P->spec;
     PixIO io;
     const void *aligned = reinterpret_cast<const void *>(uintptr_t(256));     // (pix_fusable looks at the pointer's alignment only)
+    if (S.mallat) return false;        // (the YCbCr row source has no Mallat instantiation: the image is converted to RGBA8 first, and that frame takes the fused path)
     if (S.C != 3 || !S.mct || !pix_fusable(P, 1, 4, aligned, (size_t)S.W * 4, false, io) || io.triple != 8) return false;
     return P->d_fwd_wg_jobs && !P->d_fwd_wg2_jobs && !P->d_mega_fwd_jobs && P->ctx->l0_store == 1 && !P->fwd[0][0].njobs;
 }
@@ -523,7 +531,7 @@ int plan_inverse_pixels_reduced_impl(j2k_plan *P, const int32_t *d_coeff, int re
     int r = plan_reduced(P, reduce, &R);
     if (r != J2K_OK) return r;
     if (reduce == 0) return plan_inverse_pixels_impl(P, d_coeff, d_pix, stride, guard);
-    // (a Mallat plan's pixels always go through the int32 staging frame)
+    // (the final launch of a reduced decode writes the int32 staging frame: its pixels are not fused)
     r = stage_reserve(ctx, 0, (size_t)R->Wr * R->Hr * S.C * 4 + 64);
     if (r != J2K_OK) return r;
     r = plan_inverse_reduced_impl(P, d_coeff, reduce, (int32_t *)ctx->stage[0]);

@@ -204,10 +204,17 @@ typedef struct {
                                    across all 9-7 levels, the quantiser, int32(v + 0.5), j2k_plan_set_dequantize, the windows,
                                    job order, block coders, packets, tile-parts, batches and shards are those of mode 1 --
                                    the windows now ARE the sub-bands of each resolution, streams are smaller, and
-                                   LL_r is a picture: the j2k_plan_*_reduced calls below.  Every level runs as its own
-                                   launch of the general kernels (none of the workgroup / tail / deep forms is built), so
-                                   pixels go through the int32 staging frame and j2k_plan_pixels_fused reports 0.  The
-                                   streams are still not Part-1 conformant: the packet headers are the reference's */
+                                   LL_r is a picture: the j2k_plan_*_reduced calls below.  Lossless plans have, at level 0,
+                                   the packed-RGBA8 workgroup form and single-component planes in workgroup form, where
+                                   the geometry admits them (the prefix contracts; they imply tiles a multiple of 8 wide):
+                                   the *_pixels calls then read / write the pixels in the level-0 launch, and
+                                   j2k_plan_pixels_fused reports 1, wherever a plan of modes 0 / 1 would AND that launch
+                                   is one of these workgroup forms -- RGBA8 without its workgroup table and Gray16 without
+                                   the plane table keep the int32 staging frame (report 0).  Every level below level 0 is
+                                   one launch of the general kernels.  Not built: the tail / deep / merged / fused-level
+                                   launches and the plane form below level 0, the 9-7 workgroup forms, image sources read
+                                   directly, pixel fusion of a reduced decode's final launch.
+                                   The streams are still not Part-1 conformant: the packet headers are the reference's */
 } j2k_params;
 #define J2K_CLOSED_LOOP_MALLAT 2
 
