@@ -184,13 +184,103 @@ __device__ __forceinline__ uint32_t get_bits8(const uint32_t *buf, uint32_t bitp
     return (uint32_t)(two >> sh) & 0xFF;
 }
 
+// One quad pair's share of the two bit strings: its VLC bits (vv, vl of them) and its eight MagSgn fields (ml bits in all).
+struct HtItem {
+    uint64_t vv;
+    uint32_t vl, ml;
+    uint32_t mval[8], mlen[8];
+};
+
+// The code words and MagSgn fields of quad pair `it` (row it / P, pair it % P).  bad is set on the reference's panic domain (MinInt32).
+// LROWS: the coded rows (y % 4 == 0) were staged in LDS by the caller's max scan (row r at lrows + r * w): no second trip to memory.
+template <bool LROWS>
+__device__ __forceinline__ void ht_form_item(const BlockJob &J, const int32_t *__restrict__ src, int it, int P, bool vec_ok,
+                                             const int32_t *lrows, const uint16_t *enc, HtItem &I, int &bad) {
+    const int w = J.w, stride = LROWS ? J.w : J.stride;
+    const int r = it / P, pi = it - r * P;
+    const int initial = (r == 0);
+    const int32_t *row = LROWS ? lrows + r * w : src + (size_t)(4 * r) * stride;
+    const int xb = pi * 8;
+    int v[8];
+    if ((LROWS || vec_ok) && xb + 8 <= w) {
+        const int4 a = *reinterpret_cast<const int4 *>(row + xb), b = *reinterpret_cast<const int4 *>(row + xb + 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int t = row[xb + i < w ? xb + i : w - 1];        // clamped index: unconditional load
+            v[i] = (xb + i < w) ? t : 0;
+        }
+    }
+    uint32_t rho = 0, rho2 = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if (v[i] != 0) rho |= 1u << i;
+        if (v[4 + i] != 0) rho2 |= 1u << i;
+    }
+    const uint32_t e1 = enc[(initial << 6) | rho];
+    const uint32_t e2 = enc[(initial << 6) | ((rho >> 2) << 4) | rho2];
+    uint64_t vv = (uint64_t)(e1 >> 4);
+    uint32_t vl = e1 & 0xF, ml = 0;
+    vv |= (uint64_t)(e2 >> 4) << vl;
+    vl += e2 & 0xF;
+    if (rho | rho2) {
+        uint32_t u1 = 1, u2 = 1;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (xb + i < w && uabs(v[i]) >= shl32(1, u1)) u1++;
+            if (xb + 4 + i < w && uabs(v[4 + i]) >= shl32(1, u2)) u2++;
+        }
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            if (!(q ? rho2 : rho)) continue;
+            const uint32_t u = q ? u2 : u1;
+            if (u <= 1) { vv |= (uint64_t)1 << vl; vl += 1; }
+            else if (u <= 2) { vv |= (uint64_t)2 << vl; vl += 2; }
+            else { vv |= (uint64_t)(u - 3) << (vl + 3); vl += 8; }   // (0,3) then (u-3,5)
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t rr = (i < 4) ? rho : rho2;
+        if (!((rr >> (i & 3)) & 1)) continue;
+        const uint32_t mag = uabs(v[i]);
+        if (mag >= 0x80000000u) { bad = 1; continue; }
+        const uint32_t emb = 32 - __clz(mag);
+        I.mval[i] = (mag & (shl32(1, emb - 1) - 1)) | ((v[i] < 0 ? 1u : 0u) << (emb - 1));
+        I.mlen[i] = emb;
+        ml += emb;
+    }
+    I.vv = vv; I.vl = vl; I.ml = ml;
+}
+
+// .. OR-ed into the bit strings at its places (the exclusive prefix sums of vl / ml over the items before it)
+__device__ __forceinline__ void ht_deposit_item(uint32_t *vbuf, uint32_t *mbuf, uint32_t vpos, uint32_t mpos, const HtItem &I) {
+    or_bits(vbuf, vpos, I.vv);
+    if (I.ml <= 64) {
+        // the item's fields concatenated in registers, one deposit: an eighth of the LDS atomics, and blocks of small
+        // magnitudes (1-bit fields, 32 to a word) no longer serialise on one word
+        uint64_t acc = 0;
+        uint32_t sh = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            acc |= shl64((uint64_t)I.mval[i], sh);       // mval < 2^mlen; an absent field is 0 bits of 0
+            sh += I.mlen[i];
+        }
+        if (acc) or_bits(mbuf, mpos, acc);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (I.mlen[i]) { or_bits(mbuf, mpos, (uint64_t)I.mval[i]); mpos += I.mlen[i]; }
+    }
+}
+
 // Part 1: every quad pair's code words and MagSgn fields deposited into the two LDS bit strings.  Returns false on the
 // reference's panic domain (MinInt32).  TM / TV = bits in the MagSgn / VLC strings.
-// LROWS: the coded rows (y % 4 == 0) were staged in LDS by the caller's max scan (row r at lrows + r * w): no second trip to memory.
 template <bool LROWS>
 __device__ __forceinline__ bool ht_form(const BlockJob &J, const int32_t *__restrict__ src, int lane, uint32_t *vbuf, uint32_t *mbuf,
                         uint32_t &TMout, uint32_t &TVout, const int32_t *lrows, const uint16_t *enc) {
-    const int w = J.w, h = J.h, stride = LROWS ? J.w : J.stride;
+    const int w = J.w, h = J.h;
     const int quadCols = (w + 3) / 4, P = (quadCols + 1) / 2, R = (h + 3) / 4, N = R * P;
     for (int i = lane; i < HT_VLC_WORDS; i += 64) vbuf[i] = 0;
     for (int i = lane; i < HT_MS_WORDS; i += 64) mbuf[i] = 0;
@@ -200,89 +290,12 @@ __device__ __forceinline__ bool ht_form(const BlockJob &J, const int32_t *__rest
     const bool vec_ok = ((J.stride & 3) == 0) && ((J.src_off & 3) == 0);
     for (int i0 = 0; i0 < N; i0 += 64) {
         const int it = i0 + lane;
-        uint64_t vv = 0; uint32_t vl = 0, ml = 0;
-        uint32_t mval[8], mlen[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) { mval[i] = 0; mlen[i] = 0; }
-        if (it < N) {
-            const int r = it / P, pi = it - r * P;
-            const int initial = (r == 0);
-            const int32_t *row = LROWS ? lrows + r * w : src + (size_t)(4 * r) * stride;
-            const int xb = pi * 8;
-            int v[8];
-            if ((LROWS || vec_ok) && xb + 8 <= w) {
-                const int4 a = *reinterpret_cast<const int4 *>(row + xb), b = *reinterpret_cast<const int4 *>(row + xb + 4);
-                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int t = row[xb + i < w ? xb + i : w - 1];        // clamped index: unconditional load
-                    v[i] = (xb + i < w) ? t : 0;
-                }
-            }
-            uint32_t rho = 0, rho2 = 0;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                if (v[i] != 0) rho |= 1u << i;
-                if (v[4 + i] != 0) rho2 |= 1u << i;
-            }
-            const uint32_t e1 = enc[(initial << 6) | rho];
-            const uint32_t e2 = enc[(initial << 6) | ((rho >> 2) << 4) | rho2];
-            vv = (uint64_t)(e1 >> 4);
-            vl = e1 & 0xF;
-            vv |= (uint64_t)(e2 >> 4) << vl;
-            vl += e2 & 0xF;
-            if (rho | rho2) {
-                uint32_t u1 = 1, u2 = 1;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    if (xb + i < w && uabs(v[i]) >= shl32(1, u1)) u1++;
-                    if (xb + 4 + i < w && uabs(v[4 + i]) >= shl32(1, u2)) u2++;
-                }
-#pragma unroll
-                for (int q = 0; q < 2; q++) {
-                    if (!(q ? rho2 : rho)) continue;
-                    const uint32_t u = q ? u2 : u1;
-                    if (u <= 1) { vv |= (uint64_t)1 << vl; vl += 1; }
-                    else if (u <= 2) { vv |= (uint64_t)2 << vl; vl += 2; }
-                    else { vv |= (uint64_t)(u - 3) << (vl + 3); vl += 8; }   // (0,3) then (u-3,5)
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const uint32_t rr = (i < 4) ? rho : rho2;
-                if (!((rr >> (i & 3)) & 1)) continue;
-                const uint32_t mag = uabs(v[i]);
-                if (mag >= 0x80000000u) { bad = 1; continue; }
-                const uint32_t emb = 32 - __clz(mag);
-                mval[i] = (mag & (shl32(1, emb - 1) - 1)) | ((v[i] < 0 ? 1u : 0u) << (emb - 1));
-                mlen[i] = emb;
-                ml += emb;
-            }
-        }
+        HtItem I = {};
+        if (it < N) ht_form_item<LROWS>(J, src, it, P, vec_ok, lrows, enc, I, bad);
         // exclusive prefix sums over the 64 items of this round
-        const uint32_t vs = wave_incl_scan(vl), ms = wave_incl_scan(ml);
+        const uint32_t vs = wave_incl_scan(I.vl), ms = wave_incl_scan(I.ml);
         const uint32_t vtot = wave_last(vs), mtot = wave_last(ms);
-        uint32_t vpos = vbase + vs - vl, mpos = mbase + ms - ml;
-        if (it < N) {
-            or_bits(vbuf, vpos, vv);
-            if (ml <= 64) {
-                // the item's fields concatenated in registers, one deposit: an eighth of the LDS atomics, and blocks of small
-                // magnitudes (1-bit fields, 32 to a word) no longer serialise on one word
-                uint64_t acc = 0;
-                uint32_t sh = 0;
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    acc |= shl64((uint64_t)mval[i], sh);       // mval < 2^mlen; an absent field is 0 bits of 0
-                    sh += mlen[i];
-                }
-                if (acc) or_bits(mbuf, mpos, acc);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; i++)
-                    if (mlen[i]) { or_bits(mbuf, mpos, (uint64_t)mval[i]); mpos += mlen[i]; }
-            }
-        }
+        if (it < N) ht_deposit_item(vbuf, mbuf, vbase + vs - I.vl, mbase + ms - I.ml, I);
         vbase += vtot; mbase += mtot;
     }
     bad = __any(bad);
@@ -335,9 +348,12 @@ __device__ __forceinline__ int ht_ms_find_ff(const uint32_t *mbuf, uint32_t TM, 
 
 // Part 2: the bytes.  WRITE = false only counts them (the fused encode + compact kernel needs the length of a block
 // before it knows where the block goes).  flist: HT_MS_FF_CAP halfwords of LDS.
-template <bool WRITE>
+// NW > 1: the NW wavefronts of a workgroup share the bytes, wave wv takes every NW-th 256-byte step of either segment.  Each
+// wave lists the 0xFF bytes for itself (the same list from the same string: the walk is one vector step per 0xFF byte, and
+// sharing one wave's list would cost a barrier and leave the other waves waiting for it).
+template <bool WRITE, int NW = 1>
 __device__ bool ht_emit(const BlockJob &J, uint8_t *__restrict__ out, int lane, const uint32_t *vbuf, const uint32_t *mbuf,
-                        uint32_t mbase, uint32_t vbase, long &magLenOut, long &vlcLenOut, uint16_t *flist) {
+                        uint32_t mbase, uint32_t vbase, long &magLenOut, long &vlcLenOut, uint16_t *flist, int wv = 0) {
     const size_t nsamp = (size_t)J.w * J.h;
     const size_t maxSize = nsamp * 2 < 64 ? 64 : nsamp * 2;
     const long msCap = (long)(maxSize / 2), vlcCap = (long)(maxSize / 2);
@@ -352,7 +368,8 @@ __device__ bool ht_emit(const BlockJob &J, uint8_t *__restrict__ out, int lane, 
 #endif
     uint32_t myF;
     const int nF = ht_ms_find_ff(mbuf, TM, lane, flist, myF);
-    __syncthreads();
+    if (NW == 1) __syncthreads();
+    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the list this wave reads is the one it wrote: no barrier
 #ifdef J2K_ENC_STAMP
     const long long e05 = wall_clock64();
 #endif
@@ -380,7 +397,7 @@ __device__ bool ht_emit(const BlockJob &J, uint8_t *__restrict__ out, int lane, 
         const bool inreg = nF <= 64;
         const long myK = (lane < nF) ? (long)((myF + (uint32_t)lane) >> 3) : (long)0x7FFFFFFF;
         int fi = 0;                                // 0xFF bytes that shift every byte of the chunk: kF <= kb - 2
-        for (long kb = 0; kb < K; kb += 256) {
+        for (long kb = 256 * wv; kb < K; kb += 256 * NW) {
             int fe;                                // .. that shift some of them: kF <= kb + 254
             if (inreg) {
                 fi = __popcll(__ballot(myK <= kb - 2));
@@ -420,7 +437,7 @@ __device__ bool ht_emit(const BlockJob &J, uint8_t *__restrict__ out, int lane, 
                     if (k0 + j < K) q[j] = (uint8_t)(dw >> (8 * j));
             }
         }
-        if (tail && lane == 0) out[K] = (uint8_t)get_bits8(mbuf, posK);
+        if (tail && lane == 0 && wv == 0) out[K] = (uint8_t)get_bits8(mbuf, posK);
     }
 #ifdef J2K_ENC_STAMP
     const long long e1 = wall_clock64();
@@ -430,7 +447,7 @@ __device__ bool ht_emit(const BlockJob &J, uint8_t *__restrict__ out, int lane, 
     const long nfull = TV >> 3, vlcLen = (TV + 7) >> 3;
     if (vlcLen > vlcCap) return false;
     uint8_t *vout = out + magLen + melLen;
-    for (long i0 = 4 * lane; WRITE && i0 < vlcLen; i0 += 256) {               // four bytes per lane
+    for (long i0 = 256 * wv + 4 * lane; WRITE && i0 < vlcLen; i0 += 256 * NW) {   // four bytes per lane
         uint32_t dw = ms_bits32(vbuf, (uint32_t)(8 * i0));
 #pragma unroll
         for (int jj = 0; jj < 4; jj++) {
@@ -492,33 +509,20 @@ __device__ __forceinline__ bool ht_encode_fast(const BlockJob &J, const int32_t 
 // sixteen 16-byte loads of a 64x64 block's max scan go out together; the coded rows (y % 4 == 0) are parked in LDS by the
 // scan, so forming the code words does not go back to memory.  (Before: job id -> job -> two rounds of scan loads -> two
 // rounds of row loads, each followed by table look-ups in global memory -> the alias chain, link by link: 33 us.)
-__global__ __launch_bounds__(64) void ht_encode_kernel(const BlockJob *__restrict__ jobs, int njobs,
-                                                       const int32_t *__restrict__ coef, uint8_t *__restrict__ slots,
-                                                       uint32_t *__restrict__ lens, uint8_t *__restrict__ numbps,
-                                                       int *__restrict__ fault, uint32_t *__restrict__ maglens,
-                                                       const HtUJob *__restrict__ utab, const int *__restrict__ alias_ids) {
-    // maglens != NULL (j2k_plan_encode_stream): also report where the MagSgn bytes end, and do NOT write the MEL
-    // segment's zero bytes into the slot -- the gather puts zeros straight into the stream instead of copying them
-    __shared__ uint32_t s_vbuf[HT_VLC_WORDS];
-    __shared__ uint32_t s_mbuf[HT_MS_WORDS];
-    __shared__ __align__(16) int32_t s_rows[HT_FAST_MAX_SAMPLES];
-    __shared__ uint32_t s_enc[64];
-    __shared__ uint16_t s_ff[HT_MS_FF_CAP];
-    if ((int)blockIdx.x >= njobs) return;          // njobs = entries of utab when given
-    const int lane = threadIdx.x;
+// One block coded by ONE wavefront (the whole of ht_encode_kernel's workgroup; wave 0 of ht_encode_wg_kernel's for the blocks
+// that are not on its four-wave path).  myalias: lane k's job id of the block's alias list (k < 64).  SCAN: 16-byte loads a lane
+// has in flight in the max scan (16: a 64x64 block in one round trip; the four-wave kernel's rare other blocks take 4 and keep
+// that kernel's register count, and so its residency, what its own path needs).
+template <int SCAN>
+__device__ __forceinline__ void ht_encode_block_wave(const BlockJob &J, int nalias, int aoff, int myalias, int lane, int njobs,
+                                                     const int32_t *__restrict__ coef, uint8_t *__restrict__ slots,
+                                                     uint32_t *__restrict__ lens, uint8_t *__restrict__ numbps,
+                                                     int *__restrict__ fault, uint32_t *__restrict__ maglens,
+                                                     const int *__restrict__ alias_ids, uint32_t *s_vbuf, uint32_t *s_mbuf,
+                                                     int32_t *s_rows, uint32_t *s_enc, uint16_t *s_ff) {
 #ifdef J2K_ENC_STAMP
     const long long st0 = wall_clock64();
 #endif
-    BlockJob J;
-    int jid = (int)blockIdx.x, nalias = 1, aoff = 0;
-    if (utab) {
-        const HtUJob U = utab[blockIdx.x];
-        J = U.J; jid = U.jid; nalias = U.nalias; aoff = U.alias_off;
-    } else {
-        J = jobs[jid];
-    }
-    int myalias = jid;
-    if (utab && lane < nalias) myalias = alias_ids[aoff + lane];
     s_enc[lane] = reinterpret_cast<const uint32_t *>(g_vlc_enc)[lane];
     const int w = J.w, h = J.h, stride = J.stride;
     const int32_t *src = coef + J.src_off;
@@ -542,12 +546,12 @@ __global__ __launch_bounds__(64) void ht_encode_kernel(const BlockJob *__restric
         const int wq = w >> 2, nq = wq * h;
         const int dy = 64 / wq, dx = 64 - dy * wq;
         int y = lane / wq, xq = lane - y * wq;
-        // sixteen loads in flight per step (clamped, unconditional addresses): a whole 64x64 block in one round trip
-        for (int e0 = lane; e0 < nq; e0 += 64 * 16) {
-            int4 qv[16];
-            int ys[16];
+        // SCAN (sixteen) loads in flight per step (clamped, unconditional addresses): a whole 64x64 block in one round trip
+        for (int e0 = lane; e0 < nq; e0 += 64 * SCAN) {
+            int4 qv[SCAN];
+            int ys[SCAN];
 #pragma unroll
-            for (int u = 0; u < 16; u++) {
+            for (int u = 0; u < SCAN; u++) {
                 const bool ok = e0 + 64 * u < nq;
                 const int4 t = *reinterpret_cast<const int4 *>(ok ? src + (size_t)y * stride + 4 * xq : src);
                 qv[u] = ok ? t : make_int4(0, 0, 0, 0);
@@ -556,7 +560,7 @@ __global__ __launch_bounds__(64) void ht_encode_kernel(const BlockJob *__restric
                 if (xq >= wq) { xq -= wq; y++; }
             }
 #pragma unroll
-            for (int u = 0; u < 16; u++) {
+            for (int u = 0; u < SCAN; u++) {
                 const int4 q = qv[u];
                 if (lrows && ys[u] >= 0 && ((ys[u] >> 8) & 3) == 0)
                     *reinterpret_cast<int4 *>(&s_rows[(ys[u] >> 10) * w + 4 * (ys[u] & 0xFF)]) = q;
@@ -697,6 +701,185 @@ __global__ __launch_bounds__(64) void ht_encode_kernel(const BlockJob *__restric
         }
         publish((uint32_t)total, 32 - __clz((uint32_t)maxMag), true, (uint32_t)magLen);
     }
+}
+
+__global__ __launch_bounds__(64) void ht_encode_kernel(const BlockJob *__restrict__ jobs, int njobs,
+                                                       const int32_t *__restrict__ coef, uint8_t *__restrict__ slots,
+                                                       uint32_t *__restrict__ lens, uint8_t *__restrict__ numbps,
+                                                       int *__restrict__ fault, uint32_t *__restrict__ maglens,
+                                                       const HtUJob *__restrict__ utab, const int *__restrict__ alias_ids) {
+    // maglens != NULL (j2k_plan_encode_stream): also report where the MagSgn bytes end, and do NOT write the MEL
+    // segment's zero bytes into the slot -- the gather puts zeros straight into the stream instead of copying them
+    __shared__ uint32_t s_vbuf[HT_VLC_WORDS];
+    __shared__ uint32_t s_mbuf[HT_MS_WORDS];
+    __shared__ __align__(16) int32_t s_rows[HT_FAST_MAX_SAMPLES];
+    __shared__ uint32_t s_enc[64];
+    __shared__ uint16_t s_ff[HT_MS_FF_CAP];
+    if ((int)blockIdx.x >= njobs) return;          // njobs = entries of utab when given
+    const int lane = threadIdx.x;
+    BlockJob J;
+    int jid = (int)blockIdx.x, nalias = 1, aoff = 0;
+    if (utab) {
+        const HtUJob U = utab[blockIdx.x];
+        J = U.J; jid = U.jid; nalias = U.nalias; aoff = U.alias_off;
+    } else {
+        J = jobs[jid];
+    }
+    int myalias = jid;
+    if (utab && lane < nalias) myalias = alias_ids[aoff + lane];
+    ht_encode_block_wave<16>(J, nalias, aoff, myalias, lane, njobs, coef, slots, lens, numbps, fault, maglens, alias_ids, s_vbuf, s_mbuf,
+                         s_rows, s_enc, s_ff);
+}
+
+// Workgroup barrier that orders LDS traffic only (as lds_barrier of dwt53.hip): __syncthreads() also waits for the wave's
+// outstanding global stores, and nothing one wave of the block coder reads from another goes through memory.
+__device__ __forceinline__ void ht_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// The same block coder with FOUR wavefronts per distinct window (j2k_plan_encode_stream with the alias tables, ht_enc_waves = 4).
+// The one-wave form's life is three data-parallel phases in sequence on one SIMD; here the 256 lanes share each of them:
+//   scan  every lane issues its four 16-byte loads of the block (at most 1024 quads on this path) before the first use; the
+//         maximum goes wave -> LDS -> all; the coded rows are parked in s_rows as before;
+//   form  one quad pair per lane (at most 256 pairs), bit positions = prefix sum in the wave + the totals of the waves before
+//         it (LDS), deposits by LDS atomics;
+//   emit  wave v cuts every fourth 256-byte step of the MagSgn and of the VLC bytes (ht_emit<true, 4>).
+// Three LDS-only barriers.  Blocks off this path (a width that is no multiple of 4, an unaligned window, more than
+// HT_FAST_MAX_SAMPLES coded samples) are coded by wave 0 alone with the one-wave routine; the other waves leave before the
+// first barrier (a barrier counts the waves that are still alive).  Lengths and faults are published once, by wave 0.
+__global__ __launch_bounds__(256) void ht_encode_wg_kernel(int nunique, const int32_t *__restrict__ coef, uint8_t *__restrict__ slots,
+                                                           uint32_t *__restrict__ lens, uint8_t *__restrict__ numbps,
+                                                           int *__restrict__ fault, uint32_t *__restrict__ maglens,
+                                                           const HtUJob *__restrict__ utab, const int *__restrict__ alias_ids) {
+    __shared__ uint32_t s_vbuf[HT_VLC_WORDS];
+    __shared__ uint32_t s_mbuf[HT_MS_WORDS];
+    __shared__ __align__(16) int32_t s_rows[HT_FAST_MAX_SAMPLES];
+    __shared__ uint32_t s_enc[64];
+    __shared__ uint16_t s_ff[HT_MS_FF_CAP];
+    __shared__ int s_max[4], s_bad[4];
+    __shared__ uint32_t s_tot[4][2];
+    if ((int)blockIdx.x >= nunique) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef J2K_ENC_STAMP
+    const long long st0 = wall_clock64();
+#endif
+    const HtUJob U = utab[blockIdx.x];
+    const BlockJob J = U.J;
+    const int nalias = U.nalias, aoff = U.alias_off;
+    int myalias = U.jid;
+    if (wave == 0 && lane < nalias) myalias = alias_ids[aoff + lane];
+    const int w = J.w, h = J.h, stride = J.stride;
+    const bool fast = (size_t)((h + 3) / 4) * (size_t)w <= HT_FAST_MAX_SAMPLES;
+    const bool quads = (w & 3) == 0 && (stride & 3) == 0 && (J.src_off & 3) == 0;
+    if (!(quads && fast)) {
+        if (wave != 0) return;
+        ht_encode_block_wave<4>(J, nalias, aoff, myalias, lane, nunique, coef, slots, lens, numbps, fault, maglens, alias_ids, s_vbuf,
+                             s_mbuf, s_rows, s_enc, s_ff);
+        return;
+    }
+    const int32_t *src = coef + J.src_off;
+    uint8_t *out = slots + J.out_off;
+    auto publish = [&](uint32_t len, uint32_t nb, bool has_mag, uint32_t mag) {    // wave 0 only
+        for (int k = lane; k < nalias; k += 64) {
+            const int j = k < 64 ? myalias : alias_ids[aoff + k];
+            lens[j] = len;
+            numbps[j] = (uint8_t)nb;
+            if (maglens && has_mag) maglens[j] = mag;
+        }
+    };
+
+    // ---- scan: max |x| over the whole block; w * ceil(h / 4) <= 1024 and w % 4 == 0, so the block has at most 1024 quads ----
+    int maxMag = 0;  // Go compares int32: -MinInt32 stays negative and never wins
+    {
+        const int wq = w >> 2, nq = wq * h;        // wq <= 256
+        const int dy = 256 / wq, dx = 256 - dy * wq;
+        int y = tid / wq, xq = tid - y * wq;
+        int4 qv[4];
+        int ys[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const bool ok = tid + 256 * u < nq;
+            const int4 t = *reinterpret_cast<const int4 *>(ok ? src + (size_t)y * stride + 4 * xq : src);
+            qv[u] = ok ? t : make_int4(0, 0, 0, 0);
+            ys[u] = ok ? (y << 8 | xq) : -1;
+            y += dy; xq += dx;
+            if (xq >= wq) { xq -= wq; y++; }
+        }
+        // under the loads: the code-word table and the empty bit strings
+        if (tid < 64) s_enc[tid] = reinterpret_cast<const uint32_t *>(g_vlc_enc)[tid];
+        for (int i = tid; i < HT_VLC_WORDS; i += 256) s_vbuf[i] = 0;
+        for (int i = tid; i < HT_MS_WORDS; i += 256) s_mbuf[i] = 0;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int4 q = qv[u];
+            if (ys[u] >= 0 && ((ys[u] >> 8) & 3) == 0)
+                *reinterpret_cast<int4 *>(&s_rows[(ys[u] >> 10) * w + 4 * (ys[u] & 0xFF)]) = q;
+            const int a0 = q.x < 0 ? (int)(0u - (uint32_t)q.x) : q.x, a1 = q.y < 0 ? (int)(0u - (uint32_t)q.y) : q.y;
+            const int a2 = q.z < 0 ? (int)(0u - (uint32_t)q.z) : q.z, a3 = q.w < 0 ? (int)(0u - (uint32_t)q.w) : q.w;
+            maxMag = max(max(maxMag, max(a0, a1)), max(a2, a3));
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) maxMag = max(maxMag, __shfl_xor(maxMag, o));
+    if (lane == 0) s_max[wave] = maxMag;
+    ht_lds_barrier();
+    maxMag = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
+#ifdef J2K_ENC_STAMP
+    const long long st1 = wall_clock64();
+#endif
+    if (maxMag == 0) {
+        if (wave == 0) publish(0, 0, false, 0);
+        return;
+    }
+
+    // ---- form: one quad pair per lane ----
+    const int quadCols = w >> 2, P = (quadCols + 1) / 2, R = (h + 3) / 4, N = R * P;   // N <= 256 (w = 4: one pair per coded row)
+    const uint16_t *enc = reinterpret_cast<const uint16_t *>(s_enc);
+    HtItem I = {};
+    int bad = 0;
+    if (tid < N) ht_form_item<true>(J, src, tid, P, true, s_rows, enc, I, bad);
+    const uint32_t vs = wave_incl_scan(I.vl), ms = wave_incl_scan(I.ml);
+    bad = __any(bad);
+    if (lane == 63) { s_tot[wave][0] = vs; s_tot[wave][1] = ms; s_bad[wave] = bad; }
+    ht_lds_barrier();
+    uint32_t vbase = 0, mbase = 0, TV = 0, TM = 0;
+    bad = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t a = s_tot[k][0], b = s_tot[k][1];
+        if (k < wave) { vbase += a; mbase += b; }
+        TV += a; TM += b;
+        bad |= s_bad[k];
+    }
+    if (tid < N) ht_deposit_item(s_vbuf, s_mbuf, vbase + vs - I.vl, mbase + ms - I.ml, I);
+    ht_lds_barrier();
+#ifdef J2K_ENC_STAMP
+    const long long st2 = wall_clock64();
+#endif
+    long mLen = 0, vLen = 0;
+    if (bad || !ht_emit<true, 4>(J, out, lane, s_vbuf, s_mbuf, TM, TV, mLen, vLen, s_ff, wave)) {
+        if (wave == 0) {
+            if (lane == 0) atomicMax(fault, 1);
+            publish(0, 0, false, 0);
+        }
+        return;
+    }
+    if (wave == 0) {
+        const size_t nsamp = (size_t)w * h;
+        const size_t maxSize = nsamp * 2 < 64 ? 64 : nsamp * 2;
+        const size_t melLen = maxSize / 4;
+        if (!maglens) zero_bytes(out + mLen, melLen, lane);
+        const size_t scup = melLen + (size_t)vLen + 2;
+        const size_t total = (size_t)mLen + scup;
+        if (lane == 0) {
+            out[total - 2] = (uint8_t)(scup >> 8);
+            out[total - 1] = (uint8_t)(scup & 0xFF);
+        }
+        publish((uint32_t)total, 32 - __clz((uint32_t)maxMag), true, (uint32_t)mLen);
+    }
+#ifdef J2K_ENC_STAMP
+    if (((blockIdx.x % 200) == 7 || (int)blockIdx.x >= nunique - 3) && lane == 0)
+        printf("enc4 wg %d wave %d: start %lld scan %lld form %lld emit %lld (x10 ns)  mLen %ld vLen %ld\n", (int)blockIdx.x, wave,
+               st0 % 100000, st1 - st0, st2 - st1, wall_clock64() - st2, mLen, vLen);
+#endif
 }
 
 // ================================================================================================
@@ -1764,12 +1947,15 @@ static hipError_t ht_tables_ready(hipStream_t s) {
 
 hipError_t launch_ht_encode(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots,
                             uint32_t *lens, uint8_t *numbps, int *fault, uint32_t *maglens, const HtUJob *utab, int nunique,
-                            const int *alias_ids) {
+                            const int *alias_ids, int waves) {
     if (njobs <= 0) return hipSuccess;
     hipError_t e;
     if ((e = ht_tables_ready(s)) != hipSuccess) return e;
     const int n = utab ? nunique : njobs;
-    hipLaunchKernelGGL(ht_encode_kernel, dim3(n), dim3(64), 0, s, jobs, n, coef, slots, lens, numbps, fault, maglens, utab, alias_ids);
+    if (waves == 4 && utab && alias_ids)
+        hipLaunchKernelGGL(ht_encode_wg_kernel, dim3(n), dim3(256), 0, s, n, coef, slots, lens, numbps, fault, maglens, utab, alias_ids);
+    else
+        hipLaunchKernelGGL(ht_encode_kernel, dim3(n), dim3(64), 0, s, jobs, n, coef, slots, lens, numbps, fault, maglens, utab, alias_ids);
     return hipGetLastError();
 }
 

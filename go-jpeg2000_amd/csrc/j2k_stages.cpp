@@ -718,7 +718,7 @@ int plan_encode_private_slots(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_l
     ctx->fault_armed = true;
     for (int rep_ = 0; rep_ < dev_reps(8); rep_++)
     HIPCHK(ctx, launch_ht_encode(ctx->stream, P->d_bjobs, n, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, (int *)ctx->stage[3],
-                                 P->d_maglens, P->d_ht_ujobs, P->ht_nunique, P->d_ht_alias_next));
+                                 P->d_maglens, P->d_ht_ujobs, P->ht_nunique, P->d_ht_alias_next, ctx->ht_enc_waves));
     return J2K_OK;
 }
 
