@@ -274,8 +274,17 @@ extern "C" int j2k_plan_encode_frame_image(j2k_plan *P, const j2k_image *d_img, 
     return r;
 }
 
+static int decode_frame_pixels_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int skip_planes, void *d_pix,
+                                    size_t stride);
+static int decode_frame_pixels_reduced_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
+                                            int skip_planes, void *d_pix, size_t stride);
 extern "C" int j2k_plan_decode_frame_pixels(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, void *d_pix,
                                             size_t stride) {
+    return decode_frame_pixels_impl(P, d_cs, len, d_tile_offs, sop, eph, 0, d_pix, stride);
+}
+// skip_planes: the quality floor of j2k_plan_decode_frame_pixels_coarse (0: the full decode; > 0: MQ plans only, checked by the caller)
+static int decode_frame_pixels_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int skip_planes, void *d_pix,
+                                    size_t stride) {
     if (!P) return J2K_ERR_INVALID_ARG;
     int r = cl_prepare(P);
     if (r == J2K_OK) r = cl_workspaces(P);
@@ -293,7 +302,7 @@ extern "C" int j2k_plan_decode_frame_pixels(j2k_plan *P, const uint8_t *d_cs, si
         HIPCHK(ctx, launch_ht_decode(ctx->stream, P->d_djobs, n, d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_coeff_dec, (uint32_t *)ctx->stage[2], 1, P->d_djobs_placed));
         return plan_inverse_pixels_impl(P, P->d_cl_coeff_dec, d_pix, stride, P->d_frame_status);
     } else {
-        r = j2k_plan_decode_blocks(P, d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, P->d_cl_decoded);
+        r = j2k_plan_decode_blocks_coarse(P, d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, skip_planes, P->d_cl_decoded);
         if (r == J2K_OK) r = j2k_plan_place_blocks(P, P->d_cl_decoded, P->d_cl_coeff);
     }
     // (the status word as the guard of the launches that write d_pix: a stream that was refused leaves the caller's frame alone)
@@ -306,12 +315,16 @@ extern "C" int j2k_plan_decode_frame_pixels(j2k_plan *P, const uint8_t *d_cs, si
 // <= num_resolutions - 1 - reduce only (with the MQ coder that is where the decode time is), and the inverse transform stops at level `reduce`.
 extern "C" int j2k_plan_decode_frame_pixels_reduced(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
                                                     void *d_pix, size_t stride) {
+    return decode_frame_pixels_reduced_impl(P, d_cs, len, d_tile_offs, sop, eph, reduce, 0, d_pix, stride);
+}
+static int decode_frame_pixels_reduced_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
+                                            int skip_planes, void *d_pix, size_t stride) {
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     ReducedTab *R = nullptr;
     int r = plan_reduced(P, reduce, &R);
     if (r != J2K_OK) return r;
-    if (reduce == 0) return j2k_plan_decode_frame_pixels(P, d_cs, len, d_tile_offs, sop, eph, d_pix, stride);
+    if (reduce == 0) return decode_frame_pixels_impl(P, d_cs, len, d_tile_offs, sop, eph, skip_planes, d_pix, stride);
     if (!d_pix) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     r = cl_prepare(P);
     if (r == J2K_OK) r = cl_workspaces(P);
@@ -322,10 +335,21 @@ extern "C" int j2k_plan_decode_frame_pixels_reduced(j2k_plan *P, const uint8_t *
     int32_t *coeff = ht ? P->d_cl_coeff_dec : P->d_cl_coeff;
     // (HT: straight into the windows of the plan's zeroed planes, coded rows only, as the full decode; the windows left out keep what an earlier
     //  full decode wrote -- no level >= reduce reads them)
-    r = plan_decode_blocks_jobs(P, R->d_djobs, R->njobs, d_cs, R->d_offs, R->d_lens, R->d_numbps, ht ? coeff : P->d_cl_decoded, ht ? R->d_placed : nullptr);
+    r = plan_decode_blocks_jobs(P, R->d_djobs, R->njobs, d_cs, R->d_offs, R->d_lens, R->d_numbps, ht ? coeff : P->d_cl_decoded, ht ? R->d_placed : nullptr, skip_planes);
     if (r == J2K_OK && !ht) HIPCHK(ctx, launch_place_blocks(ctx->stream, R->d_bjobs, R->d_djobs, R->njobs, R->max_block_h, P->d_cl_decoded, coeff));
     if (r == J2K_OK) r = plan_inverse_pixels_reduced_impl(P, coeff, reduce, d_pix, stride, P->d_frame_status);
     return r;
+}
+
+// Both scalability axes in one call: resolution (`reduce`, the rules of j2k_plan_decode_frame_pixels_reduced; 0 on any closed-loop plan) and
+// quality (`skip_planes`: every MQ block decoder stops after that bit plane).  A refusal comes before the first launch: d_pix is left alone.
+extern "C" int j2k_plan_decode_frame_pixels_coarse(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
+                                                   int skip_planes, void *d_pix, size_t stride) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    const int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_plan_decode_frame_pixels_coarse");
+    if (r != J2K_OK) return r;
+    if (reduce == 0) return decode_frame_pixels_impl(P, d_cs, len, d_tile_offs, sop, eph, skip_planes, d_pix, stride);
+    return decode_frame_pixels_reduced_impl(P, d_cs, len, d_tile_offs, sop, eph, reduce, skip_planes, d_pix, stride);
 }
 
 extern "C" int j2k_plan_get_decoded_offsets(const j2k_plan *P, uint64_t *offs, size_t cap) {

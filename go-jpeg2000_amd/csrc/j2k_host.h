@@ -42,7 +42,7 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
 size_t t1_sym_stride(int planes);
 hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, const uint8_t *numbps, int32_t *decoded, uint8_t *work,
-                            size_t work_per_job, int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput = 0);
+                            size_t work_per_job, int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput = 0, int skip_planes = 0);
 size_t t1_dec_split_bytes(size_t njobs);
 hipError_t launch_mq_encode(hipStream_t s, const uint8_t *ctxs, const uint8_t *decs, size_t n, uint8_t *out, size_t cap, uint32_t *out_len, int *fault);
 hipError_t launch_mq_decode(hipStream_t s, const uint8_t *data, size_t len, const uint8_t *ctxs, size_t n, uint8_t *decs, int *fault);
@@ -127,9 +127,12 @@ int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix
 int plan_inverse_pixels_impl(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride, const int *guard);
 int plan_inverse_pixels_reduced_impl(j2k_plan *P, const int32_t *d_coeff, int reduce, void *d_pix, size_t stride, const int *guard);
 // j2k_plan_decode_blocks on a job table of its own (the plan's, or the subset of a reduced-resolution decode); placed != NULL (HT): every block
-// straight into its window of the coefficient planes `d_decoded`, coded rows only
+// straight into its window of the coefficient planes `d_decoded`, coded rows only.  skip_planes: the quality floor of the _coarse calls (MQ coder;
+// the callers have checked its range and the coder)
 int plan_decode_blocks_jobs(j2k_plan *P, const j2k::BlockJob *d_djobs, int n, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
-                            const uint8_t *d_numbps, int32_t *d_decoded, const j2k::BlockJob *d_placed);
+                            const uint8_t *d_numbps, int32_t *d_decoded, const j2k::BlockJob *d_placed, int skip_planes = 0);
+// the range of skip_planes and the coder it needs: J2K_OK, or the refusal (through fail())
+int check_skip_planes(j2k_ctx *ctx, int coder, int skip_planes, const char *who);
 // the default branch of extractImageData (j2k_image.cpp): d_img's planes on the device; status_word non-null = report a palette index
 // >= npal there (the frame codec's status, asynchronous), else synchronise and return J2K_ERR_GO_PANIC before anything is written
 bool plan_rgba8_wg_fusable(const j2k_plan *P);

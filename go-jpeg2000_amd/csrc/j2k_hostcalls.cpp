@@ -228,7 +228,14 @@ extern "C" int j2k_encode_blocks(j2k_ctx *ctx, int coder, const int32_t *const *
 extern "C" int j2k_decode_blocks(j2k_ctx *ctx, int coder, const uint8_t *bytes, const uint64_t *offs, const uint32_t *lens,
                                  const uint8_t *numbps, const j2k_block *blocks, size_t nblocks, int32_t *coeffs,
                                  const uint64_t *coeff_offs) {
+    return j2k_decode_blocks_coarse(ctx, coder, bytes, offs, lens, numbps, blocks, nblocks, 0, coeffs, coeff_offs);
+}
+// ... down to bit plane skip_planes only (MQ coder; 0 = j2k_decode_blocks)
+extern "C" int j2k_decode_blocks_coarse(j2k_ctx *ctx, int coder, const uint8_t *bytes, const uint64_t *offs, const uint32_t *lens,
+                                        const uint8_t *numbps, const j2k_block *blocks, size_t nblocks, int skip_planes, int32_t *coeffs,
+                                        const uint64_t *coeff_offs) {
     if (!ctx) return J2K_ERR_INVALID_ARG;
+    { const int r = check_skip_planes(ctx, coder, skip_planes, "j2k_decode_blocks_coarse"); if (r != J2K_OK) return r; }
     if (nblocks == 0) return J2K_OK;
     if (!offs || !lens || !blocks || !coeffs || !coeff_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "NULL argument");
     if (coder != J2K_CODER_MQ && coder != J2K_CODER_HT) return fail(ctx, J2K_ERR_INVALID_ARG, "coder");
@@ -277,7 +284,7 @@ extern "C" int j2k_decode_blocks(j2k_ctx *ctx, int coder, const uint8_t *bytes, 
         int max_dim = 0;
         for (size_t j = 0; j < nblocks; j++) max_dim = std::max(max_dim, std::max(bj[j].w, bj[j].h));
         TRY(launch_t1_decode(ctx->stream, (BlockJob *)d_jobs, (int)nblocks, (uint8_t *)d_bytes, (uint64_t *)d_offs, (uint32_t *)d_lens, (uint8_t *)d_nb,
-                             (int32_t *)d_dec, (uint8_t *)d_work, wpj, max_dim, ctx->t1_dec_general, split ? (uint8_t *)d_work + gen_bytes : nullptr, ctx->t1_dec_lanes));
+                             (int32_t *)d_dec, (uint8_t *)d_work, wpj, max_dim, ctx->t1_dec_general, split ? (uint8_t *)d_work + gen_bytes : nullptr, ctx->t1_dec_lanes, 0, skip_planes));
     }
     for (size_t j = 0; j < nblocks; j++)
         TRY(hipMemcpyAsync(coeffs + coeff_offs[j], (int32_t *)d_dec + bj[j].out_off, (size_t)blocks[j].w * blocks[j].h * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -452,7 +459,7 @@ extern "C" int j2k_encode_image_host(j2k_plan *P, const j2k_image *img, int sop,
     });
 }
 
-static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride);
+static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride, int skip_planes = 0);
 // closed-loop plans: tile-parts (host) -> H2D -> parse -> block decode -> placement -> inverse transform -> image.*.Pix (host), one
 // synchronous call.  The pixel format is the plan's: components 1 / 3 / 4, precision <= 8 -> Gray / RGBA, else Gray16 / RGBA64
 // (decoder.createImage, decoder.go:417-588).
@@ -467,7 +474,20 @@ extern "C" int j2k_decode_pixels_host_reduced(j2k_plan *P, const uint8_t *cs, si
     if (r != J2K_OK) return r;
     return decode_pixels_host_impl(P, cs, len, sop, eph, reduce, pix, stride);
 }
-static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride) {
+// ... with both axes (j2k_plan_decode_frame_pixels_coarse): reduce = 0 on any closed-loop plan, reduce > 0 as j2k_decode_pixels_host_reduced
+extern "C" int j2k_decode_pixels_host_coarse(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, int skip_planes, void *pix,
+                                             size_t stride) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_decode_pixels_host_coarse");
+    if (r != J2K_OK) return r;
+    if (reduce != 0) {
+        int32_t wr = 0, hr = 0;
+        r = j2k_plan_reduced_size(P, reduce, &wr, &hr);
+        if (r != J2K_OK) return r;
+    }
+    return decode_pixels_host_impl(P, cs, len, sop, eph, reduce != 0 ? reduce : -1, pix, stride, skip_planes);
+}
+static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride, int skip_planes) {
     if (!P || !cs || !pix) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
@@ -480,8 +500,9 @@ static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, i
     if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, pixbytes)) != J2K_OK) return r;
     if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, len + 64)) != J2K_OK) return r;
     HIPCHK(ctx, hipMemcpyAsync(P->d_host_io, cs, len, hipMemcpyHostToDevice, ctx->stream));
-    r = reduce >= 0 ? j2k_plan_decode_frame_pixels_reduced(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, reduce, P->d_host_pix, stride)
-                    : j2k_plan_decode_frame_pixels(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, P->d_host_pix, stride);
+    r = skip_planes ? j2k_plan_decode_frame_pixels_coarse(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, std::max(reduce, 0), skip_planes, P->d_host_pix, stride)
+        : reduce >= 0 ? j2k_plan_decode_frame_pixels_reduced(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, reduce, P->d_host_pix, stride)
+                      : j2k_plan_decode_frame_pixels(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, P->d_host_pix, stride);
     if (r != J2K_OK) return r;
     HIPCHK(ctx, hipMemcpyAsync(pix, P->d_host_pix, pixbytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

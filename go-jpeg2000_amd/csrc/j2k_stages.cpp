@@ -870,8 +870,25 @@ extern "C" int j2k_plan_decode_blocks(j2k_plan *P, const uint8_t *d_stream, cons
     return plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_stream, d_offs, d_lens, d_numbps, d_decoded, nullptr);
 }
 
+int check_skip_planes(j2k_ctx *ctx, int coder, int skip_planes, const char *who) {
+    if (skip_planes < 0 || skip_planes > 31) return fail(ctx, J2K_ERR_INVALID_ARG, (std::string(who) + ": skip_planes outside 0 ... 31").c_str());
+    if (skip_planes > 0 && coder == J2K_CODER_HT)
+        return fail(ctx, J2K_ERR_UNSUPPORTED, (std::string(who) + ": skip_planes > 0 needs the MQ coder (the HT coder's one pass has no planes to stop between)").c_str());
+    return J2K_OK;
+}
+
+// j2k_plan_decode_blocks down to bit plane skip_planes only (MQ coder): every block's decoder stops after that plane, non-zero magnitudes take the
+// midpoint of what was left.  skip_planes = 0 is j2k_plan_decode_blocks.
+extern "C" int j2k_plan_decode_blocks_coarse(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
+                                             const uint8_t *d_numbps, int skip_planes, int32_t *d_decoded) {
+    if (!P || !d_stream || !d_offs || !d_lens || !d_numbps || !d_decoded) return J2K_ERR_INVALID_ARG;
+    const int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_plan_decode_blocks_coarse");
+    if (r != J2K_OK) return r;
+    return plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_stream, d_offs, d_lens, d_numbps, d_decoded, nullptr, skip_planes);
+}
+
 int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
-                            const uint8_t *d_numbps, int32_t *d_decoded, const BlockJob *d_placed) {
+                            const uint8_t *d_numbps, int32_t *d_decoded, const BlockJob *d_placed, int skip_planes) {
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!n) return J2K_OK;
@@ -899,7 +916,7 @@ int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const u
         if (r != J2K_OK) return r;
         HIPCHK(ctx, launch_t1_decode(ctx->stream, d_djobs, n, d_stream, d_offs, d_lens, d_numbps, d_decoded,
                                      (uint8_t *)ctx->stage[2], wpj, max_dim, ctx->t1_dec_general,
-                                     split ? (uint8_t *)ctx->stage[2] + gen_bytes : nullptr, ctx->t1_dec_lanes, mq_throughput_mode() ? 1 : 0));
+                                     split ? (uint8_t *)ctx->stage[2] + gen_bytes : nullptr, ctx->t1_dec_lanes, mq_throughput_mode() ? 1 : 0, skip_planes));
     }
     return J2K_OK;
 }

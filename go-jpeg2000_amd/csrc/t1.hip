@@ -1118,9 +1118,17 @@ __device__ __forceinline__ void t1_dec_cleanup_wave(T1DecLane &L, int32_t bit, u
             __syncthreads();
         }
 }
+// The quality floor of the j2k_*_coarse calls (skip_planes = s, 0 ... 31): a decoder stops after plane s and every non-zero magnitude
+// takes the midpoint of what it left undecoded, bit s - 1; the sign as in t1.go:1281-1289.  s = 0: no midpoint, the full decode.
+__device__ __forceinline__ uint32_t t1_coarse_mid(int skip) { return skip > 0 ? 1u << (skip - 1) : 0u; }
+__device__ __forceinline__ int32_t t1_coarse_finish(int32_t mag, uint32_t mid, bool neg) {
+    const uint32_t m = mag ? (uint32_t)mag | mid : 0u;
+    return (int32_t)(neg ? 0u - m : m);
+}
 // One block, one wavefront; all lanes call this.  Only the MQ decisions and what depends on them run on lane 0.
-__device__ __forceinline__ void t1_decode_block_wave(T1DecLane &L, int numBPS, uint8_t *mrctx, int lane) {
-    for (int bp = numBPS - 1; bp >= 0; bp--) {
+// skip: the quality floor (j2k_*_coarse): the planes below it are left undecoded.
+__device__ __forceinline__ void t1_decode_block_wave(T1DecLane &L, int numBPS, int skip, uint8_t *mrctx, int lane) {
+    for (int bp = numBPS - 1; bp >= skip; bp--) {
         const int32_t bit = bp < 32 ? (int32_t)(1u << bp) : 0;
         t1_dec_sigprop_wave(L, bit, mrctx, mrctx + 64, lane);
         t1_dec_magref_wave(L, bit, mrctx, lane);
@@ -1138,7 +1146,7 @@ template <bool LDSW>
 __global__ __launch_bounds__(64) void t1_decode_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                        const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
                                                        const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded,
-                                                       uint8_t *__restrict__ work, size_t work_per_job, int lds_work_bytes, int skip_small) {
+                                                       uint8_t *__restrict__ work, size_t work_per_job, int lds_work_bytes, int skip_small, int skip_planes) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     int vzero;                                   // see t1_decode64_kernel: keeps the serial chain's loop control off the scalar unit
     asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
@@ -1167,13 +1175,15 @@ __global__ __launch_bounds__(64) void t1_decode_kernel(const BlockJob *__restric
         T1DecLane L;
         if (lane == 0) mq_dec_init(L.d, stream + offs[jid], (long)lens[jid]);
         L.ent = T.ent; L.mq = T.mq; L.zcsc = T.zc; L.flags = flags; L.data = out; L.w = w; L.h = h; L.stride = stride;
-        t1_decode_block_wave(L, __shfl((int)numbps[jid], 0), T.mrctx, lane);
+        t1_decode_block_wave(L, __shfl((int)numbps[jid], 0), skip_planes + vzero, T.mrctx, lane);
     }
     __syncthreads();                                                      // includes the wait for the stores and atomics above
+    const uint32_t mid = t1_coarse_mid(skip_planes);
     for (size_t i = lane; i < n; i += 64) {                               // t1.go:1281-1289
-        if (!(flags[(i / w + 1) * stride + T1D_XO + (i % w)] & T1SignNeg)) continue;
+        const bool neg = (flags[(i / w + 1) * stride + T1D_XO + (i % w)] & T1SignNeg) != 0;
+        if (!neg && !mid) continue;
         const int v = __hip_atomic_load(&out[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // L2, not this CU's L1
-        out[i] = (int32_t)(0u - (uint32_t)v);
+        out[i] = t1_coarse_finish(v, mid, neg);
     }
 }
 
@@ -1200,7 +1210,7 @@ struct T1Dec64Shared {
 static_assert(sizeof(T1Dec64Shared) <= 5120, "t1_decode64_kernel: LDS per block above 10 granules (32 blocks per CU)");
 __global__ __launch_bounds__(64) void t1_decode64_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                          const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
-                                                         const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded, int min_bps) {
+                                                         const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded, int min_bps, int skip_planes) {
     __shared__ T1Dec64Shared S;
     if ((int)blockIdx.x >= njobs) return;
     if ((int)numbps[blockIdx.x] < min_bps) return;                   // the plane-stepped path took this block
@@ -1232,13 +1242,15 @@ __global__ __launch_bounds__(64) void t1_decode64_kernel(const BlockJob *__restr
         T1DecLane L;                                              // L.d is lane 0's decoder
         if (lane == 0) mq_dec_init(L.d, stream + offs[jid], (long)lens[jid]);
         L.ent = S.ent; L.mq = c_mq94.v; L.zcsc = S.zcsc; L.flags = S.flags; L.data = out; L.w = w; L.h = h; L.stride = stride;
-        t1_decode_block_wave(L, __shfl((int)numbps[jid], 0), S.mrctx, lane);
+        t1_decode_block_wave(L, __shfl((int)numbps[jid], 0), skip_planes + vzero, S.mrctx, lane);
     }
     __syncthreads();                                                      // includes the wait for lane 0's stores and atomics
+    const uint32_t mid = t1_coarse_mid(skip_planes);
     for (int i = lane; i < n; i += 64) {                                  // t1.go:1281-1289
-        if (!(S.flags[(i / w + 1) * stride + T1D_XO + (i % w)] & T1SignNeg)) continue;
+        const bool neg = (S.flags[(i / w + 1) * stride + T1D_XO + (i % w)] & T1SignNeg) != 0;
+        if (!neg && !mid) continue;
         const int v = __hip_atomic_load(&out[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // L2, not this CU's L1
-        out[i] = (int32_t)(0u - (uint32_t)v);
+        out[i] = t1_coarse_finish(v, mid, neg);
     }
 }
 
@@ -1273,13 +1285,14 @@ struct T1DecState { uint32_t C, A, CT, nmr; long long bp, len; };
 __global__ __launch_bounds__(64) void t1_dec_step_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                          const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
                                                          const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded,
-                                                         uint8_t *__restrict__ ws, int k) {
+                                                         uint8_t *__restrict__ ws, int k, int skip_planes) {
     __shared__ T1Dec64Shared S;
     if ((int)blockIdx.x >= njobs) return;
-    const int nb = (int)numbps[blockIdx.x];
+    const int nb0 = (int)numbps[blockIdx.x];
+    const int nb = max(nb0 - skip_planes, 0);                        // planes above the floor: p counts from the floor, bit plane p + skip_planes
     const int p = nb - 1 - k;                                        // this launch: SigProp of the block's k-th plane from ITS top
     const bool first = k == 0;
-    if (nb > T1DS_MAXP || p < -1) return;                            // deep blocks: t1_decode64_kernel; block finished at k = nb
+    if (nb0 > T1DS_MAXP || p < -1) return;                            // deep blocks: t1_decode64_kernel; block finished at k = nb
     const int lane = threadIdx.x;
     int vzero;                                                       // see t1_decode64_kernel
     asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
@@ -1318,7 +1331,7 @@ __global__ __launch_bounds__(64) void t1_dec_step_kernel(const BlockJob *__restr
     if (!first && p + 1 < nb) {
         // MagRef(p + 1), second half (t1.go:1331-1347): the same member ballots as when the list was written -- nothing
         // touched the flags in between -- give every member its position in the list; its decision is that bit.
-        const int32_t bit = (int32_t)(1u << (p + 1));
+        const int32_t bit = (int32_t)(1u << (p + 1 + skip_planes));
         const uint32_t *bits = reinterpret_cast<const uint32_t *>(rec + T1DS_BITS);
         int off = 0;
         for (int y = 0; y < h; y++) {
@@ -1338,16 +1351,18 @@ __global__ __launch_bounds__(64) void t1_dec_step_kernel(const BlockJob *__restr
     }
     if (p < 0) {                                                     // t1.go:1281-1289
         __syncthreads();                                             // includes the wait for the stores and atomics above
+        const uint32_t mid = t1_coarse_mid(skip_planes);
         for (int i = lane; i < n; i += 64) {
-            if (!(S.flags[(i / w + 1) * stride + T1D_XO + (i % w)] & T1SignNeg)) continue;
+            const bool neg = (S.flags[(i / w + 1) * stride + T1D_XO + (i % w)] & T1SignNeg) != 0;
+            if (!neg && !mid) continue;
             const int v = __hip_atomic_load(&out[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // L2, not this CU's L1
-            out[i] = (int32_t)(0u - (uint32_t)v);
+            out[i] = t1_coarse_finish(v, mid, neg);
         }
         return;
     }
     int nmr = 0;
     if (p < nb) {
-        t1_dec_sigprop_wave(L, (int32_t)(1u << p), S.mrctx, S.mrctx + 64, lane);
+        t1_dec_sigprop_wave(L, (int32_t)(1u << (p + skip_planes)), S.mrctx, S.mrctx + 64, lane);
         // MagRef(p), first half: members in coding order (rows, then columns) and their contexts
         uint8_t *list = rec + T1DS_LIST;
         for (int y = 0; y < h; y++) {
@@ -1535,7 +1550,7 @@ __device__ __forceinline__ void t1_magref_chain(MqLaneDec &mq, const uint32_t *m
 template <bool BITLIST>
 __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_magref_lanes_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                                  const uint64_t *__restrict__ offs, const uint8_t *__restrict__ numbps,
-                                                                 uint8_t *__restrict__ ws, const uint32_t *__restrict__ perm, int k) {
+                                                                 uint8_t *__restrict__ ws, const uint32_t *__restrict__ perm, int k, int skip_planes) {
     __shared__ uint32_t mqtab_w[T1_LANES_WPW][96];
     __shared__ __attribute__((aligned(16))) uint8_t ring_w[T1_LANES_WPW][64 * T1R_STRIDE];
     T1_LANES_PRIO();
@@ -1550,7 +1565,7 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_magref_lanes_kernel(
     bool live = jid < njobs;
     const BlockJob J = jobs[live ? jid : 0];
     const int nb = live ? (int)numbps[jid] : 0;
-    live = live && J.w <= 64 && J.h <= 64 && nb <= T1DS_MAXP && nb - 1 - k >= 0;
+    live = live && J.w <= 64 && J.h <= 64 && nb <= T1DS_MAXP && nb - skip_planes - 1 - k >= 0;     // MagRef(p) of the planes p >= the floor
     uint8_t *const rec = ws + (size_t)(live ? jid : 0) * T1DS_STRIDE;
     T1DecState *const stp = reinterpret_cast<T1DecState *>(rec + T1DS_STATE);
     T1DecState st = *stp;
@@ -1787,7 +1802,7 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
 // general_only: every block on the general kernel (A/B knob); otherwise blocks up to 64x64 take t1_decode64_kernel
 hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, const uint8_t *numbps, int32_t *decoded, uint8_t *work, size_t work_per_job,
-                            int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput) {
+                            int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput, int skip_planes) {
     if (njobs <= 0) return hipSuccess;
     if (!general_only) {
         if (split_ws) {
@@ -1803,19 +1818,19 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
             if (sig_lanes) hipLaunchKernelGGL(t1_order_kernel, dim3(1), dim3(1024), 0, s, jobs, njobs, numbps, lens, 0, perm, slot_of, ngroups * 64);
             if (sig_lanes >= 2) {
                 hipLaunchKernelGGL(t1_dec_sig_lanes_kernel<true>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, lens, numbps,
-                                   split_ws, masks, (const uint32_t *)perm, planes, 0);
+                                   split_ws, masks, (const uint32_t *)perm, planes, 0, skip_planes);
             } else
             for (int k = 0; k <= T1DS_MAXP; k++) {
                 if (sig_lanes) {
                     hipLaunchKernelGGL(t1_dec_sig_lanes_kernel<false>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, lens, numbps,
-                                       split_ws, masks, (const uint32_t *)perm, planes, k);
-                    hipLaunchKernelGGL(t1_dec_plane_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, numbps, decoded, split_ws, masks, slot_of, planes, k);
+                                       split_ws, masks, (const uint32_t *)perm, planes, k, skip_planes);
+                    hipLaunchKernelGGL(t1_dec_plane_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, numbps, decoded, split_ws, masks, slot_of, planes, k, skip_planes);
                 } else {
-                    hipLaunchKernelGGL(t1_dec_step_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, decoded, split_ws, k);
+                    hipLaunchKernelGGL(t1_dec_step_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, decoded, split_ws, k, skip_planes);
                 }
                 if (k < T1DS_MAXP) {
-                    if (sig_lanes) { if (k > 0) hipLaunchKernelGGL(t1_dec_magref_lanes_kernel<true>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, numbps, split_ws, (const uint32_t *)perm, k); }
-                    else hipLaunchKernelGGL(t1_dec_magref_lanes_kernel<false>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, numbps, split_ws, (const uint32_t *)nullptr, k);
+                    if (sig_lanes) { if (k > 0) hipLaunchKernelGGL(t1_dec_magref_lanes_kernel<true>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, numbps, split_ws, (const uint32_t *)perm, k, skip_planes); }
+                    else hipLaunchKernelGGL(t1_dec_magref_lanes_kernel<false>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, numbps, split_ws, (const uint32_t *)nullptr, k, skip_planes);
                 }
             }
         }
@@ -1823,9 +1838,9 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
             hipLaunchKernelGGL(t1_dec_assemble_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, numbps, decoded,
                                reinterpret_cast<const uint64_t *>(split_ws + t1_dec_lanes_mask_offset((size_t)njobs)),
                                reinterpret_cast<const uint32_t *>(split_ws + t1_dec_lanes_perm_offset((size_t)njobs)) + (size_t)((njobs + 63) / 64) * 64,
-                               reinterpret_cast<const uint64_t *>(split_ws + t1_dec_lanes_planes_offset((size_t)njobs)));
+                               reinterpret_cast<const uint64_t *>(split_ws + t1_dec_lanes_planes_offset((size_t)njobs)), skip_planes);
         hipLaunchKernelGGL(t1_decode64_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, decoded,
-                           split_ws ? T1DS_MAXP + 1 : 0);
+                           split_ws ? T1DS_MAXP + 1 : 0, skip_planes);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || max_dim <= 64) return e;
     }
@@ -1842,8 +1857,8 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
         // for every block (the blocks of a frame decode side by side: latency)
         int classes = throughput;
         { const char *en = tuning_env("J2K_T1_BIG_DEC_CLASSES"); if (en) classes = atoi(en); }
-        hipLaunchKernelGGL((t1_decode_big_kernel<4, 258>), dim3(njobs), dim3(rot ? 256 : 64), sizeof(T1BigDec<4, 258>), s, jobs, njobs, stream, offs, lens, numbps, decoded, rot, classes ? 0 : 1);
-        if (classes) hipLaunchKernelGGL((t1_decode_big_kernel<2, 130>), dim3(njobs), dim3(rot ? 256 : 64), sizeof(T1BigDec<2, 130>), s, jobs, njobs, stream, offs, lens, numbps, decoded, rot, 0);
+        hipLaunchKernelGGL((t1_decode_big_kernel<4, 258>), dim3(njobs), dim3(rot ? 256 : 64), sizeof(T1BigDec<4, 258>), s, jobs, njobs, stream, offs, lens, numbps, decoded, rot, classes ? 0 : 1, skip_planes);
+        if (classes) hipLaunchKernelGGL((t1_decode_big_kernel<2, 130>), dim3(njobs), dim3(rot ? 256 : 64), sizeof(T1BigDec<2, 130>), s, jobs, njobs, stream, offs, lens, numbps, decoded, rot, 0, skip_planes);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || max_dim <= 256) return e;
     }
@@ -1859,9 +1874,9 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
         }
     }
     if (wb) hipLaunchKernelGGL(t1_decode_kernel<true>, dim3(njobs), dim3(64), lds, s, jobs, njobs, stream, offs, lens, numbps, decoded,
-                               work, work_per_job, wb, skip);
+                               work, work_per_job, wb, skip, skip_planes);
     else hipLaunchKernelGGL(t1_decode_kernel<false>, dim3(njobs), dim3(64), lds, s, jobs, njobs, stream, offs, lens, numbps, decoded,
-                            work, work_per_job, wb, skip);
+                            work, work_per_job, wb, skip, skip_planes);
     return hipGetLastError();
 }
 

@@ -190,7 +190,7 @@ __device__ __forceinline__ void tbd_wave_sync() {
 template <int NWD, int RWS>
 __global__ __launch_bounds__(256) void t1_decode_big_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                            const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
-                                                           const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded, int rot, int all_sizes) {
+                                                           const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded, int rot, int all_sizes, int skip_planes) {
     extern __shared__ __attribute__((aligned(16))) uint8_t tbd_lds[];
     T1BigDec<NWD, RWS> &F = *reinterpret_cast<T1BigDec<NWD, RWS> *>(tbd_lds);
     const int jid = blockIdx.x;
@@ -246,7 +246,8 @@ __global__ __launch_bounds__(256) void t1_decode_big_kernel(const BlockJob *__re
 #endif
     };
 
-    for (int bp = nb - 1; bp >= 0; bp--) {
+    const int floor_bp = (int)tbd_u((uint32_t)skip_planes);       // the quality floor (j2k_*_coarse): planes below it stay undecoded
+    for (int bp = nb - 1; bp >= floor_bp; bp--) {
         const int32_t bit = bp < 32 ? (int32_t)(1u << bp) : 0;
         // =================== significance propagation (t1.go:1295-1319): raster order ===================
         for (int y = 0; y < h; y++) {
@@ -457,11 +458,13 @@ __global__ __launch_bounds__(256) void t1_decode_big_kernel(const BlockJob *__re
     }
     __threadfence();                                                // (the ORs above are done before the magnitudes are read back)
     // ---- signs (t1.go:1281-1289) ----
+    const uint32_t mid = t1_coarse_mid(skip_planes);                // with a floor: the midpoint into every non-zero magnitude, before its sign
     for (int y = 0; y < h; y++)
         for (int k = 0; k < nw; k++) {
             const uint64_t ng = F.NEG[y + 1][k];
+            const uint64_t touch = mid ? F.S[y + 1][k] : ng;        // (a negative sample is a significant one)
 #ifndef J2K_TBD_TRACE
-            if ((ng >> lane) & 1) { const size_t i = (size_t)y * w + 64 * k + lane; out[i] = (int32_t)(0u - (uint32_t)out[i]); }
+            if ((touch >> lane) & 1) { const size_t i = (size_t)y * w + 64 * k + lane; out[i] = t1_coarse_finish(out[i], mid, (ng >> lane) & 1); }
 #endif
         }
 }

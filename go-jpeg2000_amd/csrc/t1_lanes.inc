@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(con
                                                               const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
                                                               const uint8_t *__restrict__ numbps, uint8_t *__restrict__ ws,
                                                               uint64_t *__restrict__ masks, const uint32_t *__restrict__ perm,
-                                                              uint64_t *__restrict__ planes, int k_launch) {
+                                                              uint64_t *__restrict__ planes, int k_launch, int skip_planes) {
     __shared__ T1LShared L_w[T1_LANES_WPW];
     __shared__ T1LTables TB;
     T1_LANES_PRIO();
@@ -250,8 +250,9 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(con
     const long jid = (long)pj;
     bool live0 = pj != 0xFFFFFFFFu;
     const BlockJob J = jobs[live0 ? jid : 0];
-    const int nb = live0 ? (int)numbps[jid] : 0;
-    live0 = live0 && J.w <= 64 && J.h <= 64 && nb <= T1DS_MAXP && nb > 0;
+    const int nb0 = live0 ? (int)numbps[jid] : 0;
+    const int nb = max(nb0 - skip_planes, 0);     // the planes above the quality floor: below, plane p stands for bit plane p + skip_planes
+    live0 = live0 && J.w <= 64 && J.h <= 64 && nb0 <= T1DS_MAXP && nb > 0;
     const int w = J.w, h = J.h;
     uint8_t *const rec = ws + (size_t)(live0 ? jid : 0) * T1DS_STRIDE;
     T1DecState *const stp = reinterpret_cast<T1DecState *>(rec + T1DS_STATE);
@@ -551,13 +552,14 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(con
 // 64 rows twice per launch: 46 000 instructions per block against 16 000 now.
 __global__ __launch_bounds__(64) void t1_dec_plane_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ numbps,
                                                           int32_t *__restrict__ decoded, uint8_t *__restrict__ ws, uint64_t *__restrict__ masks,
-                                                          const uint32_t *__restrict__ slot_of, uint64_t *__restrict__ planes, int k) {
+                                                          const uint32_t *__restrict__ slot_of, uint64_t *__restrict__ planes, int k, int skip_planes) {
     __shared__ uint32_t stage[2][132];
     const int jid = blockIdx.x;
     if (jid >= njobs) return;
-    const int nb = (int)numbps[jid];
+    const int nb0 = (int)numbps[jid];
+    const int nb = max(nb0 - skip_planes, 0);                  // as in t1_dec_sig_lanes_kernel: plane p = bit plane p + skip_planes
     const int p = nb - 1 - k;
-    if (nb > T1DS_MAXP || p < -1) return;
+    if (nb0 > T1DS_MAXP || p < -1) return;
     const BlockJob J = jobs[jid];
     const int w = J.w, h = J.h;
     if (w > 64 || h > 64) return;
@@ -581,17 +583,18 @@ __global__ __launch_bounds__(64) void t1_dec_plane_kernel(const BlockJob *__rest
 // wavefront per block, lanes = columns, one row per trip; the words of a row are wave-uniform loads.
 __global__ __launch_bounds__(64) void t1_dec_assemble_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ numbps,
                                                              int32_t *__restrict__ decoded, const uint64_t *__restrict__ masks,
-                                                             const uint32_t *__restrict__ slot_of, const uint64_t *__restrict__ planes) {
+                                                             const uint32_t *__restrict__ slot_of, const uint64_t *__restrict__ planes, int skip_planes) {
     const int jid = blockIdx.x;
     if (jid >= njobs) return;
-    const int nb = (int)numbps[jid];
-    if (nb > T1DS_MAXP) return;
+    const int nb0 = (int)numbps[jid];
+    if (nb0 > T1DS_MAXP) return;
+    const int nb = max(nb0 - skip_planes, 0);                  // the planes that were decoded: word q holds bit plane q + skip_planes
     const BlockJob J = jobs[jid];
     const int w = J.w, h = J.h;
     if (w > 64 || h > 64) return;
     const int lane = threadIdx.x;
     int32_t *out = decoded + J.out_off;
-    if (nb == 0) {                                              // no planes: T1.Decode leaves the zeroed data (t1.go:1261-1289)
+    if (nb == 0) {                                              // no planes (or none above the floor): T1.Decode leaves the zeroed data (t1.go:1261-1289)
         for (int i = lane; i < w * h; i += 64) out[i] = 0;
         return;
     }
@@ -600,12 +603,14 @@ __global__ __launch_bounds__(64) void t1_dec_assemble_kernel(const BlockJob *__r
     const uint64_t *pl = planes + (size_t)jid * T1L_PLANE_WORDS;                                              // + 64 * plane + row
     const bool hi_half = lane >= 32;
     const uint32_t sh = (uint32_t)lane & 31u;
+    const uint32_t mid = t1_coarse_mid(skip_planes);
     for (int y = 0; y < h; y++) {
         uint32_t v = 0;
         for (int q = 0; q < nb; q++) {
             const uint64_t pw = pl[64 * q + y];
             v |= (((hi_half ? (uint32_t)(pw >> 32) : (uint32_t)pw) >> sh) & 1u) << q;
         }
+        v = v ? v << skip_planes | mid : 0u;
         const uint64_t ng = neg[64 * y];
         if (((hi_half ? (uint32_t)(ng >> 32) : (uint32_t)ng) >> sh) & 1u) v = 0u - v;
         if (lane < w) out[(size_t)y * w + lane] = (int32_t)v;

@@ -66,6 +66,7 @@ SYMBOLS = [
     "j2k_plan_frame_bound", "j2k_plan_encode_tile_parts", "j2k_plan_decode_tile_parts", "j2k_plan_place_blocks", "j2k_plan_frame_status", "j2k_plan_frame_parallel_tiles",
     "j2k_plan_encode_frame_pixels", "j2k_plan_decode_frame_pixels", "j2k_encode_pixels_host", "j2k_decode_pixels_host",
     "j2k_plan_reduced_size", "j2k_plan_inverse_reduced", "j2k_plan_inverse_pixels_reduced", "j2k_plan_decode_frame_pixels_reduced", "j2k_decode_pixels_host_reduced",
+    "j2k_decode_blocks_coarse", "j2k_plan_decode_blocks_coarse", "j2k_plan_decode_frame_pixels_coarse", "j2k_decode_pixels_host_coarse",
     "j2k_plan_pack_bound", "j2k_plan_pack_stream", "j2k_plan_unpack_stream", "j2k_plan_unpack_streams",
     "j2k_comm_load_error", "j2k_comm_get_unique_id", "j2k_comm_create", "j2k_comm_destroy", "j2k_comm_last_error", "j2k_comm_stream", "j2k_gather_streams", "j2k_comm_wait",
 ]
@@ -118,6 +119,10 @@ def lib():
             "j2k_plan_pack_bound": (S, [V]), "j2k_ctx_set_option": (I, [V, C.c_char_p, C.c_long]),
             "j2k_quantize": (I, [V, DP, S, C.c_double, C.POINTER(C.c_int32)]), "j2k_dequantize": (I, [V, C.POINTER(C.c_int32), S, C.c_double, DP]),
             "j2k_plan_set_dequantize": (I, [V, I]),
+            "j2k_decode_blocks_coarse": (I, [V, I, V, V, V, V, V, S, I, V, V]),
+            "j2k_plan_decode_blocks_coarse": (I, [V, V, V, V, V, I, V]),
+            "j2k_plan_decode_frame_pixels_coarse": (I, [V, V, S, V, I, I, I, I, V, S]),
+            "j2k_decode_pixels_host_coarse": (I, [V, V, S, I, I, I, I, V, S]),
         }
         for name, (res, args) in sigs.items():
             if partial and not hasattr(L, name):

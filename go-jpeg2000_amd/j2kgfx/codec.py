@@ -357,9 +357,13 @@ class FramePlan:
         return out, tile_offs
 
     @_stage
-    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0):
+    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0, skip_planes=0):
         """tile-parts cs[:length] -> pixels into pix (device uint8 [H, stride]; reduce > 0, Mallat plans: [H_r, stride], and only the
-        code-blocks of the resolutions it needs are decoded)"""
+        code-blocks of the resolutions it needs are decoded; skip_planes = k > 0, MQ plans: every block decoder stops after bit plane k)"""
+        if skip_planes:
+            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_coarse(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
+                                                                          int(bool(sop)), int(bool(eph)), int(reduce), int(skip_planes), self._p(pix), C.c_size_t(int(pix.shape[1]))))
+            return pix
         if reduce:
             self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_reduced(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
                                                                            int(bool(sop)), int(bool(eph)), int(reduce), self._p(pix), C.c_size_t(int(pix.shape[1]))))
@@ -386,10 +390,15 @@ class FramePlan:
         self.ctx.check(st)
         return dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
 
-    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0):
-        """closed-loop plans: tile-parts (bytes / numpy uint8) -> numpy uint8 pixels of `shape` = (H, stride); reduce > 0: (H_r, stride)"""
+    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0, skip_planes=0):
+        """closed-loop plans: tile-parts (bytes / numpy uint8) -> numpy uint8 pixels of `shape` = (H, stride); reduce > 0: (H_r, stride);
+        skip_planes > 0 (MQ plans): as decode_frame_pixels"""
         cs = np.ascontiguousarray(np.frombuffer(bytes(cs), np.uint8) if not isinstance(cs, np.ndarray) else cs, dtype=np.uint8)
         pix = np.zeros(shape, np.uint8)
+        if skip_planes:
+            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_coarse(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
+                                                                    int(reduce), int(skip_planes), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
+            return pix
         if reduce:
             self.ctx.check(self.ctx.L.j2k_decode_pixels_host_reduced(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
                                                                      int(reduce), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
@@ -461,9 +470,14 @@ class FramePlan:
         return offs, stream
 
     @_stage
-    def decode_blocks(self, stream, offs, lens, numbps, decoded=None):
+    def decode_blocks(self, stream, offs, lens, numbps, decoded=None, skip_planes=0):
+        """skip_planes = k > 0 (MQ plans): every block's decoder stops after bit plane k (j2k_plan_decode_blocks_coarse)"""
         t = _torch()
         decoded = decoded if decoded is not None else self.empty(self.info.decoded_elems, t.int32)
+        if skip_planes:
+            self.ctx.check(self.ctx.L.j2k_plan_decode_blocks_coarse(self.h, self._p(stream), self._p(offs), self._p(lens),
+                                                                    self._p(numbps), int(skip_planes), self._p(decoded)))
+            return decoded
         self.ctx.check(self.ctx.L.j2k_plan_decode_blocks(self.h, self._p(stream), self._p(offs), self._p(lens),
                                                          self._p(numbps), self._p(decoded)))
         return decoded

@@ -43,8 +43,9 @@ def encode_blocks(coder, planes, blocks, ctx=None):
     return out[:total.value].copy(), offs[:n], lens[:n], nb[:n]
 
 
-def decode_blocks(coder, stream, offs, lens, numbps, blocks, ctx=None):
-    """Returns a list of 2-D int32 arrays (h, w), one per block."""
+def decode_blocks(coder, stream, offs, lens, numbps, blocks, ctx=None, skip_planes=0):
+    """Returns a list of 2-D int32 arrays (h, w), one per block.  skip_planes = k > 0 (MQ coder): every block's decoder stops after
+    bit plane k; non-zero magnitudes take the midpoint of the planes left undecoded (j2k_decode_blocks_coarse)."""
     ctx = ctx or default_context()
     blocks = np.ascontiguousarray(blocks, dtype=BLOCK_DTYPE)
     n = blocks.size
@@ -56,10 +57,16 @@ def decode_blocks(coder, stream, offs, lens, numbps, blocks, ctx=None):
     coff[:n] = np.concatenate(([0], np.cumsum(sizes)[:-1])) if n else []
     coeffs = np.zeros(max(int(sizes.sum()), 1), dtype=np.int32)
     sp = stream.ctypes.data_as(C.c_void_p) if stream.size else None
-    ctx.check(ctx.L.j2k_decode_blocks(
-        ctx.h, int(coder), sp, offs.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
-        numbps.ctypes.data_as(C.c_void_p), blocks.ctypes.data_as(C.c_void_p), C.c_size_t(n),
-        coeffs.ctypes.data_as(C.c_void_p), coff.ctypes.data_as(C.c_void_p)))
+    if skip_planes:
+        ctx.check(ctx.L.j2k_decode_blocks_coarse(
+            ctx.h, int(coder), sp, offs.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
+            numbps.ctypes.data_as(C.c_void_p), blocks.ctypes.data_as(C.c_void_p), C.c_size_t(n), int(skip_planes),
+            coeffs.ctypes.data_as(C.c_void_p), coff.ctypes.data_as(C.c_void_p)))
+    else:
+        ctx.check(ctx.L.j2k_decode_blocks(
+            ctx.h, int(coder), sp, offs.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
+            numbps.ctypes.data_as(C.c_void_p), blocks.ctypes.data_as(C.c_void_p), C.c_size_t(n),
+            coeffs.ctypes.data_as(C.c_void_p), coff.ctypes.data_as(C.c_void_p)))
     return [coeffs[int(coff[i]):int(coff[i]) + int(sizes[i])].reshape(int(blocks[i]["h"]), int(blocks[i]["w"]))
             for i in range(n)]
 

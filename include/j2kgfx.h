@@ -157,6 +157,17 @@ int j2k_encode_blocks(j2k_ctx *ctx, int coder, const int32_t *const *planes, con
 int j2k_decode_blocks(j2k_ctx *ctx, int coder, const uint8_t *bytes, const uint64_t *offs,
                       const uint32_t *lens, const uint8_t *numbps, const j2k_block *blocks,
                       size_t nblocks, int32_t *coeffs, const uint64_t *coeff_offs);
+/* Quality-scalable T1.Decode (MQ coder; a feature of this library, the reference decodes every block to its last plane):
+ * skip_planes = k, 0 ... 31.  Every block's loop `for bp = numBPS-1 ... 0` (t1.go:1261-1410) runs down to plane k only -- all three
+ * passes of a plane or none; a block with numBPS <= k reads nothing of its stream and is zeros -- and every non-zero magnitude
+ * takes the midpoint of the planes left undecoded (bit k-1, for k >= 1) before its sign.  With v the sample of the full decode,
+ * |v| < 2^31:   m = |v| & ~(2^k - 1);  result = sign(v) * (m != 0 && k >= 1 ? m | 2^(k-1) : m).
+ * k = 0 is j2k_decode_blocks; k outside 0 ... 31: J2K_ERR_INVALID_ARG; k > 0 with J2K_CODER_HT: J2K_ERR_UNSUPPORTED (its one
+ * pass has no planes to stop between).  The same argument in j2k_plan_decode_blocks_coarse, j2k_plan_decode_frame_pixels_coarse
+ * and j2k_decode_pixels_host_coarse below. */
+int j2k_decode_blocks_coarse(j2k_ctx *ctx, int coder, const uint8_t *bytes, const uint64_t *offs,
+                             const uint32_t *lens, const uint8_t *numbps, const j2k_block *blocks,
+                             size_t nblocks, int skip_planes, int32_t *coeffs, const uint64_t *coeff_offs);
 /* worst-case bytes one w x h block can produce (sizing of `out`) */
 size_t j2k_block_bound(int coder, int w, int h);
 
@@ -677,6 +688,16 @@ int j2k_plan_decode_frame_pixels_reduced(j2k_plan *plan, const uint8_t *d_cs, si
                                          int sop, int eph, int reduce, void *d_pix, size_t stride);
 int j2k_decode_pixels_host_reduced(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, int reduce,
                                    void *pix, size_t stride);
+/* Both scalability axes in one call: `reduce` as above (0 on any closed-loop plan, > 0 by the rules of the _reduced calls) and the
+ * quality floor `skip_planes` of j2k_decode_blocks_coarse (uniform over the frame: there are no quality layers in the stream).  An
+ * argument, not plan state, like `reduce`: a captured graph means what it says.  skip_planes = 0 is the _reduced call (reduce = 0:
+ * j2k_plan_decode_frame_pixels).  A refused call writes nothing into d_pix / pix. */
+int j2k_plan_decode_blocks_coarse(j2k_plan *plan, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
+                                  const uint8_t *d_numbps, int skip_planes, int32_t *d_decoded);
+int j2k_plan_decode_frame_pixels_coarse(j2k_plan *plan, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs,
+                                        int sop, int eph, int reduce, int skip_planes, void *d_pix, size_t stride);
+int j2k_decode_pixels_host_coarse(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, int reduce,
+                                  int skip_planes, void *pix, size_t stride);
 
 /* The block coder's outputs as those tables.  j2k_plan_t2_packets (host table out): one packet per (tile, component,
  * resolution) of the plan in job order (encoder.go:616-673: tile, component, resolution, band, block row, block column), its
