@@ -139,12 +139,12 @@ extern "C" size_t j2k_plan_frame_bound(const j2k_plan *P) {
 // the packets of a frame written where they end up (t2dev.hip: launch_t2_encode_tile_parts).  d_stream + d_offs: the dense block stream, or
 // d_offs == NULL: d_stream is the plan's slot buffer as plan_encode_private_slots left it and every block is gathered from its slot
 static int encode_tile_parts_impl(j2k_plan *P, const uint8_t *d_data, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,
-                                  int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+                                  int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, const uint8_t *d_kept = nullptr, const uint32_t *d_rate = nullptr) {
     j2k_ctx *ctx = P->ctx;
     const long n = (long)P->blocks.size(), np = P->t2_npackets;
     const int ht = P->spec.coder == J2K_CODER_HT ? 1 : 0;
     uint64_t *d_res = reinterpret_cast<uint64_t *>((uint8_t *)P->d_t2_ws + ((j2k::t2_dev_workspace(np) + 15) & ~size_t(15)));
-    HIPCHK(ctx, j2k::launch_t2_fill_cbs(ctx->stream, n, d_offs, d_lens, d_numbps, 31, ht | 2, P->d_t2_cbs, d_res));
+    HIPCHK(ctx, j2k::launch_t2_fill_cbs(ctx->stream, n, d_offs, d_lens, d_numbps, 31, ht | 2, P->d_t2_cbs, d_res, d_kept, d_rate));
     HIPCHK(ctx, j2k::launch_t2_encode_tile_parts(ctx->stream, P->d_t2_packets, np, P->d_t2_cbs, (uint64_t)n, d_data, sop, eph, d_out, (uint64_t)cap, P->d_t2_poffs,
                                                  P->d_t2_ws, d_res, P->d_t2_ptile, P->d_tile_packet0, P->tile_count, P->tile_first, d_tile_offs, P->d_frame_status,
                                                  d_offs ? nullptr : (P->d_bjobs_alias ? P->d_bjobs_alias : P->d_bjobs), d_offs ? nullptr : (ht ? P->d_maglens : nullptr), ht, P->t2_body_slices));
@@ -162,8 +162,43 @@ extern "C" int j2k_plan_encode_tile_parts(j2k_plan *P, const uint8_t *d_stream, 
     return encode_tile_parts_impl(P, d_stream, d_offs, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs);
 }
 
+// what every rate call needs of its plan (j2k_rate.cpp)
+int rate_check(j2k_plan *P, const char *who);
+
+// j2k_plan_encode_tile_parts with every block cut after its first d_kept[j] bit planes (j2k_plan_rate_allocate): its bytes are the prefix
+// d_rate[j * 32 + d_kept[j]] of what the block coder wrote, its passes the 3 p - 2 of those planes (none, and no bytes, for p = 0), ZeroBitPlanes
+// as before.  Compaction, bodies, tile-parts, SOP and EPH are unchanged; d_kept[j] = numBPS everywhere gives j2k_plan_encode_tile_parts' bytes.
+extern "C" int j2k_plan_encode_tile_parts_kept(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,
+                                               const uint8_t *d_kept, const uint32_t *d_rate, int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    if (!d_stream || !d_offs || !d_lens || !d_numbps || !d_kept || !d_rate || !d_out || !d_tile_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    int r = rate_check(P, "j2k_plan_encode_tile_parts_kept");
+    if (r != J2K_OK) return r;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    r = cl_prepare(P);
+    if (r != J2K_OK) return r;
+    return encode_tile_parts_impl(P, d_stream, d_offs, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, d_kept, d_rate);
+}
+
+static int decode_tile_parts_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                  uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors);
 extern "C" int j2k_plan_decode_tile_parts(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
                                           uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps) {
+    return decode_tile_parts_impl(P, d_cs, len, d_tile_offs, sop, eph, d_offs, d_lens, d_numbps, nullptr);
+}
+// ... for streams whose blocks may be cut at bit planes (j2k_plan_encode_tile_parts_kept): also each block's floor, and numbps counts the planes
+// from the block's top down to bit 0 -- d_floors[j] = max(31 - ZeroBitPlanes - (passes + 2) / 3, 0), d_numbps[j] = (passes + 2) / 3 + d_floors[j];
+// j2k_plan_decode_blocks_floors decodes them.  An uncut stream gives floors 0 and j2k_plan_decode_tile_parts' tables.  MQ plans only.
+extern "C" int j2k_plan_decode_tile_parts_floors(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                                 uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    if (!d_floors) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    if (P->spec.coder != J2K_CODER_MQ) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_decode_tile_parts_floors: per-block floors need the MQ coder");
+    return decode_tile_parts_impl(P, d_cs, len, d_tile_offs, sop, eph, d_offs, d_lens, d_numbps, d_floors);
+}
+static int decode_tile_parts_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                  uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors) {
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (!d_cs || !d_offs || !d_lens || !d_numbps) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
@@ -175,7 +210,7 @@ extern "C" int j2k_plan_decode_tile_parts(j2k_plan *P, const uint8_t *d_cs, size
     // (SOP + EPH streams: a tile's packets side by side, checked against the serial rule and redone by it where a guess was off -- t2dec.hip)
     HIPCHK(ctx, j2k::launch_t2_decode_tiles(ctx->stream, P->d_t2_chains, P->tile_count, P->d_tile_packet0, P->d_t2_packets, P->t2_npackets, P->d_t2_cbs, (uint64_t)n, d_cs,
                                             (uint64_t)len, sop, eph, P->d_t2_body_base, P->d_frame_status, ctx->t2_parallel ? P->d_t2_par : nullptr,
-                                            P->spec.coder == J2K_CODER_HT ? 1 : 0, 31, d_offs, d_lens, d_numbps));
+                                            P->spec.coder == J2K_CODER_HT ? 1 : 0, 31, d_offs, d_lens, d_numbps, d_floors));
     return J2K_OK;
 }
 
@@ -350,6 +385,95 @@ extern "C" int j2k_plan_decode_frame_pixels_coarse(j2k_plan *P, const uint8_t *d
     if (r != J2K_OK) return r;
     if (reduce == 0) return decode_frame_pixels_impl(P, d_cs, len, d_tile_offs, sop, eph, skip_planes, d_pix, stride);
     return decode_frame_pixels_reduced_impl(P, d_cs, len, d_tile_offs, sop, eph, reduce, skip_planes, d_pix, stride);
+}
+
+// ---- rate-limited frames: j2k_plan_encode_frame_pixels with a budget of code-block body bytes, and the decode of what it writes -------------
+struct ClRate { uint32_t *rate; uint64_t *dist; uint8_t *kept; uint64_t *chosen; uint8_t *floors, *floors_r; };
+static int cl_rate_workspace(j2k_plan *P, ClRate &W) {
+    j2k_ctx *ctx = P->ctx;
+    const size_t n = P->blocks.size(), nr = (n + 255) & ~size_t(255);
+    const size_t bytes = nr * 32 * 8 + nr * 32 * 4 + 3 * nr + 256;
+    if (!P->d_cl_rate) {
+        if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the frame codec's workspaces are made at its first call");
+        HIPCHK(ctx, hipMalloc(&P->d_cl_rate, bytes));
+    }
+    uint8_t *b = (uint8_t *)P->d_cl_rate;
+    W.dist = (uint64_t *)b; b += nr * 32 * 8;
+    W.rate = (uint32_t *)b; b += nr * 32 * 4;
+    W.chosen = (uint64_t *)b; b += 256;
+    W.kept = b; W.floors = b + nr; W.floors_r = b + 2 * nr;
+    return J2K_OK;
+}
+
+// coefficients -> rate-limited tile-parts: block coding into the plan's slots with the tables, the allocation, then every block's kept prefix once
+// from its slot into its packet (d_lens / d_numbps: the caller's tables, filled with the UNCUT lengths and plane counts)
+int plan_encode_frame_from_coeff_rate(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int64_t max_body_bytes, int sop, int eph,
+                                      uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+    j2k_ctx *ctx = P->ctx;
+    int r = rate_check(P, "rate-limited frame encode");
+    if (r != J2K_OK) return r;
+    if (max_body_bytes < 0) return fail(ctx, J2K_ERR_INVALID_ARG, "rate-limited frame encode: a negative budget");
+    ClRate W{};
+    r = cl_prepare(P);
+    if (r == J2K_OK) r = cl_rate_workspace(P, W);
+    if (r == J2K_OK && !P->d_slots) {
+        if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: run the same calls once before j2k_ctx_capture_begin");
+        HIPCHK(ctx, hipMalloc(&P->d_slots, (size_t)P->bytes_cap + 64));
+    }
+    if (r == J2K_OK) r = j2k_plan_encode_blocks_planes(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist);
+    if (r == J2K_OK) r = j2k_plan_rate_allocate(P, W.rate, W.dist, d_numbps, max_body_bytes, W.kept, W.chosen);
+    if (r == J2K_OK) r = encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, W.kept, W.rate);
+    return r;
+}
+
+// j2k_plan_encode_frame_pixels with at most max_body_bytes of code-block bodies (packet and tile-part headers come on top: the last entry of
+// d_tile_offs says what the frame took).  A budget that cuts nothing gives j2k_plan_encode_frame_pixels' bytes.
+extern "C" int j2k_plan_encode_frame_pixels_rate(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, int64_t max_body_bytes,
+                                                 uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    if (!d_out || !d_tile_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    int r = rate_check(P, "j2k_plan_encode_frame_pixels_rate");
+    if (r != J2K_OK) return r;
+    if (max_body_bytes < 0) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_encode_frame_pixels_rate: a negative budget");
+    r = cl_prepare(P);
+    if (r == J2K_OK) r = cl_workspaces(P);
+    if (r == J2K_OK) r = j2k_plan_forward_pixels(P, format, d_pix, stride, P->d_cl_coeff);
+    if (r == J2K_OK) r = plan_encode_frame_from_coeff_rate(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, max_body_bytes, sop, eph, d_out, cap, d_tile_offs);
+    return r;
+}
+
+// j2k_plan_decode_frame_pixels_coarse for streams whose blocks may be cut at bit planes: every block runs from its own top plane down to
+// max(skip_planes, its floor from the packet header).  An uncut stream decodes as with the _coarse call.
+extern "C" int j2k_plan_decode_frame_pixels_rate(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
+                                                 int skip_planes, void *d_pix, size_t stride) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    int r = check_skip_planes(ctx, P->spec.coder, skip_planes, "j2k_plan_decode_frame_pixels_rate");
+    if (r != J2K_OK) return r;
+    if (P->spec.coder != J2K_CODER_MQ) return fail(ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_decode_frame_pixels_rate: per-block floors need the MQ coder");
+    if (!d_pix) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    ReducedTab *R = nullptr;
+    if (reduce != 0) { r = plan_reduced(P, reduce, &R); if (r != J2K_OK) return r; }
+    ClRate W{};
+    r = cl_prepare(P);
+    if (r == J2K_OK) r = cl_workspaces(P);
+    if (r == J2K_OK) r = cl_rate_workspace(P, W);
+    if (r == J2K_OK) r = decode_tile_parts_impl(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, W.floors);
+    if (r != J2K_OK) return r;
+    if (reduce == 0) {
+        r = plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, P->d_cl_decoded, nullptr, skip_planes, W.floors);
+        if (r == J2K_OK) r = j2k_plan_place_blocks(P, P->d_cl_decoded, P->d_cl_coeff);
+        if (r == J2K_OK) r = plan_inverse_pixels_impl(P, P->d_cl_coeff, d_pix, stride, P->d_frame_status);
+        return r;
+    }
+    // the subset's tables, and (the same kernel, the floors in the place of the plane counts) its floors
+    HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, W.floors, R->d_offs, R->d_lens, W.floors_r));
+    HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, R->d_offs, R->d_lens, R->d_numbps));
+    r = plan_decode_blocks_jobs(P, R->d_djobs, R->njobs, d_cs, R->d_offs, R->d_lens, R->d_numbps, P->d_cl_decoded, nullptr, skip_planes, W.floors_r);
+    if (r == J2K_OK) HIPCHK(ctx, launch_place_blocks(ctx->stream, R->d_bjobs, R->d_djobs, R->njobs, R->max_block_h, P->d_cl_decoded, P->d_cl_coeff));
+    if (r == J2K_OK) r = plan_inverse_pixels_reduced_impl(P, P->d_cl_coeff, reduce, d_pix, stride, P->d_frame_status);
+    return r;
 }
 
 extern "C" int j2k_plan_get_decoded_offsets(const j2k_plan *P, uint64_t *offs, size_t cap) {

@@ -38,11 +38,17 @@ int ht_fast_max_samples();
 hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots,
                             uint32_t *lens, uint8_t *numbps, uint8_t *work, size_t work_per_job, int *fault, int max_dim,
                             uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint8_t *bigsym = nullptr, const uint64_t *bigsym_off = nullptr,
-                            uint32_t *bignsyms = nullptr);
+                            uint32_t *bignsyms = nullptr, uint32_t *rate = nullptr);   // rate: 32 words per job, the rate tables (blocks <= 64 x 64 only)
+// rate control (rate.hip): plane distortions of every block; the allocation of a byte budget over the blocks' rate / distortion tables
+hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, uint64_t *dist);
+size_t rate_allocate_workspace(int njobs);
+hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+                                uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen);
 size_t t1_sym_stride(int planes);
 hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, const uint8_t *numbps, int32_t *decoded, uint8_t *work,
-                            size_t work_per_job, int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput = 0, int skip_planes = 0);
+                            size_t work_per_job, int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput = 0, int skip_planes = 0,
+                            const uint8_t *floors = nullptr);   // floors (device, one byte per job): job j stops at max(skip_planes, floors[j])
 size_t t1_dec_split_bytes(size_t njobs);
 hipError_t launch_mq_encode(hipStream_t s, const uint8_t *ctxs, const uint8_t *decs, size_t n, uint8_t *out, size_t cap, uint32_t *out_len, int *fault);
 hipError_t launch_mq_decode(hipStream_t s, const uint8_t *data, size_t len, const uint8_t *ctxs, size_t n, uint8_t *decs, int *fault);
@@ -66,8 +72,8 @@ void t2_read_chain(const void *src, j2k_t2_dec_state &st, int &status, long &don
 size_t t2_par_workspace(long npackets, int ntiles);
 hipError_t launch_t2_decode_tiles(hipStream_t s, void *chains, int ntiles, const int *tile_packet0, const j2k_t2_dev_packet *packets, long npackets, j2k_t2_dev_cb *cbs,
                                   uint64_t ncbs, const uint8_t *data, uint64_t len, int sop, int eph, uint64_t *body_base, int *frame_status, void *ws,
-                                  int ht, int mb, uint64_t *offs, uint32_t *lens, uint8_t *numbps);
-hipError_t launch_t2_blocks(hipStream_t s, long n, const j2k_t2_dev_cb *cbs, int ht, int mb, uint64_t total, uint64_t *offs, uint32_t *lens, uint8_t *numbps, int *status);
+                                  int ht, int mb, uint64_t *offs, uint32_t *lens, uint8_t *numbps, uint8_t *floors = nullptr);   // floors: t2_block_out's per-block floors (the _floors calls)
+hipError_t launch_t2_blocks(hipStream_t s, long n, const j2k_t2_dev_cb *cbs, int ht, int mb, uint64_t total, uint64_t *offs, uint32_t *lens, uint8_t *numbps, int *status, uint8_t *floors = nullptr);
 hipError_t launch_place_blocks(hipStream_t s, const BlockJob *src_jobs, const BlockJob *dec_jobs, int njobs, int max_h, const int32_t *decoded, int32_t *coeff, int ystep = 1);
 hipError_t launch_select_blocks(hipStream_t s, const int *ids, int m, const uint64_t *offs, const uint32_t *lens, const uint8_t *numbps, uint64_t *offs_r,
                                 uint32_t *lens_r, uint8_t *numbps_r);
@@ -119,9 +125,12 @@ T1Workspace t1_workspace(const j2k_ctx *ctx, size_t n, size_t wpj);
 int ensure(j2k_ctx *ctx, void **p, size_t bytes);
 struct PixIO { int stride = 0, single = 0, triple = 0; j2k::YccSrc ycc{}; };   // ycc.y: a YCbCr image in place of packed RGBA8 (triple 8)
 int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix = PixIO());
+int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate);
 int plan_encode_private_slots(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps);
 int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int sop, int eph, uint8_t *d_out, size_t cap,
                                  uint64_t *d_tile_offs);
+int plan_encode_frame_from_coeff_rate(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int64_t max_body_bytes, int sop, int eph,
+                                      uint8_t *d_out, size_t cap, uint64_t *d_tile_offs);
 // guard (device, or null): the launches that write d_frame write nothing if *guard != 0 -- the frame decoder's status word
 int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix = PixIO(), const int *guard = nullptr);
 int plan_inverse_pixels_impl(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride, const int *guard);
@@ -130,7 +139,7 @@ int plan_inverse_pixels_reduced_impl(j2k_plan *P, const int32_t *d_coeff, int re
 // straight into its window of the coefficient planes `d_decoded`, coded rows only.  skip_planes: the quality floor of the _coarse calls (MQ coder;
 // the callers have checked its range and the coder)
 int plan_decode_blocks_jobs(j2k_plan *P, const j2k::BlockJob *d_djobs, int n, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
-                            const uint8_t *d_numbps, int32_t *d_decoded, const j2k::BlockJob *d_placed, int skip_planes = 0);
+                            const uint8_t *d_numbps, int32_t *d_decoded, const j2k::BlockJob *d_placed, int skip_planes = 0, const uint8_t *d_floors = nullptr);
 // the range of skip_planes and the coder it needs: J2K_OK, or the refusal (through fail())
 int check_skip_planes(j2k_ctx *ctx, int coder, int skip_planes, const char *who);
 // the default branch of extractImageData (j2k_image.cpp): d_img's planes on the device; status_word non-null = report a palette index

@@ -234,8 +234,18 @@ extern "C" int j2k_decode_blocks(j2k_ctx *ctx, int coder, const uint8_t *bytes, 
 extern "C" int j2k_decode_blocks_coarse(j2k_ctx *ctx, int coder, const uint8_t *bytes, const uint64_t *offs, const uint32_t *lens,
                                         const uint8_t *numbps, const j2k_block *blocks, size_t nblocks, int skip_planes, int32_t *coeffs,
                                         const uint64_t *coeff_offs) {
+    return j2k_decode_blocks_floors(ctx, coder, bytes, offs, lens, numbps, blocks, nblocks, skip_planes, nullptr, coeffs, coeff_offs);
+}
+// ... block j down to bit plane max(skip_planes, floors[j]) (floors: host, one byte per block, 0 ... 31; NULL = j2k_decode_blocks_coarse)
+extern "C" int j2k_decode_blocks_floors(j2k_ctx *ctx, int coder, const uint8_t *bytes, const uint64_t *offs, const uint32_t *lens,
+                                        const uint8_t *numbps, const j2k_block *blocks, size_t nblocks, int skip_planes, const uint8_t *floors,
+                                        int32_t *coeffs, const uint64_t *coeff_offs) {
     if (!ctx) return J2K_ERR_INVALID_ARG;
     { const int r = check_skip_planes(ctx, coder, skip_planes, "j2k_decode_blocks_coarse"); if (r != J2K_OK) return r; }
+    if (floors) {
+        if (coder == J2K_CODER_HT) return fail(ctx, J2K_ERR_UNSUPPORTED, "j2k_decode_blocks_floors: per-block floors need the MQ coder");
+        for (size_t j = 0; j < nblocks; j++) if (floors[j] > 31) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_decode_blocks_floors: a floor outside 0 ... 31");
+    }
     if (nblocks == 0) return J2K_OK;
     if (!offs || !lens || !blocks || !coeffs || !coeff_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "NULL argument");
     if (coder != J2K_CODER_MQ && coder != J2K_CODER_HT) return fail(ctx, J2K_ERR_INVALID_ARG, "coder");
@@ -255,10 +265,11 @@ extern "C" int j2k_decode_blocks_coarse(j2k_ctx *ctx, int coder, const uint8_t *
     }
     if (nbytes && !bytes) return fail(ctx, J2K_ERR_INVALID_ARG, "bytes == NULL");
     wpj = (wpj + 255) & ~size_t(255);
-    void *d_bytes = nullptr, *d_jobs = nullptr, *d_offs = nullptr, *d_lens = nullptr, *d_nb = nullptr, *d_dec = nullptr, *d_work = nullptr;
+    void *d_bytes = nullptr, *d_jobs = nullptr, *d_offs = nullptr, *d_lens = nullptr, *d_nb = nullptr, *d_dec = nullptr, *d_work = nullptr, *d_floors = nullptr;
     int status = J2K_OK;
-    auto cleanup = [&]() { for (void *p : {d_bytes, d_jobs, d_offs, d_lens, d_nb, d_dec, d_work}) if (p) (void)hipFree(p); };
+    auto cleanup = [&]() { for (void *p : {d_bytes, d_jobs, d_offs, d_lens, d_nb, d_dec, d_work, d_floors}) if (p) (void)hipFree(p); };
     TRY(hipMalloc(&d_bytes, nbytes + 16));
+    if (floors) { TRY(hipMalloc(&d_floors, nblocks + 16)); TRY(hipMemcpyAsync(d_floors, floors, nblocks, hipMemcpyHostToDevice, ctx->stream)); }
     TRY(hipMalloc(&d_jobs, nblocks * sizeof(BlockJob)));
     TRY(hipMalloc(&d_offs, nblocks * 8));
     TRY(hipMalloc(&d_lens, nblocks * 4));
@@ -284,7 +295,7 @@ extern "C" int j2k_decode_blocks_coarse(j2k_ctx *ctx, int coder, const uint8_t *
         int max_dim = 0;
         for (size_t j = 0; j < nblocks; j++) max_dim = std::max(max_dim, std::max(bj[j].w, bj[j].h));
         TRY(launch_t1_decode(ctx->stream, (BlockJob *)d_jobs, (int)nblocks, (uint8_t *)d_bytes, (uint64_t *)d_offs, (uint32_t *)d_lens, (uint8_t *)d_nb,
-                             (int32_t *)d_dec, (uint8_t *)d_work, wpj, max_dim, ctx->t1_dec_general, split ? (uint8_t *)d_work + gen_bytes : nullptr, ctx->t1_dec_lanes, 0, skip_planes));
+                             (int32_t *)d_dec, (uint8_t *)d_work, wpj, max_dim, ctx->t1_dec_general, split ? (uint8_t *)d_work + gen_bytes : nullptr, ctx->t1_dec_lanes, 0, skip_planes, (const uint8_t *)d_floors));
     }
     for (size_t j = 0; j < nblocks; j++)
         TRY(hipMemcpyAsync(coeffs + coeff_offs[j], (int32_t *)d_dec + bj[j].out_off, (size_t)blocks[j].w * blocks[j].h * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -364,7 +375,7 @@ static int ensure_sized(j2k_ctx *ctx, void **p, size_t *cur, size_t need) {
 // image on the device and runs the forward transform into P->d_coeff (after every other buffer is sized)
 template <typename Fwd>
 static int encode_host_tail(j2k_plan *P, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint32_t *lens,
-                            uint8_t *numbps, const Fwd &forward) {
+                            uint8_t *numbps, const Fwd &forward, int64_t max_body_bytes = -1) {    // max_body_bytes >= 0: the rate-limited frame encode
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -382,7 +393,9 @@ static int encode_host_tail(j2k_plan *P, int sop, int eph, uint8_t *out, size_t 
     if ((r = forward()) != J2K_OK) return r;
     std::vector<uint64_t> toffs(nt + 1, 0);
     if (S.closed_loop) {                                     // (blocks gathered from their coding slots straight into the tile-parts: no dense stream)
-        if ((r = plan_encode_frame_from_coeff(P, (int32_t *)P->d_coeff, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps, sop, eph, (uint8_t *)P->d_host_io, bound, d_toffs)) != J2K_OK) return r;
+        if (max_body_bytes >= 0) r = plan_encode_frame_from_coeff_rate(P, (int32_t *)P->d_coeff, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps, max_body_bytes, sop, eph, (uint8_t *)P->d_host_io, bound, d_toffs);
+        else r = plan_encode_frame_from_coeff(P, (int32_t *)P->d_coeff, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps, sop, eph, (uint8_t *)P->d_host_io, bound, d_toffs);
+        if (r != J2K_OK) return r;
         HIPCHK(ctx, hipMemcpyAsync(toffs.data(), d_toffs, (nt + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     } else {
         if ((r = j2k_plan_encode_stream(P, (int32_t *)P->d_coeff, (uint8_t *)P->d_stream, (uint64_t *)P->d_offs, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps)) != J2K_OK) return r;
@@ -414,8 +427,22 @@ static int encode_host_tail(j2k_plan *P, int sop, int eph, uint8_t *out, size_t 
     return J2K_OK;
 }
 
+static int encode_pixels_host_impl(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes, uint8_t *out, size_t cap,
+                                   size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps);
 extern "C" int j2k_encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, uint8_t *out, size_t cap,
                                       size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
+    return encode_pixels_host_impl(P, format, pix, stride, sop, eph, -1, out, cap, out_len, tile_offs, lens, numbps);
+}
+// ... with at most max_body_bytes of code-block bodies (j2k_plan_encode_frame_pixels_rate); lens / numbps: the UNCUT lengths and plane counts
+extern "C" int j2k_encode_pixels_host_rate(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes, uint8_t *out,
+                                           size_t cap, size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    if (max_body_bytes < 0) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_encode_pixels_host_rate: a negative budget");
+    if (!P->spec.closed_loop) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_encode_pixels_host_rate: needs a closed-loop plan");
+    return encode_pixels_host_impl(P, format, pix, stride, sop, eph, max_body_bytes, out, cap, out_len, tile_offs, lens, numbps);
+}
+static int encode_pixels_host_impl(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes, uint8_t *out, size_t cap,
+                                   size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
     if (!P || !pix || !out_len) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
@@ -429,7 +456,7 @@ extern "C" int j2k_encode_pixels_host(j2k_plan *P, int format, const void *pix, 
     return encode_host_tail(P, sop, eph, out, cap, out_len, tile_offs, lens, numbps, [&]() {
         HIPCHK(ctx, hipMemcpyAsync(P->d_host_pix, pix, (size_t)S.H * stride, hipMemcpyHostToDevice, ctx->stream));
         return j2k_plan_forward_pixels(P, format, P->d_host_pix, stride, (int32_t *)P->d_coeff);
-    });
+    }, max_body_bytes);
 }
 
 // image.YCbCr / CMYK / Paletted in Go memory (encoder.go:178-195): each plane crosses PCIe at its native size -- the bytes the rectangle
@@ -459,7 +486,7 @@ extern "C" int j2k_encode_image_host(j2k_plan *P, const j2k_image *img, int sop,
     });
 }
 
-static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride, int skip_planes = 0);
+static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride, int skip_planes = 0, bool cut = false);
 // closed-loop plans: tile-parts (host) -> H2D -> parse -> block decode -> placement -> inverse transform -> image.*.Pix (host), one
 // synchronous call.  The pixel format is the plan's: components 1 / 3 / 4, precision <= 8 -> Gray / RGBA, else Gray16 / RGBA64
 // (decoder.createImage, decoder.go:417-588).
@@ -487,7 +514,21 @@ extern "C" int j2k_decode_pixels_host_coarse(j2k_plan *P, const uint8_t *cs, siz
     }
     return decode_pixels_host_impl(P, cs, len, sop, eph, reduce != 0 ? reduce : -1, pix, stride, skip_planes);
 }
-static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride, int skip_planes) {
+// ... of a stream whose blocks may be cut at bit planes (j2k_plan_decode_frame_pixels_rate)
+extern "C" int j2k_decode_pixels_host_rate(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, int skip_planes, void *pix,
+                                           size_t stride) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_decode_pixels_host_rate");
+    if (r != J2K_OK) return r;
+    if (P->spec.coder != J2K_CODER_MQ) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_decode_pixels_host_rate: per-block floors need the MQ coder");
+    if (reduce != 0) {
+        int32_t wr = 0, hr = 0;
+        r = j2k_plan_reduced_size(P, reduce, &wr, &hr);
+        if (r != J2K_OK) return r;
+    }
+    return decode_pixels_host_impl(P, cs, len, sop, eph, reduce != 0 ? reduce : -1, pix, stride, skip_planes, true);
+}
+static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride, int skip_planes, bool cut) {
     if (!P || !cs || !pix) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
@@ -500,7 +541,8 @@ static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, i
     if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, pixbytes)) != J2K_OK) return r;
     if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, len + 64)) != J2K_OK) return r;
     HIPCHK(ctx, hipMemcpyAsync(P->d_host_io, cs, len, hipMemcpyHostToDevice, ctx->stream));
-    r = skip_planes ? j2k_plan_decode_frame_pixels_coarse(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, std::max(reduce, 0), skip_planes, P->d_host_pix, stride)
+    r = cut ? j2k_plan_decode_frame_pixels_rate(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, std::max(reduce, 0), skip_planes, P->d_host_pix, stride)
+        : skip_planes ? j2k_plan_decode_frame_pixels_coarse(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, std::max(reduce, 0), skip_planes, P->d_host_pix, stride)
         : reduce >= 0 ? j2k_plan_decode_frame_pixels_reduced(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, reduce, P->d_host_pix, stride)
                       : j2k_plan_decode_frame_pixels(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, P->d_host_pix, stride);
     if (r != J2K_OK) return r;

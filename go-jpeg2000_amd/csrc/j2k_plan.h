@@ -236,5 +236,13 @@ struct j2k_plan {
     size_t bigsym_total = 0;
     bool dec_coded_rows_only = false;       // j2k_plan_set_decode_coded_rows_only: HT decode leaves the rows the reference's decoder never writes alone
     std::vector<j2k::ReducedTab> reduced;   // Mallat plans: [reduce], 1 ... levels
+    // rate control (j2k_plan_rate_allocate): one weight per (component, resolution, band), index (c * num_res_jobs + r) * 4 + band; the default is the
+    // band's synthesis energy gain on a Mallat plan and 1 elsewhere (plan_default_rate_weights); d_rate_wj = the weight of every job, uploaded
+    // at the first allocation after the table changed
+    std::vector<double> rate_weights;
+    double *d_rate_wj = nullptr;
+    bool rate_wj_valid = false;
+    void *d_rate_ws = nullptr;              // the allocation kernel's hulls
+    void *d_cl_rate = nullptr;              // the *_rate frame calls: rate and distortion tables, kept planes, chosen bytes, floors (cl_rate_workspace)
     bool dequantize = false;                // j2k_plan_set_dequantize: the 9-7 inverse kernels multiply every int32 coefficient by 1.0 / Quality at their load (dwt.go:514-520)
 };

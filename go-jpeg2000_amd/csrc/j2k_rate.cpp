@@ -1,0 +1,148 @@
+// j2k_rate.cpp -- rate control of the MQ block coder behind the C ABI: the plan's band weights, the table-filling block encode, the allocation
+// of a byte budget (kernels: t1.hip's PLANES instantiations, rate.hip).  include/j2kgfx.h has the contract, tests/rate_cases.py the definition.
+#include <cmath>
+
+#include "j2k_host.h"
+
+using namespace j2k;
+
+// ---- band weights: the synthesis energy gain of a sub-band ---------------------------------------------------------------------------------
+// One level of the 1-D inverse transform as the reference's lifting steps without their integer rounding (dwt.go:122-147, 213-262), run on a
+// line long enough that an impulse in its middle never meets the ends: the response to a low-pass and to a high-pass sample.
+static std::vector<double> synth_response(int wavelet, bool high) {
+    const int n = 64, half = n / 2;
+    std::vector<double> d(n, 0.0);
+    d[high ? 2 * (half / 2) + 1 : 2 * (half / 2)] = 1.0;             // already interleaved: even = low, odd = high
+    auto lift = [&](int first, double c) {                           // d[i] -= c * (d[i-1] + d[i+1]) on the samples of one parity (interior only)
+        for (int i = first ? 1 : 2; i < n - 1; i += 2) d[i] -= c * (d[i - 1] + d[i + 1]);
+    };
+    if (wavelet == W53) {
+        lift(0, 0.25);
+        lift(1, -0.5);
+    } else {
+        const double K = 1.230174104914001, KINV = 0.812893066115961;
+        for (int i = 0; i < n; i++) d[i] *= (i & 1) ? KINV : K;
+        lift(0, 0.443506852043971);
+        lift(1, 0.882911075530934);
+        lift(0, -0.052980118572961);
+        lift(1, -1.586134342059924);
+    }
+    int a = 0, b = n - 1;
+    while (a < b && d[a] == 0.0) a++;
+    while (b > a && d[b] == 0.0) b--;
+    return std::vector<double>(d.begin() + a, d.begin() + b + 1);
+}
+// one more synthesis level under a response: insert zeros, filter with the low-pass response
+static std::vector<double> synth_deeper(const std::vector<double> &f, const std::vector<double> &g0) {
+    std::vector<double> out(2 * f.size() - 1 + g0.size() - 1, 0.0);
+    for (size_t i = 0; i < f.size(); i++)
+        for (size_t k = 0; k < g0.size(); k++) out[2 * i + k] += f[i] * g0[k];
+    return out;
+}
+static double energy(const std::vector<double> &f) { double e = 0; for (double v : f) e += v * v; return e; }
+
+static void plan_default_rate_weights(j2k_plan *P) {
+    const PlanSpec &S = P->spec;
+    const int numRes = S.num_res_jobs > 0 ? S.num_res_jobs : 6;
+    P->rate_weights.assign((size_t)S.C * numRes * 4, 1.0);
+    if (!S.mallat) return;                                           // the windows of the other modes are not sub-bands: every weight 1
+    const int L = numRes - 1;
+    // 1-D gains of a low-pass / high-pass sample d levels down, d = 1 ... L (exact up to 16 levels; deeper ones continue at the last ratio)
+    std::vector<double> EL(L + 1, 1.0), EH(L + 1, 1.0);
+    const std::vector<double> g0 = synth_response(S.wavelet, false), g1 = synth_response(S.wavelet, true);
+    std::vector<double> fl = g0, fh = g1;
+    for (int d = 1; d <= L; d++) {
+        if (d > 1 && d <= 16) { fl = synth_deeper(fl, g0); fh = synth_deeper(fh, g0); }
+        if (d <= 16) { EL[d] = energy(fl); EH[d] = energy(fh); }
+        else { EL[d] = EL[d - 1] * (EL[16] / EL[15]); EH[d] = EH[d - 1] * (EH[16] / EH[15]); }
+    }
+    for (int c = 0; c < S.C; c++)
+        for (int r = 0; r < numRes; r++) {
+            double *w = &P->rate_weights[((size_t)c * numRes + r) * 4];
+            const int d = r == 0 ? L : L - r + 1;
+            w[J2K_BAND_LL] = EL[d] * EL[d];
+            w[J2K_BAND_HL] = w[J2K_BAND_LH] = EH[d] * EL[d];
+            w[J2K_BAND_HH] = EH[d] * EH[d];
+        }
+}
+
+static void plan_rate_weights(j2k_plan *P) {
+    if (P->rate_weights.empty()) plan_default_rate_weights(P);
+}
+
+// what every rate call needs of its plan
+int rate_check(j2k_plan *P, const char *who) {
+    const PlanSpec &S = P->spec;
+    const char *why = nullptr;
+    if (S.coder != J2K_CODER_MQ) why = "needs the MQ coder (the HT coder's one pass has no planes to cut between)";
+    else if (!S.closed_loop) why = "needs a closed-loop plan (only its packets can say where a block was cut)";
+    else if (S.frame_h != S.H) why = "a batch plan (frame_rows): not built";
+    else
+        for (const j2k_block &b : P->blocks)
+            if (b.w > 64 || b.h > 64) { why = "blocks above 64 x 64: not built"; break; }
+    if (why) return fail(P->ctx, J2K_ERR_UNSUPPORTED, (std::string(who) + ": " + why).c_str());
+    return J2K_OK;
+}
+
+extern "C" int j2k_plan_get_rate_weights(j2k_plan *P, double *weights, size_t cap, size_t *count) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    plan_rate_weights(P);
+    if (count) *count = P->rate_weights.size();
+    if (!weights) return cap ? J2K_ERR_INVALID_ARG : J2K_OK;
+    if (cap < P->rate_weights.size()) return J2K_ERR_CAPACITY;
+    memcpy(weights, P->rate_weights.data(), P->rate_weights.size() * sizeof(double));
+    return J2K_OK;
+}
+
+extern "C" int j2k_plan_set_rate_weights(j2k_plan *P, const double *weights, size_t count) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    if (P->ctx->capturing) return fail(P->ctx, J2K_ERR_INVALID_ARG, "capture: set the weights before j2k_ctx_capture_begin");
+    plan_rate_weights(P);
+    if (!weights) { plan_default_rate_weights(P); P->rate_wj_valid = false; return J2K_OK; }       // back to the default
+    if (count != P->rate_weights.size()) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_plan_set_rate_weights: ncomp * num_resolutions * 4 weights");
+    for (size_t i = 0; i < count; i++)
+        if (!(weights[i] >= 0.0) || !std::isfinite(weights[i])) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_plan_set_rate_weights: weights are finite and >= 0");
+    P->rate_weights.assign(weights, weights + count);
+    P->rate_wj_valid = false;
+    return J2K_OK;
+}
+
+extern "C" int j2k_plan_encode_blocks_planes(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps,
+                                             uint32_t *d_rate, uint64_t *d_dist) {
+    if (!P || !d_coeff || !d_slots || !d_lens || !d_numbps || !d_rate || !d_dist) return J2K_ERR_INVALID_ARG;
+    int r = rate_check(P, "j2k_plan_encode_blocks_planes");
+    if (r != J2K_OK) return r;
+    r = plan_encode_blocks_impl(P, d_coeff, d_slots, d_lens, d_numbps, d_rate);
+    if (r != J2K_OK) return r;
+    j2k_ctx *ctx = P->ctx;
+    HIPCHK(ctx, launch_rate_distortion(ctx->stream, P->d_bjobs, (int)P->blocks.size(), d_coeff, d_numbps, d_dist));
+    return J2K_OK;
+}
+
+extern "C" int j2k_plan_rate_allocate(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, int64_t max_body_bytes,
+                                      uint8_t *d_kept, uint64_t *d_chosen) {
+    if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    int r = rate_check(P, "j2k_plan_rate_allocate");
+    if (r != J2K_OK) return r;
+    if (max_body_bytes < 0) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_rate_allocate: a negative budget");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = P->blocks.size();
+    if (!P->rate_wj_valid || !P->d_rate_ws) {
+        if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: run the same calls once before j2k_ctx_capture_begin");
+        plan_rate_weights(P);
+        const int numRes = P->spec.num_res_jobs > 0 ? P->spec.num_res_jobs : 6;
+        std::vector<double> wj(n + 1, 1.0);
+        for (size_t j = 0; j < n; j++) {
+            const j2k_block &b = P->blocks[j];
+            wj[j] = P->rate_weights[((size_t)(b.plane % P->spec.C) * numRes + P->block_res[j]) * 4 + b.band];
+        }
+        if (!P->d_rate_wj) HIPCHK(ctx, hipMalloc((void **)&P->d_rate_wj, wj.size() * sizeof(double)));
+        if (!P->d_rate_ws) HIPCHK(ctx, hipMalloc(&P->d_rate_ws, rate_allocate_workspace((int)n)));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));              // an allocation in flight still reads the old weights
+        HIPCHK(ctx, hipMemcpy(P->d_rate_wj, wj.data(), wj.size() * sizeof(double), hipMemcpyHostToDevice));
+        P->rate_wj_valid = true;
+    }
+    HIPCHK(ctx, launch_rate_allocate(ctx->stream, (int)n, d_rate, d_dist, d_numbps, P->d_rate_wj, (uint64_t)max_body_bytes, P->d_rate_ws, d_kept, d_chosen));
+    return J2K_OK;
+}

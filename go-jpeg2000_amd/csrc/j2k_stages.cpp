@@ -643,6 +643,11 @@ static size_t t1_work_per_job(const j2k_plan *P) {
 }
 
 extern "C" int j2k_plan_encode_blocks(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps) {
+    return plan_encode_blocks_impl(P, d_coeff, d_slots, d_lens, d_numbps, nullptr);
+}
+
+// d_rate != NULL (MQ plans whose blocks are all <= 64 x 64; j2k_rate.cpp has checked): the rate tables too, 32 words per job
+int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate) {
     if (!P || !d_coeff || !d_slots || !d_lens || !d_numbps) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -690,7 +695,7 @@ extern "C" int j2k_plan_encode_blocks(j2k_plan *P, const int32_t *d_coeff, uint8
         }
         HIPCHK(ctx, launch_t1_encode(ctx->stream, P->d_bjobs, n, d_coeff, d_slots, d_lens, d_numbps, ws, wpj, d_fault, max_dim,
                                      W.stride ? ws + W.off_sym : nullptr, W.stride, (uint32_t *)(ws + W.off_nsyms),
-                                     ctx->t1_lanes > 0 ? ctx->t1_lanes : (mq_throughput_mode() ? -1 : 0), bigsym, P->d_bigsym_off, bignsyms));
+                                     ctx->t1_lanes > 0 ? ctx->t1_lanes : (mq_throughput_mode() ? -1 : 0), bigsym, P->d_bigsym_off, bignsyms, d_rate));
     }
     return J2K_OK;
 }
@@ -887,8 +892,19 @@ extern "C" int j2k_plan_decode_blocks_coarse(j2k_plan *P, const uint8_t *d_strea
     return plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_stream, d_offs, d_lens, d_numbps, d_decoded, nullptr, skip_planes);
 }
 
+// j2k_plan_decode_blocks_coarse with a floor per block beside the uniform one: block j stops at max(skip_planes, d_floors[j]) (d_floors: device, one
+// byte per job, 0 ... 31 -- not checked, a larger value simply leaves the block zeros).  d_floors = NULL is j2k_plan_decode_blocks_coarse.
+extern "C" int j2k_plan_decode_blocks_floors(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
+                                             const uint8_t *d_numbps, int skip_planes, const uint8_t *d_floors, int32_t *d_decoded) {
+    if (!P || !d_stream || !d_offs || !d_lens || !d_numbps || !d_decoded) return J2K_ERR_INVALID_ARG;
+    const int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_plan_decode_blocks_floors");
+    if (r != J2K_OK) return r;
+    if (d_floors && P->spec.coder == J2K_CODER_HT) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_decode_blocks_floors: per-block floors need the MQ coder");
+    return plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_stream, d_offs, d_lens, d_numbps, d_decoded, nullptr, skip_planes, d_floors);
+}
+
 int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
-                            const uint8_t *d_numbps, int32_t *d_decoded, const BlockJob *d_placed, int skip_planes) {
+                            const uint8_t *d_numbps, int32_t *d_decoded, const BlockJob *d_placed, int skip_planes, const uint8_t *d_floors) {
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!n) return J2K_OK;
@@ -916,7 +932,7 @@ int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const u
         if (r != J2K_OK) return r;
         HIPCHK(ctx, launch_t1_decode(ctx->stream, d_djobs, n, d_stream, d_offs, d_lens, d_numbps, d_decoded,
                                      (uint8_t *)ctx->stage[2], wpj, max_dim, ctx->t1_dec_general,
-                                     split ? (uint8_t *)ctx->stage[2] + gen_bytes : nullptr, ctx->t1_dec_lanes, mq_throughput_mode() ? 1 : 0, skip_planes));
+                                     split ? (uint8_t *)ctx->stage[2] + gen_bytes : nullptr, ctx->t1_dec_lanes, mq_throughput_mode() ? 1 : 0, skip_planes, d_floors));
     }
     return J2K_OK;
 }

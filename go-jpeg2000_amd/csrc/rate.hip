@@ -1,0 +1,183 @@
+// rate.hip -- rate control of the MQ block coder (a feature of this library; the reference reads Options.CompressionRatio nowhere): the
+// distortion of every block at every plane cut, and the allocation of a byte budget over the blocks' (rate, distortion) tables.
+// tests/rate_cases.py is the definition both kernels agree with bit for bit; DESIGN.md 7 has the argument.
+//
+//   rate[j * 32 + p]   bytes of block j's codeword that decode its first p bit planes (t1.hip, the PLANES instantiations), p = 0 ... numBPS
+//   dist[j * 32 + p]   sum over the block of (|v| - |coarse(v, numBPS - p)|)^2 in wrapping uint64 arithmetic (0 above numBPS)
+//   kept[j]            the planes the allocation keeps of block j
+#include "j2k_internal.h"
+
+namespace j2k {
+
+#define RATE_STRIDE 32
+
+// One wavefront per block, lanes = columns.  Every sample adds to the sum of each floor k = 1 ... numBPS: what a decoder that stops after
+// plane k leaves of the magnitude is |v| with its low k bits replaced by the midpoint 2^(k-1), or nothing where |v| < 2^k.
+// KMAX: the floors this instantiation sums (the block's numBPS <= KMAX): a block of 8 planes does not pay for 31.  Lane k returns floor k's sum.
+template <int KMAX>
+__device__ __forceinline__ uint64_t rate_distortion_sums(const BlockJob &J, const int32_t *__restrict__ src, int lane) {
+    uint64_t acc[KMAX + 1];
+#pragma unroll
+    for (int k = 0; k <= KMAX; k++) acc[k] = 0;
+    for (int y = 0; y < J.h; y++)
+        for (int x = lane; x < J.w; x += 64) {
+            const int32_t v = src[(size_t)y * J.stride + x];
+            const uint32_t a = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+#pragma unroll
+            for (int k = 1; k <= KMAX; k++) {            // (floors above numBPS see |v| < 2^k and sum |v|^2: never stored)
+                const uint32_t half = 1u << (k - 1), low = a & (2u * half - 1u);
+                const uint32_t d = (a >> k) ? (low >= half ? low - half : half - low) : low;
+                acc[k] += (uint64_t)d * d;
+            }
+        }
+    uint64_t mine = 0;
+#pragma unroll
+    for (int k = 1; k <= KMAX; k++) {
+        uint64_t s = acc[k];
+        for (int o = 32; o > 0; o >>= 1) s += (uint64_t)__shfl_xor((unsigned long long)s, o);
+        if (lane == k) mine = s;
+    }
+    return mine;
+}
+
+__global__ __launch_bounds__(64) void rate_distortion_kernel(const BlockJob *__restrict__ jobs, int njobs, const int32_t *__restrict__ coef,
+                                                              const uint8_t *__restrict__ numbps, uint64_t *__restrict__ dist) {
+    const int jid = blockIdx.x;
+    if (jid >= njobs) return;
+    const int lane = threadIdx.x;
+    const BlockJob J = jobs[jid];
+    const int nb = min((int)numbps[jid], RATE_STRIDE - 1);
+    const int32_t *src = coef + J.src_off;
+    uint64_t mine = 0;                                   // wave-uniform choice
+    if (nb == 0) mine = 0;
+    else if (nb <= 8) mine = rate_distortion_sums<8>(J, src, lane);
+    else if (nb <= 12) mine = rate_distortion_sums<12>(J, src, lane);
+    else if (nb <= 16) mine = rate_distortion_sums<16>(J, src, lane);
+    else mine = rate_distortion_sums<RATE_STRIDE - 1>(J, src, lane);
+    if (lane < RATE_STRIDE) dist[(size_t)jid * RATE_STRIDE + (lane <= nb ? nb - lane : lane)] = lane <= nb ? mine : 0;
+}
+
+// ---- allocation: one workgroup for the frame ----------------------------------------------------------------------------------------------
+// Workspace per block: the planes of its hull points (32 bytes), their incoming slopes (32 doubles), the count.
+#define RATE_WG 1024
+struct RateWs {
+    double *slope;      // [n][32]
+    uint8_t *plane;     // [n][32]
+    uint32_t *count;    // [n]
+};
+__host__ __device__ inline RateWs rate_ws(void *ws, size_t n) {
+    RateWs W;
+    W.slope = reinterpret_cast<double *>(ws);
+    W.count = reinterpret_cast<uint32_t *>(W.slope + n * RATE_STRIDE);
+    W.plane = reinterpret_cast<uint8_t *>(W.count + n);
+    return W;
+}
+size_t rate_allocate_workspace(int njobs) { return (size_t)njobs * (RATE_STRIDE * 9 + 4) + 256; }
+
+// sum over the workgroup, the same value in every thread (integer sums: the order does not matter)
+__device__ __forceinline__ uint64_t wg_sum(uint64_t v, uint64_t *sh) {
+    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
+    __syncthreads();                                     // the previous sum has been read
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint64_t t = 0;
+    for (int i = 0; i < RATE_WG / 64; i++) t += sh[i];
+    return t;
+}
+
+__global__ __launch_bounds__(RATE_WG) void rate_allocate_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
+                                                                const uint8_t *__restrict__ numbps, const double *__restrict__ weights, uint64_t budget,
+                                                                void *__restrict__ ws, uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen) {
+    __shared__ uint64_t sh[RATE_WG / 64];
+    const int tid = threadIdx.x;
+    const RateWs W = rate_ws(ws, (size_t)njobs);
+    // nothing to cut?
+    uint64_t part = 0;
+    for (int j = tid; j < njobs; j += RATE_WG) part += rate[(size_t)j * RATE_STRIDE + min((int)numbps[j], RATE_STRIDE - 1)];
+    const uint64_t total = wg_sum(part, sh);
+    if (total <= budget) {
+        for (int j = tid; j < njobs; j += RATE_WG) kept[j] = (uint8_t)min((int)numbps[j], RATE_STRIDE - 1);
+        if (tid == 0) *chosen = total;
+        return;
+    }
+    // hulls: the upper-left convex hull of (rate, distortion) from p = 0, pop while the new point is not less steep
+    for (int j = tid; j < njobs; j += RATE_WG) {
+        const uint32_t *R = rate + (size_t)j * RATE_STRIDE;
+        const uint64_t *D = dist + (size_t)j * RATE_STRIDE;
+        double *sl = W.slope + (size_t)j * RATE_STRIDE;
+        uint8_t *pt = W.plane + (size_t)j * RATE_STRIDE;
+        const int nb = min((int)numbps[j], RATE_STRIDE - 1);
+        const double w = weights[j];
+        int cnt = 1;
+        pt[0] = 0; sl[0] = 0.0;
+        for (int p = 1; p <= nb; p++) {
+            const uint32_t Rp = R[p];
+            const uint64_t Dp = D[p];
+            for (;;) {
+                const int a = pt[cnt - 1];
+                if (!(Dp < D[a])) break;                                 // no less distortion: never a hull point
+                const bool free_ = Rp <= R[a];
+                double s = __builtin_huge_val();
+                if (!free_) {
+                    const double num = w * (double)(D[a] - Dp);          // one multiply, one divide (-ffp-contract=off; nothing to fuse anyway)
+                    s = num / (double)(Rp - R[a]);
+                }
+                if (cnt > 1) {
+                    if (s >= sl[cnt - 1]) { cnt--; continue; }
+                    pt[cnt] = (uint8_t)p; sl[cnt] = s; cnt++;
+                } else if (free_) {
+                    pt[0] = (uint8_t)p;                                  // less distortion for no more bytes: the new start
+                } else {
+                    pt[cnt] = (uint8_t)p; sl[cnt] = s; cnt++;
+                }
+                break;
+            }
+        }
+        W.count[j] = (uint32_t)cnt;
+    }
+    // (each thread reads back only what it wrote itself: no barrier needed between the hulls and the search)
+    auto pick = [&](int j, double lam) -> int {
+        const double *sl = W.slope + (size_t)j * RATE_STRIDE;
+        const int cnt = (int)W.count[j];
+        int i = 0;
+        while (i + 1 < cnt && sl[i + 1] >= lam) i++;
+        return W.plane[(size_t)j * RATE_STRIDE + i];
+    };
+    auto bytes_at = [&](uint64_t bits) -> uint64_t {
+        const double lam = __longlong_as_double((long long)bits);
+        uint64_t b = 0;
+        for (int j = tid; j < njobs; j += RATE_WG) b += rate[(size_t)j * RATE_STRIDE + pick(j, lam)];
+        return wg_sum(b, sh);
+    };
+    // the smallest bit pattern of a non-negative double whose choice fits: bisection over the patterns, 64 steps (the patterns above
+    // +infinity are NaNs: no slope is >= a NaN, every block is at its start point, whose rate is 0 -- the top of the range always fits)
+    uint64_t lo = 0, hi = 0x7FFFFFFFFFFFFFFFull;
+    for (int step = 0; step < 64; step++) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        const uint64_t b = bytes_at(mid);                // every thread takes every step: wg_sum has barriers
+        if (lo < hi) { if (b <= budget) hi = mid; else lo = mid + 1; }
+    }
+    const double lam = __longlong_as_double((long long)hi);
+    uint64_t b = 0;
+    for (int j = tid; j < njobs; j += RATE_WG) {
+        const int p = pick(j, lam);
+        kept[j] = (uint8_t)p;
+        b += rate[(size_t)j * RATE_STRIDE + p];
+    }
+    b = wg_sum(b, sh);
+    if (tid == 0) *chosen = b;
+}
+
+hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, uint64_t *dist) {
+    if (njobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rate_distortion_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, numbps, dist);
+    return hipGetLastError();
+}
+
+hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+                                uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen) {
+    hipLaunchKernelGGL(rate_allocate_kernel, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, budget, ws, kept, chosen);
+    return hipGetLastError();
+}
+
+}  // namespace j2k

@@ -465,12 +465,19 @@ __device__ __forceinline__ void mq_run(MqEnc &e, const uint32_t *mqtab, uint32_t
 //                 blocks the split path marked T1F_SKIPPED.
 // SPLIT = true : the symbols go to `gsym` (job j at j * sym_stride, chunks padded to 16 with no-op symbols, count in
 //                nsyms[j]) for t1_mq_lanes_kernel; blocks with more than `plane_budget` bit planes are marked T1F_SKIPPED.
-template <bool SPLIT>
+// PLANES: the block's rate table too (rate_control: j2k_plan_encode_blocks_planes): rate[jid * T1_RATE_STRIDE + p] = bytes of the
+//                block's codeword that decode its first p bit planes, p = 0 ... numBPS; the entries above numBPS repeat the last.
+//                SPLIT = false: the symbols are drained at every plane end and the coder's byte index is read there.  SPLIT = true:
+//                the table holds the symbol index of every plane end (in the padded list) for t1_mq_lanes_kernel<true>, which
+//                replaces each mark by the byte count when its lane passes it.
+#define T1_RATE_STRIDE 32
+#define T1_RATE_MARGIN 5u   /* bytes past the coder's byte index that hold everything the registers held at a plane end */
+template <bool SPLIT, bool PLANES = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void t1_encode64_kernel(const BlockJob *__restrict__ jobs, int njobs, const int32_t *__restrict__ coef,
                                                          uint8_t *__restrict__ slots, uint32_t *__restrict__ lens,
                                                          uint8_t *__restrict__ numbps, int *__restrict__ fault,
                                                          uint8_t *__restrict__ gsym, size_t sym_stride, uint32_t *__restrict__ nsyms,
-                                                         int plane_budget, const uint32_t *__restrict__ only_skipped) {
+                                                         int plane_budget, const uint32_t *__restrict__ only_skipped, uint32_t *__restrict__ rate = nullptr) {
     __shared__ T1Fast F;
     const int jid = blockIdx.x;
     if (jid >= njobs) return;
@@ -482,6 +489,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
         if (SPLIT && lane == 0) nsyms[jid] = 0;
         return;
     }
+    uint32_t *const rrow = PLANES ? rate + (size_t)jid * T1_RATE_STRIDE : nullptr;
     const size_t n = (size_t)w * h;
     build_tables(F.T, J.band, lane);
     __syncthreads();
@@ -511,6 +519,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
     }
     if (maxVal == 0) {
         if (lane == 0) { lens[jid] = 0; numbps[jid] = 0; if (SPLIT) nsyms[jid] = 0; }
+        if (PLANES && lane < T1_RATE_STRIDE) rrow[lane] = 0;
         return;
     }
     const int numBPS = 32 - __clz(maxVal);
@@ -720,6 +729,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
             nsym += __shfl(incl, 63);
         }
         S = Sc;
+        if (PLANES) {                                       // the end of plane numBPS - bp
+            if (SPLIT) { if (lane == 0) rrow[numBPS - bp] = gtotal + nsym; }
+            else { T1F_DRAIN(); if (lane == 0) rrow[numBPS - bp] = (uint32_t)e.bp + T1_RATE_MARGIN; }
+        }
     }
     T1F_DRAIN();
 #undef T1F_DRAIN
@@ -730,6 +743,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
         nsyms[jid] = govf ? 0u : gtotal;
         if (govf) lens[jid] = 0;
         numbps[jid] = (uint8_t)numBPS;
+        if (PLANES) {
+            if (govf) { for (int p = 0; p < T1_RATE_STRIDE; p++) rrow[p] = 0; }      // a faulted block: no marks left where byte counts belong
+            else rrow[0] = 0;
+        }
         return;
     }
     // ---- flush (t1_fast5.go:878-898) ----
@@ -744,6 +761,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
     if (e.overflow) atomicMax(fault, 2);
     lens[jid] = end > 1 ? (uint32_t)(end - 1) : 0;
     numbps[jid] = (uint8_t)numBPS;
+    if (PLANES) {
+        const uint32_t len = end > 1 ? (uint32_t)(end - 1) : 0;
+        rrow[0] = 0;
+        for (int p = 1; p < T1_RATE_STRIDE; p++) rrow[p] = p < numBPS ? min(rrow[p], len) : len;
+    }
 }
 
 #include "t1_big.inc"
@@ -776,9 +798,13 @@ __device__ __forceinline__ void t1_wave_sync() {       // LDS written by this wa
 // symbol falls by K and the kernel runs at the latency of one chain.  All lane-varying state is in registers (A, C, CT,
 // the pending byte) or in a lane-interleaved LDS array (the table entry of each context's current state).  Lanes whose
 // list has ended are fed the no-op symbol (context 31: Qe = 0, never renormalises).
+// PLANES: `rate` holds every block's plane-end marks (t1_encode64_kernel<true, true>); a lane that has coded the symbols up to its next
+// mark replaces the mark by its byte index + T1_RATE_MARGIN, and after the flush clamps the table to the codeword's length.
+template <bool PLANES = false>
 __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const BlockJob *__restrict__ jobs, int njobs, int K, const uint8_t *__restrict__ gsym,
                                                          size_t sym_stride, const uint32_t *__restrict__ nsyms, uint8_t *__restrict__ slots,
-                                                         uint32_t *__restrict__ lens, int *__restrict__ fault, const uint32_t *__restrict__ perm) {
+                                                         uint32_t *__restrict__ lens, int *__restrict__ fault, const uint32_t *__restrict__ perm,
+                                                         uint32_t *__restrict__ rate = nullptr, const uint8_t *__restrict__ numbps = nullptr) {
     __shared__ uint32_t mqtab_w[T1_LANES_WPW][96];
     __shared__ uint32_t ce_w[T1_LANES_WPW][T1F_NCTX * 64];
     T1_LANES_PRIO();
@@ -834,6 +860,9 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const Bl
         const bool in = i0 < n;
         return make_uint4(in ? v.x : null16.x, in ? v.y : null16.y, in ? v.z : null16.z, in ? v.w : null16.w);
     };
+    uint32_t *const rrow = PLANES ? rate + (size_t)(live ? jid : 0) * T1_RATE_STRIDE : nullptr;
+    const uint32_t nbl = (PLANES && n) ? numbps[jid] : 0u;
+    uint32_t pl = 1, mark = nbl ? rrow[1] : 0xFFFFFFFFu;       // the plane whose end comes next, and the symbol count there
     uint4 cur = fetch(0);
     uint32_t idx = (cur.x & 31u) * 64 + lane;
     uint32_t ent = ce[idx];
@@ -883,6 +912,11 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const Bl
                 }
             }
             idx = idxn;
+            if (PLANES && i0 + (uint32_t)q + 1u == mark) {
+                rrow[pl] = bp + T1_RATE_MARGIN;
+                pl++;
+                mark = pl <= nbl ? rrow[pl] : 0xFFFFFFFFu;
+            }
         }
         cur = nxt;
     }
@@ -898,6 +932,10 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const Bl
     else if (bp >= 1) { if (bp - 1 < cap) out[bp - 1] = (uint8_t)curb; else ovf = 1; }
     if (ovf) atomicMax(fault, 2);
     lens[jid] = end > 1 ? (uint32_t)(end - 1) : 0;
+    if (PLANES) {
+        const uint32_t len = end > 1 ? end - 1 : 0u;
+        for (uint32_t p = 1; p < T1_RATE_STRIDE; p++) rrow[p] = p < nbl ? min(rrow[p], len) : len;
+    }
 }
 
 // ---- MQ decoder (mqc.go:352-497) --------------------------------------------------------------
@@ -1120,6 +1158,8 @@ __device__ __forceinline__ void t1_dec_cleanup_wave(T1DecLane &L, int32_t bit, u
 }
 // The quality floor of the j2k_*_coarse calls (skip_planes = s, 0 ... 31): a decoder stops after plane s and every non-zero magnitude
 // takes the midpoint of what it left undecoded, bit s - 1; the sign as in t1.go:1281-1289.  s = 0: no midpoint, the full decode.
+// per-block floors (the j2k_*_floors calls): block j runs with max(skip_planes, floors[j])
+__device__ __forceinline__ int t1_floor_of(int skip, const uint8_t *__restrict__ floors, long j) { return floors ? max(skip, (int)floors[j]) : skip; }
 __device__ __forceinline__ uint32_t t1_coarse_mid(int skip) { return skip > 0 ? 1u << (skip - 1) : 0u; }
 __device__ __forceinline__ int32_t t1_coarse_finish(int32_t mag, uint32_t mid, bool neg) {
     const uint32_t m = mag ? (uint32_t)mag | mid : 0u;
@@ -1146,12 +1186,13 @@ template <bool LDSW>
 __global__ __launch_bounds__(64) void t1_decode_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                        const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
                                                        const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded,
-                                                       uint8_t *__restrict__ work, size_t work_per_job, int lds_work_bytes, int skip_small, int skip_planes) {
+                                                       uint8_t *__restrict__ work, size_t work_per_job, int lds_work_bytes, int skip_small, int skip_uniform, const uint8_t *__restrict__ floors) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     int vzero;                                   // see t1_decode64_kernel: keeps the serial chain's loop control off the scalar unit
     asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
     const int jid = (int)blockIdx.x + vzero;
     if (jid >= njobs) return;
+    const int skip_planes = t1_floor_of(skip_uniform, floors, jid);       // this block's floor: the call's, or its own if that is higher
     const int lane = threadIdx.x;
     const BlockJob J = jobs[jid];
     if (skip_small && J.w <= skip_small && J.h <= skip_small) return;   // skip_small = 64 / 256: t1_decode64_kernel (and t1_decode_big_kernel) take these
@@ -1210,9 +1251,10 @@ struct T1Dec64Shared {
 static_assert(sizeof(T1Dec64Shared) <= 5120, "t1_decode64_kernel: LDS per block above 10 granules (32 blocks per CU)");
 __global__ __launch_bounds__(64) void t1_decode64_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                          const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
-                                                         const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded, int min_bps, int skip_planes) {
+                                                         const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded, int min_bps, int skip_uniform, const uint8_t *__restrict__ floors) {
     __shared__ T1Dec64Shared S;
     if ((int)blockIdx.x >= njobs) return;
+    const int skip_planes = t1_floor_of(skip_uniform, floors, blockIdx.x);       // this block's floor: the call's, or its own if that is higher
     if ((int)numbps[blockIdx.x] < min_bps) return;                   // the plane-stepped path took this block
     const int lane = threadIdx.x;
     // The block index as a VECTOR value the compiler cannot prove uniform: everything derived from it (block size, loop
@@ -1285,9 +1327,10 @@ struct T1DecState { uint32_t C, A, CT, nmr; long long bp, len; };
 __global__ __launch_bounds__(64) void t1_dec_step_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                          const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
                                                          const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded,
-                                                         uint8_t *__restrict__ ws, int k, int skip_planes) {
+                                                         uint8_t *__restrict__ ws, int k, int skip_uniform, const uint8_t *__restrict__ floors) {
     __shared__ T1Dec64Shared S;
     if ((int)blockIdx.x >= njobs) return;
+    const int skip_planes = t1_floor_of(skip_uniform, floors, blockIdx.x);       // this block's floor: the call's, or its own if that is higher
     const int nb0 = (int)numbps[blockIdx.x];
     const int nb = max(nb0 - skip_planes, 0);                        // planes above the floor: p counts from the floor, bit plane p + skip_planes
     const int p = nb - 1 - k;                                        // this launch: SigProp of the block's k-th plane from ITS top
@@ -1550,7 +1593,7 @@ __device__ __forceinline__ void t1_magref_chain(MqLaneDec &mq, const uint32_t *m
 template <bool BITLIST>
 __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_magref_lanes_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                                  const uint64_t *__restrict__ offs, const uint8_t *__restrict__ numbps,
-                                                                 uint8_t *__restrict__ ws, const uint32_t *__restrict__ perm, int k, int skip_planes) {
+                                                                 uint8_t *__restrict__ ws, const uint32_t *__restrict__ perm, int k, int skip_uniform, const uint8_t *__restrict__ floors) {
     __shared__ uint32_t mqtab_w[T1_LANES_WPW][96];
     __shared__ __attribute__((aligned(16))) uint8_t ring_w[T1_LANES_WPW][64 * T1R_STRIDE];
     T1_LANES_PRIO();
@@ -1563,6 +1606,7 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_magref_lanes_kernel(
     const long jid = pj == 0xFFFFFFFFu ? (long)njobs : (long)pj;
     for (int q = lane; q < 94; q += 64) mqtab[q] = c_mq94.v[q];
     bool live = jid < njobs;
+    const int skip_planes = t1_floor_of(skip_uniform, floors, live ? jid : 0);       // this block's floor: the call's, or its own if that is higher
     const BlockJob J = jobs[live ? jid : 0];
     const int nb = live ? (int)numbps[jid] : 0;
     live = live && J.w <= 64 && J.h <= 64 && nb <= T1DS_MAXP && nb - skip_planes - 1 - k >= 0;     // MagRef(p) of the planes p >= the floor
@@ -1716,7 +1760,7 @@ size_t t1_sym_stride(int planes) { return ((size_t)(planes + 2) * 4096 + 1024 + 
 // nsyms = njobs words); blocks with more bit planes than the stride allows fall back to the one-kernel path.
 hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots,
                             uint32_t *lens, uint8_t *numbps, uint8_t *work, size_t work_per_job, int *fault, int max_dim,
-                            uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint8_t *bigsym, const uint64_t *bigsym_off, uint32_t *bignsyms) {
+                            uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint8_t *bigsym, const uint64_t *bigsym_off, uint32_t *bignsyms, uint32_t *rate) {
     if (njobs <= 0) return hipSuccess;
     static int serial_only = -1;   // J2K_T1_SERIAL=1: A/B against the serial kernel
     if (serial_only < 0) serial_only = 0;          // (round 1's A/B switch J2K_T1_SERIAL: gone, the serial kernel only takes what the others leave)
@@ -1724,8 +1768,12 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
         if (sym && nsyms) {
             int planes = (int)((sym_stride - 1024) / 4096) - 2;
             if (planes > 31) planes = 31;
+            // rate != null (j2k_plan_encode_blocks_planes): the PLANES instantiations of the <= 64 x 64 kernels; the others are launched as before
+            if (rate) hipLaunchKernelGGL((t1_encode64_kernel<true, true>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
+                                         sym, sym_stride, nsyms, planes, (const uint32_t *)nullptr, rate);
+            else
             hipLaunchKernelGGL(t1_encode64_kernel<true>, dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                               sym, sym_stride, nsyms, planes, (const uint32_t *)nullptr);
+                               sym, sym_stride, nsyms, planes, (const uint32_t *)nullptr, (uint32_t *)nullptr);
             // blocks per wavefront: the kernel runs at the latency of one chain whatever K is, so K decides how much of the
             // device a frame's chains occupy while they run.  Measured on a 4K 12-bit frame (7005 blocks): one frame alone
             // 15.8 ms at K = 4, 18.0 at K = 32 (each wavefront waits for its slowest lane); three or more frames in flight
@@ -1741,14 +1789,25 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
             uint32_t *perm = lane_order ? nsyms + njobs : nullptr;       // njobs + 64 words behind nsyms (t1_workspace in j2k_stages.cpp)
             if (perm) hipLaunchKernelGGL(t1_order_kernel, dim3(1), dim3(1024), 0, s, jobs, njobs, (const uint8_t *)nullptr, (const uint32_t *)nsyms, 1, perm,
                                          (uint32_t *)nullptr, njobs);
-            hipLaunchKernelGGL(t1_mq_lanes_kernel, dim3(((njobs + K - 1) / K + T1_LANES_WPW - 1) / T1_LANES_WPW), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, K, sym, sym_stride, nsyms,
-                               slots, lens, fault, (const uint32_t *)perm);
-            if (planes < 31)
+            const dim3 lgrid(((njobs + K - 1) / K + T1_LANES_WPW - 1) / T1_LANES_WPW);
+            if (rate) hipLaunchKernelGGL(t1_mq_lanes_kernel<true>, lgrid, dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, K, sym, sym_stride, nsyms,
+                                         slots, lens, fault, (const uint32_t *)perm, rate, (const uint8_t *)numbps);
+            else
+            hipLaunchKernelGGL(t1_mq_lanes_kernel<false>, lgrid, dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, K, sym, sym_stride, nsyms,
+                               slots, lens, fault, (const uint32_t *)perm, (uint32_t *)nullptr, (const uint8_t *)nullptr);
+            if (planes < 31) {
+                if (rate) hipLaunchKernelGGL((t1_encode64_kernel<false, true>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
+                                             (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nsyms, rate);
+                else
                 hipLaunchKernelGGL(t1_encode64_kernel<false>, dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                                   (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nsyms);
+                                   (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nsyms, (uint32_t *)nullptr);
+            }
+        } else if (rate) {
+            hipLaunchKernelGGL((t1_encode64_kernel<false, true>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
+                               (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nullptr, rate);
         } else {
             hipLaunchKernelGGL(t1_encode64_kernel<false>, dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                               (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nullptr);
+                               (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nullptr, (uint32_t *)nullptr);
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || max_dim <= 64) return e;
@@ -1802,7 +1861,7 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
 // general_only: every block on the general kernel (A/B knob); otherwise blocks up to 64x64 take t1_decode64_kernel
 hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, const uint8_t *numbps, int32_t *decoded, uint8_t *work, size_t work_per_job,
-                            int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput, int skip_planes) {
+                            int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput, int skip_planes, const uint8_t *floors) {
     if (njobs <= 0) return hipSuccess;
     if (!general_only) {
         if (split_ws) {
@@ -1818,19 +1877,19 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
             if (sig_lanes) hipLaunchKernelGGL(t1_order_kernel, dim3(1), dim3(1024), 0, s, jobs, njobs, numbps, lens, 0, perm, slot_of, ngroups * 64);
             if (sig_lanes >= 2) {
                 hipLaunchKernelGGL(t1_dec_sig_lanes_kernel<true>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, lens, numbps,
-                                   split_ws, masks, (const uint32_t *)perm, planes, 0, skip_planes);
+                                   split_ws, masks, (const uint32_t *)perm, planes, 0, skip_planes, floors);
             } else
             for (int k = 0; k <= T1DS_MAXP; k++) {
                 if (sig_lanes) {
                     hipLaunchKernelGGL(t1_dec_sig_lanes_kernel<false>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, lens, numbps,
-                                       split_ws, masks, (const uint32_t *)perm, planes, k, skip_planes);
-                    hipLaunchKernelGGL(t1_dec_plane_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, numbps, decoded, split_ws, masks, slot_of, planes, k, skip_planes);
+                                       split_ws, masks, (const uint32_t *)perm, planes, k, skip_planes, floors);
+                    hipLaunchKernelGGL(t1_dec_plane_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, numbps, decoded, split_ws, masks, slot_of, planes, k, skip_planes, floors);
                 } else {
-                    hipLaunchKernelGGL(t1_dec_step_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, decoded, split_ws, k, skip_planes);
+                    hipLaunchKernelGGL(t1_dec_step_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, decoded, split_ws, k, skip_planes, floors);
                 }
                 if (k < T1DS_MAXP) {
-                    if (sig_lanes) { if (k > 0) hipLaunchKernelGGL(t1_dec_magref_lanes_kernel<true>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, numbps, split_ws, (const uint32_t *)perm, k, skip_planes); }
-                    else hipLaunchKernelGGL(t1_dec_magref_lanes_kernel<false>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, numbps, split_ws, (const uint32_t *)nullptr, k, skip_planes);
+                    if (sig_lanes) { if (k > 0) hipLaunchKernelGGL(t1_dec_magref_lanes_kernel<true>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, numbps, split_ws, (const uint32_t *)perm, k, skip_planes, floors); }
+                    else hipLaunchKernelGGL(t1_dec_magref_lanes_kernel<false>, dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, numbps, split_ws, (const uint32_t *)nullptr, k, skip_planes, floors);
                 }
             }
         }
@@ -1838,9 +1897,9 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
             hipLaunchKernelGGL(t1_dec_assemble_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, numbps, decoded,
                                reinterpret_cast<const uint64_t *>(split_ws + t1_dec_lanes_mask_offset((size_t)njobs)),
                                reinterpret_cast<const uint32_t *>(split_ws + t1_dec_lanes_perm_offset((size_t)njobs)) + (size_t)((njobs + 63) / 64) * 64,
-                               reinterpret_cast<const uint64_t *>(split_ws + t1_dec_lanes_planes_offset((size_t)njobs)), skip_planes);
+                               reinterpret_cast<const uint64_t *>(split_ws + t1_dec_lanes_planes_offset((size_t)njobs)), skip_planes, floors);
         hipLaunchKernelGGL(t1_decode64_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, decoded,
-                           split_ws ? T1DS_MAXP + 1 : 0, skip_planes);
+                           split_ws ? T1DS_MAXP + 1 : 0, skip_planes, floors);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || max_dim <= 64) return e;
     }
@@ -1857,8 +1916,8 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
         // for every block (the blocks of a frame decode side by side: latency)
         int classes = throughput;
         { const char *en = tuning_env("J2K_T1_BIG_DEC_CLASSES"); if (en) classes = atoi(en); }
-        hipLaunchKernelGGL((t1_decode_big_kernel<4, 258>), dim3(njobs), dim3(rot ? 256 : 64), sizeof(T1BigDec<4, 258>), s, jobs, njobs, stream, offs, lens, numbps, decoded, rot, classes ? 0 : 1, skip_planes);
-        if (classes) hipLaunchKernelGGL((t1_decode_big_kernel<2, 130>), dim3(njobs), dim3(rot ? 256 : 64), sizeof(T1BigDec<2, 130>), s, jobs, njobs, stream, offs, lens, numbps, decoded, rot, 0, skip_planes);
+        hipLaunchKernelGGL((t1_decode_big_kernel<4, 258>), dim3(njobs), dim3(rot ? 256 : 64), sizeof(T1BigDec<4, 258>), s, jobs, njobs, stream, offs, lens, numbps, decoded, rot, classes ? 0 : 1, skip_planes, floors);
+        if (classes) hipLaunchKernelGGL((t1_decode_big_kernel<2, 130>), dim3(njobs), dim3(rot ? 256 : 64), sizeof(T1BigDec<2, 130>), s, jobs, njobs, stream, offs, lens, numbps, decoded, rot, 0, skip_planes, floors);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || max_dim <= 256) return e;
     }
@@ -1874,9 +1933,9 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
         }
     }
     if (wb) hipLaunchKernelGGL(t1_decode_kernel<true>, dim3(njobs), dim3(64), lds, s, jobs, njobs, stream, offs, lens, numbps, decoded,
-                               work, work_per_job, wb, skip, skip_planes);
+                               work, work_per_job, wb, skip, skip_planes, floors);
     else hipLaunchKernelGGL(t1_decode_kernel<false>, dim3(njobs), dim3(64), lds, s, jobs, njobs, stream, offs, lens, numbps, decoded,
-                            work, work_per_job, wb, skip, skip_planes);
+                            work, work_per_job, wb, skip, skip_planes, floors);
     return hipGetLastError();
 }
 

@@ -190,11 +190,12 @@ __device__ __forceinline__ void tbd_wave_sync() {
 template <int NWD, int RWS>
 __global__ __launch_bounds__(256) void t1_decode_big_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                            const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
-                                                           const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded, int rot, int all_sizes, int skip_planes) {
+                                                           const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded, int rot, int all_sizes, int skip_uniform, const uint8_t *__restrict__ floors) {
     extern __shared__ __attribute__((aligned(16))) uint8_t tbd_lds[];
     T1BigDec<NWD, RWS> &F = *reinterpret_cast<T1BigDec<NWD, RWS> *>(tbd_lds);
     const int jid = blockIdx.x;
     if (jid >= njobs) return;
+    const int skip_planes = t1_floor_of(skip_uniform, floors, jid);       // this block's floor: the call's, or its own if that is higher
     const BlockJob J = jobs[jid];
     const int w = (int)tbd_u((uint32_t)J.w), h = (int)tbd_u((uint32_t)J.h);
     if ((w <= 64 && h <= 64) || w > 256 || h > 256) return;       // t1_decode64_kernel / the general kernel take these

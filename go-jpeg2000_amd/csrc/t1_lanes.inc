@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(con
                                                               const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
                                                               const uint8_t *__restrict__ numbps, uint8_t *__restrict__ ws,
                                                               uint64_t *__restrict__ masks, const uint32_t *__restrict__ perm,
-                                                              uint64_t *__restrict__ planes, int k_launch, int skip_planes) {
+                                                              uint64_t *__restrict__ planes, int k_launch, int skip_uniform, const uint8_t *__restrict__ floors) {
     __shared__ T1LShared L_w[T1_LANES_WPW];
     __shared__ T1LTables TB;
     T1_LANES_PRIO();
@@ -249,6 +249,7 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(con
     const uint32_t pj = perm[group * 64 + lane];
     const long jid = (long)pj;
     bool live0 = pj != 0xFFFFFFFFu;
+    const int skip_planes = t1_floor_of(skip_uniform, floors, live0 ? jid : 0);       // this block's floor: the call's, or its own if that is higher
     const BlockJob J = jobs[live0 ? jid : 0];
     const int nb0 = live0 ? (int)numbps[jid] : 0;
     const int nb = max(nb0 - skip_planes, 0);     // the planes above the quality floor: below, plane p stands for bit plane p + skip_planes
@@ -552,10 +553,11 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(con
 // 64 rows twice per launch: 46 000 instructions per block against 16 000 now.
 __global__ __launch_bounds__(64) void t1_dec_plane_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ numbps,
                                                           int32_t *__restrict__ decoded, uint8_t *__restrict__ ws, uint64_t *__restrict__ masks,
-                                                          const uint32_t *__restrict__ slot_of, uint64_t *__restrict__ planes, int k, int skip_planes) {
+                                                          const uint32_t *__restrict__ slot_of, uint64_t *__restrict__ planes, int k, int skip_uniform, const uint8_t *__restrict__ floors) {
     __shared__ uint32_t stage[2][132];
     const int jid = blockIdx.x;
     if (jid >= njobs) return;
+    const int skip_planes = t1_floor_of(skip_uniform, floors, jid);       // this block's floor: the call's, or its own if that is higher
     const int nb0 = (int)numbps[jid];
     const int nb = max(nb0 - skip_planes, 0);                  // as in t1_dec_sig_lanes_kernel: plane p = bit plane p + skip_planes
     const int p = nb - 1 - k;
@@ -583,9 +585,10 @@ __global__ __launch_bounds__(64) void t1_dec_plane_kernel(const BlockJob *__rest
 // wavefront per block, lanes = columns, one row per trip; the words of a row are wave-uniform loads.
 __global__ __launch_bounds__(64) void t1_dec_assemble_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ numbps,
                                                              int32_t *__restrict__ decoded, const uint64_t *__restrict__ masks,
-                                                             const uint32_t *__restrict__ slot_of, const uint64_t *__restrict__ planes, int skip_planes) {
+                                                             const uint32_t *__restrict__ slot_of, const uint64_t *__restrict__ planes, int skip_uniform, const uint8_t *__restrict__ floors) {
     const int jid = blockIdx.x;
     if (jid >= njobs) return;
+    const int skip_planes = t1_floor_of(skip_uniform, floors, jid);       // this block's floor: the call's, or its own if that is higher
     const int nb0 = (int)numbps[jid];
     if (nb0 > T1DS_MAXP) return;
     const int nb = max(nb0 - skip_planes, 0);                  // the planes that were decoded: word q holds bit plane q + skip_planes

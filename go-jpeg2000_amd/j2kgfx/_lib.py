@@ -67,6 +67,10 @@ SYMBOLS = [
     "j2k_plan_encode_frame_pixels", "j2k_plan_decode_frame_pixels", "j2k_encode_pixels_host", "j2k_decode_pixels_host",
     "j2k_plan_reduced_size", "j2k_plan_inverse_reduced", "j2k_plan_inverse_pixels_reduced", "j2k_plan_decode_frame_pixels_reduced", "j2k_decode_pixels_host_reduced",
     "j2k_decode_blocks_coarse", "j2k_plan_decode_blocks_coarse", "j2k_plan_decode_frame_pixels_coarse", "j2k_decode_pixels_host_coarse",
+    "j2k_decode_blocks_floors", "j2k_plan_decode_blocks_floors",
+    "j2k_plan_encode_tile_parts_kept", "j2k_plan_decode_tile_parts_floors", "j2k_plan_encode_frame_pixels_rate", "j2k_plan_decode_frame_pixels_rate",
+    "j2k_encode_pixels_host_rate", "j2k_decode_pixels_host_rate",
+    "j2k_plan_encode_blocks_planes", "j2k_plan_rate_allocate", "j2k_plan_get_rate_weights", "j2k_plan_set_rate_weights",
     "j2k_plan_pack_bound", "j2k_plan_pack_stream", "j2k_plan_unpack_stream", "j2k_plan_unpack_streams",
     "j2k_comm_load_error", "j2k_comm_get_unique_id", "j2k_comm_create", "j2k_comm_destroy", "j2k_comm_last_error", "j2k_comm_stream", "j2k_gather_streams", "j2k_comm_wait",
 ]
@@ -123,6 +127,18 @@ def lib():
             "j2k_plan_decode_blocks_coarse": (I, [V, V, V, V, V, I, V]),
             "j2k_plan_decode_frame_pixels_coarse": (I, [V, V, S, V, I, I, I, I, V, S]),
             "j2k_decode_pixels_host_coarse": (I, [V, V, S, I, I, I, I, V, S]),
+            "j2k_decode_blocks_floors": (I, [V, I, V, V, V, V, V, S, I, V, V, V]),
+            "j2k_plan_decode_blocks_floors": (I, [V, V, V, V, V, I, V, V]),
+            "j2k_plan_encode_blocks_planes": (I, [V, V, V, V, V, V, V]),
+            "j2k_plan_encode_tile_parts_kept": (I, [V, V, V, V, V, V, V, I, I, V, S, V]),
+            "j2k_plan_decode_tile_parts_floors": (I, [V, V, S, V, I, I, V, V, V, V]),
+            "j2k_plan_encode_frame_pixels_rate": (I, [V, I, V, S, I, I, C.c_int64, V, S, V]),
+            "j2k_plan_decode_frame_pixels_rate": (I, [V, V, S, V, I, I, I, I, V, S]),
+            "j2k_encode_pixels_host_rate": (I, [V, I, V, S, I, I, C.c_int64, V, S, C.POINTER(S), V, V, V]),
+            "j2k_decode_pixels_host_rate": (I, [V, V, S, I, I, I, I, V, S]),
+            "j2k_plan_rate_allocate": (I, [V, V, V, V, C.c_int64, V, V]),
+            "j2k_plan_get_rate_weights": (I, [V, V, S, C.POINTER(S)]),
+            "j2k_plan_set_rate_weights": (I, [V, V, S]),
         }
         for name, (res, args) in sigs.items():
             if partial and not hasattr(L, name):

@@ -174,15 +174,52 @@ class FramePlan:
         return pix
 
     @_stage
-    def encode_blocks(self, coeff, slots=None, lens=None, numbps=None):
+    def encode_blocks(self, coeff, slots=None, lens=None, numbps=None, planes=False):
+        """planes=True (closed-loop MQ plans, blocks <= 64 x 64): also the rate and distortion tables of every block, int32 / int64
+        [blocks, 32] holding uint32 / uint64 values (j2k_plan_encode_blocks_planes) -- returns (slots, lens, numbps, rate, dist)"""
         t = _torch()
         n = int(self.info.blocks)
         slots = slots if slots is not None else self.empty(self.info.bytes_cap, t.uint8)
         lens = lens if lens is not None else self.empty(n, t.int32)
         numbps = numbps if numbps is not None else self.empty(n, t.uint8)
+        if planes:
+            rate = t.zeros((max(n, 1), 32), dtype=t.int32, device=self.device)
+            dist = t.zeros((max(n, 1), 32), dtype=t.int64, device=self.device)
+            self.ctx.check(self.ctx.L.j2k_plan_encode_blocks_planes(self.h, self._p(coeff), self._p(slots), self._p(lens),
+                                                                    self._p(numbps), self._p(rate), self._p(dist)))
+            return slots, lens, numbps, rate, dist
         self.ctx.check(self.ctx.L.j2k_plan_encode_blocks(self.h, self._p(coeff), self._p(slots), self._p(lens),
                                                          self._p(numbps)))
         return slots, lens, numbps
+
+    @_stage
+    def rate_allocate(self, rate, dist, numbps, max_body_bytes, kept=None, chosen=None):
+        """the planes to keep of every block so that the code-block BODY bytes are at most max_body_bytes (packet and tile-part headers
+        come on top): returns (kept uint8 [blocks], chosen int64 [1] = the body bytes of that choice)  (j2k_plan_rate_allocate)"""
+        t = _torch()
+        n = int(self.info.blocks)
+        kept = kept if kept is not None else self.empty(n, t.uint8)
+        chosen = chosen if chosen is not None else t.zeros(1, dtype=t.int64, device=self.device)
+        self.ctx.check(self.ctx.L.j2k_plan_rate_allocate(self.h, self._p(rate), self._p(dist), self._p(numbps), C.c_int64(int(max_body_bytes)),
+                                                         self._p(kept), self._p(chosen)))
+        return kept, chosen
+
+    def rate_weights(self):
+        """float64 [ncomp, num_resolutions, 4]: the weight of every (component, resolution, band) in rate_allocate.  Default on a Mallat
+        plan: the band's synthesis energy gain; on other plans 1 (their windows are not sub-bands)."""
+        n = C.c_size_t(0)
+        self.ctx.check(self.ctx.L.j2k_plan_get_rate_weights(self.h, None, C.c_size_t(0), C.byref(n)))
+        out = np.zeros(n.value, dtype=np.float64)
+        self.ctx.check(self.ctx.L.j2k_plan_get_rate_weights(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size), C.byref(n)))
+        return out.reshape(self.ncomp, -1, 4)
+
+    def set_rate_weights(self, weights=None):
+        """weights: float64 of rate_weights()'s shape, finite and >= 0; None restores the default"""
+        if weights is None:
+            self.ctx.check(self.ctx.L.j2k_plan_set_rate_weights(self.h, None, C.c_size_t(0)))
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        self.ctx.check(self.ctx.L.j2k_plan_set_rate_weights(self.h, w.ctypes.data_as(C.c_void_p), C.c_size_t(w.size)))
 
     def set_decode_coded_rows_only(self, on=True):
         """HT coder: decode_blocks leaves the rows the reference's decoder never writes (y % 4 != 0) untouched -- the pooled
@@ -307,23 +344,35 @@ class FramePlan:
         return int(self.ctx.L.j2k_plan_frame_bound(self.h))
 
     @_stage
-    def encode_tile_parts(self, stream, offs, lens, numbps, sop=False, eph=False, out=None, tile_offs=None):
-        """the block coder's outputs -> SOT | SOD | packets per tile, end to end: (out uint8, tile_offs int64[tiles + 1])"""
+    def encode_tile_parts(self, stream, offs, lens, numbps, sop=False, eph=False, out=None, tile_offs=None, kept=None, rate=None):
+        """the block coder's outputs -> SOT | SOD | packets per tile, end to end: (out uint8, tile_offs int64[tiles + 1]).  kept + rate
+        (rate_allocate, encode_blocks(planes=True)): every block cut after its first kept[j] bit planes (j2k_plan_encode_tile_parts_kept)"""
         t = _torch()
         out = out if out is not None else self.empty(self.frame_bound(), t.uint8)
         tile_offs = tile_offs if tile_offs is not None else self.empty(int(self.info.tiles) + 1, t.int64)[:int(self.info.tiles) + 1]
+        if kept is not None:
+            self.ctx.check(self.ctx.L.j2k_plan_encode_tile_parts_kept(self.h, self._p(stream), self._p(offs), self._p(lens), self._p(numbps), self._p(kept), self._p(rate),
+                                                                      int(bool(sop)), int(bool(eph)), self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs)))
+            return out, tile_offs
         self.ctx.check(self.ctx.L.j2k_plan_encode_tile_parts(self.h, self._p(stream), self._p(offs), self._p(lens), self._p(numbps), int(bool(sop)),
                                                              int(bool(eph)), self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs)))
         return out, tile_offs
 
     @_stage
-    def decode_tile_parts(self, cs, length, tile_offs=None, sop=False, eph=False, offs=None, lens=None, numbps=None):
-        """tile-parts cs[:length] -> (offs, lens, numbps) as decode_blocks takes them (offsets into cs)"""
+    def decode_tile_parts(self, cs, length, tile_offs=None, sop=False, eph=False, offs=None, lens=None, numbps=None, floors=None):
+        """tile-parts cs[:length] -> (offs, lens, numbps) as decode_blocks takes them (offsets into cs).  floors = True or a device uint8
+        [blocks] tensor (MQ plans): also every block's floor, for streams cut at bit planes -- returns (offs, lens, numbps, floors) with
+        numbps counted from each block's top plane down to bit 0 (j2k_plan_decode_tile_parts_floors)"""
         t = _torch()
         n = int(self.info.blocks)
         offs = offs if offs is not None else self.empty(n + 1, t.int64)
         lens = lens if lens is not None else self.empty(n, t.int32)
         numbps = numbps if numbps is not None else self.empty(n, t.uint8)
+        if floors is not None and floors is not False:
+            floors = self.empty(n, t.uint8) if floors is True else floors
+            self.ctx.check(self.ctx.L.j2k_plan_decode_tile_parts_floors(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
+                                                                        int(bool(sop)), int(bool(eph)), self._p(offs), self._p(lens), self._p(numbps), self._p(floors)))
+            return offs, lens, numbps, floors
         self.ctx.check(self.ctx.L.j2k_plan_decode_tile_parts(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
                                                              int(bool(sop)), int(bool(eph)), self._p(offs), self._p(lens), self._p(numbps)))
         return offs, lens, numbps
@@ -347,19 +396,32 @@ class FramePlan:
         return int(n.value)
 
     @_stage
-    def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None):
-        """pixels (a Go Pix layout, device uint8 [H, stride]) -> tile-parts: (out uint8, tile_offs int64[tiles + 1])"""
+    def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None, max_body_bytes=None):
+        """pixels (a Go Pix layout, device uint8 [H, stride]) -> tile-parts: (out uint8, tile_offs int64[tiles + 1]).  max_body_bytes (closed-loop
+        MQ plans): at most that many bytes of code-block bodies -- packet and tile-part headers come on top, tile_offs[-1] says what the frame took
+        (j2k_plan_encode_frame_pixels_rate); decode with truncated=True"""
         t = _torch()
         out = out if out is not None else self.empty(self.frame_bound(), t.uint8)
         tile_offs = tile_offs if tile_offs is not None else self.empty(int(self.info.tiles) + 1, t.int64)[:int(self.info.tiles) + 1]
+        if max_body_bytes is not None:
+            self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_rate(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
+                                                                        C.c_int64(int(max_body_bytes)), self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs)))
+            return out, tile_offs
         self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
                                                                self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs)))
         return out, tile_offs
 
     @_stage
-    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0, skip_planes=0):
+    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False):
         """tile-parts cs[:length] -> pixels into pix (device uint8 [H, stride]; reduce > 0, Mallat plans: [H_r, stride], and only the
-        code-blocks of the resolutions it needs are decoded; skip_planes = k > 0, MQ plans: every block decoder stops after bit plane k)"""
+        code-blocks of the resolutions it needs are decoded; skip_planes = k > 0, MQ plans: every block decoder stops after bit plane k;
+        truncated=True, MQ plans: the stream's blocks may be cut at bit planes (encode_frame_pixels(max_body_bytes=...)) -- every block runs
+        from its own top plane down to max(skip_planes, its floor) (j2k_plan_decode_frame_pixels_rate).  Without it a cut stream decodes by
+        the old rule, numbps = coded planes.)"""
+        if truncated:
+            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_rate(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
+                                                                        int(bool(sop)), int(bool(eph)), int(reduce), int(skip_planes), self._p(pix), C.c_size_t(int(pix.shape[1]))))
+            return pix
         if skip_planes:
             self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_coarse(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
                                                                           int(bool(sop)), int(bool(eph)), int(reduce), int(skip_planes), self._p(pix), C.c_size_t(int(pix.shape[1]))))
@@ -373,8 +435,9 @@ class FramePlan:
         return pix
 
     # ---- host memory in, host memory out: the one-call forms (j2k_encode_pixels_host / j2k_decode_pixels_host) -------------------
-    def encode_pixels_host(self, fmt, pix, sop=False, eph=False, cap=None):
-        """pix: numpy uint8 [H, stride] (a Go Pix layout) -> dict(bytes, tile_offs, lens, numbps): every tile as a tile-part"""
+    def encode_pixels_host(self, fmt, pix, sop=False, eph=False, cap=None, max_body_bytes=None):
+        """pix: numpy uint8 [H, stride] (a Go Pix layout) -> dict(bytes, tile_offs, lens, numbps): every tile as a tile-part.  max_body_bytes: as
+        encode_frame_pixels (j2k_encode_pixels_host_rate; lens / numbps are the uncut ones)"""
         L = self.ctx.L
         n, nt = int(self.info.blocks), int(self.info.tiles)
         L.j2k_plan_tile_parts_bound.restype = C.c_size_t
@@ -383,18 +446,27 @@ class FramePlan:
         out = np.zeros(max(cap, 1), np.uint8)
         toffs = np.zeros(nt + 1, np.uint64); lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
         olen = C.c_size_t(0)
-        st = L.j2k_encode_pixels_host(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
-                                      out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen), toffs.ctypes.data_as(C.c_void_p),
-                                      lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p))
+        if max_body_bytes is not None:
+            st = L.j2k_encode_pixels_host_rate(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
+                                               C.c_int64(int(max_body_bytes)), out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen),
+                                               toffs.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p))
+        else:
+            st = L.j2k_encode_pixels_host(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
+                                          out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen), toffs.ctypes.data_as(C.c_void_p),
+                                          lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p))
         self.encoded_len = olen.value
         self.ctx.check(st)
         return dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
 
-    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0, skip_planes=0):
+    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False):
         """closed-loop plans: tile-parts (bytes / numpy uint8) -> numpy uint8 pixels of `shape` = (H, stride); reduce > 0: (H_r, stride);
-        skip_planes > 0 (MQ plans): as decode_frame_pixels"""
+        skip_planes > 0 (MQ plans), truncated: as decode_frame_pixels"""
         cs = np.ascontiguousarray(np.frombuffer(bytes(cs), np.uint8) if not isinstance(cs, np.ndarray) else cs, dtype=np.uint8)
         pix = np.zeros(shape, np.uint8)
+        if truncated:
+            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_rate(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
+                                                                  int(reduce), int(skip_planes), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
+            return pix
         if skip_planes:
             self.ctx.check(self.ctx.L.j2k_decode_pixels_host_coarse(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
                                                                     int(reduce), int(skip_planes), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
@@ -470,10 +542,15 @@ class FramePlan:
         return offs, stream
 
     @_stage
-    def decode_blocks(self, stream, offs, lens, numbps, decoded=None, skip_planes=0):
-        """skip_planes = k > 0 (MQ plans): every block's decoder stops after bit plane k (j2k_plan_decode_blocks_coarse)"""
+    def decode_blocks(self, stream, offs, lens, numbps, decoded=None, skip_planes=0, floors=None):
+        """skip_planes = k > 0 (MQ plans): every block's decoder stops after bit plane k (j2k_plan_decode_blocks_coarse); floors: device uint8
+        [blocks], block j stops after plane max(skip_planes, floors[j]) (j2k_plan_decode_blocks_floors)"""
         t = _torch()
         decoded = decoded if decoded is not None else self.empty(self.info.decoded_elems, t.int32)
+        if floors is not None:
+            self.ctx.check(self.ctx.L.j2k_plan_decode_blocks_floors(self.h, self._p(stream), self._p(offs), self._p(lens), self._p(numbps),
+                                                                    int(skip_planes), self._p(floors), self._p(decoded)))
+            return decoded
         if skip_planes:
             self.ctx.check(self.ctx.L.j2k_plan_decode_blocks_coarse(self.h, self._p(stream), self._p(offs), self._p(lens),
                                                                     self._p(numbps), int(skip_planes), self._p(decoded)))

@@ -43,9 +43,10 @@ def encode_blocks(coder, planes, blocks, ctx=None):
     return out[:total.value].copy(), offs[:n], lens[:n], nb[:n]
 
 
-def decode_blocks(coder, stream, offs, lens, numbps, blocks, ctx=None, skip_planes=0):
+def decode_blocks(coder, stream, offs, lens, numbps, blocks, ctx=None, skip_planes=0, floors=None):
     """Returns a list of 2-D int32 arrays (h, w), one per block.  skip_planes = k > 0 (MQ coder): every block's decoder stops after
-    bit plane k; non-zero magnitudes take the midpoint of the planes left undecoded (j2k_decode_blocks_coarse)."""
+    bit plane k; non-zero magnitudes take the midpoint of the planes left undecoded (j2k_decode_blocks_coarse).  floors (MQ coder):
+    one floor per block, 0 ... 31 -- block j stops after plane max(skip_planes, floors[j]) (j2k_decode_blocks_floors)."""
     ctx = ctx or default_context()
     blocks = np.ascontiguousarray(blocks, dtype=BLOCK_DTYPE)
     n = blocks.size
@@ -57,7 +58,14 @@ def decode_blocks(coder, stream, offs, lens, numbps, blocks, ctx=None, skip_plan
     coff[:n] = np.concatenate(([0], np.cumsum(sizes)[:-1])) if n else []
     coeffs = np.zeros(max(int(sizes.sum()), 1), dtype=np.int32)
     sp = stream.ctypes.data_as(C.c_void_p) if stream.size else None
-    if skip_planes:
+    if floors is not None:
+        fl = np.ascontiguousarray(floors, dtype=np.uint8)
+        assert fl.size == n
+        ctx.check(ctx.L.j2k_decode_blocks_floors(
+            ctx.h, int(coder), sp, offs.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
+            numbps.ctypes.data_as(C.c_void_p), blocks.ctypes.data_as(C.c_void_p), C.c_size_t(n), int(skip_planes),
+            fl.ctypes.data_as(C.c_void_p), coeffs.ctypes.data_as(C.c_void_p), coff.ctypes.data_as(C.c_void_p)))
+    elif skip_planes:
         ctx.check(ctx.L.j2k_decode_blocks_coarse(
             ctx.h, int(coder), sp, offs.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
             numbps.ctypes.data_as(C.c_void_p), blocks.ctypes.data_as(C.c_void_p), C.c_size_t(n), int(skip_planes),

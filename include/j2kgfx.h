@@ -698,6 +698,74 @@ int j2k_plan_decode_frame_pixels_coarse(j2k_plan *plan, const uint8_t *d_cs, siz
                                         int sop, int eph, int reduce, int skip_planes, void *d_pix, size_t stride);
 int j2k_decode_pixels_host_coarse(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, int reduce,
                                   int skip_planes, void *pix, size_t stride);
+/* A floor per block beside the uniform one (MQ coder): block j's decoder stops after bit plane max(skip_planes, floors[j]) -- by the same
+ * loop bound or plane shift, in every decode kernel form -- and its result is that of the _coarse call at that floor.  floors: one byte
+ * per block, 0 ... 31 (j2k_decode_blocks_floors: host memory, checked, J2K_ERR_INVALID_ARG; j2k_plan_decode_blocks_floors: device memory,
+ * not checked -- a block whose floor is at or above its numBPS is zeros).  floors = NULL is the _coarse call; floors != NULL with
+ * J2K_CODER_HT: J2K_ERR_UNSUPPORTED.  The calls without floors behave as before on every input. */
+int j2k_decode_blocks_floors(j2k_ctx *ctx, int coder, const uint8_t *bytes, const uint64_t *offs, const uint32_t *lens,
+                             const uint8_t *numbps, const j2k_block *blocks, size_t nblocks, int skip_planes,
+                             const uint8_t *floors, int32_t *coeffs, const uint64_t *coeff_offs);
+int j2k_plan_decode_blocks_floors(j2k_plan *plan, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
+                                  const uint8_t *d_numbps, int skip_planes, const uint8_t *d_floors, int32_t *d_decoded);
+
+/* ---- rate control of the MQ block coder (a feature of this library: the reference reads Options.CompressionRatio nowhere) ----------
+ * "Which bit planes of which blocks fit N bytes best": the block encoder fills a rate table per block, a second kernel the matching
+ * distortions, a third one allocates the budget.  Tables have 32 entries per job, entry p = "the first p bit planes kept", p = 0 ...
+ * numBPS (numBPS <= 31); tests/rate_cases.py is the definition the device agrees with bit for bit.
+ *   d_rate[j * 32 + p]   uint32: bytes of block j's codeword (a prefix of the bytes j2k_plan_encode_blocks writes, which are unchanged)
+ *                        whose decode has the first p planes right: with k = numBPS - p, |decoded| >> k == |v| >> k and the signs
+ *                        agree wherever that is not 0 (the decoder feeds 0xFF past the end of its data, mqc.go:402-413).  [0] = 0,
+ *                        [numBPS] = d_lens[j], non-decreasing; the entries above numBPS repeat d_lens[j].  A bound, not the minimum:
+ *                        the coder's byte index at the plane's end + 5, capped at the length (DESIGN.md 7 has the argument)
+ *   d_dist[j * 32 + p]   uint64: sum over the block of (|v| - |coarse(v, k)|)^2, coarse = the result of j2k_decode_blocks_coarse at
+ *                        floor k, wrapping arithmetic; [numBPS] = 0 and so are the entries above
+ * j2k_plan_encode_blocks_planes   j2k_plan_encode_blocks + both tables (the same slots, lens and numbps)
+ * j2k_plan_rate_allocate          d_kept[j] = planes kept of block j, *d_chosen = sum of d_rate[j * 32 + d_kept[j]] <= max_body_bytes.
+ *                                 Nothing is cut if the full lengths fit.  Otherwise every block's choice is the last point of its convex
+ *                                 hull of (rate, weight * distortion) whose slope is >= lambda, and lambda is the smallest float64 (by bit
+ *                                 pattern, found by 64 steps of bisection) whose choices fit: one workgroup, integer sums, reproducible
+ *                                 bit for bit.  The budget counts CODE-BLOCK BODY bytes; packet and tile-part headers come on top.
+ * j2k_plan_get_rate_weights /     the weight of every (component, resolution, band): ncomp * num_resolutions * 4 float64, index
+ * j2k_plan_set_rate_weights       (c * num_resolutions + r) * 4 + band.  Default on a Mallat plan: the synthesis energy gain of the band
+ *                                 (the 1-D synthesis low-pass / high-pass impulse responses iterated through the levels), component
+ *                                 weight 1; on other plans the windows are not sub-bands and every weight is 1 -- weights other than 1
+ *                                 mean something in Mallat mode only.  set(NULL, 0) restores the default; weights are finite and >= 0.
+ * J2K_ERR_UNSUPPORTED: an HT plan, a plan without closed_loop, a batch plan (frame_rows), a plan with blocks above 64 x 64.
+ * J2K_ERR_INVALID_ARG: a negative budget.  Both before anything is launched.
+ * j2k_plan_encode_tile_parts_kept    j2k_plan_encode_tile_parts with block j cut after its first d_kept[j] planes: its bytes are the prefix
+ *                                    d_rate[j * 32 + d_kept[j]], its passes the 3 p - 2 of those planes (p = 0: no passes, no bytes, in no
+ *                                    layer), ZeroBitPlanes = 31 - numBPS as before -- today's byte format.  d_kept[j] = numBPS everywhere
+ *                                    gives j2k_plan_encode_tile_parts' bytes.
+ * j2k_plan_decode_tile_parts_floors  j2k_plan_decode_tile_parts + each block's floor: d_floors[j] = max(31 - ZeroBitPlanes - (passes + 2) / 3,
+ *                                    0), d_numbps[j] = (passes + 2) / 3 + d_floors[j]; j2k_plan_decode_blocks_floors decodes that.  The
+ *                                    calls without floors keep their rule (numbps = (passes + 2) / 3) on every input.
+ * j2k_plan_encode_frame_pixels_rate  j2k_plan_encode_frame_pixels with at most max_body_bytes of code-block bodies (headers on top: the
+ *                                    last entry of d_tile_offs says what the frame took); a budget that cuts nothing gives its bytes.
+ * j2k_plan_decode_frame_pixels_rate  j2k_plan_decode_frame_pixels_coarse for such streams: block j runs down to max(skip_planes, its floor);
+ *                                    reduce as there.
+ * j2k_encode_pixels_host_rate /      the synchronous host-memory forms (j2k_encode_pixels_host / j2k_decode_pixels_host_coarse); lens and
+ * j2k_decode_pixels_host_rate        numbps of the encode are the UNCUT lengths and plane counts.
+ * No pass-level truncation, no quality layers, no budget that includes headers. */
+int j2k_plan_encode_tile_parts_kept(j2k_plan *plan, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
+                                    const uint8_t *d_numbps, const uint8_t *d_kept, const uint32_t *d_rate, int sop, int eph,
+                                    uint8_t *d_out, size_t cap, uint64_t *d_tile_offs);
+int j2k_plan_decode_tile_parts_floors(j2k_plan *plan, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                      uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors);
+int j2k_plan_encode_frame_pixels_rate(j2k_plan *plan, int format, const void *d_pix, size_t stride, int sop, int eph,
+                                      int64_t max_body_bytes, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs);
+int j2k_plan_decode_frame_pixels_rate(j2k_plan *plan, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                      int reduce, int skip_planes, void *d_pix, size_t stride);
+int j2k_encode_pixels_host_rate(j2k_plan *plan, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes,
+                                uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps);
+int j2k_decode_pixels_host_rate(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, int reduce, int skip_planes,
+                                void *pix, size_t stride);
+int j2k_plan_encode_blocks_planes(j2k_plan *plan, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps,
+                                  uint32_t *d_rate, uint64_t *d_dist);
+int j2k_plan_rate_allocate(j2k_plan *plan, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps,
+                           int64_t max_body_bytes, uint8_t *d_kept, uint64_t *d_chosen);
+int j2k_plan_get_rate_weights(j2k_plan *plan, double *weights, size_t cap, size_t *count);
+int j2k_plan_set_rate_weights(j2k_plan *plan, const double *weights, size_t count);
 
 /* The block coder's outputs as those tables.  j2k_plan_t2_packets (host table out): one packet per (tile, component,
  * resolution) of the plan in job order (encoder.go:616-673: tile, component, resolution, band, block row, block column), its
