@@ -108,3 +108,30 @@ extern "C" int j2k_parse_tile_parts(const uint8_t *cs, size_t len, j2k_tile_part
     *nparts = n;
     return n > cap ? J2K_ERR_CAPACITY : J2K_OK;
 }
+
+// A layered stream (quality layers) cut to its first `keep` layers: tile-part t = cs[tile_offs[t], layer_offs[t * nlayers + keep - 1])
+// with Psot patched to the new length, end to end; out_tile_offs[0 ... ntiles] = where each starts in `out` (+ the total).  Host memory only, no
+// device: what a server does before it sends a lower quality.  keep = nlayers copies the stream.
+extern "C" int j2k_tile_parts_keep_layers(const uint8_t *cs, size_t len, const uint64_t *tile_offs, const uint64_t *layer_offs, int ntiles, int nlayers, int keep,
+                                          uint8_t *out, size_t cap, size_t *out_len, uint64_t *out_tile_offs) {
+    if (!tile_offs || !layer_offs || !out_len || ntiles < 0 || nlayers < 1 || nlayers > J2K_MAX_LAYERS || keep < 1 || keep > nlayers || (ntiles && !cs)) return J2K_ERR_INVALID_ARG;
+    size_t need = 0;
+    for (int t = 0; t < ntiles; t++) {
+        const uint64_t a = tile_offs[t], b = layer_offs[(size_t)t * nlayers + (keep - 1)];
+        if (a > len || b > len || b < a || b - a < 14 || b > tile_offs[t + 1] || b - a > 0xFFFFFFFFull) return J2K_ERR_INVALID_ARG;
+        if (rd16(cs + a) != M_SOT) return J2K_ERR_INVALID_ARG;
+        need += (size_t)(b - a);
+    }
+    *out_len = need;
+    if (cap < need || (need && !out)) return J2K_ERR_CAPACITY;
+    size_t pos = 0;
+    for (int t = 0; t < ntiles; t++) {
+        const uint64_t a = tile_offs[t], b = layer_offs[(size_t)t * nlayers + (keep - 1)];
+        if (out_tile_offs) out_tile_offs[t] = (uint64_t)pos;
+        memcpy(out + pos, cs + a, (size_t)(b - a));
+        be32(out + pos + 6, (uint32_t)(b - a));                     // Psot
+        pos += (size_t)(b - a);
+    }
+    if (out_tile_offs) out_tile_offs[ntiles] = (uint64_t)pos;
+    return J2K_OK;
+}

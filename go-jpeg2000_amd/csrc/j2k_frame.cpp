@@ -97,7 +97,7 @@ extern "C" int j2k_t2_decode_packets_device(j2k_ctx *ctx, const j2k_t2_dev_packe
 }
 
 // ---- the closed-loop frame codec (j2k_params.closed_loop) -------------------------------------------------------------------
-static int cl_prepare(j2k_plan *P) {
+int cl_prepare(j2k_plan *P) {
     j2k_ctx *ctx = P->ctx;
     if (!P->spec.closed_loop) return fail(ctx, J2K_ERR_UNSUPPORTED, "the plan was not made with j2k_params.closed_loop: the reference's code-block windows overlap and its packets cannot be read back");
     if (P->d_t2_packets) return J2K_OK;
@@ -255,7 +255,7 @@ extern "C" int j2k_plan_frame_status(j2k_plan *P) {
     return J2K_OK;
 }
 
-static int cl_workspaces(j2k_plan *P) {
+int cl_workspaces(j2k_plan *P) {
     j2k_ctx *ctx = P->ctx;
     if (P->d_cl_coeff) return J2K_OK;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the frame codec's workspaces are made at its first call");
@@ -388,8 +388,7 @@ extern "C" int j2k_plan_decode_frame_pixels_coarse(j2k_plan *P, const uint8_t *d
 }
 
 // ---- rate-limited frames: j2k_plan_encode_frame_pixels with a budget of code-block body bytes, and the decode of what it writes -------------
-struct ClRate { uint32_t *rate; uint64_t *dist; uint8_t *kept; uint64_t *chosen; uint8_t *floors, *floors_r; };
-static int cl_rate_workspace(j2k_plan *P, ClRate &W) {
+int cl_rate_workspace(j2k_plan *P, ClRate &W) {
     j2k_ctx *ctx = P->ctx;
     const size_t n = P->blocks.size(), nr = (n + 255) & ~size_t(255);
     const size_t bytes = nr * 32 * 8 + nr * 32 * 4 + 3 * nr + 256;
@@ -461,16 +460,25 @@ extern "C" int j2k_plan_decode_frame_pixels_rate(j2k_plan *P, const uint8_t *d_c
     if (r == J2K_OK) r = cl_rate_workspace(P, W);
     if (r == J2K_OK) r = decode_tile_parts_impl(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, W.floors);
     if (r != J2K_OK) return r;
+    return plan_decode_frame_tables(P, d_cs, R, reduce, skip_planes, W.floors, W.floors_r, d_pix, stride);
+}
+
+// the block tables of a frame (the plan's d_cl_offs / d_cl_lens / d_cl_numbps, offsets into d_data) and every block's floor -> pixels: MQ block
+// decode down to max(skip_planes, floor), placement, inverse transform; reduce > 0 (R = its tables): the subset of the resolutions it needs
+int plan_decode_frame_tables(j2k_plan *P, const uint8_t *d_data, ReducedTab *R, int reduce, int skip_planes, const uint8_t *d_floors, uint8_t *d_floors_r, void *d_pix,
+                             size_t stride) {
+    j2k_ctx *ctx = P->ctx;
+    int r;
     if (reduce == 0) {
-        r = plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, P->d_cl_decoded, nullptr, skip_planes, W.floors);
+        r = plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_data, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, P->d_cl_decoded, nullptr, skip_planes, d_floors);
         if (r == J2K_OK) r = j2k_plan_place_blocks(P, P->d_cl_decoded, P->d_cl_coeff);
         if (r == J2K_OK) r = plan_inverse_pixels_impl(P, P->d_cl_coeff, d_pix, stride, P->d_frame_status);
         return r;
     }
     // the subset's tables, and (the same kernel, the floors in the place of the plane counts) its floors
-    HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, W.floors, R->d_offs, R->d_lens, W.floors_r));
+    HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, d_floors, R->d_offs, R->d_lens, d_floors_r));
     HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, R->d_offs, R->d_lens, R->d_numbps));
-    r = plan_decode_blocks_jobs(P, R->d_djobs, R->njobs, d_cs, R->d_offs, R->d_lens, R->d_numbps, P->d_cl_decoded, nullptr, skip_planes, W.floors_r);
+    r = plan_decode_blocks_jobs(P, R->d_djobs, R->njobs, d_data, R->d_offs, R->d_lens, R->d_numbps, P->d_cl_decoded, nullptr, skip_planes, d_floors_r);
     if (r == J2K_OK) HIPCHK(ctx, launch_place_blocks(ctx->stream, R->d_bjobs, R->d_djobs, R->njobs, R->max_block_h, P->d_cl_decoded, P->d_cl_coeff));
     if (r == J2K_OK) r = plan_inverse_pixels_reduced_impl(P, P->d_cl_coeff, reduce, d_pix, stride, P->d_frame_status);
     return r;

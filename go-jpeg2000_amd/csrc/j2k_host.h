@@ -44,6 +44,15 @@ hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs
 size_t rate_allocate_workspace(int njobs);
 hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
                                 uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen);
+hipError_t launch_rate_allocate_layers(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+                                       const uint64_t *budgets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen);
+// quality layers (t2dev.hip, t2dec.hip)
+hipError_t launch_t2_fill_layer_cbs(hipStream_t s, long n, int nlayers, const uint64_t *offs, const BlockJob *slot_jobs, const uint32_t *lens, const uint8_t *numbps,
+                                    int mb, const uint8_t *kept, const uint32_t *rate, j2k_t2_dev_cb *cbs, uint64_t *reset);
+hipError_t launch_t2_layer_ends(hipStream_t s, int count, int nlayers, const int *end_packet, const uint64_t *poffs, uint64_t *layer_offs);
+hipError_t launch_t2_decode_tiles_layers(hipStream_t s, void *chains, int ntiles, const j2k_t2_dev_packet *packets, long npackets, j2k_t2_dev_cb *cbs, long n,
+                                         int nlayers, const uint8_t *data, uint64_t len, int sop, int eph, uint64_t *body_base, int *frame_status, int mb,
+                                         uint8_t *dense, uint64_t dense_cap, uint64_t *offs, uint32_t *lens, uint8_t *numbps, uint8_t *floors);
 size_t t1_sym_stride(int planes);
 hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, const uint8_t *numbps, int32_t *decoded, uint8_t *work,
@@ -118,11 +127,22 @@ void plan_t2_packets(const j2k_plan *P, int layer, std::vector<j2k_t2_dev_packet
 // the tables of a Mallat plan decoded `reduce` resolutions down (made at the first use of that `reduce`, kept in the plan); the refusals of
 // include/j2kgfx.h: J2K_ERR_UNSUPPORTED on any other plan, J2K_ERR_INVALID_ARG for a `reduce` the geometry does not allow
 int plan_reduced(j2k_plan *P, int reduce, j2k::ReducedTab **out);
+void free_layer_tabs(j2k_plan *P);           // j2k_layers.cpp
+// the closed-loop frame codec's tables and workspaces, made at first use (j2k_frame.cpp)
+int cl_prepare(j2k_plan *P);
+int cl_workspaces(j2k_plan *P);
+struct ClRate { uint32_t *rate; uint64_t *dist; uint8_t *kept; uint64_t *chosen; uint8_t *floors, *floors_r; };
+int cl_rate_workspace(j2k_plan *P, ClRate &W);
+int plan_decode_frame_tables(j2k_plan *P, const uint8_t *d_data, j2k::ReducedTab *R, int reduce, int skip_planes, const uint8_t *d_floors, uint8_t *d_floors_r,
+                             void *d_pix, size_t stride);
+int rate_check(j2k_plan *P, const char *who);    // what every rate call needs of its plan (j2k_rate.cpp)
+int rate_upload_weights(j2k_plan *P);            // the per-job weights and the allocation workspace on the device (j2k_rate.cpp)
 
 // ---- stages (j2k_stages.cpp) ----
 struct T1Workspace { size_t off_nsyms, off_sym, stride, total; };
 T1Workspace t1_workspace(const j2k_ctx *ctx, size_t n, size_t wpj);
 int ensure(j2k_ctx *ctx, void **p, size_t bytes);
+int ensure_sized(j2k_ctx *ctx, void **p, size_t *cur, size_t need);   // a buffer that grows (synchronises when it does; j2k_hostcalls.cpp)
 struct PixIO { int stride = 0, single = 0, triple = 0; j2k::YccSrc ycc{}; };   // ycc.y: a YCbCr image in place of packed RGBA8 (triple 8)
 int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix = PixIO());
 int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate);

@@ -359,7 +359,7 @@ extern "C" int j2k_encode_frame(j2k_plan *P, int32_t *const *planes, int32_t *co
 
 
 // a plan-owned device buffer that grows with what the call needs (the stream is drained before it is replaced)
-static int ensure_sized(j2k_ctx *ctx, void **p, size_t *cur, size_t need) {
+int ensure_sized(j2k_ctx *ctx, void **p, size_t *cur, size_t need) {
     if (*p && *cur >= need) return J2K_OK;
     if (*p) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(*p)); *p = nullptr; *cur = 0; }
     HIPCHK(ctx, hipMalloc(p, std::max<size_t>(need, 64)));

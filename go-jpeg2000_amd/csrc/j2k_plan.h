@@ -143,6 +143,22 @@ struct ReducedTab {
     uint64_t *d_offs = nullptr; uint32_t *d_lens = nullptr; uint8_t *d_numbps = nullptr;
 };
 
+// Quality layers (j2k_plan_*_layers): the tables of one layer count L -- the stream's on the encode side, the layers read on the
+// decode side (the same tables: a tile's packet sequence once per layer, the layer outermost).  Made at the first use of that L, kept in the plan.
+struct LayerTab {
+    bool built = false;
+    int npackets = 0;                          // L x the plan's
+    j2k_t2_dev_packet *d_packets = nullptr;    // J2K_T2_LAYERED set; packet (tile, l, q): layer l, cb0 = l * blocks + the plan packet's
+    int *d_tile_packet0 = nullptr;             // first packet of every tile (+ the count)
+    int32_t *d_ptile = nullptr;                // packet -> tile
+    int *d_end_packet = nullptr;               // [tile * L + l]: the packet behind layer l of the tile (t2_layer_ends_kernel)
+    j2k_t2_dev_cb *d_cbs = nullptr;            // L x blocks entries
+    uint64_t *d_poffs = nullptr;               // encode: packet offsets
+    void *d_ws = nullptr;                      // encode: the packet coder's workspace + its result words
+    uint64_t *d_body_base = nullptr;           // decode
+    uint8_t *d_kept = nullptr;                 // frame encode only, made at its first use: L x blocks cumulative cuts
+};
+
 }  // namespace j2k
 
 struct j2k_plan {
@@ -244,5 +260,9 @@ struct j2k_plan {
     bool rate_wj_valid = false;
     void *d_rate_ws = nullptr;              // the allocation kernel's hulls
     void *d_cl_rate = nullptr;              // the *_rate frame calls: rate and distortion tables, kept planes, chosen bytes, floors (cl_rate_workspace)
+    std::vector<j2k::LayerTab> layer_tabs;  // quality layers: [L], 1 ... J2K_MAX_LAYERS
+    void *d_cl_dense = nullptr;             // j2k_plan_decode_frame_pixels_layers: the gathered codewords (at least the stream's length) ...
+    size_t cl_dense_bytes = 0;
+    uint8_t *d_cl_lfloors = nullptr;        // ... and the blocks' floors (whole frame | the subset of a reduced decode)
     bool dequantize = false;                // j2k_plan_set_dequantize: the 9-7 inverse kernels multiply every int32 coefficient by 1.0 / Quality at their load (dwt.go:514-520)
 };

@@ -127,6 +127,14 @@ extern "C" int j2k_plan_rate_allocate(j2k_plan *P, const uint32_t *d_rate, const
     if (r != J2K_OK) return r;
     if (max_body_bytes < 0) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_rate_allocate: a negative budget");
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    r = rate_upload_weights(P);
+    if (r != J2K_OK) return r;
+    HIPCHK(ctx, launch_rate_allocate(ctx->stream, (int)P->blocks.size(), d_rate, d_dist, d_numbps, P->d_rate_wj, (uint64_t)max_body_bytes, P->d_rate_ws, d_kept, d_chosen));
+    return J2K_OK;
+}
+
+int rate_upload_weights(j2k_plan *P) {
+    j2k_ctx *ctx = P->ctx;
     const size_t n = P->blocks.size();
     if (!P->rate_wj_valid || !P->d_rate_ws) {
         if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: run the same calls once before j2k_ctx_capture_begin");
@@ -143,6 +151,5 @@ extern "C" int j2k_plan_rate_allocate(j2k_plan *P, const uint32_t *d_rate, const
         HIPCHK(ctx, hipMemcpy(P->d_rate_wj, wj.data(), wj.size() * sizeof(double), hipMemcpyHostToDevice));
         P->rate_wj_valid = true;
     }
-    HIPCHK(ctx, launch_rate_allocate(ctx->stream, (int)n, d_rate, d_dist, d_numbps, P->d_rate_wj, (uint64_t)max_body_bytes, P->d_rate_ws, d_kept, d_chosen));
     return J2K_OK;
 }

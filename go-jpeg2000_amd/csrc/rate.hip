@@ -85,23 +85,10 @@ __device__ __forceinline__ uint64_t wg_sum(uint64_t v, uint64_t *sh) {
     return t;
 }
 
-__global__ __launch_bounds__(RATE_WG) void rate_allocate_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
-                                                                const uint8_t *__restrict__ numbps, const double *__restrict__ weights, uint64_t budget,
-                                                                void *__restrict__ ws, uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen) {
-    __shared__ uint64_t sh[RATE_WG / 64];
-    const int tid = threadIdx.x;
-    const RateWs W = rate_ws(ws, (size_t)njobs);
-    // nothing to cut?
-    uint64_t part = 0;
-    for (int j = tid; j < njobs; j += RATE_WG) part += rate[(size_t)j * RATE_STRIDE + min((int)numbps[j], RATE_STRIDE - 1)];
-    const uint64_t total = wg_sum(part, sh);
-    if (total <= budget) {
-        for (int j = tid; j < njobs; j += RATE_WG) kept[j] = (uint8_t)min((int)numbps[j], RATE_STRIDE - 1);
-        if (tid == 0) *chosen = total;
-        return;
-    }
-    // hulls: the upper-left convex hull of (rate, distortion) from p = 0, pop while the new point is not less steep
-    for (int j = tid; j < njobs; j += RATE_WG) {
+// hulls: the upper-left convex hull of (rate, distortion) from p = 0, pop while the new point is not less steep (every thread its own blocks)
+__device__ __forceinline__ void rate_hulls(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist, const uint8_t *__restrict__ numbps,
+                                           const double *__restrict__ weights, const RateWs &W) {
+    for (int j = threadIdx.x; j < njobs; j += RATE_WG) {
         const uint32_t *R = rate + (size_t)j * RATE_STRIDE;
         const uint64_t *D = dist + (size_t)j * RATE_STRIDE;
         double *sl = W.slope + (size_t)j * RATE_STRIDE;
@@ -135,37 +122,87 @@ __global__ __launch_bounds__(RATE_WG) void rate_allocate_kernel(int njobs, const
         }
         W.count[j] = (uint32_t)cnt;
     }
-    // (each thread reads back only what it wrote itself: no barrier needed between the hulls and the search)
-    auto pick = [&](int j, double lam) -> int {
-        const double *sl = W.slope + (size_t)j * RATE_STRIDE;
-        const int cnt = (int)W.count[j];
-        int i = 0;
-        while (i + 1 < cnt && sl[i + 1] >= lam) i++;
-        return W.plane[(size_t)j * RATE_STRIDE + i];
-    };
-    auto bytes_at = [&](uint64_t bits) -> uint64_t {
-        const double lam = __longlong_as_double((long long)bits);
-        uint64_t b = 0;
-        for (int j = tid; j < njobs; j += RATE_WG) b += rate[(size_t)j * RATE_STRIDE + pick(j, lam)];
-        return wg_sum(b, sh);
-    };
-    // the smallest bit pattern of a non-negative double whose choice fits: bisection over the patterns, 64 steps (the patterns above
-    // +infinity are NaNs: no slope is >= a NaN, every block is at its start point, whose rate is 0 -- the top of the range always fits)
+}
+__device__ __forceinline__ int rate_pick(const RateWs &W, int j, double lam) {
+    const double *sl = W.slope + (size_t)j * RATE_STRIDE;
+    const int cnt = (int)W.count[j];
+    int i = 0;
+    while (i + 1 < cnt && sl[i + 1] >= lam) i++;
+    return W.plane[(size_t)j * RATE_STRIDE + i];
+}
+// The smallest bit pattern of a non-negative double whose choice fits: bisection over the patterns, 64 steps (the patterns above
+// +infinity are NaNs: no slope is >= a NaN, every block is at its start point, whose rate is 0 -- the top of the range always fits).
+// Writes that choice to kept[0 ... njobs) and returns its bytes.  (Each thread reads back only the hulls it built itself: no barrier
+// needed between rate_hulls and the search.)
+__device__ __forceinline__ uint64_t rate_search(int njobs, const uint32_t *__restrict__ rate, const RateWs &W, uint64_t budget, uint64_t *sh,
+                                                uint8_t *__restrict__ kept) {
+    const int tid = threadIdx.x;
     uint64_t lo = 0, hi = 0x7FFFFFFFFFFFFFFFull;
     for (int step = 0; step < 64; step++) {
         const uint64_t mid = lo + (hi - lo) / 2;
-        const uint64_t b = bytes_at(mid);                // every thread takes every step: wg_sum has barriers
+        const double lam = __longlong_as_double((long long)mid);
+        uint64_t b = 0;
+        for (int j = tid; j < njobs; j += RATE_WG) b += rate[(size_t)j * RATE_STRIDE + rate_pick(W, j, lam)];
+        b = wg_sum(b, sh);                               // every thread takes every step: wg_sum has barriers
         if (lo < hi) { if (b <= budget) hi = mid; else lo = mid + 1; }
     }
     const double lam = __longlong_as_double((long long)hi);
     uint64_t b = 0;
     for (int j = tid; j < njobs; j += RATE_WG) {
-        const int p = pick(j, lam);
+        const int p = rate_pick(W, j, lam);
         kept[j] = (uint8_t)p;
         b += rate[(size_t)j * RATE_STRIDE + p];
     }
-    b = wg_sum(b, sh);
+    return wg_sum(b, sh);
+}
+
+__global__ __launch_bounds__(RATE_WG) void rate_allocate_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
+                                                                const uint8_t *__restrict__ numbps, const double *__restrict__ weights, uint64_t budget,
+                                                                void *__restrict__ ws, uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen) {
+    __shared__ uint64_t sh[RATE_WG / 64];
+    const int tid = threadIdx.x;
+    const RateWs W = rate_ws(ws, (size_t)njobs);
+    // nothing to cut?
+    uint64_t part = 0;
+    for (int j = tid; j < njobs; j += RATE_WG) part += rate[(size_t)j * RATE_STRIDE + min((int)numbps[j], RATE_STRIDE - 1)];
+    const uint64_t total = wg_sum(part, sh);
+    if (total <= budget) {
+        for (int j = tid; j < njobs; j += RATE_WG) kept[j] = (uint8_t)min((int)numbps[j], RATE_STRIDE - 1);
+        if (tid == 0) *chosen = total;
+        return;
+    }
+    rate_hulls(njobs, rate, dist, numbps, weights, W);
+    const uint64_t b = rate_search(njobs, rate, W, budget, sh, kept);
     if (tid == 0) *chosen = b;
+}
+
+struct RateBudgets { uint64_t b[32]; };
+// The same for nlayers cumulative budgets in one launch (quality layers): layer l is rate_allocate_kernel's result for budgets[l],
+// kept[l * njobs + j] and chosen[l].  The hulls are built once (and not at all when every budget holds the full lengths); each layer that cuts
+// runs its own 64-step bisection over them.  "The smallest lambda that fits" makes kept monotone in the budget.
+__global__ __launch_bounds__(RATE_WG) void rate_allocate_layers_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
+                                                                       const uint8_t *__restrict__ numbps, const double *__restrict__ weights,
+                                                                       const RateBudgets budgets, int nlayers, void *__restrict__ ws,
+                                                                       uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen) {
+    __shared__ uint64_t sh[RATE_WG / 64];
+    const int tid = threadIdx.x;
+    const RateWs W = rate_ws(ws, (size_t)njobs);
+    uint64_t part = 0;
+    for (int j = tid; j < njobs; j += RATE_WG) part += rate[(size_t)j * RATE_STRIDE + min((int)numbps[j], RATE_STRIDE - 1)];
+    const uint64_t total = wg_sum(part, sh);
+    bool have_hulls = false;                             // (uniform over the workgroup: budgets and total are)
+    for (int l = 0; l < nlayers; l++) {
+        const uint64_t budget = budgets.b[l];
+        uint8_t *kl = kept + (size_t)l * njobs;
+        if (total <= budget) {
+            for (int j = tid; j < njobs; j += RATE_WG) kl[j] = (uint8_t)min((int)numbps[j], RATE_STRIDE - 1);
+            if (tid == 0) chosen[l] = total;
+            continue;
+        }
+        if (!have_hulls) { rate_hulls(njobs, rate, dist, numbps, weights, W); have_hulls = true; }
+        const uint64_t b = rate_search(njobs, rate, W, budget, sh, kl);
+        if (tid == 0) chosen[l] = b;
+    }
 }
 
 hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, uint64_t *dist) {
@@ -177,6 +214,15 @@ hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs
 hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
                                 uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen) {
     hipLaunchKernelGGL(rate_allocate_kernel, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, budget, ws, kept, chosen);
+    return hipGetLastError();
+}
+
+// budgets: nlayers <= 32 values on the host (a kernel argument); kept: nlayers x njobs bytes; chosen: nlayers x uint64
+hipError_t launch_rate_allocate_layers(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+                                       const uint64_t *budgets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen) {
+    RateBudgets B{};
+    for (int l = 0; l < nlayers && l < 32; l++) B.b[l] = budgets[l];
+    hipLaunchKernelGGL(rate_allocate_layers_kernel, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, B, nlayers, ws, kept, chosen);
     return hipGetLastError();
 }
 

@@ -214,11 +214,20 @@ struct T2Chain {
 #endif
 };
 
+// LAYERED (quality layers; the launches of launch_t2_decode_tiles_layers only): the packets are a tile's sequence once per layer,
+// entry l * lstride + j of the table = block j in layer l, and the header of layer l > 0 follows the library's own rule, not the reference's
+// (whose decoder cannot read what its encoder writes there): one "contributes" bit per block, ZeroBitPlanes behind it iff the block has not
+// contributed in an earlier layer, then the passes and the length of the INCREMENT.  IncludedInLayers of entry (l, j) = the block's first
+// contributing layer as far as the layers 0 ... l say (layer 0: its unary value; INT_MAX: none yet), which is what layer l + 1 looks at.  Every
+// field of every entry of a packet is written (clean = 2).  The instantiation without it is the kernel as it was: same registers, LDS, occupancy
+// (docs/KERNEL_NOTES.md 4v).
+#define T2D_NO_LAYER 0x7FFFFFFF
+template <bool LAYERED>
 __global__ __launch_bounds__(64) void t2_decode_kernel(T2Chain *__restrict__ chains, const j2k_t2_dev_packet *__restrict__ packets, long npackets_all,
                                                        j2k_t2_dev_cb *__restrict__ cbs, uint64_t ncbs, const uint8_t *__restrict__ data, int sop, int eph, int clean,
                                                        uint64_t *__restrict__ body_base, int *__restrict__ frame_status,
                                                        const T2Chain *__restrict__ pchains, const uint64_t *__restrict__ seeds, const uint32_t *__restrict__ tile_par,
-                                                       const int *__restrict__ tile_packet0) {
+                                                       const int *__restrict__ tile_packet0, int64_t lstride) {
     __shared__ uint64_t raw[T2D_RAW / 8];
     __shared__ uint32_t bits[T2D_CHUNK * 8 / 32 + 4];
     __shared__ uint16_t sbit[T2D_CHUNK + 2];
@@ -280,6 +289,10 @@ __global__ __launch_bounds__(64) void t2_decode_kernel(T2Chain *__restrict__ cha
         const j2k_t2_dev_packet P = packets[pk];
         if (P.ncb < 0 || P.cb0 < 0 || (uint64_t)P.cb0 + (uint64_t)P.ncb > ncbs) { status = J2K_ERR_INVALID_ARG; break; }
         const int layer = P.layer;
+        if (LAYERED) {
+            if (layer < 0 || lstride <= 0 || (layer > 0 && P.cb0 < lstride)) { status = J2K_ERR_INVALID_ARG; break; }   // (entry (l - 1, j) lies lstride entries before)
+            __syncthreads();                                        // (one wavefront: the entries lane 0 wrote for the layer before are visible to all lanes)
+        }
         const uint32_t lenbits = (P.flags & J2K_T2_WIDE_LEN) ? 5u : 3u;
         if (P.flags & J2K_T2_FRESH) { carried_ff = false; if (!(P.flags & J2K_T2_SEATED)) r.seat(0, 0, false); }   // NewPacketDecoder
         if (sop && pos + 6 <= end && r.byte_at(pos) == 0xFFu && r.byte_at(pos + 1) == 0x91u) pos += 6;     // t2.go:470-474
@@ -291,7 +304,7 @@ __global__ __launch_bounds__(64) void t2_decode_kernel(T2Chain *__restrict__ cha
         // layer).  `clean`: layer 0 is decoded only and the table holds nothing from before -- 1: the caller zeroed it; 2 (frame calls): it
         // may hold anything, this kernel writes EVERY field of every block of the packets it decodes (also of an empty packet) and flags
         // the packets it did not reach (body_base = ~0), which is all t2_finish_kernel looks at.  No such block, nothing is read.
-        const bool old_matters = !clean || layer != 0;
+        const bool old_matters = !LAYERED && (!clean || layer != 0);
         // decodePacketHeader (t2.go:506-571) as ONE loop over its reading steps -- presence bit, then per code-block inclusion,
         // zero bit planes, pass count + length -- so that the chunk builder above has a single call site
 #ifdef J2K_T2D_STATS
@@ -384,6 +397,12 @@ __global__ __launch_bounds__(64) void t2_decode_kernel(T2Chain *__restrict__ cha
                     inc = uv == 0;
                     incl_layers = (int)uv;
                     if (lane == 0) { if (clean) *reinterpret_cast<int4 *>(&pc[i]) = int4{incl_layers, 0, 0, 0}; else pc[i].included_in_layers = incl_layers; }
+                } else if (LAYERED) {
+                    inc = r.get(1) == 1;
+                    if (r.eof) { status = J2K_ERR_INVALID_ARG; break; }
+                    const int prev = (int)t2_uni((uint32_t)pc[i - lstride].included_in_layers);
+                    incl_layers = (uint32_t)prev < (uint32_t)layer ? prev : (inc ? layer : T2D_NO_LAYER);
+                    if (lane == 0) *reinterpret_cast<int4 *>(&pc[i]) = int4{incl_layers, 0, 0, 0};
                 } else {
                     inc = r.get(1) == 1;
                     if (r.eof) { status = J2K_ERR_INVALID_ARG; break; }
@@ -431,7 +450,14 @@ __global__ __launch_bounds__(64) void t2_decode_kernel(T2Chain *__restrict__ cha
         const uint64_t t_c_ = wall_clock64(); t_hdr_ += t_c_ - t_b_;
 #endif
         if (status != J2K_OK) break;
-        if (!present && clean == 2)                                                              // an empty packet: its blocks hold nothing
+        if (LAYERED && !present) {                                                               // an empty packet: no block contributes, what the layers before said stands
+            for (int64_t q = lane; q < P.ncb; q += 64) {
+                const int prev = layer > 0 ? pc[q - lstride].included_in_layers : T2D_NO_LAYER;
+                j2k_t2_dev_cb e{};
+                e.included_in_layers = (uint32_t)prev < (uint32_t)layer ? prev : T2D_NO_LAYER;
+                pc[q] = e;
+            }
+        } else if (!present && clean == 2)                                                       // an empty packet: its blocks hold nothing
             for (int64_t q = lane; q < P.ncb; q += 64) pc[q] = j2k_t2_dev_cb{};
         if (!present && old_matters) {
             for (int64_t q = 0; q < P.ncb; q++) {
@@ -758,6 +784,113 @@ hipError_t launch_select_blocks(hipStream_t s, const int *ids, int m, const uint
     return hipGetLastError();
 }
 
+// ---- quality layers: the segments of a block -> one contiguous codeword --------------------------------------------------------------------
+// A layered stream holds block j's bytes as up to one segment per layer; the MQ block decoders read one contiguous range.  After
+// the LAYERED packet parse of k layers:
+//   t2_layer_bodies_kernel   a workgroup per packet: segment offsets from "within the packet's bodies" to "within the stream"; the entries of a
+//                            packet its chain did not reach say "nothing" (not what a frame before left there)
+//   t2_layer_tables_kernel   ONE workgroup: per block the sums of passes and bytes over its segments, ZeroBitPlanes from the entry of its first
+//                            layer, floor and plane count by the rule of the _floors calls on the sums, and (a scan over the blocks) where its
+//                            bytes go in the dense buffer
+//   t2_layer_gather_kernel   a wavefront per block: the segments end to end at that place (copy_bytes: 16-byte vector stores, the byte-granular
+//                            head and tail in plain C++)
+// A segment counts iff it has passes and bytes and lies inside the stream -- the same test in both kernels.
+__device__ __forceinline__ bool t2_layer_seg(const j2k_t2_dev_cb &e, uint64_t total) {
+    return e.data_len > 0 && e.num_passes > 0 && e.data_off <= total && e.data_len <= total - e.data_off;
+}
+__global__ __launch_bounds__(256) void t2_layer_bodies_kernel(const j2k_t2_dev_packet *__restrict__ packets, j2k_t2_dev_cb *__restrict__ cbs, uint64_t ncbs,
+                                                              const uint64_t *__restrict__ body_base) {
+    const j2k_t2_dev_packet P = packets[blockIdx.x];
+    const uint64_t b = body_base[blockIdx.x];
+    if (P.ncb < 0 || P.cb0 < 0 || (uint64_t)P.cb0 + (uint64_t)P.ncb > ncbs) return;
+    for (int64_t i = threadIdx.x; i < P.ncb; i += 256) {
+        j2k_t2_dev_cb &cb = cbs[P.cb0 + i];
+        if (b == ~0ull) { j2k_t2_dev_cb e{}; e.included_in_layers = T2D_NO_LAYER; cb = e; }
+        else if (cb.data_len > 0) cb.data_off += b;
+    }
+}
+#define T2L_WG 1024
+__global__ __launch_bounds__(T2L_WG) void t2_layer_tables_kernel(long n, int nlayers, const j2k_t2_dev_cb *__restrict__ cbs, int mb, uint64_t total, uint64_t cap,
+                                                                 uint64_t *__restrict__ offs, uint32_t *__restrict__ lens, uint8_t *__restrict__ numbps,
+                                                                 uint8_t *__restrict__ floors, int *__restrict__ status) {
+    __shared__ uint64_t sum_s[T2L_WG];
+    const int t = threadIdx.x;
+    // per block, neighbouring lanes on neighbouring blocks (entries 24 bytes apart) ...
+    for (long j = t; j < n; j += T2L_WG) {
+        int passes = 0, zbp = -1;
+        uint64_t len = 0;
+        for (int l = 0; l < nlayers; l++) {
+            const j2k_t2_dev_cb e = cbs[(size_t)l * n + j];
+            if (e.included_in_layers == l) zbp = e.zero_bit_planes;                 // the block's first layer: the only header that carries them
+            if (t2_layer_seg(e, total)) { passes += e.num_passes; len += e.data_len; }
+        }
+        const bool has = len > 0 && zbp >= 0 && len <= 0xFFFFFFFFull && passes > 0;
+        int nb = 0, floor = 0;
+        if (has) { nb = (passes + 2) / 3; floor = max(mb - zbp - nb, 0); nb += floor; }
+        const bool bad = nb > 31;                                                     // (a foreign stream: dropped, the frame's status says so)
+        if (bad && status) atomicMin(status, J2K_ERR_INVALID_ARG);
+        const bool keep = has && !bad;
+        lens[j] = keep ? (uint32_t)len : 0u;
+        numbps[j] = (uint8_t)(keep ? nb : 0);
+        floors[j] = (uint8_t)(keep ? floor : 0);
+    }
+    __syncthreads();                                                                  // (the workgroup's stores to lens are visible to all of it)
+    // ... then the offsets: every thread a contiguous chunk of the lengths, a scan over the chunks' bytes
+    const long chunk = (n + T2L_WG - 1) / T2L_WG, j0 = min((long)t * chunk, n), j1 = min(j0 + chunk, n);
+    uint64_t mine = 0;
+    for (long j = j0; j < j1; j++) mine += lens[j];
+    sum_s[t] = mine;
+    __syncthreads();
+    for (int d = 1; d < T2L_WG; d <<= 1) {                                            // inclusive scan of the chunks' bytes
+        const uint64_t u = t >= d ? sum_s[t - d] : 0;
+        __syncthreads();
+        sum_s[t] += u;
+        __syncthreads();
+    }
+    uint64_t off = sum_s[t] - mine;
+    for (long j = j0; j < j1; j++) {
+        const uint32_t len = lens[j];
+        if (off + len > cap) {                                                        // the dense buffer is too small: the block is dropped
+            if (len && status) atomicMin(status, J2K_ERR_CAPACITY);
+            lens[j] = 0; numbps[j] = 0; floors[j] = 0; offs[j] = 0;
+        } else offs[j] = len ? off : 0;
+        off += len;
+    }
+}
+__global__ __launch_bounds__(64) void t2_layer_gather_kernel(long n, int nlayers, const j2k_t2_dev_cb *__restrict__ cbs, const uint8_t *__restrict__ data,
+                                                             uint64_t total, const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
+                                                             uint8_t *__restrict__ dense) {
+    const long j = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (j >= n) return;
+    const uint32_t len = lens[j];
+    if (!len) return;
+    uint8_t *dst = dense + offs[j];                                                   // (offs[j] + len <= the buffer's size: t2_layer_tables_kernel)
+    uint32_t pos = 0;
+    for (int l = 0; l < nlayers; l++) {
+        const j2k_t2_dev_cb e = cbs[(size_t)l * n + j];
+        if (!t2_layer_seg(e, total)) continue;
+        if (e.data_len > len - pos) break;                                            // (cannot happen: len is the sum of exactly these)
+        copy_bytes(dst + pos, data + e.data_off, e.data_len, lane);
+        pos += e.data_len;
+    }
+}
+// launch_t2_decode_tiles for the first `nlayers` layers of a layered stream: every tile's packets by its serial chain (a layer's header depends on
+// the headers of the layers before it: no side-by-side guess), then the tables and the dense buffer above.  packets: the tile's sequence once per
+// layer with J2K_T2_LAYERED set; cbs: nlayers * n entries; chains: made by launch_t2_tile_chains with the same table's tile_packet0.
+hipError_t launch_t2_decode_tiles_layers(hipStream_t s, void *chains, int ntiles, const j2k_t2_dev_packet *packets, long npackets, j2k_t2_dev_cb *cbs, long n,
+                                         int nlayers, const uint8_t *data, uint64_t len, int sop, int eph, uint64_t *body_base, int *frame_status, int mb,
+                                         uint8_t *dense, uint64_t dense_cap, uint64_t *offs, uint32_t *lens, uint8_t *numbps, uint8_t *floors) {
+    if (ntiles <= 0 || npackets <= 0 || n <= 0) return hipSuccess;
+    const uint64_t ncbs = (uint64_t)n * (uint64_t)nlayers;
+    hipLaunchKernelGGL(t2_decode_kernel<true>, dim3((unsigned)ntiles), dim3(64), 0, s, reinterpret_cast<T2Chain *>(chains), packets, npackets, cbs, ncbs, data, sop, eph, 2,
+                       body_base, frame_status, (const T2Chain *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (const int *)nullptr, (int64_t)n);
+    hipLaunchKernelGGL(t2_layer_bodies_kernel, dim3((unsigned)npackets), dim3(256), 0, s, packets, cbs, ncbs, body_base);
+    hipLaunchKernelGGL(t2_layer_tables_kernel, dim3(1), dim3(T2L_WG), 0, s, n, nlayers, cbs, mb, len, dense_cap, offs, lens, numbps, floors, frame_status);
+    hipLaunchKernelGGL(t2_layer_gather_kernel, dim3((unsigned)n), dim3(64), 0, s, n, nlayers, cbs, data, len, offs, lens, dense);
+    return hipGetLastError();
+}
+
 size_t t2_chain_bytes() { return sizeof(T2Chain); }
 
 hipError_t launch_t2_tile_chains(hipStream_t s, const uint8_t *cs, uint64_t len, const uint64_t *tile_offs, int ntiles, int tile_first,
@@ -771,8 +904,8 @@ hipError_t launch_t2_tile_chains(hipStream_t s, const uint8_t *cs, uint64_t len,
 hipError_t launch_t2_decode_packets(hipStream_t s, void *chains, int nchains, const j2k_t2_dev_packet *packets, long npackets, j2k_t2_dev_cb *cbs, uint64_t ncbs,
                                     const uint8_t *data, int sop, int eph, int clean, uint64_t *body_base, int *frame_status) {
     if (nchains <= 0 || npackets <= 0) return hipSuccess;
-    hipLaunchKernelGGL(t2_decode_kernel, dim3((unsigned)nchains), dim3(64), 0, s, reinterpret_cast<T2Chain *>(chains), packets, npackets, cbs, ncbs, data, sop, eph,
-                       clean, body_base, frame_status, (const T2Chain *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (const int *)nullptr);
+    hipLaunchKernelGGL(t2_decode_kernel<false>, dim3((unsigned)nchains), dim3(64), 0, s, reinterpret_cast<T2Chain *>(chains), packets, npackets, cbs, ncbs, data, sop, eph,
+                       clean, body_base, frame_status, (const T2Chain *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (const int *)nullptr, (int64_t)0);
     hipLaunchKernelGGL(t2_bodies_kernel, dim3((unsigned)npackets), dim3(256), 0, s, packets, cbs, ncbs, body_base);
     return hipGetLastError();
 }
@@ -795,13 +928,13 @@ hipError_t launch_t2_decode_tiles(hipStream_t s, void *chains, int ntiles, const
         const unsigned seg = (unsigned)std::min<uint64_t>(std::max(1, 2048 / ntiles), std::max<uint64_t>(1, len / (uint64_t)ntiles / 16384 + 1));
         hipLaunchKernelGGL(t2_marks_kernel, dim3(seg, (unsigned)ntiles), dim3(256), 0, s, tc, tile_packet0, data, marks, cnt);
         hipLaunchKernelGGL(t2_seed_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, tc, tile_packet0, data, marks, cnt, pch, seeds, tile_par);
-        hipLaunchKernelGGL(t2_decode_kernel, dim3((unsigned)npackets), dim3(64), 0, s, pch, packets, npackets, cbs, ncbs, data, sop, eph, 2, body_base, (int *)nullptr,
-                           (const T2Chain *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (const int *)nullptr);
-        hipLaunchKernelGGL(t2_decode_kernel, dim3((unsigned)ntiles), dim3(64), 0, s, tc, packets, npackets, cbs, ncbs, data, sop, eph, 2, body_base, frame_status,
-                           (const T2Chain *)pch, (const uint64_t *)seeds, (const uint32_t *)tile_par, tile_packet0);
+        hipLaunchKernelGGL(t2_decode_kernel<false>, dim3((unsigned)npackets), dim3(64), 0, s, pch, packets, npackets, cbs, ncbs, data, sop, eph, 2, body_base, (int *)nullptr,
+                           (const T2Chain *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (const int *)nullptr, (int64_t)0);
+        hipLaunchKernelGGL(t2_decode_kernel<false>, dim3((unsigned)ntiles), dim3(64), 0, s, tc, packets, npackets, cbs, ncbs, data, sop, eph, 2, body_base, frame_status,
+                           (const T2Chain *)pch, (const uint64_t *)seeds, (const uint32_t *)tile_par, tile_packet0, (int64_t)0);
     } else
-        hipLaunchKernelGGL(t2_decode_kernel, dim3((unsigned)ntiles), dim3(64), 0, s, tc, packets, npackets, cbs, ncbs, data, sop, eph, 2, body_base, frame_status,
-                           (const T2Chain *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (const int *)nullptr);
+        hipLaunchKernelGGL(t2_decode_kernel<false>, dim3((unsigned)ntiles), dim3(64), 0, s, tc, packets, npackets, cbs, ncbs, data, sop, eph, 2, body_base, frame_status,
+                           (const T2Chain *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (const int *)nullptr, (int64_t)0);
     hipLaunchKernelGGL(t2_finish_kernel, dim3((unsigned)npackets), dim3(256), 0, s, packets, cbs, ncbs, body_base, ht, mb, len, offs, lens, numbps, frame_status, floors);
     return hipGetLastError();
 }

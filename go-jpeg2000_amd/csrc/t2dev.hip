@@ -411,7 +411,65 @@ hipError_t launch_t2_fill_cbs(hipStream_t s, long n, const uint64_t *offs, const
     return hipGetLastError();
 }
 
-static unsigned t2_body_slices() {                                  // J2K_T2_BODY_SLICES (tuning): wavefronts that share a packet's bodies
+// Quality layers (tests/layer_cases.py): the code-block table of an L-layer stream, entry l * n + j = block j's share of layer l.
+// kept[l * n + j] = the cumulative cut P_l of block j (rate_allocate_layers_kernel); normalised so that no layer adds passes without bytes:
+// Q_l = P_l if R[P_l] > R[Q_(l-1)] else Q_(l-1).  Layer l carries the bytes [R[Q_(l-1)], R[Q_l]) and passes_of(Q_l) - passes_of(Q_(l-1)) passes;
+// IncludedInLayers = the block's first contributing layer in EVERY entry (L: none), so that t2_fields writes unary(first) at layer 0, the
+// "contributes" bit above it, and ZeroBitPlanes exactly where l == first.  base[j]: where block j's codeword starts in `data` (its offset in
+// the dense stream, or its coding slot's: slot_jobs).  One thread per block.
+__global__ __launch_bounds__(256) void t2_fill_layer_cbs_kernel(long n, int nlayers, const uint64_t *__restrict__ offs, const BlockJob *__restrict__ slot_jobs,
+                                                                const uint32_t *__restrict__ lens, const uint8_t *__restrict__ numbps, int mb,
+                                                                const uint8_t *__restrict__ kept, const uint32_t *__restrict__ rate,
+                                                                j2k_t2_dev_cb *__restrict__ cbs, uint64_t *__restrict__ reset) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j == 0 && reset) { reset[0] = 0; reset[1] = 0; reset[2] = 0; }
+    if (j >= n) return;
+    const int nb = min((int)numbps[j], 31);
+    const uint32_t full = lens[j];
+    const uint64_t base = offs ? offs[j] : (uint64_t)slot_jobs[j].out_off;
+    const int zbp = mb > nb ? mb - nb : 0;
+    int first = nlayers, q = 0;
+    uint32_t rq = 0;
+    for (int l = 0; l < nlayers; l++) {                          // pass 1: the first contributing layer
+        const int p = min((int)kept[(size_t)l * n + j], nb);
+        const uint32_t rp = min(rate[j * 32 + p], full);
+        if (p > q && rp > rq) { first = l; break; }
+    }
+    for (int l = 0; l < nlayers; l++) {
+        const int p = min((int)kept[(size_t)l * n + j], nb);
+        const uint32_t rp = min(rate[j * 32 + p], full);
+        j2k_t2_dev_cb cb{};
+        cb.included_in_layers = first;
+        cb.zero_bit_planes = zbp;
+        cb.data_off = base + rq;
+        if (p > q && rp > rq) {
+            cb.num_passes = (3 * p - 2) - (q > 0 ? 3 * q - 2 : 0);
+            cb.data_len = rp - rq;
+            q = p; rq = rp;
+        }
+        cbs[(size_t)l * n + j] = cb;
+    }
+}
+hipError_t launch_t2_fill_layer_cbs(hipStream_t s, long n, int nlayers, const uint64_t *offs, const BlockJob *slot_jobs, const uint32_t *lens, const uint8_t *numbps,
+                                    int mb, const uint8_t *kept, const uint32_t *rate, j2k_t2_dev_cb *cbs, uint64_t *reset) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(t2_fill_layer_cbs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, nlayers, offs, slot_jobs, lens, numbps, mb, kept, rate, cbs, reset);
+    return hipGetLastError();
+}
+// layer_offs[i] = where the packet end_packet[i] starts in the tile-parts = the end of layer i % L of tile i / L (behind that tile's and
+// the earlier tiles' SOT | SOD heads): from the packet offsets t2_scan_kernel left
+__global__ __launch_bounds__(256) void t2_layer_ends_kernel(int count, int nlayers, const int *__restrict__ end_packet, const uint64_t *__restrict__ poffs,
+                                                            uint64_t *__restrict__ layer_offs) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < count) layer_offs[i] = poffs[end_packet[i]] + 14ull * (uint64_t)(i / nlayers + 1);
+}
+hipError_t launch_t2_layer_ends(hipStream_t s, int count, int nlayers, const int *end_packet, const uint64_t *poffs, uint64_t *layer_offs) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(t2_layer_ends_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, count, nlayers, end_packet, poffs, layer_offs);
+    return hipGetLastError();
+}
+
+static unsigned t2_body_slices() {                                 // J2K_T2_BODY_SLICES (tuning): wavefronts that share a packet's bodies
     static const unsigned n = [] { const char *e = tuning_env("J2K_T2_BODY_SLICES"); const long v = e ? atol(e) : 0; return (unsigned)(v >= 1 && v <= 64 ? v : T2_BODY_SLICES); }();
     return n;
 }

@@ -71,11 +71,15 @@ SYMBOLS = [
     "j2k_plan_encode_tile_parts_kept", "j2k_plan_decode_tile_parts_floors", "j2k_plan_encode_frame_pixels_rate", "j2k_plan_decode_frame_pixels_rate",
     "j2k_encode_pixels_host_rate", "j2k_decode_pixels_host_rate",
     "j2k_plan_encode_blocks_planes", "j2k_plan_rate_allocate", "j2k_plan_get_rate_weights", "j2k_plan_set_rate_weights",
+    "j2k_plan_rate_allocate_layers", "j2k_plan_encode_tile_parts_layers", "j2k_plan_decode_tile_parts_layers", "j2k_plan_frame_bound_layers",
+    "j2k_plan_encode_frame_pixels_layers", "j2k_plan_decode_frame_pixels_layers", "j2k_encode_pixels_host_layers", "j2k_decode_pixels_host_layers",
+    "j2k_tile_parts_keep_layers",
     "j2k_plan_pack_bound", "j2k_plan_pack_stream", "j2k_plan_unpack_stream", "j2k_plan_unpack_streams",
     "j2k_comm_load_error", "j2k_comm_get_unique_id", "j2k_comm_create", "j2k_comm_destroy", "j2k_comm_last_error", "j2k_comm_stream", "j2k_gather_streams", "j2k_comm_wait",
 ]
 CLOSED_LOOP_MALLAT = 2                               # j2k_params.closed_loop: the closed loop over a Mallat decomposition
-T2_FRESH, T2_WIDE_LEN, T2_SEATED = 1, 2, 4          # j2k_t2_dev_packet.flags (closed-loop mode)
+T2_FRESH, T2_WIDE_LEN, T2_SEATED, T2_LAYERED = 1, 2, 4, 8   # j2k_t2_dev_packet.flags (closed-loop mode)
+MAX_LAYERS = 32                                       # quality layers of one stream (J2K_MAX_LAYERS)
 PIX_GRAY8, PIX_GRAY16, PIX_RGBA8, PIX_RGBA64, PIX_NRGBA8, PIX_NRGBA64 = range(6)
 IMG_YCBCR, IMG_CMYK, IMG_PALETTED = 16, 17, 18       # j2k_image.kind (encoder.go:178-195, the default branch)
 YCBCR_444, YCBCR_422, YCBCR_420, YCBCR_440, YCBCR_411, YCBCR_410 = range(6)   # image.YCbCrSubsampleRatio
@@ -139,6 +143,15 @@ def lib():
             "j2k_plan_rate_allocate": (I, [V, V, V, V, C.c_int64, V, V]),
             "j2k_plan_get_rate_weights": (I, [V, V, S, C.POINTER(S)]),
             "j2k_plan_set_rate_weights": (I, [V, V, S]),
+            "j2k_plan_rate_allocate_layers": (I, [V, V, V, V, I64P, I, V, V]),
+            "j2k_plan_encode_tile_parts_layers": (I, [V, V, V, V, V, V, V, I, I, I, V, S, V, V]),
+            "j2k_plan_decode_tile_parts_layers": (I, [V, V, S, V, I, I, I, V, S, V, V, V, V]),
+            "j2k_plan_frame_bound_layers": (S, [V, I]),
+            "j2k_plan_encode_frame_pixels_layers": (I, [V, I, V, S, I, I, I64P, I, V, S, V, V]),
+            "j2k_plan_decode_frame_pixels_layers": (I, [V, V, S, V, I, I, I, I, I, V, S]),
+            "j2k_encode_pixels_host_layers": (I, [V, I, V, S, I, I, I64P, I, V, S, C.POINTER(S), V, V, V, V]),
+            "j2k_decode_pixels_host_layers": (I, [V, V, S, I, I, I, I, I, V, S]),
+            "j2k_tile_parts_keep_layers": (I, [V, S, V, V, I, I, I, V, S, C.POINTER(S), V]),
         }
         for name, (res, args) in sigs.items():
             if partial and not hasattr(L, name):

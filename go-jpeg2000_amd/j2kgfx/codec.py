@@ -204,6 +204,24 @@ class FramePlan:
                                                          self._p(kept), self._p(chosen)))
         return kept, chosen
 
+    def _layer_bytes(self, layer_bytes):
+        b = [int(x) for x in layer_bytes]
+        return (C.c_int64 * max(len(b), 1))(*b), len(b)
+
+    @_stage
+    def rate_allocate_layers(self, rate, dist, numbps, layer_bytes, kept=None, chosen=None):
+        """rate_allocate for L cumulative budgets in one launch: (kept uint8 [L, blocks], chosen int64 [L])  (j2k_plan_rate_allocate_layers)"""
+        t = _torch()
+        n = int(self.info.blocks)
+        arr, L = self._layer_bytes(layer_bytes)
+        kept = kept if kept is not None else self.empty(max(L, 1) * n, t.uint8)
+        chosen = chosen if chosen is not None else t.zeros(max(L, 1), dtype=t.int64, device=self.device)
+        self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_layers(self.h, self._p(rate), self._p(dist), self._p(numbps), arr, L, self._p(kept), self._p(chosen)))
+        return kept[:L * n].view(L, n), chosen[:L]
+
+    def frame_bound_layers(self, nlayers):
+        return int(self.ctx.L.j2k_plan_frame_bound_layers(self.h, int(nlayers)))
+
     def rate_weights(self):
         """float64 [ncomp, num_resolutions, 4]: the weight of every (component, resolution, band) in rate_allocate.  Default on a Mallat
         plan: the band's synthesis energy gain; on other plans 1 (their windows are not sub-bands)."""
@@ -344,10 +362,21 @@ class FramePlan:
         return int(self.ctx.L.j2k_plan_frame_bound(self.h))
 
     @_stage
-    def encode_tile_parts(self, stream, offs, lens, numbps, sop=False, eph=False, out=None, tile_offs=None, kept=None, rate=None):
+    def encode_tile_parts(self, stream, offs, lens, numbps, sop=False, eph=False, out=None, tile_offs=None, kept=None, rate=None, layers=None):
         """the block coder's outputs -> SOT | SOD | packets per tile, end to end: (out uint8, tile_offs int64[tiles + 1]).  kept + rate
-        (rate_allocate, encode_blocks(planes=True)): every block cut after its first kept[j] bit planes (j2k_plan_encode_tile_parts_kept)"""
+        (rate_allocate, encode_blocks(planes=True)): every block cut after its first kept[j] bit planes (j2k_plan_encode_tile_parts_kept).
+        layers = L with kept [L, blocks] (rate_allocate_layers): the layered stream -> (out, tile_offs, layer_offs int64 [tiles * L])
+        (j2k_plan_encode_tile_parts_layers)"""
         t = _torch()
+        if layers is not None:
+            nt, L = int(self.info.tiles), int(layers)
+            out = out if out is not None else self.empty(self.frame_bound_layers(L) or 64, t.uint8)
+            tile_offs = tile_offs if tile_offs is not None else self.empty(nt + 1, t.int64)[:nt + 1]
+            layer_offs = self.empty(nt * max(L, 1), t.int64)[:nt * max(L, 1)]
+            self.ctx.check(self.ctx.L.j2k_plan_encode_tile_parts_layers(self.h, self._p(stream), self._p(offs), self._p(lens), self._p(numbps), self._p(kept), self._p(rate),
+                                                                        L, int(bool(sop)), int(bool(eph)), self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs),
+                                                                        self._p(layer_offs)))
+            return out, tile_offs, layer_offs
         out = out if out is not None else self.empty(self.frame_bound(), t.uint8)
         tile_offs = tile_offs if tile_offs is not None else self.empty(int(self.info.tiles) + 1, t.int64)[:int(self.info.tiles) + 1]
         if kept is not None:
@@ -359,7 +388,7 @@ class FramePlan:
         return out, tile_offs
 
     @_stage
-    def decode_tile_parts(self, cs, length, tile_offs=None, sop=False, eph=False, offs=None, lens=None, numbps=None, floors=None):
+    def decode_tile_parts(self, cs, length, tile_offs=None, sop=False, eph=False, offs=None, lens=None, numbps=None, floors=None, layers=None):
         """tile-parts cs[:length] -> (offs, lens, numbps) as decode_blocks takes them (offsets into cs).  floors = True or a device uint8
         [blocks] tensor (MQ plans): also every block's floor, for streams cut at bit planes -- returns (offs, lens, numbps, floors) with
         numbps counted from each block's top plane down to bit 0 (j2k_plan_decode_tile_parts_floors)"""
@@ -368,6 +397,15 @@ class FramePlan:
         offs = offs if offs is not None else self.empty(n + 1, t.int64)
         lens = lens if lens is not None else self.empty(n, t.int32)
         numbps = numbps if numbps is not None else self.empty(n, t.uint8)
+        if layers is not None:
+            # the first `layers` layers of a layered stream: every block's segments gathered into a dense buffer -- returns (dense, offs, lens,
+            # numbps, floors), offsets into dense; decode_blocks(dense, offs, lens, numbps, floors=floors) (j2k_plan_decode_tile_parts_layers)
+            floors = self.empty(n, t.uint8) if floors is None or floors is True or floors is False else floors
+            dense = self.empty(int(length) + 64, t.uint8)
+            self.ctx.check(self.ctx.L.j2k_plan_decode_tile_parts_layers(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
+                                                                        int(bool(sop)), int(bool(eph)), int(layers), self._p(dense), C.c_size_t(int(dense.numel())),
+                                                                        self._p(offs), self._p(lens), self._p(numbps), self._p(floors)))
+            return dense, offs, lens, numbps, floors
         if floors is not None and floors is not False:
             floors = self.empty(n, t.uint8) if floors is True else floors
             self.ctx.check(self.ctx.L.j2k_plan_decode_tile_parts_floors(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
@@ -396,11 +434,24 @@ class FramePlan:
         return int(n.value)
 
     @_stage
-    def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None, max_body_bytes=None):
+    def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None, max_body_bytes=None, layer_bytes=None):
         """pixels (a Go Pix layout, device uint8 [H, stride]) -> tile-parts: (out uint8, tile_offs int64[tiles + 1]).  max_body_bytes (closed-loop
         MQ plans): at most that many bytes of code-block bodies -- packet and tile-part headers come on top, tile_offs[-1] says what the frame took
-        (j2k_plan_encode_frame_pixels_rate); decode with truncated=True"""
+        (j2k_plan_encode_frame_pixels_rate); decode with truncated=True.  layer_bytes = [B_0 <= B_1 <= ...] (the same plans; not together with
+        max_body_bytes): ONE stream of len(layer_bytes) quality layers, layer l cut as max_body_bytes = B_l would -> (out, tile_offs, layer_offs
+        int64 [tiles * L], where every layer of every tile ends) (j2k_plan_encode_frame_pixels_layers); decode with layers=k"""
         t = _torch()
+        if layer_bytes is not None:
+            if max_body_bytes is not None:
+                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "encode_frame_pixels: layer_bytes and max_body_bytes together")
+            arr, L = self._layer_bytes(layer_bytes)
+            nt = int(self.info.tiles)
+            out = out if out is not None else self.empty(self.frame_bound_layers(L) or 64, t.uint8)
+            tile_offs = tile_offs if tile_offs is not None else self.empty(nt + 1, t.int64)[:nt + 1]
+            layer_offs = self.empty(nt * max(L, 1), t.int64)[:nt * max(L, 1)]
+            self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_layers(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
+                                                                          arr, L, self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs), self._p(layer_offs)))
+            return out, tile_offs, layer_offs
         out = out if out is not None else self.empty(self.frame_bound(), t.uint8)
         tile_offs = tile_offs if tile_offs is not None else self.empty(int(self.info.tiles) + 1, t.int64)[:int(self.info.tiles) + 1]
         if max_body_bytes is not None:
@@ -412,12 +463,18 @@ class FramePlan:
         return out, tile_offs
 
     @_stage
-    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False):
+    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None):
         """tile-parts cs[:length] -> pixels into pix (device uint8 [H, stride]; reduce > 0, Mallat plans: [H_r, stride], and only the
         code-blocks of the resolutions it needs are decoded; skip_planes = k > 0, MQ plans: every block decoder stops after bit plane k;
         truncated=True, MQ plans: the stream's blocks may be cut at bit planes (encode_frame_pixels(max_body_bytes=...)) -- every block runs
         from its own top plane down to max(skip_planes, its floor) (j2k_plan_decode_frame_pixels_rate).  Without it a cut stream decodes by
-        the old rule, numbps = coded planes.)"""
+        the old rule, numbps = coded planes.)  layers = k: cs is a layered stream (encode_frame_pixels(layer_bytes=...)); the first k layers of
+        every tile-part are read, what follows them is ignored (j2k_plan_decode_frame_pixels_layers)"""
+        if layers is not None:
+            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_layers(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
+                                                                          int(bool(sop)), int(bool(eph)), int(layers), int(reduce), int(skip_planes), self._p(pix),
+                                                                          C.c_size_t(int(pix.shape[1]))))
+            return pix
         if truncated:
             self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_rate(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
                                                                         int(bool(sop)), int(bool(eph)), int(reduce), int(skip_planes), self._p(pix), C.c_size_t(int(pix.shape[1]))))
@@ -435,11 +492,28 @@ class FramePlan:
         return pix
 
     # ---- host memory in, host memory out: the one-call forms (j2k_encode_pixels_host / j2k_decode_pixels_host) -------------------
-    def encode_pixels_host(self, fmt, pix, sop=False, eph=False, cap=None, max_body_bytes=None):
+    def encode_pixels_host(self, fmt, pix, sop=False, eph=False, cap=None, max_body_bytes=None, layer_bytes=None):
         """pix: numpy uint8 [H, stride] (a Go Pix layout) -> dict(bytes, tile_offs, lens, numbps): every tile as a tile-part.  max_body_bytes: as
-        encode_frame_pixels (j2k_encode_pixels_host_rate; lens / numbps are the uncut ones)"""
+        encode_frame_pixels (j2k_encode_pixels_host_rate; lens / numbps are the uncut ones); layer_bytes: as encode_frame_pixels, the dict also
+        holds layer_offs uint64 [tiles * L] (j2k_encode_pixels_host_layers)"""
         L = self.ctx.L
         n, nt = int(self.info.blocks), int(self.info.tiles)
+        if layer_bytes is not None:
+            if max_body_bytes is not None:
+                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "encode_pixels_host: layer_bytes and max_body_bytes together")
+            arr, nl = self._layer_bytes(layer_bytes)
+            cap = int(cap) if cap is not None else (self.frame_bound_layers(nl) or 64) + 64
+            pix = np.ascontiguousarray(pix, dtype=np.uint8)
+            out = np.zeros(max(cap, 1), np.uint8)
+            toffs = np.zeros(nt + 1, np.uint64); loffs = np.zeros(max(nt * nl, 1), np.uint64)
+            lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
+            olen = C.c_size_t(0)
+            st = L.j2k_encode_pixels_host_layers(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)), arr, nl,
+                                                 out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen), toffs.ctypes.data_as(C.c_void_p),
+                                                 loffs.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p))
+            self.encoded_len = olen.value
+            self.ctx.check(st)
+            return dict(bytes=out[:olen.value].copy(), tile_offs=toffs, layer_offs=loffs[:nt * nl].copy(), lens=lens[:n].copy(), numbps=nbps[:n].copy())
         L.j2k_plan_tile_parts_bound.restype = C.c_size_t
         cap = int(cap) if cap is not None else max(self.frame_bound(), int(L.j2k_plan_tile_parts_bound(self.h))) + 64
         pix = np.ascontiguousarray(pix, dtype=np.uint8)
@@ -458,11 +532,15 @@ class FramePlan:
         self.ctx.check(st)
         return dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
 
-    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False):
+    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None):
         """closed-loop plans: tile-parts (bytes / numpy uint8) -> numpy uint8 pixels of `shape` = (H, stride); reduce > 0: (H_r, stride);
         skip_planes > 0 (MQ plans), truncated: as decode_frame_pixels"""
         cs = np.ascontiguousarray(np.frombuffer(bytes(cs), np.uint8) if not isinstance(cs, np.ndarray) else cs, dtype=np.uint8)
         pix = np.zeros(shape, np.uint8)
+        if layers is not None:                   # a layered stream, its first `layers` layers (j2k_decode_pixels_host_layers)
+            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_layers(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
+                                                                    int(layers), int(reduce), int(skip_planes), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
+            return pix
         if truncated:
             self.ctx.check(self.ctx.L.j2k_decode_pixels_host_rate(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
                                                                   int(reduce), int(skip_planes), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))

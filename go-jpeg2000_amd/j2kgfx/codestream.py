@@ -72,3 +72,23 @@ def parse_tile_parts(cs):
     parts = (TilePart * max(n.value, 1))()
     _check(L.j2k_parse_tile_parts(dp, C.c_size_t(d.size), parts, C.c_size_t(n.value), C.byref(n)), "parse_tile_parts")
     return [(parts[i], d[int(parts[i].data_off):int(parts[i].data_off + parts[i].data_len)].tobytes()) for i in range(n.value)]
+
+
+def keep_layers(cs, tile_offs, layer_offs, keep):
+    """a layered stream (FramePlan.encode_frame_pixels(layer_bytes=...)) cut to its first `keep` layers: every tile-part ends after layer
+    keep - 1, Psot patched -> (bytes, tile_offs uint64 [tiles + 1]).  tile_offs [tiles + 1] and layer_offs [tiles * L] as the encode returned
+    them.  Host only, no device (j2k_tile_parts_keep_layers); decode the result with layers=keep"""
+    d, dp = _u8(cs)
+    toffs = np.ascontiguousarray(tile_offs, dtype=np.uint64)
+    loffs = np.ascontiguousarray(layer_offs, dtype=np.uint64)
+    nt = toffs.size - 1
+    if nt < 0 or (nt and loffs.size % nt) or (nt == 0 and loffs.size):
+        raise _lib.J2KError(_lib.ERR_INVALID_ARG, "keep_layers: layer_offs holds tiles * L entries")
+    nl = loffs.size // nt if nt else 1
+    out = np.zeros(max(d.size, 1), np.uint8)
+    otoffs = np.zeros(nt + 1, np.uint64)
+    n = C.c_size_t(0)
+    _check(_lib.lib().j2k_tile_parts_keep_layers(dp, C.c_size_t(d.size), toffs.ctypes.data_as(C.c_void_p), loffs.ctypes.data_as(C.c_void_p), int(nt), int(nl),
+                                                 int(keep), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size), C.byref(n), otoffs.ctypes.data_as(C.c_void_p)),
+           "keep_layers")
+    return out[:n.value].tobytes(), otoffs

@@ -602,10 +602,14 @@ typedef struct j2k_t2_dev_cb { int32_t included_in_layers, zero_bit_planes, num_
  *                    writer's / reader's "last byte was 0xFF" flag starts clear
  *   J2K_T2_WIDE_LEN  the length-of-length field has 5 bits (the reference's 3 wrap for blocks of 128 bytes or more, t2.go:408-437)
  *   J2K_T2_SEATED    decoder only: the header is read from Position() and Position() moves past it (the reference's header
- *                    reader runs over the buffer on its own and Position() only moves over markers and bodies, t2.go:463-503) */
+ *                    reader runs over the buffer on its own and Position() only moves over markers and bodies, t2.go:463-503)
+ *   J2K_T2_LAYERED   decoder, the j2k_plan_*_layers calls only (every other call ignores it): the packet belongs to a layered stream -- the header
+ *                    of layer l > 0 carries one "contributes" bit per block, ZeroBitPlanes behind it iff the block has not contributed before,
+ *                    then the passes and the length of the layer's INCREMENT ("Quality layers" below) */
 #define J2K_T2_FRESH 1
 #define J2K_T2_WIDE_LEN 2
 #define J2K_T2_SEATED 4
+#define J2K_T2_LAYERED 8
 typedef struct j2k_t2_dev_packet { int32_t layer, incl_tree_w, imsb_tree_w, flags; int64_t cb0, ncb; } j2k_t2_dev_packet;
 int j2k_t2_encode_packets_device(j2k_ctx *ctx, const j2k_t2_dev_packet *d_packets, size_t npackets, const j2k_t2_dev_cb *d_cbs, size_t ncbs,
                                  const uint8_t *d_data, int sop, int eph, uint8_t *bio_delay, uint8_t *d_out, size_t cap,
@@ -746,7 +750,7 @@ int j2k_plan_decode_blocks_floors(j2k_plan *plan, const uint8_t *d_stream, const
  *                                    reduce as there.
  * j2k_encode_pixels_host_rate /      the synchronous host-memory forms (j2k_encode_pixels_host / j2k_decode_pixels_host_coarse); lens and
  * j2k_decode_pixels_host_rate        numbps of the encode are the UNCUT lengths and plane counts.
- * No pass-level truncation, no quality layers, no budget that includes headers. */
+ * No pass-level truncation, no budget that includes headers; quality layers: the _layers calls below. */
 int j2k_plan_encode_tile_parts_kept(j2k_plan *plan, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
                                     const uint8_t *d_numbps, const uint8_t *d_kept, const uint32_t *d_rate, int sop, int eph,
                                     uint8_t *d_out, size_t cap, uint64_t *d_tile_offs);
@@ -766,6 +770,50 @@ int j2k_plan_rate_allocate(j2k_plan *plan, const uint32_t *d_rate, const uint64_
                            int64_t max_body_bytes, uint8_t *d_kept, uint64_t *d_chosen);
 int j2k_plan_get_rate_weights(j2k_plan *plan, double *weights, size_t cap, size_t *count);
 int j2k_plan_set_rate_weights(j2k_plan *plan, const double *weights, size_t count);
+
+/* Quality layers (the library's own; the reference declares Options.NumLayers / Config.QualityLayers and only ever writes layer 0).  One encode
+ * with L cumulative budgets of code-block body bytes, layer_bytes[0] <= ... <= layer_bytes[L - 1], 1 <= L <= J2K_MAX_LAYERS, yields ONE stream:
+ * every tile-part is SOT | SOD | the tile's packet sequence once per layer, the layer outermost, so a byte prefix of every tile-part that ends at
+ * a layer's end is a lower-quality version of the frame.  Layer l's cuts are those of j2k_plan_rate_allocate for layer_bytes[l]; a block's bytes
+ * in layer l are its codeword between the cuts of layers l - 1 and l.  Format and reader rule: DESIGN.md 7; definition: tests/layer_cases.py.
+ * L = 1 is byte for byte the stream of the _rate / _kept calls.  Plans: as j2k_plan_rate_allocate (closed-loop MQ, blocks <= 64 x 64, no batch),
+ * else J2K_ERR_UNSUPPORTED; L outside 1 ... 32, a negative or a decreasing budget: J2K_ERR_INVALID_ARG.  The tables of a layer count are made at
+ * its first use and kept in the plan (capture: run the call once before).
+ *   j2k_plan_rate_allocate_layers      all L allocations in one launch: d_kept[l * blocks + j], d_chosen[l]; layer_bytes is host memory
+ *   j2k_plan_encode_tile_parts_layers  the block coder's outputs + d_kept (L x blocks) + d_rate -> layered tile-parts; d_layer_offs[t * L + l] =
+ *                                      where layer l of tile t ENDS in d_out (the last one = d_tile_offs[t + 1])
+ *   j2k_plan_decode_tile_parts_layers  reads the first `layers` layers of every tile-part (whatever follows them up to the tile-part's end is
+ *                                      ignored: the reader needs no L) and gathers every block's segments into d_dense (dense_cap bytes; the
+ *                                      stream's length always suffices): d_offs / d_lens (into d_dense) / d_numbps / d_floors as the _floors
+ *                                      calls give them -- j2k_plan_decode_blocks_floors decodes them from d_dense.  More layers than the stream
+ *                                      holds: the packet decoder's error (J2K_ERR_INVALID_ARG in j2k_plan_frame_status)
+ *   j2k_plan_frame_bound_layers        capacity that always suffices for an L-layer frame
+ *   j2k_plan_encode_frame_pixels_layers / j2k_plan_decode_frame_pixels_layers   the frame calls (decode: layers, reduce and skip_planes together)
+ *   j2k_encode_pixels_host_layers / j2k_decode_pixels_host_layers               the synchronous host-memory forms
+ *   j2k_tile_parts_keep_layers         HOST ONLY, no device: the stream cut to its first `keep` layers (Psot patched), out_tile_offs[ntiles + 1]
+ * No sub-plane truncation, no header bytes in the budgets, no HT, no conformant Part-1 packet headers, no main header that carries L. */
+#define J2K_MAX_LAYERS 32
+int j2k_plan_rate_allocate_layers(j2k_plan *plan, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps,
+                                  const int64_t *layer_bytes, int nlayers, uint8_t *d_kept, uint64_t *d_chosen);
+int j2k_plan_encode_tile_parts_layers(j2k_plan *plan, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
+                                      const uint8_t *d_numbps, const uint8_t *d_kept, const uint32_t *d_rate, int nlayers, int sop, int eph,
+                                      uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs);
+int j2k_plan_decode_tile_parts_layers(j2k_plan *plan, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                      int layers, uint8_t *d_dense, size_t dense_cap, uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps,
+                                      uint8_t *d_floors);
+size_t j2k_plan_frame_bound_layers(const j2k_plan *plan, int nlayers);
+int j2k_plan_encode_frame_pixels_layers(j2k_plan *plan, int format, const void *d_pix, size_t stride, int sop, int eph,
+                                        const int64_t *layer_bytes, int nlayers, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs,
+                                        uint64_t *d_layer_offs);
+int j2k_plan_decode_frame_pixels_layers(j2k_plan *plan, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                        int layers, int reduce, int skip_planes, void *d_pix, size_t stride);
+int j2k_encode_pixels_host_layers(j2k_plan *plan, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *layer_bytes,
+                                  int nlayers, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs,
+                                  uint32_t *lens, uint8_t *numbps);
+int j2k_decode_pixels_host_layers(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, int layers, int reduce,
+                                  int skip_planes, void *pix, size_t stride);
+int j2k_tile_parts_keep_layers(const uint8_t *cs, size_t len, const uint64_t *tile_offs, const uint64_t *layer_offs, int ntiles, int nlayers,
+                               int keep, uint8_t *out, size_t cap, size_t *out_len, uint64_t *out_tile_offs);
 
 /* The block coder's outputs as those tables.  j2k_plan_t2_packets (host table out): one packet per (tile, component,
  * resolution) of the plan in job order (encoder.go:616-673: tile, component, resolution, band, block row, block column), its
