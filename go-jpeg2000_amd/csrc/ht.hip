@@ -1466,7 +1466,7 @@ __device__ uint32_t ht_loaded_bits(const HtDecShared &S, uint32_t nff, long segL
 // caller, which has the records in registers): the LDS string is prepared only as far as it will be read.
 // STRIDED (the closed-loop frame decoder): row y of the block lies at out + y * os_ -- its window of a coefficient plane -- instead of out + y * w
 template <bool STRIDED>
-__device__ bool ht_extract_fast(HtDecShared &S, const uint8_t *__restrict__ data, long len, long scup, int w, int h,
+__device__ __forceinline__ bool ht_extract_fast(HtDecShared &S, const uint8_t *__restrict__ data, long len, long scup, int w, int h,
                                 int32_t *__restrict__ out, int lane, bool bigu, const uint32_t (&mpos2)[2], uint32_t total_bits,
                                 const uint32_t (&raw0)[4], int os_) {
     const size_t os64 = STRIDED ? (size_t)os_ : (size_t)64, osw = STRIDED ? (size_t)os_ : (size_t)w;
@@ -1685,17 +1685,13 @@ __device__ bool ht_extract_fast(HtDecShared &S, const uint8_t *__restrict__ data
 // four independent wavefronts per workgroup, one block each (no workgroup barrier anywhere on the fast path)
 // STRIDED: J.out_off / J.stride are the block's window of a coefficient plane (closed-loop plans: the windows partition the plane) and only the
 // coded rows are ever written -- the caller's planes were zeroed once (j2k_plan_decode_frame_pixels); no dense block, no placement copy
+// ht_decode_block: one block of any shape and any stream, by one wavefront (the whole of ht_decode_kernel; the cold side of ht_decode_lean_kernel)
 template <bool STRIDED>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void ht_decode_kernel(const BlockJob *__restrict__ jobs, int njobs,
-                                                        const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offs,
-                                                        const uint32_t *__restrict__ lens, int32_t *__restrict__ decoded,
-                                                        const uint32_t *__restrict__ pairs, int coded_rows_only_) {
+__device__ __forceinline__ void ht_decode_block(HtDecShared &S, const int jid, const int lane, const BlockJob *__restrict__ jobs,
+                                                const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offs,
+                                                const uint32_t *__restrict__ lens, int32_t *__restrict__ decoded,
+                                                const uint32_t *__restrict__ pairs, int coded_rows_only_) {
     const int coded_rows_only = STRIDED ? 1 : coded_rows_only_;
-    __shared__ HtDecShared S4[4];
-    HtDecShared &S = S4[threadIdx.x >> 6];
-    const int jid = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (jid >= njobs) return;
-    const int lane = threadIdx.x & 63;
 #ifdef J2K_DEC_STAMP
     const long long d0 = wall_clock64();
 #endif
@@ -1925,6 +1921,214 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     }
 }
 
+template <bool STRIDED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void ht_decode_kernel(const BlockJob *__restrict__ jobs, int njobs,
+                                                        const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offs,
+                                                        const uint32_t *__restrict__ lens, int32_t *__restrict__ decoded,
+                                                        const uint32_t *__restrict__ pairs, int coded_rows_only_) {
+    __shared__ HtDecShared S4[4];
+    const int jid = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (jid >= njobs) return;
+    ht_decode_block<STRIDED>(S4[threadIdx.x >> 6], jid, threadIdx.x & 63, jobs, stream, offs, lens, decoded, pairs, coded_rows_only_);
+}
+
+// ---- ht_decode_lean_kernel (option ht_dec_lean, the default): the same decoder with the common case written out on its own ----
+// A block is LEAN when its width is 8, 16, 32 or 64 (P = w / 8 pairs per coded row, every pair with all 8 columns; the walk took it, so it has at
+// most 1024 coded samples and N = P R <= 128 pairs), its window is 16-byte aligned, it was not refused, and no u exceeds 31.  All of that is
+// wave-uniform.  Such a block takes the code below: no width masks, pair -> (row, column) by shifts, the guard `it < N` folded into rho once,
+// one u-VLC decode per record (the first-row rule differs from the later-row rule in one case only, patched in for the first P lanes), records
+// kept in registers (no S.pair), 32-bit offsets from one base, and none of the u > 31 machinery.  Every other block -- and a lean candidate in which
+// a u above 31 turns up, before anything but zero rows has been stored -- goes through ht_decode_block at the end, which starts the block afresh.
+// (55 VGPRs: eight wavefronts per SIMD would fit, and gained 0.7 % on the headline, but cost the closed-loop HT configuration 0.6 %: KERNEL_NOTES 4w)
+template <bool STRIDED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void ht_decode_lean_kernel(const BlockJob *__restrict__ jobs, int njobs,
+                                                        const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offs,
+                                                        const uint32_t *__restrict__ lens, int32_t *__restrict__ decoded,
+                                                        const uint32_t *__restrict__ pairs, int coded_rows_only_) {
+    const int coded_rows_only = STRIDED ? 1 : coded_rows_only_;
+    __shared__ HtDecShared S4[4];
+    // the wavefront's number as a scalar: the job, its lengths and every test on them are then scalar work and scalar branches
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    HtDecShared &S = S4[wave];
+    const int jid = blockIdx.x * 4 + wave;
+    if (jid >= njobs) return;
+    const int lane = threadIdx.x & 63;
+    const BlockJob J = jobs[jid];
+    const int w = J.w, h = J.h;
+    const uint32_t os = STRIDED ? (uint32_t)J.stride : (uint32_t)w;   // row stride of the output
+    int32_t *out = decoded + J.out_off;
+    const uint32_t *rec = pairs + (size_t)jid * HT_WALK_REC;
+    const uint32_t rr[2] = {rec[lane], rec[64 + lane]};
+    const uint64_t my_off = offs[jid];
+    const uint32_t my_len = lens[jid], my_scup = rec[HT_WALK_MAX_PAIRS];
+    const uint32_t tag = (uint32_t)__builtin_amdgcn_readfirstlane((int)rr[0]);   // lane 0's (every lane is active here)
+    const bool lean = tag != HT_PAIR_ZERO && tag != HT_PAIR_SERIAL && (w == 64 || w == 32 || w == 16 || w == 8) && (((uintptr_t)out) & 15) == 0 &&
+                      (!STRIDED || (os & 3) == 0);
+    if (lean) {
+    const uint32_t psh = (uint32_t)__builtin_ctz((unsigned)w) - 3, P = 1u << psh;   // pair it = (row it >> psh, pair it & (P - 1) of the row)
+    const uint32_t R = (uint32_t)(h + 3) >> 2, N = R << psh;
+    // the first 1 KB of the MagSgn segment, then the zero rows behind it (ht_decode_block: why in this order)
+    const uint8_t *data = stream + my_off;
+    const long segLen = (long)my_len - (long)my_scup;
+    const long maxbytes = (long)HT_DEC_MWORDS * 4 - 16;
+    const uint32_t nb = (uint32_t)(segLen < maxbytes ? segLen : maxbytes);
+    const uint32_t d = (uint32_t)((uintptr_t)data & 3);        // segment byte k lives at aligned byte d + k
+    const uint32_t *wsrc = reinterpret_cast<const uint32_t *>(data - d);
+    const uint32_t ndw = (d + nb + 3) >> 2;                     // aligned dwords covering the segment
+    uint32_t raw0[4] = {0, 0, 0, 0};
+    if (ndw > 0) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const uint32_t j = 64 * c + lane;
+            raw0[c] = wsrc[j < ndw ? j : ndw - 1];
+        }
+    }
+    if (!coded_rows_only) {                                     // (dense blocks only: row stride w) quad i lies in row i / (w / 4); the coded rows are left out
+        const uint32_t nq = (uint32_t)(w * h) >> 2, qsh = psh + 1;
+        for (uint32_t i = lane; i < nq; i += 64)
+            if ((i >> qsh) & 3) st_decoded(out + 4 * i, 0, 0, 0, 0);
+    }
+    // u0 / u1 of every pair and its position in the MagSgn bit string
+    uint32_t info2[2] = {0, 0}, mpos2[2] = {0, 0}, total_bits = 0;           // info: rho | rho2 << 4 | u0 << 8 | u1 << 14, in registers (no S.pair)
+    bool bigu = false;
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+        if (64u * t >= N) break;
+        const uint32_t it = lane + 64 * t;
+        const uint32_t r = rr[t], mode = (r >> 13) & 3, vw = r >> 16;
+        // decode_uvlc_later, and for the block's first row (lanes 0..7 of round 0) decode_uvlc(.., initial): they differ only when both u-VLCs are
+        // present and the first prefix is three bits long (ht.go:756-764)
+        const uint32_t t1 = (mode & 1) ? uvlc_entry(vw) : 0u;
+        const uint32_t pl1 = t1 & 3;
+        const uint32_t v1 = vw >> pl1;
+        const uint32_t t2 = (mode & 2) ? uvlc_entry(v1) : 0u;
+        const uint32_t pl2 = t2 & 3;
+        const uint32_t v2 = v1 >> pl2;
+        const uint32_t sl1 = (t1 >> 2) & 7, sl2 = (t2 >> 2) & 7;
+        uint32_t a = (t1 >> 5) + (v2 & ((1u << sl1) - 1)) + 1;
+        uint32_t b = (t2 >> 5) + ((v2 >> sl1) & ((1u << sl2) - 1)) + 1;
+        if (t == 0) {
+            const bool first = it < P && mode == 3 && pl1 == 3;
+            a = first ? (t1 >> 5) + ((v1 >> 1) & ((1u << sl1) - 1)) + 1 : a;
+            b = first ? (v1 & 1) + 2 : b;
+        }
+        const bool live = it < N;                                // the rows of the block (a record past them says nothing)
+        if (live && (a > 31 || b > 31)) bigu = true;             // (32 as well: the extraction reads a sample's u + 1 bits from one 32-bit window)
+        const uint32_t rhos = live ? (r & 0xFF) : 0u;
+        info2[t] = rhos | a << 8 | b << 14;                       // (a, b <= 31 wherever the lean code goes on)
+        const uint32_t nbits = __popc(rhos & 0xF) * (a + 1) + __popc(rhos >> 4) * (b + 1);
+        const uint32_t ns = wave_incl_scan(nbits);
+        mpos2[t] = total_bits + ns - nbits;
+        total_bits += wave_last(ns);
+    }
+    if (!__any(bigu)) {                                          // (otherwise: ht_decode_block below; only zero rows have been stored so far)
+    // MagSgn bytes -> the LDS bit string (ht_extract_fast without its u > 32 branches)
+    {
+        const uint32_t zw = min((uint32_t)HT_DEC_MWORDS, ((nb * 8) >> 5) + 3u);
+        for (uint32_t i = lane; i < zw; i += 64) S.mbuf[i] = 0;    // deposits reach 8 x (bytes staged) bits
+    }
+    wave_sync();
+    constexpr int PF = 4;
+    uint32_t off = 0, carry = 0;
+    for (uint32_t j0 = 0; j0 < ndw; j0 += 64 * PF) {
+        uint32_t raw[PF];
+#pragma unroll
+        for (int c = 0; c < PF; c++) {
+            const uint32_t j = j0 + 64 * c + lane;
+            if (j0 == 0) raw[c] = raw0[c];
+            else raw[c] = wsrc[j < ndw ? j : ndw - 1];
+        }
+#pragma unroll
+        for (int c = 0; c < PF; c++) {
+            if (j0 + 64 * c >= ndw) break;
+            const uint32_t j = j0 + 64 * c + lane;
+            const uint32_t dw = raw[c];
+            uint32_t prev3 = __shfl_up(dw >> 24, 1);
+            if (lane == 0) prev3 = carry;
+            carry = __shfl(dw >> 24, 63);
+            const int k0 = (int)(4 * j) - (int)d;                // segment index of this dword's byte 0
+            uint32_t wd[4], tot = 0;
+            bool plain = (j < ndw) && k0 >= 1 && k0 + 4 <= (int)nb && prev3 != 0xFF;
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int k = k0 + t;
+                const uint32_t pb = t ? ((dw >> (8 * (t - 1))) & 0xFF) : prev3;
+                const bool valid = (j < ndw) && k >= 0 && k < (int)nb;
+                wd[t] = valid ? ((k > 0 && pb == 0xFF) ? 7u : 8u) : 0u;
+                if (t && pb == 0xFF) plain = false;
+                tot += wd[t];
+            }
+            const uint32_t ws = wave_incl_scan(tot);
+            uint32_t pos = off + ws - tot;
+            if (plain) {
+                if (dw) or_bits(S.mbuf, pos, (uint64_t)dw);
+            } else {
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const uint32_t bt = (dw >> (8 * t)) & 0xFF;
+                    if (wd[t] && bt) or_bits(S.mbuf, pos, (uint64_t)bt);
+                    pos += wd[t];
+                }
+            }
+            off += wave_last(ws);
+        }
+    }
+    wave_sync();
+    if ((long)nb == segLen) {   // everything past the segment reads as ones, as far as it is read
+        const uint32_t wd0 = off >> 5;
+        const uint32_t wend = min((uint32_t)HT_DEC_MWORDS, (total_bits >> 5) + 3u);
+        for (uint32_t i = wd0 + lane; i < wend; i += 64)
+            S.mbuf[i] = (i == wd0) ? (S.mbuf[i] | (0xFFFFFFFFu << (off & 31))) : 0xFFFFFFFFu;
+    }
+    wave_sync();
+    // samples: lane = (row of this round, pair), 8 samples each; then four whole rows per store instruction (ht_extract_fast: why)
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+        if (64u * t >= N) break;
+        uint32_t mpos = mpos2[t];
+        int vals[8];
+        const uint32_t info = info2[t], u0 = (info >> 8) & 0x3F, u1 = (info >> 14) & 0x3F;
+        const uint32_t half0 = 1u << (u0 - 1), half1 = 1u << (u1 - 1);
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const uint32_t emb = (i < 4) ? u0 : u1;
+            const bool on = (info >> i) & 1;
+            const uint32_t wd = mpos >> 5;
+            const uint32_t win = __builtin_amdgcn_alignbit(S.mbuf[wd + 1], S.mbuf[wd], mpos & 31);
+            const uint32_t mag = __builtin_amdgcn_ubfe(win, 0, emb) + ((i < 4) ? half0 : half1);
+            const uint32_t sg = 0u - ((win >> emb) & 1);
+            vals[i] = on ? (int32_t)((mag ^ sg) - sg) : 0;
+            mpos += on ? emb + 1 : 0u;
+        }
+        if (w != 64) {                                                     // narrow blocks: the pair's 32 bytes as they lie
+            const uint32_t it = lane + 64 * t;
+            int32_t *orow = out + (4 * (it >> psh) * os + 8 * (it & (P - 1)));
+            if (it < N) {
+                st_decoded(orow, vals[0], vals[1], vals[2], vals[3]);
+                st_decoded(orow + 4, vals[4], vals[5], vals[6], vals[7]);
+            }
+            continue;
+        }
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+            const uint32_t drow = half * 4 + (lane >> 4), q = lane & 15;   // the row of this round / 16-byte piece I store
+            const int src = (int)(drow * 8 + (q >> 1));                    // the lane that decoded it
+            int o[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int a = __shfl(vals[i], src), b = __shfl(vals[4 + i], src);
+                o[i] = (q & 1) ? b : a;
+            }
+            const uint32_t rg = 8 * t + drow;                              // coded row index in the block
+            if (rg < R) st_decoded(out + (4 * rg * os + 4 * q), o[0], o[1], o[2], o[3]);
+        }
+    }
+    return;
+    }   // no u above 31
+    }   // lean
+    ht_decode_block<STRIDED>(S, jid, lane, jobs, stream, offs, lens, decoded, pairs, coded_rows_only_);
+}
+
 // ---------------------------------------------------------------------------------
 static bool g_tables_ready[16] = {false};
 
@@ -1977,7 +2181,7 @@ size_t ht_decode_scratch_words(int njobs) { return (size_t)njobs * (HT_WALK_REC 
 
 // placed_jobs != NULL: the blocks are written straight into their windows of the coefficient planes `decoded` (ht_decode_kernel<true>)
 hipError_t launch_ht_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
-                            const uint32_t *lens, int32_t *decoded, uint32_t *scratch, int coded_rows_only, const BlockJob *placed_jobs) {
+                            const uint32_t *lens, int32_t *decoded, uint32_t *scratch, int coded_rows_only, const BlockJob *placed_jobs, int lean) {
     if (njobs <= 0) return hipSuccess;
     hipError_t e;
     if ((e = ht_tables_ready(s)) != hipSuccess) return e;
@@ -1989,9 +2193,9 @@ hipError_t launch_ht_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
     hipLaunchKernelGGL(ht_walk_kernel, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(256), sizeof(HtWalkShared), s, jobs, njobs, vbits, pairs);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     for (int rep_ = 0; rep_ < dev_reps(128); rep_++)
-    if (placed_jobs) hipLaunchKernelGGL(ht_decode_kernel<true>, dim3((njobs + 3) / 4), dim3(256), 0, s, placed_jobs, njobs, stream, offs, lens, decoded, pairs, 1);
+    if (placed_jobs) hipLaunchKernelGGL(lean ? ht_decode_lean_kernel<true> : ht_decode_kernel<true>, dim3((njobs + 3) / 4), dim3(256), 0, s, placed_jobs, njobs, stream, offs, lens, decoded, pairs, 1);
     else
-    hipLaunchKernelGGL(ht_decode_kernel<false>, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, decoded, pairs, coded_rows_only);
+    hipLaunchKernelGGL(lean ? ht_decode_lean_kernel<false> : ht_decode_kernel<false>, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, decoded, pairs, coded_rows_only);
     return hipGetLastError();
 }
 
