@@ -1129,10 +1129,17 @@ __device__ bool init_mel_ok(const uint8_t *data, long len, long lcup, long scup)
     int unstuff = 0;
     long num = 4 - (pos & 3);
     if (num > 4) num = 4;
-    for (long i = 0; i < num && size > 0; i++) {
-        if (unstuff && pos < len && data[pos] > 0x8F) return false;
+    // the (at most four) bytes the loop looks at, requested together: one round trip, not one per byte
+    uint32_t d[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) d[i] = (i < num && i < size && pos + i < len) ? data[pos + i] : 0xFFu;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if (!(i < num && size > 0)) break;
+        const bool in = pos < len;
+        if (unstuff && in && d[i] > 0x8F) return false;
         uint32_t b;
-        if (size > 0 && pos < len) { b = data[pos]; pos++; size--; } else b = 0xFF;
+        if (in) { b = d[i]; pos++; size--; } else b = 0xFF;
         if (size == 1) b |= 0x0F;
         unstuff = (b == 0xFF);
     }
@@ -1193,6 +1200,130 @@ __device__ __forceinline__ uint32_t get_bits32_cut(const uint32_t *buf, uint32_t
 // each 8 bits wide, or 7 when the previous byte is > 0x8F and this one's low 7 bits are all ones (the byte itself
 // is OR-ed in whole at the shorter advance); after scup-2 bytes, zeros.  Byte widths depend only on the neighbour
 // byte, so all bytes are placed in parallel: prefix sum of widths, OR-deposit into LDS, coalesced copy to global.
+// The pieces below are shared by ht_vlcprep_kernel (one block per wavefront, the string copied out to global) and
+// ht_front_kernel (several blocks per wavefront, the string deposited where the walk reads it).
+struct HtVlcHead {
+    const uint8_t *data;
+    uint32_t len, scup, tag;      // tag: 0, HT_PAIR_SERIAL or HT_PAIR_ZERO; scup: 0 with a tag
+    uint32_t b0;                  // data[len - 2], the byte the VLC reader starts in (0 with a tag)
+    int N;
+};
+
+// what the prep decides about block jid before it touches a VLC byte; per thread, from the block's own inputs only
+__device__ __forceinline__ HtVlcHead ht_vlc_head(const BlockJob *__restrict__ jobs, int jid, const uint8_t *__restrict__ stream,
+                                                 const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens) {
+    const int w = jobs[jid].w, h = jobs[jid].h;
+    const long len = (long)lens[jid];
+    const uint8_t *data = stream + offs[jid];
+    const int quadCols = (w + 3) / 4, P = (quadCols + 1) / 2, R = (h + 3) / 4, N = R * P;
+    const bool fast = (size_t)R * (size_t)w <= HT_FAST_MAX_SAMPLES && N <= HT_WALK_MAX_PAIRS;
+    uint32_t tag = 0, b0 = 0;
+    long scup = 0;
+    if (!fast) tag = HT_PAIR_SERIAL;
+    else if (len < 2) tag = HT_PAIR_ZERO;                            // ht.go:94-100
+    else {
+        b0 = data[len - 2];
+        scup = (long)data[len - 1] + ((long)(b0 & 0x0F) << 8);
+        if (scup < 2 || scup > len) tag = HT_PAIR_ZERO;              // ht.go:104-111
+        else if (!init_mel_ok(data, len, len, scup)) tag = HT_PAIR_ZERO;   // ht.go:117-122
+    }
+    return HtVlcHead{data, (uint32_t)len, tag ? 0u : (uint32_t)scup, tag, tag ? 0u : b0, N};
+}
+
+// reverse-reader bytes the block's string takes: the VLC segment, cut where 128 pairs cannot reach (at most 744)
+__device__ __forceinline__ long ht_vlc_nbytes(const HtVlcHead &H) {
+    const long size = (long)H.scup - 2;
+    const long maxbytes = (long)(46 * H.N + 7) / 8 + 8;
+    return size < maxbytes ? size : maxbytes;
+}
+#define HT_VLC_STEPS 3                         /* 256-byte steps that cover ht_vlc_nbytes */
+
+// Four stream bytes per lane per step: reverse-reader bytes k = 256c + 4l + 1 .. + 4 are the four bytes ENDING at
+// data[lcup - 3 - 256c - 4l]; one (unaligned) 4-byte load, byte-swapped so that byte j is the j-th in reading order.
+// In two halves, so that a caller can request the bytes of many steps and blocks before it looks at the first:
+// ht_vlc_load4 only loads -- no branch on the lane, nothing that waits for the data (nb >= 4; the few blocks with a shorter
+// segment read it byte by byte, there and then) -- and ht_vlc_bytes makes the four bytes of it.  A group the segment ends
+// in, or lies beyond, loads the segment's FIRST four bytes instead (still this block's own VLC bytes): the s = k + 3 - nb
+// bytes too many are shifted out, a group beyond the segment is zero.
+__device__ __forceinline__ uint32_t ht_vlc_load4(const uint8_t *data, long lcup, long nb, long k) {
+    const long e = lcup - 2 - k;                                     // address of byte k; the other three sit below it
+    uint32_t dw = 0;
+    if (nb >= 4) {
+        const long lo = lcup - 2 - nb;                               // the segment's first byte
+        __builtin_memcpy(&dw, data + (e - 3 > lo ? e - 3 : lo), 4);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (k + j <= nb) dw |= (uint32_t)data[e - j] << (8 * j);
+    }
+    return dw;
+}
+__device__ __forceinline__ uint32_t ht_vlc_bytes(uint32_t dw, long nb, long k) {
+    if (nb < 4) return dw;
+    if (k > nb) return 0;
+    const long s = k + 3 > nb ? k + 3 - nb : 0;
+    return __builtin_bswap32(dw) >> (8 * s);
+}
+
+// A byte's width (7 or 8) needs only its predecessor; one prefix sum of the per-lane totals, one OR-deposit of the
+// four bytes merged at their offsets (a 7-bit advance lets the next byte overlap the top bit: OR, as revRead does).
+__device__ __forceinline__ void ht_vlc_step(uint32_t *vb, long nb, long k, int lane, uint32_t dw, uint32_t &carry, uint32_t &off) {
+    uint32_t prev = __shfl_up(dw >> 24, 1);
+    if (lane == 0) prev = carry;
+    carry = __shfl(dw >> 24, 63);                                    // only read again when all 256 bytes of this step exist
+    uint32_t wsum = 0;
+    uint64_t merged = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t bj = (dw >> (8 * j)) & 0xFF;
+        const uint32_t wj = (k + j <= nb) ? ((prev > 0x8F && (bj & 0x7F) == 0x7F) ? 7u : 8u) : 0u;
+        merged |= (uint64_t)bj << wsum;
+        wsum += wj;
+        prev = bj;
+    }
+    const uint32_t ws = wave_incl_scan(wsum);
+    if (merged) or_bits(vb, off + ws - wsum, merged);
+    off += wave_last(ws);
+}
+
+// One block by one wavefront (H wave-uniform): the record flags, and for a block without a tag its bit string in
+// vb[0 .. HT_VBITS_WORDS + 8) (LDS; the deposit's last words land in the slack).  The caller has requested the bytes of
+// every step (pre[c] = ht_vlc_load4 of step c, lane's k = 256c + 4 lane + 1): no step waits for a round trip of its own.
+__device__ __forceinline__ void ht_vlc_unstuff(const HtVlcHead &H, int lane, uint32_t *vb, uint32_t *rec, const uint32_t *pre) {
+    if (H.tag) {                                                     // wave-uniform
+        if (lane == 0) { rec[0] = H.tag; rec[HT_WALK_MAX_PAIRS] = 0; }
+        return;
+    }
+    for (int i = lane; i < HT_VBITS_WORDS + 8; i += 64) vb[i] = 0;
+    wave_sync();
+    const uint32_t b0 = H.b0;
+    const uint32_t t0 = b0 >> 4;
+    uint32_t off = 4 - ((t0 & 7) >> 2);
+    if (lane == 0) atomicOr(&vb[0], t0);
+    const long nb = ht_vlc_nbytes(H);
+    uint32_t carry = b0 | 0x0F;                                      // "previous byte" of k = 1
+#pragma unroll
+    for (int c = 0; c < HT_VLC_STEPS; c++) {
+        const long k = 1 + 256 * c + 4 * lane;                       // first of this lane's four bytes
+        if (1 + 256 * c <= nb) ht_vlc_step(vb, nb, k, lane, ht_vlc_bytes(pre[c], nb, k), carry, off);
+    }
+    wave_sync();
+    if (lane == 0) { rec[0] = 0; rec[HT_WALK_MAX_PAIRS] = H.scup; }   // not a tag; SCUP travels in the flag word
+}
+
+// block jid, start to end, by one wavefront; returns its tag
+__device__ __forceinline__ uint32_t ht_vlcprep_block(const BlockJob *__restrict__ jobs, int jid, const uint8_t *__restrict__ stream,
+                                                     const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens, int lane,
+                                                     uint32_t *vb, uint32_t *rec) {
+    const HtVlcHead H = ht_vlc_head(jobs, jid, stream, offs, lens);
+    const long nb = H.tag ? 0 : ht_vlc_nbytes(H);
+    uint32_t pre[HT_VLC_STEPS];
+#pragma unroll
+    for (int c = 0; c < HT_VLC_STEPS; c++) pre[c] = ht_vlc_load4(H.data, (long)H.len, nb, 1 + 256 * c + 4 * lane);
+    ht_vlc_unstuff(H, lane, vb, rec, pre);
+    return H.tag;
+}
+
 __global__ __launch_bounds__(256) void ht_vlcprep_kernel(const BlockJob *__restrict__ jobs, int njobs,
                                                          const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offs,
                                                          const uint32_t *__restrict__ lens, uint32_t *__restrict__ vbits,
@@ -1202,73 +1333,9 @@ __global__ __launch_bounds__(256) void ht_vlcprep_kernel(const BlockJob *__restr
     const int jid = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (jid >= njobs) return;
     const int lane = threadIdx.x & 63;
-    const int w = jobs[jid].w, h = jobs[jid].h;
-    const long len = (long)lens[jid];
-    const uint8_t *data = stream + offs[jid];
-    uint32_t *rec = pairs + (size_t)jid * HT_WALK_REC;
-    const int quadCols = (w + 3) / 4, P = (quadCols + 1) / 2, R = (h + 3) / 4, N = R * P;
-    const bool fast = (size_t)R * (size_t)w <= HT_FAST_MAX_SAMPLES && N <= HT_WALK_MAX_PAIRS;
-    uint32_t tag = 0;
-    long scup = 0;
-    if (!fast) tag = HT_PAIR_SERIAL;
-    else if (len < 2) tag = HT_PAIR_ZERO;                            // ht.go:94-100
-    else {
-        scup = (long)data[len - 1] + ((long)(data[len - 2] & 0x0F) << 8);
-        if (scup < 2 || scup > len) tag = HT_PAIR_ZERO;              // ht.go:104-111
-        else if (!init_mel_ok(data, len, len, scup)) tag = HT_PAIR_ZERO;   // ht.go:117-122
-    }
-    if (tag) {                                                       // wave-uniform
-        if (lane == 0) { rec[0] = tag; rec[HT_WALK_MAX_PAIRS] = 0; }
-        return;
-    }
-    for (int i = lane; i < HT_VBITS_WORDS + 8; i += 64) vb[i] = 0;
-    wave_sync();
-    const long lcup = len;
-    const uint32_t b0 = data[lcup - 2];
-    const uint32_t t0 = b0 >> 4;
-    uint32_t off = 4 - ((t0 & 7) >> 2);
-    if (lane == 0) atomicOr(&vb[0], t0);
-    const long size = scup - 2;
-    const long maxbytes = (long)(46 * N + 7) / 8 + 8;
-    const long nb = size < maxbytes ? size : maxbytes;
-    // Four stream bytes per lane per step: reverse-reader bytes k = 256c + 4l + 1 .. + 4 are the four bytes ENDING at
-    // data[lcup - 3 - 256c - 4l]; one (unaligned) 4-byte load, byte-swapped so that byte j is the j-th in reading order.
-    // A byte's width (7 or 8) needs only its predecessor; one prefix sum of the per-lane totals, one OR-deposit of the
-    // four bytes merged at their offsets (a 7-bit advance lets the next byte overlap the top bit: OR, as revRead does).
-    uint32_t carry = b0 | 0x0F;                                      // "previous byte" of k = 1
-    for (long k0 = 1; k0 <= nb; k0 += 256) {
-        const long k = k0 + 4 * lane;                                // first of this lane's four bytes
-        const long e = lcup - 2 - k;                                 // its address; the other three sit below it
-        uint32_t dw = 0;
-        if (k + 3 <= nb) {
-            __builtin_memcpy(&dw, data + e - 3, 4);
-            dw = __builtin_bswap32(dw);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (k + j <= nb) dw |= (uint32_t)data[e - j] << (8 * j);
-        }
-        uint32_t prev = __shfl_up(dw >> 24, 1);
-        if (lane == 0) prev = carry;
-        carry = __shfl(dw >> 24, 63);                                // only read again when all 256 bytes of this step exist
-        uint32_t wsum = 0;
-        uint64_t merged = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint32_t bj = (dw >> (8 * j)) & 0xFF;
-            const uint32_t wj = (k + j <= nb) ? ((prev > 0x8F && (bj & 0x7F) == 0x7F) ? 7u : 8u) : 0u;
-            merged |= (uint64_t)bj << wsum;
-            wsum += wj;
-            prev = bj;
-        }
-        const uint32_t ws = wave_incl_scan(wsum);
-        if (merged) or_bits(vb, off + ws - wsum, merged);
-        off += wave_last(ws);
-    }
-    wave_sync();
+    if (ht_vlcprep_block(jobs, jid, stream, offs, lens, lane, vb, pairs + (size_t)jid * HT_WALK_REC)) return;
     uint32_t *dst = vbits + (size_t)jid * HT_VBITS_WORDS;
     for (int i = lane; i < HT_VBITS_WORDS; i += 64) dst[i] = vb[i];
-    if (lane == 0) { rec[0] = 0; rec[HT_WALK_MAX_PAIRS] = (uint32_t)scup; }   // not a tag; SCUP travels in the flag word
 }
 
 #ifndef HT_WALK_BLOCKS
@@ -1296,6 +1363,78 @@ __device__ __forceinline__ uint32_t uvlc_used_later(uint32_t vlc, uint32_t uOff1
 // record store:  rho | rho2 << 4 | (uOff1 << 1 | uOff2) << 13 | (the 16 stream bits at the u-VLC) << 16  (bits 8..12: scratch).
 // The first row (other table, other u-VLC rule) and code words with a length nibble above 7 use two lookups.
 // A pair consumes at most 46 bits and HT_VBITS_WORDS covers 128 of them plus the read-ahead, so no clamping.
+//
+// The walk of one workgroup's blocks by its wavefront 0, all 64 lanes active on entry: lane l walks the string at `row` and writes the
+// block's records to `rec`.  Shared by ht_walk_kernel and ht_front_kernel.  Returns the bits the lane consumed.
+__device__ __forceinline__ uint32_t ht_walk_lane(const uint32_t *row, const uint16_t *tbl0, const uint16_t *tbl1, const uint16_t *pair1,
+                                                 uint32_t *rec, int w, int h, bool have, uint32_t tag) {
+    const int quadCols = (w + 3) / 4, P = (quadCols + 1) / 2, R = (h + 3) / 4;
+    // the walking wavefront's trip count: the largest pair count among its blocks -- reduced while all 64 lanes are still
+    // active (a butterfly over a wave with holes leaves different partial maxima in different lanes: taken after the early
+    // returns below it cut some blocks' walks short, found by tools/fuzz_gpu.py on a frame of mixed block sizes)
+    const bool walks = have && tag != HT_PAIR_SERIAL && tag != HT_PAIR_ZERO;
+    int nsteps = walks ? R * P : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nsteps = max(nsteps, __shfl_xor(nsteps, o));
+    nsteps = min(__builtin_amdgcn_readfirstlane(nsteps), HT_WALK_MAX_PAIRS);
+    if (!walks) return 0;
+    uint32_t pos = 0;
+#define HT_FETCH(w0, w1)                                                          \
+    uint32_t w0, w1;                                                               \
+    {                                                                              \
+        const uint32_t *p_ = row + (pos >> 5);                                     \
+        const uint32_t d0_ = p_[0], d1_ = p_[1], d2_ = p_[2];                      \
+        w0 = __builtin_amdgcn_alignbit(d1_, d0_, pos & 31);                        \
+        w1 = __builtin_amdgcn_alignbit(d2_, d1_, pos & 31);                        \
+    }
+    // ---- first row: tbl0, general u-VLC ----
+    for (int pi = 0; pi < P; pi++) {
+        HT_FETCH(w0, w1)
+        const uint32_t qinf = tbl0[w0 & 0x7F];                    // first quad: context is always 0
+        const uint32_t rho = (qinf >> 4) & 0xF, uOff1 = (qinf >> 3) & 1, len1 = qinf & 0xF;
+        const uint32_t qinf2 = tbl0[((rho >> 2) << 7) | ((w0 >> len1) & 0x7F)];
+        const uint32_t rho2 = (qinf2 >> 4) & 0xF, uOff2 = (qinf2 >> 3) & 1, len = len1 + (qinf2 & 0xF);
+        const uint32_t vw = __builtin_amdgcn_alignbit(w1, w0, len);  // len <= 30
+        const uint32_t mode = (uOff1 << 1) | uOff2;
+        uint32_t u[2];
+        const uint32_t used = decode_uvlc(vw, mode, u, 1);
+        pos += len + used;
+        rec[pi] = rho | rho2 << 4 | mode << 13 | vw << 16;           // (the later rows' layout; bits 8..12 are not read)
+    }
+    // ---- later rows ----
+    // A lone wavefront retires about one instruction per 8-9 cycles whatever their dependencies (measured here and on the MQ
+    // coder), so what a step costs is its instruction COUNT plus the one LDS round trip of the table look-up: the loop is
+    // kept to the instructions the next position needs.  The u-VLC's length comes from two nibble tables in 32-bit
+    // constants (prefix lengths 3,1,2,1,3,1,2,1 and totals 8,1,2,1,4,1,2,1 for the three prefix bits), the record is the
+    // table entry as it is (rho | rho2 << 4 | len << 8 | uOff2 << 13 | uOff1 << 14) with the 16 stream bits at the u-VLC on
+    // top, and the trip count is the wavefront's maximum (scalar loop control): a lane whose block has fewer pairs walks on
+    // through its zero-padded row and writes records nobody reads (every block owns HT_WALK_MAX_PAIRS record words).
+    // (Tried: the stream words prefetched a step ahead into registers -- the selects cost what the round trip saves.)
+    {
+        for (int it = P; it < nsteps; it++) {
+            HT_FETCH(w0, w1)
+            uint32_t e = pair1[w0 & 0x3FFF];
+            if (e & 0x8000) {                                            // rare: length nibble > 7
+                const uint32_t qinf = tbl1[w0 & 0x7F];
+                const uint32_t rho = (qinf >> 4) & 0xF, len1 = qinf & 0xF;
+                const uint32_t qinf2 = tbl1[((rho >> 2) << 7) | ((w0 >> len1) & 0x7F)];
+                e = rho | (qinf2 & 0xF0) | (len1 + (qinf2 & 0xF)) << 8 | ((qinf2 >> 3) & 1) << 13 | ((qinf >> 3) & 1) << 14;
+            }
+            const uint32_t len = (e >> 8) & 0x1F;
+            const uint32_t vw = __builtin_amdgcn_alignbit(w1, w0, len);
+            // u-VLC length (see decode_uvlc_later): the first prefix is read iff uOff2 (bit 13), the second iff uOff1 (bit 14)
+            const uint32_t m1 = (uint32_t)((int32_t)(e << 18) >> 31), m2 = (uint32_t)((int32_t)(e << 17) >> 31);
+            const uint32_t pl1 = (0x12131213u >> ((vw & 7) << 2)) & 3 & m1;
+            const uint32_t t1 = (0x12141218u >> ((vw & 7) << 2)) & 0xF & m1;
+            const uint32_t t2 = (0x12141218u >> (((vw >> pl1) & 7) << 2)) & 0xF & m2;
+            pos += len + t1 + t2;
+            rec[it] = (e & 0x7FFF) | vw << 16;
+        }
+    }
+#undef HT_FETCH
+    return pos;
+}
+
 __global__ __launch_bounds__(256) void ht_walk_kernel(const BlockJob *__restrict__ jobs, int njobs,
                                                      const uint32_t *__restrict__ vbits, uint32_t *__restrict__ pairs) {
     extern __shared__ __align__(16) unsigned char walk_smem[];
@@ -1343,76 +1482,112 @@ __global__ __launch_bounds__(256) void ht_walk_kernel(const BlockJob *__restrict
     const long long st1 = __builtin_amdgcn_s_memtime();
 #endif
     if (tid >= 64) return;
-    const int quadCols = (w + 3) / 4, P = (quadCols + 1) / 2, R = (h + 3) / 4;
-    // the walking wavefront's trip count: the largest pair count among its blocks -- reduced while all 64 lanes are still
-    // active (a butterfly over a wave with holes leaves different partial maxima in different lanes: taken after the early
-    // returns below it cut some blocks' walks short, found by tools/fuzz_gpu.py on a frame of mixed block sizes)
-    const bool walks = have && tag != HT_PAIR_SERIAL && tag != HT_PAIR_ZERO;
-    int nsteps = walks ? R * P : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nsteps = max(nsteps, __shfl_xor(nsteps, o));
-    nsteps = min(__builtin_amdgcn_readfirstlane(nsteps), HT_WALK_MAX_PAIRS);
-    if (!walks) return;
-    const uint32_t *row = &S.vb[lane][0];
-    uint32_t pos = 0;
-#define HT_FETCH(w0, w1)                                                          \
-    uint32_t w0, w1;                                                               \
-    {                                                                              \
-        const uint32_t *p_ = row + (pos >> 5);                                     \
-        const uint32_t d0_ = p_[0], d1_ = p_[1], d2_ = p_[2];                      \
-        w0 = __builtin_amdgcn_alignbit(d1_, d0_, pos & 31);                        \
-        w1 = __builtin_amdgcn_alignbit(d2_, d1_, pos & 31);                        \
-    }
-    // ---- first row: tbl0, general u-VLC ----
-    for (int pi = 0; pi < P; pi++) {
-        HT_FETCH(w0, w1)
-        const uint32_t qinf = S.tbl0[w0 & 0x7F];                    // first quad: context is always 0
-        const uint32_t rho = (qinf >> 4) & 0xF, uOff1 = (qinf >> 3) & 1, len1 = qinf & 0xF;
-        const uint32_t qinf2 = S.tbl0[((rho >> 2) << 7) | ((w0 >> len1) & 0x7F)];
-        const uint32_t rho2 = (qinf2 >> 4) & 0xF, uOff2 = (qinf2 >> 3) & 1, len = len1 + (qinf2 & 0xF);
-        const uint32_t vw = __builtin_amdgcn_alignbit(w1, w0, len);  // len <= 30
-        const uint32_t mode = (uOff1 << 1) | uOff2;
-        uint32_t u[2];
-        const uint32_t used = decode_uvlc(vw, mode, u, 1);
-        pos += len + used;
-        rec[pi] = rho | rho2 << 4 | mode << 13 | vw << 16;           // (the later rows' layout; bits 8..12 are not read)
-    }
-    // ---- later rows ----
-    // A lone wavefront retires about one instruction per 8-9 cycles whatever their dependencies (measured here and on the MQ
-    // coder), so what a step costs is its instruction COUNT plus the one LDS round trip of the table look-up: the loop is
-    // kept to the instructions the next position needs.  The u-VLC's length comes from two nibble tables in 32-bit
-    // constants (prefix lengths 3,1,2,1,3,1,2,1 and totals 8,1,2,1,4,1,2,1 for the three prefix bits), the record is the
-    // table entry as it is (rho | rho2 << 4 | len << 8 | uOff2 << 13 | uOff1 << 14) with the 16 stream bits at the u-VLC on
-    // top, and the trip count is the wavefront's maximum (scalar loop control): a lane whose block has fewer pairs walks on
-    // through its zero-padded row and writes records nobody reads (every block owns HT_WALK_MAX_PAIRS record words).
-    // (Tried: the stream words prefetched a step ahead into registers -- the selects cost what the round trip saves.)
-    {
-        for (int it = P; it < nsteps; it++) {
-            HT_FETCH(w0, w1)
-            uint32_t e = S.pair1[w0 & 0x3FFF];
-            if (e & 0x8000) {                                            // rare: length nibble > 7
-                const uint32_t qinf = S.tbl1[w0 & 0x7F];
-                const uint32_t rho = (qinf >> 4) & 0xF, len1 = qinf & 0xF;
-                const uint32_t qinf2 = S.tbl1[((rho >> 2) << 7) | ((w0 >> len1) & 0x7F)];
-                e = rho | (qinf2 & 0xF0) | (len1 + (qinf2 & 0xF)) << 8 | ((qinf2 >> 3) & 1) << 13 | ((qinf >> 3) & 1) << 14;
-            }
-            const uint32_t len = (e >> 8) & 0x1F;
-            const uint32_t vw = __builtin_amdgcn_alignbit(w1, w0, len);
-            // u-VLC length (see decode_uvlc_later): the first prefix is read iff uOff2 (bit 13), the second iff uOff1 (bit 14)
-            const uint32_t m1 = (uint32_t)((int32_t)(e << 18) >> 31), m2 = (uint32_t)((int32_t)(e << 17) >> 31);
-            const uint32_t pl1 = (0x12131213u >> ((vw & 7) << 2)) & 3 & m1;
-            const uint32_t t1 = (0x12141218u >> ((vw & 7) << 2)) & 0xF & m1;
-            const uint32_t t2 = (0x12141218u >> (((vw >> pl1) & 7) << 2)) & 0xF & m2;
-            pos += len + t1 + t2;
-            rec[it] = (e & 0x7FFF) | vw << 16;
-        }
-    }
-#undef HT_FETCH
+    const uint32_t pos = ht_walk_lane(&S.vb[lane][0], S.tbl0, S.tbl1, S.pair1, rec, w, h, have, tag);
+    (void)pos;
 #ifdef J2K_WALK_STAMP
     const long long st2 = __builtin_amdgcn_s_memtime();
     if ((blockIdx.x == 0 || blockIdx.x == 50) && lane == 0)
-        printf("walk wg %d: staging %lld cyc, loop %lld cyc (%d pairs, %d bits)\n", (int)blockIdx.x, st1 - st0, st2 - st1, R * P, (int)pos);
+        printf("walk wg %d: staging %lld cyc, loop %lld cyc (%d x %d, %d bits)\n", (int)blockIdx.x, st1 - st0, st2 - st1, w, h, (int)pos);
 #endif
+}
+
+// ---- kernels 1 + 2 in one launch (option ht_dec_front = 1): the workgroup unstuffs the strings its own wavefront 0 then walks ----
+// A walk workgroup needs the strings of its own HT_WALK_BLOCKS blocks and nobody else's, so the prep needs no device-wide launch
+// boundary: NW wavefronts prep HT_WALK_BLOCKS / NW blocks each straight into the rows of the walk's LDS (nothing goes to the
+// global vbits scratch), the first four also stage the tables as ht_walk_kernel does, one barrier, wavefront 0 walks.
+// A wavefront's blocks are prepped together, not one after the other: lane b validates block b (ht_vlc_head: job, length, offset,
+// the two tail bytes, the MEL start -- one chain of round trips for all of them), the verdicts are broadcast, the VLC bytes of every
+// block and step are requested, and only then does the wavefront deposit block after block (ht_vlc_unstuff, the same code as kernel 1).
+#ifndef HT_FRONT_NW
+#define HT_FRONT_NW 16                         /* wavefronts per workgroup: 4, 8 or 16 (docs/KERNEL_NOTES.md 4x) */
+#endif
+#ifndef HT_FRONT_PRIO
+#define HT_FRONT_PRIO 0                        /* 1: the walking wavefront raises its priority once the prep is over (measured: no difference) */
+#endif
+// row stride: odd, and the deposit's slack (HT_VBITS_WORDS + 8 words, what ht_vlc_unstuff clears and may touch) stays inside the row
+#define HT_FROW (((HT_VBITS_WORDS + 8) | 1))
+struct HtFrontShared {
+    uint32_t vb[HT_WALK_BLOCKS][HT_FROW];
+    uint16_t pair1[16384];
+    uint16_t tbl0[512], tbl1[512];
+    uint32_t tag[HT_WALK_BLOCKS];              // ht_vlc_head's verdict per block, for the walking lane
+};
+static_assert(sizeof(HtFrontShared) <= 90 * 1024, "ht_front_kernel: LDS");
+
+__device__ __forceinline__ uint32_t wave_bcast(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void ht_front_kernel(const BlockJob *__restrict__ jobs, int njobs,
+                                                          const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offs,
+                                                          const uint32_t *__restrict__ lens, uint32_t *__restrict__ pairs) {
+    static_assert(NW >= 4 && HT_WALK_BLOCKS % NW == 0, "the tables are staged by four wavefronts; every wavefront preps the same number of blocks");
+    constexpr int B = HT_WALK_BLOCKS / NW;                    // blocks per wavefront
+    extern __shared__ __align__(16) unsigned char front_smem[];
+    HtFrontShared &S = *reinterpret_cast<HtFrontShared *>(front_smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int jid0 = blockIdx.x * HT_WALK_BLOCKS;
+    const int jid = jid0 + lane;
+    const bool have = lane < HT_WALK_BLOCKS && jid < njobs;
+    const int nblk = min(HT_WALK_BLOCKS, njobs - jid0);
+    uint32_t *rec = pairs + (size_t)jid * HT_WALK_REC;
+    // ---- phase A: table loads first (they land under the prep), then this wavefront's blocks ----
+    // (the walking lanes' block sizes: asked for by every wavefront, without a branch, so that nothing waits for them before phase B)
+    const int w = jobs[min(jid, njobs - 1)].w, h = jobs[min(jid, njobs - 1)].h;
+    // (eight named registers, not an array: the array stayed in the private segment here, with a wait for every load in front of its spill)
+    uint4 t0, t1, t2, t3, t4, t5, t6, t7, tq;
+    if (tid < 256) {
+        const uint4 *g = reinterpret_cast<const uint4 *>(g_vlc_pair1) + tid;
+        t0 = g[0]; t1 = g[256]; t2 = g[512]; t3 = g[768]; t4 = g[1024]; t5 = g[1280]; t6 = g[1536]; t7 = g[1792];
+        if (tid < 128) tq = reinterpret_cast<const uint4 *>(tid < 64 ? c_vlc_tbl0 : c_vlc_tbl1)[tid & 63];       // contexts 0..3 = 1 KiB each
+    }
+    const int b0 = wave * B;
+    const int nmine = min(B, nblk - b0);                      // <= 0: a prep wavefront without a block (the last workgroup)
+    if (nmine > 0) {
+        // lane b asks about block b0 + b; the lanes beyond the wavefront's blocks repeat its last one and are not listened to
+        const HtVlcHead Hl = ht_vlc_head(jobs, jid0 + b0 + min(lane, nmine - 1), stream, offs, lens);
+        // (the block's bytes as an offset into `stream`, so that the loads stay global ones: a pointer put together from two
+        // broadcast words is a flat one, and the waits of flat loads put the requests one behind the other)
+        const uint64_t dof = (uint64_t)(Hl.data - stream);
+        const uint32_t dlo = (uint32_t)dof, dhi = (uint32_t)(dof >> 32);
+        auto head_of = [&](int b) {                           // b wave-uniform
+            return HtVlcHead{stream + ((uint64_t)wave_bcast(dlo, b) | ((uint64_t)wave_bcast(dhi, b) << 32)),
+                             wave_bcast(Hl.len, b), wave_bcast(Hl.scup, b), wave_bcast(Hl.tag, b), wave_bcast(Hl.b0, b), (int)wave_bcast((uint32_t)Hl.N, b)};
+        };
+        // every block's VLC bytes requested before the first is used, and parked as they are in the block's own row (3 x 64 words)
+        uint32_t pre[B][HT_VLC_STEPS];
+#pragma unroll
+        for (int b = 0; b < B; b++) {
+            const HtVlcHead H = head_of(b);
+            const long nb = (b < nmine && !H.tag) ? ht_vlc_nbytes(H) : 0;   // (nothing is loaded beyond nb: a step the block lacks costs no load)
+#pragma unroll
+            for (int c = 0; c < HT_VLC_STEPS; c++) pre[b][c] = ht_vlc_load4(H.data, (long)H.len, nb, 1 + 256 * c + 4 * lane);
+        }
+#pragma unroll
+        for (int b = 0; b < B; b++)
+#pragma unroll
+            for (int c = 0; c < HT_VLC_STEPS; c++) S.vb[b0 + b][64 * c + lane] = pre[b][c];
+        wave_sync();
+        for (int b = 0; b < nmine; b++) {
+            uint32_t *row = &S.vb[b0 + b][0];
+            const uint32_t dw[HT_VLC_STEPS] = {row[lane], row[64 + lane], row[128 + lane]};   // read before ht_vlc_unstuff clears the row (one wavefront: DS in order)
+            const HtVlcHead H = head_of(b);
+            ht_vlc_unstuff(H, lane, row, pairs + (size_t)(jid0 + b0 + b) * HT_WALK_REC, dw);
+            if (lane == 0) S.tag[b0 + b] = H.tag;
+        }
+    }
+    if (tid < 256) {
+        uint4 *d = reinterpret_cast<uint4 *>(S.pair1) + tid;
+        d[0] = t0; d[256] = t1; d[512] = t2; d[768] = t3; d[1024] = t4; d[1280] = t5; d[1536] = t6; d[1792] = t7;
+        if (tid < 128) reinterpret_cast<uint4 *>(tid < 64 ? S.tbl0 : S.tbl1)[tid & 63] = tq;
+    }
+    __syncthreads();
+    // ---- phase B: wavefront 0 walks (the rows of refused and serial blocks were never written: their lanes do not walk) ----
+    if (tid >= 64) return;
+#if HT_FRONT_PRIO
+    __builtin_amdgcn_s_setprio(3);
+#endif
+    const uint32_t tag = have ? S.tag[lane] : HT_PAIR_ZERO;
+    (void)ht_walk_lane(&S.vb[lane][0], S.tbl0, S.tbl1, S.pair1, rec, w, h, have, tag);
 }
 
 #define HT_MAX_FF 64
@@ -2144,6 +2319,8 @@ static hipError_t ht_tables_ready(hipStream_t s) {
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ht_walk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)sizeof(HtWalkShared))) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ht_front_kernel<HT_FRONT_NW>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)sizeof(HtFrontShared))) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;   // once per device: other streams may use the tables next
     g_tables_ready[dev] = true;
     return hipSuccess;
@@ -2180,17 +2357,24 @@ int ht_fast_max_samples() { return HT_FAST_MAX_SAMPLES; }
 size_t ht_decode_scratch_words(int njobs) { return (size_t)njobs * (HT_WALK_REC + HT_VBITS_WORDS); }
 
 // placed_jobs != NULL: the blocks are written straight into their windows of the coefficient planes `decoded` (ht_decode_kernel<true>)
+// front: 1 = ht_front_kernel, 3 = ht_vlcprep_kernel + ht_walk_kernel (the same records either way; vbits is only used by the latter)
 hipError_t launch_ht_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
-                            const uint32_t *lens, int32_t *decoded, uint32_t *scratch, int coded_rows_only, const BlockJob *placed_jobs, int lean) {
+                            const uint32_t *lens, int32_t *decoded, uint32_t *scratch, int coded_rows_only, const BlockJob *placed_jobs, int lean,
+                            int front) {
     if (njobs <= 0) return hipSuccess;
     hipError_t e;
     if ((e = ht_tables_ready(s)) != hipSuccess) return e;
     uint32_t *pairs = scratch, *vbits = scratch + (size_t)njobs * HT_WALK_REC;
-    for (int rep_ = 0; rep_ < dev_reps(32); rep_++)
-    hipLaunchKernelGGL(ht_vlcprep_kernel, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, vbits, pairs);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    for (int rep_ = 0; rep_ < dev_reps(64); rep_++)
-    hipLaunchKernelGGL(ht_walk_kernel, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(256), sizeof(HtWalkShared), s, jobs, njobs, vbits, pairs);
+    if (front == 1) {
+        for (int rep_ = 0; rep_ < dev_reps(32 | 64); rep_++)
+        hipLaunchKernelGGL(ht_front_kernel<HT_FRONT_NW>, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(64 * HT_FRONT_NW), sizeof(HtFrontShared), s, jobs, njobs, stream, offs, lens, pairs);
+    } else {
+        for (int rep_ = 0; rep_ < dev_reps(32); rep_++)
+        hipLaunchKernelGGL(ht_vlcprep_kernel, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, vbits, pairs);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        for (int rep_ = 0; rep_ < dev_reps(64); rep_++)
+        hipLaunchKernelGGL(ht_walk_kernel, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(256), sizeof(HtWalkShared), s, jobs, njobs, vbits, pairs);
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     for (int rep_ = 0; rep_ < dev_reps(128); rep_++)
     if (placed_jobs) hipLaunchKernelGGL(lean ? ht_decode_lean_kernel<true> : ht_decode_kernel<true>, dim3((njobs + 3) / 4), dim3(256), 0, s, placed_jobs, njobs, stream, offs, lens, decoded, pairs, 1);

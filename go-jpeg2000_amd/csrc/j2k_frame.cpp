@@ -334,7 +334,7 @@ static int decode_frame_pixels_impl(j2k_plan *P, const uint8_t *d_cs, size_t len
         const int n = (int)P->blocks.size();
         r = stage_reserve(ctx, 2, ht_decode_scratch_words(n) * 4 + 256);
         if (r != J2K_OK) return r;
-        HIPCHK(ctx, launch_ht_decode(ctx->stream, P->d_djobs, n, d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_coeff_dec, (uint32_t *)ctx->stage[2], 1, P->d_djobs_placed, ctx->ht_dec_lean));
+        HIPCHK(ctx, launch_ht_decode(ctx->stream, P->d_djobs, n, d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_coeff_dec, (uint32_t *)ctx->stage[2], 1, P->d_djobs_placed, ctx->ht_dec_lean, ctx->ht_dec_front));
         return plan_inverse_pixels_impl(P, P->d_cl_coeff_dec, d_pix, stride, P->d_frame_status);
     } else {
         r = j2k_plan_decode_blocks_coarse(P, d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, skip_planes, P->d_cl_decoded);

@@ -283,7 +283,7 @@ extern "C" int j2k_decode_blocks_floors(j2k_ctx *ctx, int coder, const uint8_t *
     else TRY(hipMemsetAsync(d_nb, 0, nblocks, ctx->stream));
     if (coder == J2K_CODER_HT) {
         TRY(hipMalloc(&d_work, ht_decode_scratch_words((int)nblocks) * 4 + 256));
-        TRY(launch_ht_decode(ctx->stream, (BlockJob *)d_jobs, (int)nblocks, (uint8_t *)d_bytes, (uint64_t *)d_offs, (uint32_t *)d_lens, (int32_t *)d_dec, (uint32_t *)d_work, 0, nullptr, ctx->ht_dec_lean));
+        TRY(launch_ht_decode(ctx->stream, (BlockJob *)d_jobs, (int)nblocks, (uint8_t *)d_bytes, (uint64_t *)d_offs, (uint32_t *)d_lens, (int32_t *)d_dec, (uint32_t *)d_work, 0, nullptr, ctx->ht_dec_lean, ctx->ht_dec_front));
     } else {
         // the same choice of decoder as j2k_plan_decode_blocks (the two entry points used to differ), and the same fall-back
         // to the one-launch kernels when the lanes decoder's workspace cannot be had

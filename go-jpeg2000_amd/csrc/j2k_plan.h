@@ -28,6 +28,7 @@ struct j2k_ctx {
     bool l0_xcd = true;        // XCD-aware order of the workgroup jobs (J2K_L0_XCD=0: plane-major order)
     bool ht_alias = true;      // j2k_plan_encode_stream (HT): code each distinct block window once (J2K_HT_ALIAS=0: every job)
     int ht_enc_waves = 4;      // ... with this many wavefronts per distinct window (J2K_HT_ENC_WAVES: 1 = ht_encode_kernel, 4 = ht_encode_wg_kernel)
+    int ht_dec_front = 3;      // HT block decode, kernels 1 + 2 (J2K_HT_DEC_FRONT: 3 = ht_vlcprep_kernel + ht_walk_kernel, two launches; 1 = ht_front_kernel, the workgroup unstuffs the strings it walks)
     int ht_dec_lean = 1;       // HT block decode, third kernel (J2K_HT_DEC_LEAN: 1 = ht_decode_lean_kernel, the 64-wide common case written out and everything else out of line; 0 = ht_decode_kernel)
     int l0_inv_wpe = 5;        // its occupancy variant (J2K_L0_INV_WPE: 5 = all in registers, 26.4 us; 6 = odd row parked in LDS for 6 waves per SIMD, measured slower: 33.6 us)
     bool l0_wg_inv = true;     // the inverse level 0 to RGBA8 in workgroup form too (J2K_L0_WG_INV=0: the general kernel)

@@ -912,7 +912,7 @@ int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const u
         int r = stage_reserve(ctx, 2, ht_decode_scratch_words(n) * 4 + 256);
         if (r != J2K_OK) return r;
         HIPCHK(ctx, launch_ht_decode(ctx->stream, d_djobs, n, d_stream, d_offs, d_lens, d_decoded, (uint32_t *)ctx->stage[2],
-                                     (d_placed || P->dec_coded_rows_only) ? 1 : 0, d_placed, ctx->ht_dec_lean));
+                                     (d_placed || P->dec_coded_rows_only) ? 1 : 0, d_placed, ctx->ht_dec_lean, ctx->ht_dec_front));
     } else {
         size_t wpj = 0;                                  // the one-block decoder's workspace holds the flags only
         int max_dim = 0;
