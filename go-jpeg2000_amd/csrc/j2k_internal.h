@@ -71,6 +71,13 @@ struct LLPlane {
     int32_t nc, pad_;     // 1, or 3 = inverse RCT / ICT on the triple
 };
 
+// One tile-component for the need set of a region decode (area.hip): its tile's rectangle in the frame and its decomposition levels
+struct AreaPlane {
+    int32_t x0, y0, w, h;
+    int32_t levels;
+    int32_t pad_[3];
+};
+
 // launch wrappers (dwt53.hip, dwt97.hip, mct.hip, ht.hip, t1.hip)
 // A YCbCr image read by the 5-3 level-0 workgroup kernel itself (j2k_plan_forward_image): the planes at the frame's origin
 // (Rect.Min even and >= 0), one chroma stride for Cb and Cr (Go's CStride); ratio J2K_YCBCR_444 / 422 / 420.
@@ -137,6 +144,12 @@ hipError_t launch_colorspace(hipStream_t s, int cs, int32_t *planes, int ncomp, 
 hipError_t launch_pack_pixels(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, uint8_t *pix, size_t stride);
 hipError_t launch_pack_pixels_rect(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, int x0, int y0, int rw, int rh, uint8_t *pix,
                                    size_t stride, const int *guard = nullptr);   // the rectangle (x0, y0, rw, rh) of the frame only
+// ... written to pix at origin (0, 0): pix holds rh rows of rw pixels (region decode)
+hipError_t launch_pack_pixels_window(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, int x0, int y0, int rw, int rh, uint8_t *pix,
+                                     size_t stride, const int *guard);
+// region decode (area.hip): the need set of a rectangle; the table entries of the blocks outside it emptied
+hipError_t launch_area_blocks(hipStream_t s, const j2k_block *blocks, int n, const AreaPlane *planes, int x0, int y0, int x1, int y1, int reduce, int margin,
+                              uint8_t *need, uint32_t *lens, uint8_t *numbps, uint8_t *floors);
 // image.YCbCr / CMYK / Paletted -> packed RGBA8 (image.hip); *flag = J2K_ERR_GO_PANIC for a palette index >= npal
 hipError_t launch_image_to_rgba8(hipStream_t s, const j2k_image &img, uint32_t *pix, size_t stride_px, int *flag);
 

@@ -266,5 +266,10 @@ struct j2k_plan {
     void *d_cl_dense = nullptr;             // j2k_plan_decode_frame_pixels_layers: the gathered codewords (at least the stream's length) ...
     size_t cl_dense_bytes = 0;
     uint8_t *d_cl_lfloors = nullptr;        // ... and the blocks' floors (whole frame | the subset of a reduced decode)
+    // region decode (j2k_area.cpp), made at the first area call: the jobs' windows and every plane's tile rectangle for area_blocks_kernel, and the
+    // int32 staging frame [C][H][W] the whole-frame inverse writes before the window is packed
+    j2k_block *d_area_blocks = nullptr;
+    j2k::AreaPlane *d_area_planes = nullptr;
+    int32_t *d_area_frame = nullptr;
     bool dequantize = false;                // j2k_plan_set_dequantize: the 9-7 inverse kernels multiply every int32 coefficient by 1.0 / Quality at their load (dwt.go:514-520)
 };

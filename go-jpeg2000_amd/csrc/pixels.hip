@@ -93,6 +93,43 @@ __global__ __launch_bounds__(256) void pack_pixels_kernel(const int32_t *__restr
     }
 }
 
+// pack_pixels_kernel for a region decode: the rectangle (x0, y0, rw, rh) of the w x h planes into a pix that holds that rectangle ALONE, at
+// origin (0, 0) -- rh rows of rw pixels.  A kernel of its own, so that pack_pixels_kernel stays the code it was.
+__global__ __launch_bounds__(256) void pack_pixels_window_kernel(const int32_t *__restrict__ planes, int ncomp, int precision, int w, int h, int x0, int y0, int rw,
+                                                                 int rh, uint8_t *__restrict__ pix, size_t stride, const int *__restrict__ guard) {
+    if (guard && *guard) return;             // (a stream that was refused leaves the caller's buffer alone)
+    const size_t n = (size_t)w * h, m = (size_t)rw * rh;
+    const int max_val = (int)((1u << precision) - 1);
+    const bool wide = precision > 8;
+    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < m; j += (size_t)gridDim.x * 256) {
+        const int y = (int)(j / (size_t)rw), x = (int)(j - (size_t)y * rw);          // in the rectangle = in pix
+        const size_t i = (size_t)(y0 + y) * w + x0 + x;
+        uint8_t *row = pix + (size_t)y * stride;
+        int v[4];
+        for (int c = 0; c < ncomp; c++) {
+            int t = planes[(size_t)c * n + i];
+            t = t < 0 ? 0 : (t > max_val ? max_val : t);
+            if (wide) t = go_muldiv(t, 65535, max_val);
+            else if (precision != 8) t = go_muldiv(t, 255, max_val);
+            v[c] = t;
+        }
+        if (ncomp == 1) {
+            if (wide) { row[2 * (size_t)x] = (uint8_t)((uint32_t)v[0] >> 8); row[2 * (size_t)x + 1] = (uint8_t)v[0]; }
+            else row[x] = (uint8_t)v[0];
+        } else {
+            const int a = ncomp == 4 ? v[3] : (wide ? 65535 : 255);
+            if (wide) {
+                uint8_t *q = row + 8 * (size_t)x;
+                const int o[4] = {v[0], v[1], v[2], a};
+                for (int c = 0; c < 4; c++) { q[2 * c] = (uint8_t)((uint32_t)o[c] >> 8); q[2 * c + 1] = (uint8_t)o[c]; }
+            } else {
+                *reinterpret_cast<uint32_t *>(row + 4 * (size_t)x) =
+                    ((uint32_t)v[0] & 0xFF) | ((uint32_t)v[1] & 0xFF) << 8 | ((uint32_t)v[2] & 0xFF) << 16 | ((uint32_t)a & 0xFF) << 24;
+            }
+        }
+    }
+}
+
 hipError_t launch_unpack_pixels(hipStream_t s, const uint8_t *pix, size_t stride, int format, int w, int h, int src_max, int dst_max,
                                 int32_t *planes) {
     const size_t n = (size_t)w * h;
@@ -109,6 +146,15 @@ hipError_t launch_pack_pixels_rect(hipStream_t s, const int32_t *planes, int nco
     if (!m) return hipSuccess;
     const int blocks = (int)std::min<size_t>((m + 255) / 256, 65536);
     hipLaunchKernelGGL(pack_pixels_kernel, dim3(blocks), dim3(256), 0, s, planes, ncomp, precision, w, h, x0, y0, rw, rh, pix, stride, guard);
+    return hipGetLastError();
+}
+hipError_t launch_pack_pixels_window(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, int x0, int y0, int rw, int rh, uint8_t *pix,
+                                     size_t stride, const int *guard) {
+    if (x0 < 0 || y0 < 0 || rw < 0 || rh < 0 || x0 + rw > w || y0 + rh > h) return hipErrorInvalidValue;
+    const size_t m = (size_t)rw * rh;
+    if (!m) return hipSuccess;
+    const int blocks = (int)std::min<size_t>((m + 255) / 256, 65536);
+    hipLaunchKernelGGL(pack_pixels_window_kernel, dim3(blocks), dim3(256), 0, s, planes, ncomp, precision, w, h, x0, y0, rw, rh, pix, stride, guard);
     return hipGetLastError();
 }
 hipError_t launch_pack_pixels(hipStream_t s, const int32_t *planes, int ncomp, int precision, int w, int h, uint8_t *pix, size_t stride) {

@@ -74,6 +74,7 @@ SYMBOLS = [
     "j2k_plan_rate_allocate_layers", "j2k_plan_encode_tile_parts_layers", "j2k_plan_decode_tile_parts_layers", "j2k_plan_frame_bound_layers",
     "j2k_plan_encode_frame_pixels_layers", "j2k_plan_decode_frame_pixels_layers", "j2k_encode_pixels_host_layers", "j2k_decode_pixels_host_layers",
     "j2k_tile_parts_keep_layers",
+    "j2k_plan_area_shape", "j2k_plan_area_blocks", "j2k_plan_decode_frame_pixels_area", "j2k_decode_pixels_host_area",
     "j2k_plan_pack_bound", "j2k_plan_pack_stream", "j2k_plan_unpack_stream", "j2k_plan_unpack_streams",
     "j2k_comm_load_error", "j2k_comm_get_unique_id", "j2k_comm_create", "j2k_comm_destroy", "j2k_comm_last_error", "j2k_comm_stream", "j2k_gather_streams", "j2k_comm_wait",
 ]
@@ -90,6 +91,12 @@ class Image(C.Structure):
     _fields_ = [("kind", C.c_int32), ("ratio", C.c_int32), ("min_x", C.c_int32), ("min_y", C.c_int32),
                 ("width", C.c_int32), ("height", C.c_int32), ("plane", C.c_void_p * 3), ("stride", C.c_int64 * 3),
                 ("len", C.c_uint64 * 3), ("palette", C.c_void_p), ("npal", C.c_int32), ("pad_", C.c_int32)]
+
+
+class Rect(C.Structure):
+    """j2k_rect: half-open, full-resolution frame coordinates (the area= of the decode calls)"""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32)]
+
 
 _lib = None
 
@@ -152,6 +159,10 @@ def lib():
             "j2k_encode_pixels_host_layers": (I, [V, I, V, S, I, I, I64P, I, V, S, C.POINTER(S), V, V, V, V]),
             "j2k_decode_pixels_host_layers": (I, [V, V, S, I, I, I, I, I, V, S]),
             "j2k_tile_parts_keep_layers": (I, [V, S, V, V, I, I, I, V, S, C.POINTER(S), V]),
+            "j2k_plan_area_shape": (I, [V, C.POINTER(Rect), I, C.POINTER(I), C.POINTER(I)]),
+            "j2k_plan_area_blocks": (I, [V, C.POINTER(Rect), I, V]),
+            "j2k_plan_decode_frame_pixels_area": (I, [V, V, S, V, I, I, I, I, I, I, C.POINTER(Rect), V, S]),
+            "j2k_decode_pixels_host_area": (I, [V, V, S, I, I, I, I, I, I, C.POINTER(Rect), V, S]),
         }
         for name, (res, args) in sigs.items():
             if partial and not hasattr(L, name):

@@ -144,6 +144,30 @@ class FramePlan:
         self.ctx.check(self.ctx.L.j2k_plan_reduced_size(self.h, int(reduce), C.byref(w), C.byref(h)))
         return int(h.value), int(w.value)
 
+    # ---- region decode (Mallat MQ plans; j2k_plan_*_area) -----------------------------------
+    @staticmethod
+    def _rect(area):
+        x0, y0, x1, y1 = (int(v) for v in area)
+        return _lib.Rect(x0, y0, x1, y1)
+
+    def area_shape(self, area, reduce=0):
+        """(h, w) of what a decode with area=(x0, y0, x1, y1) (half-open, full-resolution frame coordinates) and reduce=... returns: the
+        rectangle [ceil(x0 / 2^reduce), ceil(x1 / 2^reduce)) x [ceil(y0 / 2^reduce), ceil(y1 / 2^reduce)) of the reduced frame (j2k_plan_area_shape)"""
+        w, h = C.c_int(0), C.c_int(0)
+        r = self._rect(area)
+        self.ctx.check(self.ctx.L.j2k_plan_area_shape(self.h, C.byref(r), int(reduce), C.byref(w), C.byref(h)))
+        return int(h.value), int(w.value)
+
+    @_stage
+    def area_blocks(self, area, reduce=0, need=None):
+        """device uint8 [blocks]: 1 for every code-block a decode of `area` at `reduce` needs (j2k_plan_area_blocks)"""
+        t = _torch()
+        n = int(self.info.blocks)
+        need = need if need is not None else self.empty(n, t.uint8)
+        r = self._rect(area)
+        self.ctx.check(self.ctx.L.j2k_plan_area_blocks(self.h, C.byref(r), int(reduce), self._p(need)))
+        return need[:n]
+
     @_stage
     def inverse(self, coeff, frame=None, reduce=0):
         """reduce > 0 (Mallat plans): stop at level `reduce`, frame = int32 [C, H_r, W_r] (reduced_shape)"""
@@ -463,13 +487,23 @@ class FramePlan:
         return out, tile_offs
 
     @_stage
-    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None):
+    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None, area=None):
         """tile-parts cs[:length] -> pixels into pix (device uint8 [H, stride]; reduce > 0, Mallat plans: [H_r, stride], and only the
         code-blocks of the resolutions it needs are decoded; skip_planes = k > 0, MQ plans: every block decoder stops after bit plane k;
         truncated=True, MQ plans: the stream's blocks may be cut at bit planes (encode_frame_pixels(max_body_bytes=...)) -- every block runs
         from its own top plane down to max(skip_planes, its floor) (j2k_plan_decode_frame_pixels_rate).  Without it a cut stream decodes by
         the old rule, numbps = coded planes.)  layers = k: cs is a layered stream (encode_frame_pixels(layer_bytes=...)); the first k layers of
-        every tile-part are read, what follows them is ignored (j2k_plan_decode_frame_pixels_layers)"""
+        every tile-part are read, what follows them is ignored (j2k_plan_decode_frame_pixels_layers).  area = (x0, y0, x1, y1), Mallat MQ plans,
+        with any of the others: only that rectangle, pix = [h, stride] with (h, w) = area_shape(area, reduce), and only the code-blocks the
+        rectangle needs are decoded (j2k_plan_decode_frame_pixels_area)"""
+        if area is not None:
+            r = self._rect(area)
+            if pix.dim() != 2 or int(pix.shape[0]) != self.area_shape(area, reduce)[0]:
+                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "decode_frame_pixels: pix is not area_shape(area, reduce) rows")
+            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_area(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
+                                                                        int(bool(sop)), int(bool(eph)), int(layers or 0), int(bool(truncated)), int(reduce), int(skip_planes),
+                                                                        C.byref(r), self._p(pix), C.c_size_t(int(pix.shape[1]))))
+            return pix
         if layers is not None:
             self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_layers(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
                                                                           int(bool(sop)), int(bool(eph)), int(layers), int(reduce), int(skip_planes), self._p(pix),
@@ -532,10 +566,21 @@ class FramePlan:
         self.ctx.check(st)
         return dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
 
-    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None):
+    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None, area=None, pix=None):
         """closed-loop plans: tile-parts (bytes / numpy uint8) -> numpy uint8 pixels of `shape` = (H, stride); reduce > 0: (H_r, stride);
-        skip_planes > 0 (MQ plans), truncated: as decode_frame_pixels"""
+        skip_planes > 0 (MQ plans), truncated: as decode_frame_pixels; area: as decode_frame_pixels, shape = (h, stride) with h of area_shape
+        (j2k_decode_pixels_host_area; pix: a numpy uint8 array of `shape` to write instead of a new one -- a refused call leaves it alone)"""
         cs = np.ascontiguousarray(np.frombuffer(bytes(cs), np.uint8) if not isinstance(cs, np.ndarray) else cs, dtype=np.uint8)
+        if area is not None:
+            r = self._rect(area)
+            if len(shape) != 2 or int(shape[0]) != self.area_shape(area, reduce)[0]:
+                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "decode_pixels_host: shape is not area_shape(area, reduce) rows")
+            pix = pix if pix is not None else np.zeros(shape, np.uint8)
+            assert pix.dtype == np.uint8 and pix.shape == tuple(shape) and pix.flags.c_contiguous
+            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_area(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
+                                                                  int(layers or 0), int(bool(truncated)), int(reduce), int(skip_planes), C.byref(r),
+                                                                  pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
+            return pix
         pix = np.zeros(shape, np.uint8)
         if layers is not None:                   # a layered stream, its first `layers` layers (j2k_decode_pixels_host_layers)
             self.ctx.check(self.ctx.L.j2k_decode_pixels_host_layers(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),

@@ -815,6 +815,37 @@ int j2k_decode_pixels_host_layers(j2k_plan *plan, const uint8_t *cs, size_t len,
 int j2k_tile_parts_keep_layers(const uint8_t *cs, size_t len, const uint64_t *tile_offs, const uint64_t *layer_offs, int ntiles, int nlayers,
                                int keep, uint8_t *out, size_t cap, size_t *out_len, uint64_t *out_tile_offs);
 
+/* Region decode (the library's own; the reference declares Config.DecodeArea and never reads it): the pixels of a rectangle of the frame,
+ * decoding only the code-blocks that rectangle needs.  `area` is half-open, in full-resolution frame coordinates, 0 <= x0 < x1 <= W and
+ * 0 <= y0 < y1 <= H.  With `reduce` = r the result is the rectangle [ceil(x0 / 2^r), ceil(x1 / 2^r)) x [ceil(y0 / 2^r), ceil(y1 / 2^r)) of
+ * the reduced frame, bit for bit what the call without `area` writes there.
+ *   The need set (definition: tests/area_cases.py).  Per tile the rectangle is cut to the tile and walked down the synthesis of
+ * the wavelet: at level l an interval [a, b) of a dimension of n samples needs the low-pass samples [max(0, a / 2 - m), min(ceil(n / 2),
+ * (b - 1) / 2 + m + 1)) and the high-pass samples [max(0, a / 2 - m), min(n / 2, (b - 1) / 2 + m + 1)), m = 1 for the 5-3 and 2 for the 9-7;
+ * the low-pass interval goes on to level l + 1.  A code-block is needed iff its window meets one of these rectangles of the plane.  One
+ * launch computes the set from the rectangle (a kernel argument: no host table per rectangle, no synchronisation) and empties the parsed
+ * table entries of every other block, which the MQ block decoders turn into zeros without reading a byte of them.  Every packet is still
+ * parsed and the inverse transform runs on the whole (reduced) frame into a staging frame of the plan; a rectangle pack writes the window to
+ * d_pix at origin (0, 0), rows of `stride` bytes, under the frame status word (a refused stream leaves d_pix alone).
+ *   Plans: Mallat, MQ coder, one frame, every tile (J2K_ERR_UNSUPPORTED for prefix-layout, HT, batch and shard plans).  A rectangle that is
+ * inverted, empty, outside the frame or empty after `reduce`, or a stride shorter than a row of the result: J2K_ERR_INVALID_ARG.  What the
+ * call without `area` refuses (reduce, skip_planes, layers) is refused in the same way.  Every refusal comes before the first launch.
+ *   j2k_plan_area_shape               HOST ONLY: width and height of the result
+ *   j2k_plan_area_blocks              the need set alone: d_need[j] = 1 iff job j is needed (device, one byte per job; asynchronous)
+ *   j2k_plan_decode_frame_pixels_area the frame call with every axis: layers (0: not a layered stream, else the first `layers` layers as
+ *                                     j2k_plan_decode_frame_pixels_layers), truncated (non-zero: per-block floors as the _rate call), reduce,
+ *                                     skip_planes
+ *   j2k_decode_pixels_host_area       its synchronous host-memory form; pix is written only if the stream was accepted
+ * The tables of the need-set launch are made at the first area call of a plan (capture: run the call once before; a captured graph is valid
+ * for the rectangle it captured). */
+typedef struct j2k_rect { int32_t x0, y0, x1, y1; } j2k_rect;
+int j2k_plan_area_shape(const j2k_plan *plan, const j2k_rect *area, int reduce, int *out_w, int *out_h);
+int j2k_plan_area_blocks(j2k_plan *plan, const j2k_rect *area, int reduce, uint8_t *d_need);
+int j2k_plan_decode_frame_pixels_area(j2k_plan *plan, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                      int layers, int truncated, int reduce, int skip_planes, const j2k_rect *area, void *d_pix, size_t stride);
+int j2k_decode_pixels_host_area(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, int layers, int truncated, int reduce,
+                                int skip_planes, const j2k_rect *area, void *pix, size_t stride);
+
 /* The block coder's outputs as those tables.  j2k_plan_t2_packets (host table out): one packet per (tile, component,
  * resolution) of the plan in job order (encoder.go:616-673: tile, component, resolution, band, block row, block column), its
  * code-blocks = the plan's jobs of that resolution, tree widths = block columns of its first band; layer as given.
