@@ -4,14 +4,9 @@
 // agree with exactly; DESIGN.md 7 has the rule and its margins.  The windows of a Mallat plan partition each plane, and level l's sub-bands
 // are the rectangles [w_{l+1}, w_l) x [0, h_{l+1}), [0, w_{l+1}) x [h_{l+1}, h_l) and [w_{l+1}, w_l) x [h_{l+1}, h_l) of it, so the whole
 // rule is integer rectangle tests in plane coordinates: at most 3 L + 1 per block.
-#include "j2k_internal.h"
+#include "area_walk.h"
 
 namespace j2k {
-
-// [x0, x1) x [y0, y1) meets the window (wx, wy, ww, wh)?  An empty rectangle meets nothing.
-__device__ __forceinline__ bool area_meets(int x0, int x1, int y0, int y1, int wx, int wy, int ww, int wh) {
-    return x0 < x1 && y0 < y1 && x0 < wx + ww && wx < x1 && y0 < wy + wh && wy < y1;
-}
 
 // One thread per block job.  need (optional): 1 / 0 per job.  lens / numbps / floors (each optional): the parsed block tables of the frame;
 // the entries of a block that is not needed become 0 -- no bytes, no bit planes -- so every MQ decode kernel leaves that block zeros without
@@ -23,27 +18,8 @@ __global__ __launch_bounds__(256) void area_blocks_kernel(const j2k_block *__res
     if (j >= n) return;
     const j2k_block b = blocks[j];
     const AreaPlane T = planes[b.plane];
-    const int rnd = (1 << reduce) - 1;
-    // the output rectangle of the reduced frame (the canvas rule), cut to the tile's reduced rectangle and made relative to it
-    const int tx = T.x0 >> reduce, ty = T.y0 >> reduce;
-    int wl = (T.w + rnd) >> reduce, hl = (T.h + rnd) >> reduce;                  // w_reduce, h_reduce
-    int xa = max((ax0 + rnd) >> reduce, tx) - tx, xb = min((ax1 + rnd) >> reduce, tx + wl) - tx;
-    int ya = max((ay0 + rnd) >> reduce, ty) - ty, yb = min((ay1 + rnd) >> reduce, ty + hl) - ty;
-    bool hit = false;
-    if (xa < xb && ya < yb) {
-        for (int l = reduce; l < T.levels && !hit; l++) {
-            const int wn = (wl + 1) >> 1, hn = (hl + 1) >> 1;                    // w_{l+1}, h_{l+1}
-            const int x0 = max(0, (xa >> 1) - margin), xe = ((xb - 1) >> 1) + margin + 1;
-            const int y0 = max(0, (ya >> 1) - margin), ye = ((yb - 1) >> 1) + margin + 1;
-            const int lx1 = min(wn, xe), hx1 = min(wl >> 1, xe), ly1 = min(hn, ye), hy1 = min(hl >> 1, ye);
-            hit = area_meets(wn + x0, wn + hx1, y0, ly1, b.x0, b.y0, b.w, b.h) ||
-                  area_meets(x0, lx1, hn + y0, hn + hy1, b.x0, b.y0, b.w, b.h) ||
-                  area_meets(wn + x0, wn + hx1, hn + y0, hn + hy1, b.x0, b.y0, b.w, b.h);
-            xa = x0; xb = lx1; ya = y0; yb = ly1;
-            wl = wn; hl = hn;
-        }
-        hit = hit || area_meets(xa, xb, ya, yb, b.x0, b.y0, b.w, b.h);           // LL of the last level (reduce = levels: the window itself)
-    }
+    const bool hit = area_walk(T, ax0, ay0, ax1, ay1, reduce, margin,
+                               [&](int x0, int x1, int y0, int y1) { return area_meets(x0, x1, y0, y1, b.x0, b.y0, b.w, b.h); });
     if (need) need[j] = hit ? 1 : 0;
     if (!hit) {
         if (lens) lens[j] = 0;
@@ -52,11 +28,29 @@ __global__ __launch_bounds__(256) void area_blocks_kernel(const j2k_block *__res
     }
 }
 
+// Region-of-interest encode (include/j2kgfx.h, j2k_plan_roi_windows): one thread per block job, win[4 j ...] = (fx, fy, fw, fh), the footprint of
+// the rectangle inside block j relative to its window, all 0 when there is none.  tests/roi_cases.py is the definition.
+__global__ __launch_bounds__(256) void roi_windows_kernel(const j2k_block *__restrict__ blocks, int n, const AreaPlane *__restrict__ planes, int rx0, int ry0,
+                                                          int rx1, int ry1, int margin, int32_t *__restrict__ win) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const j2k_block b = blocks[j];
+    const RoiWin F = roi_window(b, planes[b.plane], rx0, ry0, rx1, ry1, margin);
+    int32_t *o = win + (size_t)j * 4;
+    o[0] = F.x; o[1] = F.y; o[2] = F.w; o[3] = F.h;
+}
+
 hipError_t launch_area_blocks(hipStream_t s, const j2k_block *blocks, int n, const AreaPlane *planes, int x0, int y0, int x1, int y1, int reduce, int margin,
                               uint8_t *need, uint32_t *lens, uint8_t *numbps, uint8_t *floors) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(area_blocks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, blocks, n, planes, x0, y0, x1, y1, reduce, margin, need, lens, numbps,
                        floors);
+    return hipGetLastError();
+}
+
+hipError_t launch_roi_windows(hipStream_t s, const j2k_block *blocks, int n, const AreaPlane *planes, int x0, int y0, int x1, int y1, int margin, int32_t *win) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(roi_windows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, blocks, n, planes, x0, y0, x1, y1, margin, win);
     return hipGetLastError();
 }
 

@@ -40,8 +40,8 @@ extern "C" int j2k_plan_area_shape(const j2k_plan *P, const j2k_rect *area, int 
     return J2K_OK;
 }
 
-// the plan data of area_blocks_kernel, uploaded at the first area call
-static int area_tables(j2k_plan *P, bool frame) {
+// the plan data of area_blocks_kernel, uploaded at the first area call (or the first region-of-interest encode: j2k_rate.cpp)
+int area_tables(j2k_plan *P, bool frame) {
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
     if (P->d_area_planes && (!frame || P->d_area_frame)) return J2K_OK;

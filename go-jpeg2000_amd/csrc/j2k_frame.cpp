@@ -407,7 +407,7 @@ int cl_rate_workspace(j2k_plan *P, ClRate &W) {
 // coefficients -> rate-limited tile-parts: block coding into the plan's slots with the tables, the allocation, then every block's kept prefix once
 // from its slot into its packet (d_lens / d_numbps: the caller's tables, filled with the UNCUT lengths and plane counts)
 int plan_encode_frame_from_coeff_rate(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int64_t max_body_bytes, int sop, int eph,
-                                      uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+                                      uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, const j2k_rect *roi, int roi_gain) {
     j2k_ctx *ctx = P->ctx;
     int r = rate_check(P, "rate-limited frame encode");
     if (r != J2K_OK) return r;
@@ -419,7 +419,7 @@ int plan_encode_frame_from_coeff_rate(j2k_plan *P, const int32_t *d_coeff, uint3
         if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: run the same calls once before j2k_ctx_capture_begin");
         HIPCHK(ctx, hipMalloc(&P->d_slots, (size_t)P->bytes_cap + 64));
     }
-    if (r == J2K_OK) r = j2k_plan_encode_blocks_planes(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist);
+    if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, roi, roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
     if (r == J2K_OK) r = j2k_plan_rate_allocate(P, W.rate, W.dist, d_numbps, max_body_bytes, W.kept, W.chosen);
     if (r == J2K_OK) r = encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, W.kept, W.rate);
     return r;

@@ -41,6 +41,10 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
                             uint32_t *bignsyms = nullptr, uint32_t *rate = nullptr);   // rate: 32 words per job, the rate tables (blocks <= 64 x 64 only)
 // rate control (rate.hip): plane distortions of every block; the allocation of a byte budget over the blocks' rate / distortion tables
 hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, uint64_t *dist);
+// region of interest (area.hip, rate.hip): every block's footprint of a rectangle; the distortions with that footprint weighted `gain` times
+hipError_t launch_roi_windows(hipStream_t s, const j2k_block *blocks, int n, const AreaPlane *planes, int x0, int y0, int x1, int y1, int margin, int32_t *win);
+hipError_t launch_rate_distortion_roi(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, const j2k_block *blocks,
+                                      const AreaPlane *planes, int x0, int y0, int x1, int y1, int margin, uint32_t gain, uint64_t *dist);
 size_t rate_allocate_workspace(int njobs);
 hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
                                 uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen);
@@ -137,6 +141,15 @@ int plan_decode_frame_tables(j2k_plan *P, const uint8_t *d_data, j2k::ReducedTab
                              void *d_pix, size_t stride);
 int rate_check(j2k_plan *P, const char *who);    // what every rate call needs of its plan (j2k_rate.cpp)
 int rate_upload_weights(j2k_plan *P);            // the per-job weights and the allocation workspace on the device (j2k_rate.cpp)
+// the plan data of area_blocks_kernel (and of the region-of-interest kernels), uploaded at first use; frame: also the staging frame of a region
+// decode (j2k_area.cpp)
+int area_tables(j2k_plan *P, bool frame);
+// region-of-interest encode (j2k_rate.cpp).  roi_check: every refusal its plan, rectangle and gain decide (host only; after rate_check).
+// plan_encode_blocks_planes_roi: j2k_plan_encode_blocks_planes with the rectangle's footprint weighted roi_gain times in d_dist; roi == NULL is
+// that call itself.  The callers have checked.
+int roi_check(j2k_plan *P, const j2k_rect *roi, int roi_gain, const char *who);
+int plan_encode_blocks_planes_roi(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate, uint64_t *d_dist,
+                                  const j2k_rect *roi, int roi_gain);
 
 // ---- stages (j2k_stages.cpp) ----
 struct T1Workspace { size_t off_nsyms, off_sym, stride, total; };
@@ -150,7 +163,7 @@ int plan_encode_private_slots(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_l
 int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int sop, int eph, uint8_t *d_out, size_t cap,
                                  uint64_t *d_tile_offs);
 int plan_encode_frame_from_coeff_rate(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int64_t max_body_bytes, int sop, int eph,
-                                      uint8_t *d_out, size_t cap, uint64_t *d_tile_offs);
+                                      uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, const j2k_rect *roi = nullptr, int roi_gain = 1);   // roi: checked by the caller
 // guard (device, or null): the launches that write d_frame write nothing if *guard != 0 -- the frame decoder's status word
 int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix = PixIO(), const int *guard = nullptr);
 int plan_inverse_pixels_impl(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride, const int *guard);

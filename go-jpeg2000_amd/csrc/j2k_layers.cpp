@@ -165,7 +165,7 @@ extern "C" int j2k_plan_decode_tile_parts_layers(j2k_plan *P, const uint8_t *d_c
 // coefficients -> layered tile-parts: block coding into the plan's slots with the tables, the allocation of the L budgets in one launch, then every
 // block's increments from its slot into its L packets (d_lens / d_numbps: the caller's tables, filled with the UNCUT lengths and plane counts)
 static int encode_frame_from_coeff_layers(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, const uint64_t *budgets, int L, int sop, int eph,
-                                          uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs) {
+                                          uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs, const j2k_rect *roi = nullptr, int roi_gain = 1) {
     j2k_ctx *ctx = P->ctx;
     ClRate W{};
     LayerTab *T = nullptr;
@@ -177,7 +177,7 @@ static int encode_frame_from_coeff_layers(j2k_plan *P, const int32_t *d_coeff, u
         if (!P->d_slots) HIPCHK(ctx, hipMalloc(&P->d_slots, (size_t)P->bytes_cap + 64));
         if (!T->d_kept) HIPCHK(ctx, hipMalloc((void **)&T->d_kept, std::max<size_t>(P->blocks.size() * (size_t)L, 64)));
     }
-    if (r == J2K_OK) r = j2k_plan_encode_blocks_planes(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist);
+    if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, roi, roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
     if (r == J2K_OK) r = rate_upload_weights(P);
     if (r != J2K_OK) return r;
     HIPCHK(ctx, launch_rate_allocate_layers(ctx->stream, (int)P->blocks.size(), W.rate, W.dist, d_numbps, P->d_rate_wj, budgets, L, P->d_rate_ws, T->d_kept, W.chosen));      // (W.chosen: 32 words, one per layer)
@@ -199,6 +199,33 @@ extern "C" int j2k_plan_encode_frame_pixels_layers(j2k_plan *P, int format, cons
     if (r == J2K_OK) r = j2k_plan_forward_pixels(P, format, d_pix, stride, P->d_cl_coeff);
     if (r == J2K_OK) r = encode_frame_from_coeff_layers(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, budgets, nlayers, sop, eph, d_out, cap, d_tile_offs, d_layer_offs);
     return r;
+}
+
+// Region-of-interest encode, one call for both budget forms: nlayers = 1 with d_layer_offs == NULL is j2k_plan_encode_frame_pixels_rate with
+// max_body_bytes = layer_bytes[0], anything else j2k_plan_encode_frame_pixels_layers; the only new step is the distortion launch, which takes the
+// rectangle and the gain (rate.hip).  Every refusal comes before the first launch.
+static int roi_frame_check(j2k_plan *P, const int64_t *layer_bytes, int nlayers, bool layered, const j2k_rect *roi, int roi_gain, uint64_t *budgets, const char *who) {
+    int r = layers_check(P, nlayers, who);
+    if (r == J2K_OK) r = roi_check(P, roi, roi_gain, who);
+    if (r == J2K_OK) r = budgets_check(P->ctx, layer_bytes, nlayers, budgets, who);
+    if (r == J2K_OK && !layered && nlayers != 1) r = fail(P->ctx, J2K_ERR_INVALID_ARG, (std::string(who) + ": more than one budget needs the layer ends (layer_offs)").c_str());
+    return r;
+}
+extern "C" int j2k_plan_encode_frame_pixels_roi(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
+                                                const j2k_rect *roi, int roi_gain, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    if (!d_out || !d_tile_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    uint64_t budgets[J2K_MAX_LAYERS];
+    int r = roi_frame_check(P, layer_bytes, nlayers, d_layer_offs != nullptr, roi, roi_gain, budgets, "j2k_plan_encode_frame_pixels_roi");
+    if (r != J2K_OK) return r;
+    r = cl_prepare(P);
+    if (r == J2K_OK) r = cl_workspaces(P);
+    if (r == J2K_OK) r = area_tables(P, false);
+    if (r == J2K_OK) r = j2k_plan_forward_pixels(P, format, d_pix, stride, P->d_cl_coeff);
+    if (r != J2K_OK) return r;
+    if (!d_layer_offs) return plan_encode_frame_from_coeff_rate(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, layer_bytes[0], sop, eph, d_out, cap, d_tile_offs, roi, roi_gain);
+    return encode_frame_from_coeff_layers(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, budgets, nlayers, sop, eph, d_out, cap, d_tile_offs, d_layer_offs, roi, roi_gain);
 }
 
 // the first `layers` layers of every tile-part -> pixels: the LAYERED packet read, the blocks' segments gathered into the plan's dense buffer, then
@@ -232,30 +259,39 @@ extern "C" int j2k_plan_decode_frame_pixels_layers(j2k_plan *P, const uint8_t *d
 }
 
 // ---- host memory in, host memory out ---------------------------------------------------------------------------------------------------------
-extern "C" int j2k_encode_pixels_host_layers(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
-                                             uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps) {
+// with_roi: j2k_encode_pixels_host_roi, whose layer_offs == NULL asks for the single-budget (_rate) stream
+static int encode_pixels_host_layers_impl(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
+                                          bool with_roi, const j2k_rect *roi, int roi_gain, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs,
+                                          uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, const char *who) {
     if (!P || !pix || !out_len) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
-    int r = layers_check(P, nlayers, "j2k_encode_pixels_host_layers");
-    if (r != J2K_OK) return r;
     uint64_t budgets[J2K_MAX_LAYERS];
-    r = budgets_check(ctx, layer_bytes, nlayers, budgets, "j2k_encode_pixels_host_layers");
+    int r;
+    if (with_roi) r = roi_frame_check(P, layer_bytes, nlayers, layer_offs != nullptr, roi, roi_gain, budgets, who);
+    else {
+        r = layers_check(P, nlayers, who);
+        if (r == J2K_OK) r = budgets_check(ctx, layer_bytes, nlayers, budgets, who);
+    }
     if (r != J2K_OK) return r;
     const PlanSpec &S = P->spec;
     const int pb = format == J2K_PIX_GRAY8 ? 1 : format == J2K_PIX_GRAY16 ? 2 : (format == J2K_PIX_RGBA8 || format == J2K_PIX_NRGBA8) ? 4 :
                    (format == J2K_PIX_RGBA64 || format == J2K_PIX_NRGBA64) ? 8 : 0;
     if (!pb || stride < (size_t)S.W * pb) return fail(ctx, J2K_ERR_INVALID_ARG, "pixel format / stride");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t nb = P->blocks.size(), nt = (size_t)P->tile_count, nl = nt * (size_t)nlayers;
-    const size_t bound = j2k_plan_frame_bound_layers(P, nlayers);
+    const size_t nb = P->blocks.size(), nt = (size_t)P->tile_count;
+    size_t nl = nt * (size_t)nlayers;
+    const size_t bound = with_roi ? std::max(j2k_plan_frame_bound_layers(P, nlayers), j2k_plan_frame_bound(P)) : j2k_plan_frame_bound_layers(P, nlayers);
     const size_t toff_at = (bound + 64 + 15) & ~size_t(15);                                  // the tile-parts, and behind them their offsets and the layer ends
     if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, (size_t)S.H * stride)) != J2K_OK) return r;
     if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, toff_at + (nt + 1 + nl + 2) * 8)) != J2K_OK) return r;
     uint64_t *d_toffs = reinterpret_cast<uint64_t *>((uint8_t *)P->d_host_io + toff_at), *d_loffs = d_toffs + nt + 1;
     HIPCHK(ctx, hipMemcpyAsync(P->d_host_pix, pix, (size_t)S.H * stride, hipMemcpyHostToDevice, ctx->stream));
-    r = j2k_plan_encode_frame_pixels_layers(P, format, P->d_host_pix, stride, sop, eph, layer_bytes, nlayers, (uint8_t *)P->d_host_io, bound, d_toffs, d_loffs);
+    if (with_roi) r = j2k_plan_encode_frame_pixels_roi(P, format, P->d_host_pix, stride, sop, eph, layer_bytes, nlayers, roi, roi_gain, (uint8_t *)P->d_host_io, bound, d_toffs,
+                                                       layer_offs ? d_loffs : nullptr);
+    else r = j2k_plan_encode_frame_pixels_layers(P, format, P->d_host_pix, stride, sop, eph, layer_bytes, nlayers, (uint8_t *)P->d_host_io, bound, d_toffs, d_loffs);
     if (r != J2K_OK) return r;
+    if (with_roi && !layer_offs) nl = 0;                                                     // (the single-budget stream has no layer ends)
     std::vector<uint64_t> offs(nt + 1 + nl, 0);
     HIPCHK(ctx, hipMemcpyAsync(offs.data(), d_toffs, offs.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (lens && nb) HIPCHK(ctx, hipMemcpyAsync(lens, P->d_cl_lens, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -270,6 +306,20 @@ extern "C" int j2k_encode_pixels_host_layers(j2k_plan *P, int format, const void
     if (total > cap || (total && !out)) return fail(ctx, J2K_ERR_CAPACITY, "out too small (*out_len says what the tile-parts take)");
     if (total) HIPCHK(ctx, hipMemcpy(out, P->d_host_io, total, hipMemcpyDeviceToHost));
     return J2K_OK;
+}
+
+extern "C" int j2k_encode_pixels_host_layers(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
+                                             uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps) {
+    return encode_pixels_host_layers_impl(P, format, pix, stride, sop, eph, layer_bytes, nlayers, false, nullptr, 1, out, cap, out_len, tile_offs, layer_offs, lens, numbps,
+                                          "j2k_encode_pixels_host_layers");
+}
+// the synchronous host-memory form of j2k_plan_encode_frame_pixels_roi (layer_offs == NULL with nlayers = 1: the single-budget stream)
+extern "C" int j2k_encode_pixels_host_roi(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
+                                          const j2k_rect *roi, int roi_gain, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs,
+                                          uint32_t *lens, uint8_t *numbps) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    return encode_pixels_host_layers_impl(P, format, pix, stride, sop, eph, layer_bytes, nlayers, true, roi, roi_gain, out, cap, out_len, tile_offs, layer_offs, lens, numbps,
+                                          "j2k_encode_pixels_host_roi");
 }
 
 extern "C" int j2k_decode_pixels_host_layers(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int layers, int reduce, int skip_planes, void *pix,

@@ -119,6 +119,54 @@ extern "C" int j2k_plan_encode_blocks_planes(j2k_plan *P, const int32_t *d_coeff
     return J2K_OK;
 }
 
+// ---- region of interest: the footprint of a rectangle counts roi_gain times in the distortion tables (tests/roi_cases.py) --------
+int roi_check(j2k_plan *P, const j2k_rect *roi, int roi_gain, const char *who) {
+    j2k_ctx *ctx = P->ctx;
+    const PlanSpec &S = P->spec;
+    const std::string w(who);
+    if (!S.mallat) return fail(ctx, J2K_ERR_UNSUPPORTED, (w + ": a region of interest needs a Mallat plan (the prefix layout has no spatial footprint below level 0)").c_str());
+    if (P->tile_count != P->tiles_x * P->tiles_y) return fail(ctx, J2K_ERR_UNSUPPORTED, (w + ": a region of interest on a shard plan (tile_first / tile_count)").c_str());
+    if (!roi) return fail(ctx, J2K_ERR_INVALID_ARG, (w + ": no rectangle").c_str());
+    if (roi->x0 < 0 || roi->y0 < 0 || roi->x0 >= roi->x1 || roi->y0 >= roi->y1 || roi->x1 > S.W || roi->y1 > S.H)
+        return fail(ctx, J2K_ERR_INVALID_ARG, (w + ": the rectangle is inverted, empty or outside the frame").c_str());
+    if (roi_gain < 1 || roi_gain > 65535) return fail(ctx, J2K_ERR_INVALID_ARG, (w + ": roi_gain is 1 ... 65535").c_str());
+    return J2K_OK;
+}
+
+extern "C" int j2k_plan_roi_windows(j2k_plan *P, const j2k_rect *roi, int32_t *d_win) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    int r = rate_check(P, "j2k_plan_roi_windows");
+    if (r == J2K_OK) r = roi_check(P, roi, 1, "j2k_plan_roi_windows");
+    if (r != J2K_OK) return r;
+    if (!d_win) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    if ((r = area_tables(P, false)) != J2K_OK) return r;
+    HIPCHK(ctx, launch_roi_windows(ctx->stream, P->d_area_blocks, (int)P->blocks.size(), P->d_area_planes, roi->x0, roi->y0, roi->x1, roi->y1,
+                                   P->spec.wavelet == W97 ? 2 : 1, d_win));
+    return J2K_OK;
+}
+
+int plan_encode_blocks_planes_roi(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate, uint64_t *d_dist,
+                                  const j2k_rect *roi, int roi_gain) {
+    if (!roi) return j2k_plan_encode_blocks_planes(P, d_coeff, d_slots, d_lens, d_numbps, d_rate, d_dist);
+    j2k_ctx *ctx = P->ctx;
+    int r = area_tables(P, false);
+    if (r == J2K_OK) r = plan_encode_blocks_impl(P, d_coeff, d_slots, d_lens, d_numbps, d_rate);
+    if (r != J2K_OK) return r;
+    HIPCHK(ctx, launch_rate_distortion_roi(ctx->stream, P->d_bjobs, (int)P->blocks.size(), d_coeff, d_numbps, P->d_area_blocks, P->d_area_planes, roi->x0, roi->y0,
+                                           roi->x1, roi->y1, P->spec.wavelet == W97 ? 2 : 1, (uint32_t)roi_gain, d_dist));
+    return J2K_OK;
+}
+
+extern "C" int j2k_plan_encode_blocks_planes_roi(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate,
+                                                 uint64_t *d_dist, const j2k_rect *roi, int roi_gain) {
+    if (!P || !d_coeff || !d_slots || !d_lens || !d_numbps || !d_rate || !d_dist) return J2K_ERR_INVALID_ARG;
+    int r = rate_check(P, "j2k_plan_encode_blocks_planes_roi");
+    if (r == J2K_OK) r = roi_check(P, roi, roi_gain, "j2k_plan_encode_blocks_planes_roi");
+    if (r != J2K_OK) return r;
+    return plan_encode_blocks_planes_roi(P, d_coeff, d_slots, d_lens, d_numbps, d_rate, d_dist, roi, roi_gain);
+}
+
 extern "C" int j2k_plan_rate_allocate(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, int64_t max_body_bytes,
                                       uint8_t *d_kept, uint64_t *d_chosen) {
     if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen) return J2K_ERR_INVALID_ARG;

@@ -4,8 +4,9 @@
 //
 //   rate[j * 32 + p]   bytes of block j's codeword that decode its first p bit planes (t1.hip, the PLANES instantiations), p = 0 ... numBPS
 //   dist[j * 32 + p]   sum over the block of (|v| - |coarse(v, numBPS - p)|)^2 in wrapping uint64 arithmetic (0 above numBPS)
+//                      (region of interest, tests/roi_cases.py: the samples that reconstruct a rectangle of the frame count `gain` times)
 //   kept[j]            the planes the allocation keeps of block j
-#include "j2k_internal.h"
+#include "area_walk.h"
 
 namespace j2k {
 
@@ -54,6 +55,45 @@ __global__ __launch_bounds__(64) void rate_distortion_kernel(const BlockJob *__r
     else if (nb <= 12) mine = rate_distortion_sums<12>(J, src, lane);
     else if (nb <= 16) mine = rate_distortion_sums<16>(J, src, lane);
     else mine = rate_distortion_sums<RATE_STRIDE - 1>(J, src, lane);
+    if (lane < RATE_STRIDE) dist[(size_t)jid * RATE_STRIDE + (lane <= nb ? nb - lane : lane)] = lane <= nb ? mine : 0;
+}
+
+// ---- region of interest: the distortion of the samples that reconstruct a rectangle of the frame counts `gain` times ----------------------
+// tests/roi_cases.py is the definition: D_roi[p] = D[p] + (gain - 1) * D_in[p] (mod 2^64), D_in the same sum over the block's footprint F_j
+// alone (area_walk.h: roi_window).  The footprint is a sub-window of the block, so D_in is rate_distortion_sums on a job of that window.
+__device__ __forceinline__ uint64_t rate_distortion_of(int nb, const BlockJob &J, const int32_t *__restrict__ src, int lane) {
+    if (nb <= 8) return rate_distortion_sums<8>(J, src, lane);
+    if (nb <= 12) return rate_distortion_sums<12>(J, src, lane);
+    if (nb <= 16) return rate_distortion_sums<16>(J, src, lane);
+    return rate_distortion_sums<RATE_STRIDE - 1>(J, src, lane);
+}
+
+// One wavefront per block, as rate_distortion_kernel; blocks / planes: the tables of area_blocks_kernel (job j = block j).  Every choice below
+// is wave-uniform: the block, its numBPS, the rectangle and the gain are.
+__global__ __launch_bounds__(64) void rate_distortion_roi_kernel(const BlockJob *__restrict__ jobs, int njobs, const int32_t *__restrict__ coef,
+                                                                  const uint8_t *__restrict__ numbps, const j2k_block *__restrict__ blocks,
+                                                                  const AreaPlane *__restrict__ planes, int rx0, int ry0, int rx1, int ry1, int margin,
+                                                                  uint32_t gain, uint64_t *__restrict__ dist) {
+    const int jid = blockIdx.x;
+    if (jid >= njobs) return;
+    const int lane = threadIdx.x;
+    const BlockJob J = jobs[jid];
+    const int nb = min((int)numbps[jid], RATE_STRIDE - 1);
+    uint64_t mine = 0;
+    if (nb > 0) {
+        mine = rate_distortion_of(nb, J, coef + J.src_off, lane);
+        if (gain > 1) {
+            const j2k_block b = blocks[jid];
+            const RoiWin F = roi_window(b, planes[b.plane], rx0, ry0, rx1, ry1, margin);
+            if (F.w == J.w && F.h == J.h) mine *= (uint64_t)gain;            // the whole block: gain * D
+            else if (F.w > 0) {
+                BlockJob S = J;
+                S.src_off = J.src_off + (int64_t)F.y * J.stride + F.x;
+                S.w = F.w; S.h = F.h;
+                mine += (uint64_t)(gain - 1) * rate_distortion_of(nb, S, coef + S.src_off, lane);
+            }
+        }
+    }
     if (lane < RATE_STRIDE) dist[(size_t)jid * RATE_STRIDE + (lane <= nb ? nb - lane : lane)] = lane <= nb ? mine : 0;
 }
 
@@ -211,7 +251,14 @@ hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs
     return hipGetLastError();
 }
 
-hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+hipError_t launch_rate_distortion_roi(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, const j2k_block *blocks,
+                                      const AreaPlane *planes, int x0, int y0, int x1, int y1, int margin, uint32_t gain, uint64_t *dist) {
+    if (njobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rate_distortion_roi_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, numbps, blocks, planes, x0, y0, x1, y1, margin, gain, dist);
+    return hipGetLastError();
+}
+
+hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate,const uint64_t *dist, const uint8_t *numbps, const double *weights,
                                 uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen) {
     hipLaunchKernelGGL(rate_allocate_kernel, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, budget, ws, kept, chosen);
     return hipGetLastError();

@@ -75,6 +75,7 @@ SYMBOLS = [
     "j2k_plan_encode_frame_pixels_layers", "j2k_plan_decode_frame_pixels_layers", "j2k_encode_pixels_host_layers", "j2k_decode_pixels_host_layers",
     "j2k_tile_parts_keep_layers",
     "j2k_plan_area_shape", "j2k_plan_area_blocks", "j2k_plan_decode_frame_pixels_area", "j2k_decode_pixels_host_area",
+    "j2k_plan_roi_windows", "j2k_plan_encode_blocks_planes_roi", "j2k_plan_encode_frame_pixels_roi", "j2k_encode_pixels_host_roi",
     "j2k_plan_pack_bound", "j2k_plan_pack_stream", "j2k_plan_unpack_stream", "j2k_plan_unpack_streams",
     "j2k_comm_load_error", "j2k_comm_get_unique_id", "j2k_comm_create", "j2k_comm_destroy", "j2k_comm_last_error", "j2k_comm_stream", "j2k_gather_streams", "j2k_comm_wait",
 ]
@@ -94,7 +95,7 @@ class Image(C.Structure):
 
 
 class Rect(C.Structure):
-    """j2k_rect: half-open, full-resolution frame coordinates (the area= of the decode calls)"""
+    """j2k_rect: half-open, full-resolution frame coordinates (the area= of the decode calls, the roi= of the encode calls)"""
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32)]
 
 
@@ -163,6 +164,10 @@ def lib():
             "j2k_plan_area_blocks": (I, [V, C.POINTER(Rect), I, V]),
             "j2k_plan_decode_frame_pixels_area": (I, [V, V, S, V, I, I, I, I, I, I, C.POINTER(Rect), V, S]),
             "j2k_decode_pixels_host_area": (I, [V, V, S, I, I, I, I, I, I, C.POINTER(Rect), V, S]),
+            "j2k_plan_roi_windows": (I, [V, C.POINTER(Rect), V]),
+            "j2k_plan_encode_blocks_planes_roi": (I, [V, V, V, V, V, V, V, C.POINTER(Rect), I]),
+            "j2k_plan_encode_frame_pixels_roi": (I, [V, I, V, S, I, I, I64P, I, C.POINTER(Rect), I, V, S, V, V]),
+            "j2k_encode_pixels_host_roi": (I, [V, I, V, S, I, I, I64P, I, C.POINTER(Rect), I, V, S, C.POINTER(S), V, V, V, V]),
         }
         for name, (res, args) in sigs.items():
             if partial and not hasattr(L, name):

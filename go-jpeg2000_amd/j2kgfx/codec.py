@@ -168,6 +168,18 @@ class FramePlan:
         self.ctx.check(self.ctx.L.j2k_plan_area_blocks(self.h, C.byref(r), int(reduce), self._p(need)))
         return need[:n]
 
+    # ---- region-of-interest encode (Mallat closed-loop MQ plans; j2k_plan_*_roi) --------------
+    @_stage
+    def roi_windows(self, roi, win=None):
+        """device int32 [blocks, 4]: (fx, fy, fw, fh), the footprint of roi=(x0, y0, x1, y1) (half-open, full-resolution frame coordinates)
+        inside every code-block, relative to the block's window; all 0 where there is none (j2k_plan_roi_windows)"""
+        t = _torch()
+        n = int(self.info.blocks)
+        win = win if win is not None else t.zeros((max(n, 1), 4), dtype=t.int32, device=self.device)
+        r = self._rect(roi)
+        self.ctx.check(self.ctx.L.j2k_plan_roi_windows(self.h, C.byref(r), self._p(win)))
+        return win[:n]
+
     @_stage
     def inverse(self, coeff, frame=None, reduce=0):
         """reduce > 0 (Mallat plans): stop at level `reduce`, frame = int32 [C, H_r, W_r] (reduced_shape)"""
@@ -198,9 +210,13 @@ class FramePlan:
         return pix
 
     @_stage
-    def encode_blocks(self, coeff, slots=None, lens=None, numbps=None, planes=False):
+    def encode_blocks(self, coeff, slots=None, lens=None, numbps=None, planes=False, roi=None, roi_gain=16):
         """planes=True (closed-loop MQ plans, blocks <= 64 x 64): also the rate and distortion tables of every block, int32 / int64
-        [blocks, 32] holding uint32 / uint64 values (j2k_plan_encode_blocks_planes) -- returns (slots, lens, numbps, rate, dist)"""
+        [blocks, 32] holding uint32 / uint64 values (j2k_plan_encode_blocks_planes) -- returns (slots, lens, numbps, rate, dist).
+        roi=(x0, y0, x1, y1) with planes=True (Mallat plans): the distortion of the samples that reconstruct that rectangle counts roi_gain
+        (1 ... 65535) times in dist; everything else is identical (j2k_plan_encode_blocks_planes_roi)"""
+        if roi is not None and not planes:
+            raise ValueError("encode_blocks: roi= weights the distortion tables -- it needs planes=True")
         t = _torch()
         n = int(self.info.blocks)
         slots = slots if slots is not None else self.empty(self.info.bytes_cap, t.uint8)
@@ -209,6 +225,11 @@ class FramePlan:
         if planes:
             rate = t.zeros((max(n, 1), 32), dtype=t.int32, device=self.device)
             dist = t.zeros((max(n, 1), 32), dtype=t.int64, device=self.device)
+            if roi is not None:
+                r = self._rect(roi)
+                self.ctx.check(self.ctx.L.j2k_plan_encode_blocks_planes_roi(self.h, self._p(coeff), self._p(slots), self._p(lens), self._p(numbps), self._p(rate),
+                                                                            self._p(dist), C.byref(r), int(roi_gain)))
+                return slots, lens, numbps, rate, dist
             self.ctx.check(self.ctx.L.j2k_plan_encode_blocks_planes(self.h, self._p(coeff), self._p(slots), self._p(lens),
                                                                     self._p(numbps), self._p(rate), self._p(dist)))
             return slots, lens, numbps, rate, dist
@@ -458,13 +479,33 @@ class FramePlan:
         return int(n.value)
 
     @_stage
-    def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None, max_body_bytes=None, layer_bytes=None):
+    def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16):
         """pixels (a Go Pix layout, device uint8 [H, stride]) -> tile-parts: (out uint8, tile_offs int64[tiles + 1]).  max_body_bytes (closed-loop
         MQ plans): at most that many bytes of code-block bodies -- packet and tile-part headers come on top, tile_offs[-1] says what the frame took
         (j2k_plan_encode_frame_pixels_rate); decode with truncated=True.  layer_bytes = [B_0 <= B_1 <= ...] (the same plans; not together with
         max_body_bytes): ONE stream of len(layer_bytes) quality layers, layer l cut as max_body_bytes = B_l would -> (out, tile_offs, layer_offs
-        int64 [tiles * L], where every layer of every tile ends) (j2k_plan_encode_frame_pixels_layers); decode with layers=k"""
+        int64 [tiles * L], where every layer of every tile ends) (j2k_plan_encode_frame_pixels_layers); decode with layers=k.
+        roi=(x0, y0, x1, y1) with either budget (Mallat plans): a region of interest -- the distortion of the coefficients that reconstruct that
+        rectangle counts roi_gain times (an integer 1 ... 65535, a weight on energy: 4^s is about s bit planes of priority), so the budget
+        goes there first.  The stream and its decoders are as without it; decode with area=roi for the rectangle alone
+        (j2k_plan_encode_frame_pixels_roi).  roi=None takes the calls it took before"""
         t = _torch()
+        if roi is not None:
+            if max_body_bytes is None and layer_bytes is None:
+                raise ValueError("encode_frame_pixels: roi= shifts a budget -- give max_body_bytes= or layer_bytes=")
+            if max_body_bytes is not None and layer_bytes is not None:
+                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "encode_frame_pixels: layer_bytes and max_body_bytes together")
+            layered = layer_bytes is not None
+            arr, L = self._layer_bytes(layer_bytes if layered else [max_body_bytes])
+            nt = int(self.info.tiles)
+            r = self._rect(roi)
+            out = out if out is not None else self.empty((self.frame_bound_layers(L) or 64) if layered else self.frame_bound(), t.uint8)
+            tile_offs = tile_offs if tile_offs is not None else self.empty(nt + 1, t.int64)[:nt + 1]
+            layer_offs = self.empty(nt * max(L, 1), t.int64)[:nt * max(L, 1)] if layered else None
+            self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_roi(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
+                                                                       arr, L, C.byref(r), int(roi_gain), self._p(out), C.c_size_t(int(out.numel())),
+                                                                       self._p(tile_offs), self._p(layer_offs) if layered else None))
+            return (out, tile_offs, layer_offs) if layered else (out, tile_offs)
         if layer_bytes is not None:
             if max_body_bytes is not None:
                 raise _lib.J2KError(_lib.ERR_INVALID_ARG, "encode_frame_pixels: layer_bytes and max_body_bytes together")
@@ -526,12 +567,37 @@ class FramePlan:
         return pix
 
     # ---- host memory in, host memory out: the one-call forms (j2k_encode_pixels_host / j2k_decode_pixels_host) -------------------
-    def encode_pixels_host(self, fmt, pix, sop=False, eph=False, cap=None, max_body_bytes=None, layer_bytes=None):
+    def encode_pixels_host(self, fmt, pix, sop=False, eph=False, cap=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16):
         """pix: numpy uint8 [H, stride] (a Go Pix layout) -> dict(bytes, tile_offs, lens, numbps): every tile as a tile-part.  max_body_bytes: as
         encode_frame_pixels (j2k_encode_pixels_host_rate; lens / numbps are the uncut ones); layer_bytes: as encode_frame_pixels, the dict also
-        holds layer_offs uint64 [tiles * L] (j2k_encode_pixels_host_layers)"""
+        holds layer_offs uint64 [tiles * L] (j2k_encode_pixels_host_layers); roi, roi_gain with either budget: as encode_frame_pixels
+        (j2k_encode_pixels_host_roi)"""
         L = self.ctx.L
         n, nt = int(self.info.blocks), int(self.info.tiles)
+        if roi is not None:
+            if max_body_bytes is None and layer_bytes is None:
+                raise ValueError("encode_pixels_host: roi= shifts a budget -- give max_body_bytes= or layer_bytes=")
+            if max_body_bytes is not None and layer_bytes is not None:
+                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "encode_pixels_host: layer_bytes and max_body_bytes together")
+            layered = layer_bytes is not None
+            arr, nl = self._layer_bytes(layer_bytes if layered else [max_body_bytes])
+            r = self._rect(roi)
+            cap = int(cap) if cap is not None else max(self.frame_bound_layers(nl) or 64, self.frame_bound()) + 64
+            pix = np.ascontiguousarray(pix, dtype=np.uint8)
+            out = np.zeros(max(cap, 1), np.uint8)
+            toffs = np.zeros(nt + 1, np.uint64); loffs = np.zeros(max(nt * nl, 1), np.uint64)
+            lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
+            olen = C.c_size_t(0)
+            st = L.j2k_encode_pixels_host_roi(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)), arr, nl,
+                                              C.byref(r), int(roi_gain), out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen),
+                                              toffs.ctypes.data_as(C.c_void_p), loffs.ctypes.data_as(C.c_void_p) if layered else None,
+                                              lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p))
+            self.encoded_len = olen.value
+            self.ctx.check(st)
+            res = dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
+            if layered:
+                res["layer_offs"] = loffs[:nt * nl].copy()
+            return res
         if layer_bytes is not None:
             if max_body_bytes is not None:
                 raise _lib.J2KError(_lib.ERR_INVALID_ARG, "encode_pixels_host: layer_bytes and max_body_bytes together")

@@ -846,6 +846,41 @@ int j2k_plan_decode_frame_pixels_area(j2k_plan *plan, const uint8_t *d_cs, size_
 int j2k_decode_pixels_host_area(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, int layers, int truncated, int reduce,
                                 int skip_planes, const j2k_rect *area, void *pix, size_t stride);
 
+/* Region-of-interest encode (the library's own; the reference has nothing usable here): a rectangle of the frame that the rate control of the
+ * closed-loop MQ codec favours.  `roi` is half-open, in full-resolution frame coordinates, as `area` above; `roi_gain` = g is an integer in
+ * 1 ... 65535.  Not Maxshift and no change of format: the distortion of the coefficients that reconstruct the rectangle counts g times in the
+ * blocks' distortion tables, and the allocation of the budget(s) does the rest.  Streams, packets and every decoder are as before: read such a
+ * stream with the _rate / _layers decode calls like any other, and with `area` = the same rectangle.  The decoder is not told.
+ *   The rule (definition: tests/roi_cases.py).  Per tile the rectangle is cut to the tile; its need rectangles at reduce = 0 (the
+ * region decode's, margins 1 for the 5-3 and 2 for the 9-7) are its footprint in the plane.  A block lies in one band and a band has one need
+ * rectangle, so the footprint inside block j is one window F_j, possibly empty.  d_dist[j * 32 + p] = D[p] + (g - 1) * D_in[p] mod 2^64, D the
+ * table of j2k_plan_encode_blocks_planes and D_in the same sum over F_j alone: g = 1 or no footprint gives D, a block wholly inside g * D.
+ * g weights energy: g = 4^s gives the rectangle about s bit planes of priority; with 8- to 16-bit sources every product stays far below 2^53,
+ * so the allocation's float64 slopes see exact integers.  d_rate, the band weights, the hull, the bisection and the packets are untouched.
+ *   j2k_plan_roi_windows               d_win[4 j ...] = (fx, fy, fw, fh) of F_j relative to block j's window, all 0 when empty (device int32,
+ *                                      4 per job; asynchronous)
+ *   j2k_plan_encode_blocks_planes_roi  j2k_plan_encode_blocks_planes with the table above in d_dist (slots, lens, numbps, rate: identical)
+ *   j2k_plan_encode_frame_pixels_roi   the frame call for both budget forms: nlayers = 1 with d_layer_offs = NULL writes the stream of
+ *                                      j2k_plan_encode_frame_pixels_rate for max_body_bytes = layer_bytes[0]; with d_layer_offs it is
+ *                                      j2k_plan_encode_frame_pixels_layers.  Only the distortion launch differs: it takes the rectangle and the gain
+ *   j2k_encode_pixels_host_roi         its synchronous host-memory form (layer_offs = NULL with nlayers = 1: the single-budget stream)
+ * The rectangle and the gain are kernel arguments: no host table per rectangle, no synchronisation; a captured graph is valid for the rectangle
+ * and gain it captured (the plan tables of the region decode are made at the first call: run it once before a capture).
+ *   J2K_ERR_UNSUPPORTED: what j2k_plan_rate_allocate refuses (HT, no closed loop, batch, blocks above 64 x 64), a plan that is not Mallat (the
+ * prefix layout has no spatial footprint below level 0), a shard plan.  J2K_ERR_INVALID_ARG: a rectangle that is inverted, empty or outside the
+ * frame, roi_gain outside 1 ... 65535, no budgets, what the _layers call refuses of its budgets, more than one budget without d_layer_offs.
+ * Every refusal comes before the first launch.  One rectangle, no mask, no per-coefficient shift; block-granular in effect, since whole bit
+ * planes of whole blocks are kept or cut. */
+int j2k_plan_roi_windows(j2k_plan *plan, const j2k_rect *roi, int32_t *d_win);
+int j2k_plan_encode_blocks_planes_roi(j2k_plan *plan, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps,
+                                      uint32_t *d_rate, uint64_t *d_dist, const j2k_rect *roi, int roi_gain);
+int j2k_plan_encode_frame_pixels_roi(j2k_plan *plan, int format, const void *d_pix, size_t stride, int sop, int eph,
+                                     const int64_t *layer_bytes, int nlayers, const j2k_rect *roi, int roi_gain, uint8_t *d_out, size_t cap,
+                                     uint64_t *d_tile_offs, uint64_t *d_layer_offs);
+int j2k_encode_pixels_host_roi(j2k_plan *plan, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *layer_bytes,
+                               int nlayers, const j2k_rect *roi, int roi_gain, uint8_t *out, size_t cap, size_t *out_len,
+                               uint64_t *tile_offs, uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps);
+
 /* The block coder's outputs as those tables.  j2k_plan_t2_packets (host table out): one packet per (tile, component,
  * resolution) of the plan in job order (encoder.go:616-673: tile, component, resolution, band, block row, block column), its
  * code-blocks = the plan's jobs of that resolution, tree widths = block columns of its first band; layer as given.
