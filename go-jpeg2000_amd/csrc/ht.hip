@@ -1167,6 +1167,7 @@ __device__ bool init_mel_ok(const uint8_t *data, long len, long lcup, long scup)
 #define HT_WALK_REC 132                        /* words per block: 128 pair records + flags (+pad) */
 #define HT_PAIR_SERIAL 0xFFFFFFFFu              /* record[0]: decode this block with the serial path */
 #define HT_PAIR_ZERO 0xFFFFFFFEu                /* record[0]: invalid stream -> output stays zero     */
+#define HT_PAIR_DUP 0xFFFFFFFDu                 /* record[0]: the block's bytes equal its leader's, whose wavefront stores this block's rows too (record[1]: the leader; ht_vlcprep_dedup_kernel and the DEDUP instantiations only) */
 
 // Single-wavefront workgroups: DS instructions of one wave execute in order, so LDS written by one lane is
 // visible to the others without an s_barrier; only the compiler must not reorder.  Unlike __syncthreads()
@@ -1338,6 +1339,64 @@ __global__ __launch_bounds__(256) void ht_vlcprep_kernel(const BlockJob *__restr
     for (int i = lane; i < HT_VBITS_WORDS; i += 64) dst[i] = vb[i];
 }
 
+// ---- byte-identical blocks once (option ht_dec_dedup; launch_ht_decode passes the plan's tables) ----
+// The reference addresses every block window from the top left and its HT coder ignores the band, so in any stream its encoder wrote the jobs of one
+// window carry the same bytes (the encoder codes each window once: ht_encode_wg_kernel).  The plan names, per job, a LEADER with the same window,
+// width and height (rep[jid]; jid itself: none).  The table is a hint and is never trusted: the follower's wavefront compares the two blocks here, and
+// only when they are equal does it write HT_PAIR_DUP and stop -- no unstuffing, no bit string, no walk, no decode; ht_decode_lean_kernel<false, true>'s leader
+// wavefront stores its rows to the follower's block as well.  On any difference the block goes on exactly as in ht_vlcprep_kernel and decodes itself.
+//
+// What is compared: the lengths, and EVERY byte [0, len) of the two blocks.  That is a superset of what any decode path reads -- the parallel paths read
+// the MagSgn segment [0, len - scup) (ht_extract_fast and the lean path, whole, in 1 KB batches), the at most four bytes at the MEL start (init_mel_ok),
+// the VLC bytes [len - 2 - ht_vlc_nbytes, len - 2) (ht_vlc_load4) and the two trailer bytes (ht_vlc_head); the serial path of ht_decode_block reads the
+// same segments byte by byte; nothing reads the interior of the MEL run, which is a few bytes and rides along rather than being cut out of the loop.
+// Same bytes, same w, h and len give the same tag, records and samples, on whichever path the leader ends up; nothing else enters the decision.
+// (A block shorter than four bytes is never a follower: the compare works in 4-byte pieces, the last one pulled back to end at len.)
+// Round trips: rep[jid] rides with the job, offs[rep] / lens[rep] with the trailer bytes, the first 1 KB of both blocks with the VLC bytes: four, as before.
+// A block longer than 1 KB takes one more per KB, and stops at the first batch that differs.
+__global__ __launch_bounds__(256) void ht_vlcprep_dedup_kernel(const BlockJob *__restrict__ jobs, int njobs,
+                                                               const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offs,
+                                                               const uint32_t *__restrict__ lens, uint32_t *__restrict__ vbits,
+                                                               uint32_t *__restrict__ pairs, const int32_t *__restrict__ rep) {
+    __shared__ uint32_t vb4[4][HT_VBITS_WORDS + 8];
+    uint32_t *vb = vb4[threadIdx.x >> 6];
+    const int jid = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (jid >= njobs) return;
+    const int lane = threadIdx.x & 63;
+    uint32_t *rec = pairs + (size_t)jid * HT_WALK_REC;
+    const int ldr = rep[jid];
+    const uint64_t loff = offs[ldr];
+    const uint32_t llen = lens[ldr];
+    const HtVlcHead H = ht_vlc_head(jobs, jid, stream, offs, lens);
+    const long nb = H.tag ? 0 : ht_vlc_nbytes(H);
+    uint32_t pre[HT_VLC_STEPS];
+#pragma unroll
+    for (int c = 0; c < HT_VLC_STEPS; c++) pre[c] = ht_vlc_load4(H.data, (long)H.len, nb, 1 + 256 * c + 4 * lane);
+    if (ldr != jid && H.tag == 0 && llen == H.len && H.len >= 4) {       // wave-uniform
+        const uint8_t *mine = H.data, *theirs = stream + loff;
+        const uint32_t len = H.len, nd = (len + 3) >> 2;
+        bool same = true;
+        for (uint32_t j0 = 0; j0 < nd && same; j0 += 256) {
+            uint32_t x[4], y[4];
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const uint32_t p = min(4 * (j0 + 64 * c + lane), len - 4);   // piece j of both blocks; past the end: the last piece again
+                __builtin_memcpy(&x[c], mine + p, 4);
+                __builtin_memcpy(&y[c], theirs + p, 4);
+            }
+            same = __all((x[0] == y[0]) & (x[1] == y[1]) & (x[2] == y[2]) & (x[3] == y[3]));
+        }
+        if (same) {
+            if (lane == 0) { rec[0] = HT_PAIR_DUP; rec[1] = (uint32_t)ldr; rec[HT_WALK_MAX_PAIRS] = H.scup; }   // (the leader: for the decode kernel)
+            return;
+        }
+    }
+    ht_vlc_unstuff(H, lane, vb, rec, pre);
+    if (H.tag) return;
+    uint32_t *dst = vbits + (size_t)jid * HT_VBITS_WORDS;
+    for (int i = lane; i < HT_VBITS_WORDS; i += 64) dst[i] = vb[i];
+}
+
 #ifndef HT_WALK_BLOCKS
 #define HT_WALK_BLOCKS 64                      /* blocks (= walking lanes) per workgroup: 64 or 32 */
 #endif
@@ -1366,13 +1425,14 @@ __device__ __forceinline__ uint32_t uvlc_used_later(uint32_t vlc, uint32_t uOff1
 //
 // The walk of one workgroup's blocks by its wavefront 0, all 64 lanes active on entry: lane l walks the string at `row` and writes the
 // block's records to `rec`.  Shared by ht_walk_kernel and ht_front_kernel.  Returns the bits the lane consumed.
+template <bool DEDUP = false>
 __device__ __forceinline__ uint32_t ht_walk_lane(const uint32_t *row, const uint16_t *tbl0, const uint16_t *tbl1, const uint16_t *pair1,
                                                  uint32_t *rec, int w, int h, bool have, uint32_t tag) {
     const int quadCols = (w + 3) / 4, P = (quadCols + 1) / 2, R = (h + 3) / 4;
     // the walking wavefront's trip count: the largest pair count among its blocks -- reduced while all 64 lanes are still
     // active (a butterfly over a wave with holes leaves different partial maxima in different lanes: taken after the early
     // returns below it cut some blocks' walks short, found by tools/fuzz_gpu.py on a frame of mixed block sizes)
-    const bool walks = have && tag != HT_PAIR_SERIAL && tag != HT_PAIR_ZERO;
+    const bool walks = have && tag != HT_PAIR_SERIAL && tag != HT_PAIR_ZERO && tag != (DEDUP ? HT_PAIR_DUP : HT_PAIR_ZERO);   // (a DUP block has no string: its leader is walked)
     int nsteps = walks ? R * P : 0;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) nsteps = max(nsteps, __shfl_xor(nsteps, o));
@@ -1435,6 +1495,8 @@ __device__ __forceinline__ uint32_t ht_walk_lane(const uint32_t *row, const uint
     return pos;
 }
 
+// DEDUP (behind ht_vlcprep_dedup_kernel): a lane whose block is tagged HT_PAIR_DUP idles (the chain per block is what the kernel costs, so nothing else changes)
+template <bool DEDUP>
 __global__ __launch_bounds__(256) void ht_walk_kernel(const BlockJob *__restrict__ jobs, int njobs,
                                                      const uint32_t *__restrict__ vbits, uint32_t *__restrict__ pairs) {
     extern __shared__ __align__(16) unsigned char walk_smem[];
@@ -1482,7 +1544,7 @@ __global__ __launch_bounds__(256) void ht_walk_kernel(const BlockJob *__restrict
     const long long st1 = __builtin_amdgcn_s_memtime();
 #endif
     if (tid >= 64) return;
-    const uint32_t pos = ht_walk_lane(&S.vb[lane][0], S.tbl0, S.tbl1, S.pair1, rec, w, h, have, tag);
+    const uint32_t pos = ht_walk_lane<DEDUP>(&S.vb[lane][0], S.tbl0, S.tbl1, S.pair1, rec, w, h, have, tag);
     (void)pos;
 #ifdef J2K_WALK_STAMP
     const long long st2 = __builtin_amdgcn_s_memtime();
@@ -1865,7 +1927,7 @@ template <bool STRIDED>
 __device__ __forceinline__ void ht_decode_block(HtDecShared &S, const int jid, const int lane, const BlockJob *__restrict__ jobs,
                                                 const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offs,
                                                 const uint32_t *__restrict__ lens, int32_t *__restrict__ decoded,
-                                                const uint32_t *__restrict__ pairs, int coded_rows_only_) {
+                                                const uint32_t *__restrict__ pairs, int coded_rows_only_, const int rjid) {   // rjid: whose records the block decodes from (jid; a DUP block: its leader)
     const int coded_rows_only = STRIDED ? 1 : coded_rows_only_;
 #ifdef J2K_DEC_STAMP
     const long long d0 = wall_clock64();
@@ -1876,7 +1938,7 @@ __device__ __forceinline__ void ht_decode_block(HtDecShared &S, const int jid, c
     int32_t *out = decoded + J.out_off;
     const size_t n = (size_t)w * h;
     // records first (their latency hides behind the zero fill)
-    const uint32_t *rec = pairs + (size_t)jid * HT_WALK_REC;
+    const uint32_t *rec = pairs + (size_t)rjid * HT_WALK_REC;
     const uint32_t r0 = rec[lane], r1 = rec[64 + lane];
     const uint64_t my_off = offs[jid];                         // (issued with the records: one round trip for all of them)
     const uint32_t my_len = lens[jid], my_scup = rec[HT_WALK_MAX_PAIRS];
@@ -2104,7 +2166,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     __shared__ HtDecShared S4[4];
     const int jid = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (jid >= njobs) return;
-    ht_decode_block<STRIDED>(S4[threadIdx.x >> 6], jid, threadIdx.x & 63, jobs, stream, offs, lens, decoded, pairs, coded_rows_only_);
+    ht_decode_block<STRIDED>(S4[threadIdx.x >> 6], jid, threadIdx.x & 63, jobs, stream, offs, lens, decoded, pairs, coded_rows_only_, jid);
 }
 
 // ---- ht_decode_lean_kernel (option ht_dec_lean, the default): the same decoder with the common case written out on its own ----
@@ -2115,11 +2177,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
 // kept in registers (no S.pair), 32-bit offsets from one base, and none of the u > 31 machinery.  Every other block -- and a lean candidate in which
 // a u above 31 turns up, before anything but zero rows has been stored -- goes through ht_decode_block at the end, which starts the block afresh.
 // (55 VGPRs: eight wavefronts per SIMD would fit, and gained 0.7 % on the headline, but cost the closed-loop HT configuration 0.6 %: KERNEL_NOTES 4w)
-template <bool STRIDED>
+// DEDUP (fol != null; behind ht_vlcprep_dedup_kernel): a leader reads its follower list (fol[8 jid + 1 ..]: ids) with the job, the followers' tags and
+// offsets with the second round trip, keeps the output bases of those the prep verified and issues every store of the lean path once per base.  A block
+// tagged HT_PAIR_DUP only finds out, from its leader's records, that the leader stays on the lean path, and returns.  (A leader that leaves it decodes
+// itself alone, and so does each of its followers: the general decoder in a loop over the followers -- one wavefront, block after block -- makes the
+// job loop-variant all through its 9 000 instructions and spilt registers on the lean path: 72 VGPRs + 212 bytes of private segment.)
+template <bool STRIDED, bool DEDUP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void ht_decode_lean_kernel(const BlockJob *__restrict__ jobs, int njobs,
                                                         const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offs,
                                                         const uint32_t *__restrict__ lens, int32_t *__restrict__ decoded,
-                                                        const uint32_t *__restrict__ pairs, int coded_rows_only_) {
+                                                        const uint32_t *__restrict__ pairs, int coded_rows_only_, const int32_t *__restrict__ fol) {
+    static_assert(!(STRIDED && DEDUP), "followers are dense blocks with the leader's row stride");
     const int coded_rows_only = STRIDED ? 1 : coded_rows_only_;
     __shared__ HtDecShared S4[4];
     // the wavefront's number as a scalar: the job, its lengths and every test on them are then scalar work and scalar branches
@@ -2137,7 +2205,47 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     const uint64_t my_off = offs[jid];
     const uint32_t my_len = lens[jid], my_scup = rec[HT_WALK_MAX_PAIRS];
     const uint32_t tag = (uint32_t)__builtin_amdgcn_readfirstlane((int)rr[0]);   // lane 0's (every lane is active here)
-    const bool lean = tag != HT_PAIR_ZERO && tag != HT_PAIR_SERIAL && (w == 64 || w == 32 || w == 16 || w == 8) && (((uintptr_t)out) & 15) == 0 &&
+    // DEDUP.  A block tagged HT_PAIR_DUP (record 1: its leader) takes the leader's records and goes as far as the leader's decision for or against the
+    // lean path, which is the same here (same records, same width, same alignment of the window: both offsets are multiples of four samples): lean, and
+    // the leader stores this block's rows; otherwise both take the general decoder, this block on its own bytes with the leader's records.
+    // A leader: lane i < 7 looks after follower i of its list -- the id (0: none; a follower is never job 0), whether the prep verified it, where its
+    // block starts -- and `fmask` has a bit per verified follower.  (The lean path has no scalar register to spare: the bases stay in two VGPRs and a
+    // store site reads them lane by lane.)
+    uint32_t rv[2] = {rr[0], rr[1]}, tagv = tag;
+    int rjid = jid;
+    uint32_t fmask = 0, flo = 0, fhi = 0;
+    if constexpr (DEDUP) {
+        if (tag == HT_PAIR_DUP) {
+            rjid = __builtin_amdgcn_readlane((int)rr[0], 1);
+            const uint32_t *lrec = pairs + (size_t)rjid * HT_WALK_REC;
+            rv[0] = lrec[lane]; rv[1] = lrec[64 + lane];
+            tagv = (uint32_t)__builtin_amdgcn_readfirstlane((int)rv[0]);
+        } else {
+            int fid = 0;
+            if (lane < J2K_HT_DEC_MAX_FOLLOWERS) fid = fol[(size_t)jid * (J2K_HT_DEC_MAX_FOLLOWERS + 1) + 1 + lane];
+            bool ok = false;
+            if (fid > 0) {
+                ok = pairs[(size_t)fid * HT_WALK_REC] == HT_PAIR_DUP;
+                const uint64_t a = (uint64_t)(uintptr_t)(decoded + jobs[fid].out_off);
+                flo = (uint32_t)a; fhi = (uint32_t)(a >> 32);
+            }
+            fmask = (uint32_t)__ballot(ok);
+        }
+    }
+    const bool mine = !DEDUP || rjid == jid;                 // not a DUP block: loads, stores and decodes
+    // every store of the lean path: the block's own, and the same 16 bytes at the same place of every verified follower
+    auto st_all = [&](int32_t *p, int a, int b, int c, int d) {
+        st_decoded(p, a, b, c, d);
+        if constexpr (DEDUP) {
+            for (uint32_t m = fmask; m; m &= m - 1) {
+                const int i = __builtin_ctz(m);
+                int32_t *fo = reinterpret_cast<int32_t *>((uintptr_t)((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)flo, i) |
+                                                                      (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)fhi, i) << 32));
+                st_decoded(fo + (p - out), a, b, c, d);
+            }
+        }
+    };
+    const bool lean = tagv != HT_PAIR_ZERO && tagv != HT_PAIR_SERIAL && (w == 64 || w == 32 || w == 16 || w == 8) && (((uintptr_t)out) & 15) == 0 &&
                       (!STRIDED || (os & 3) == 0);
     if (lean) {
     const uint32_t psh = (uint32_t)__builtin_ctz((unsigned)w) - 3, P = 1u << psh;   // pair it = (row it >> psh, pair it & (P - 1) of the row)
@@ -2151,17 +2259,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     const uint32_t *wsrc = reinterpret_cast<const uint32_t *>(data - d);
     const uint32_t ndw = (d + nb + 3) >> 2;                     // aligned dwords covering the segment
     uint32_t raw0[4] = {0, 0, 0, 0};
-    if (ndw > 0) {
+    if (ndw > 0 && mine) {
 #pragma unroll
         for (int c = 0; c < 4; c++) {
             const uint32_t j = 64 * c + lane;
             raw0[c] = wsrc[j < ndw ? j : ndw - 1];
         }
     }
-    if (!coded_rows_only) {                                     // (dense blocks only: row stride w) quad i lies in row i / (w / 4); the coded rows are left out
+    if (!coded_rows_only && mine) {                                     // (dense blocks only: row stride w) quad i lies in row i / (w / 4); the coded rows are left out
         const uint32_t nq = (uint32_t)(w * h) >> 2, qsh = psh + 1;
         for (uint32_t i = lane; i < nq; i += 64)
-            if ((i >> qsh) & 3) st_decoded(out + 4 * i, 0, 0, 0, 0);
+            if ((i >> qsh) & 3) st_all(out + 4 * i, 0, 0, 0, 0);
     }
     // u0 / u1 of every pair and its position in the MagSgn bit string
     uint32_t info2[2] = {0, 0}, mpos2[2] = {0, 0}, total_bits = 0;           // info: rho | rho2 << 4 | u0 << 8 | u1 << 14, in registers (no S.pair)
@@ -2170,7 +2278,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     for (int t = 0; t < 2; t++) {
         if (64u * t >= N) break;
         const uint32_t it = lane + 64 * t;
-        const uint32_t r = rr[t], mode = (r >> 13) & 3, vw = r >> 16;
+        const uint32_t r = rv[t], mode = (r >> 13) & 3, vw = r >> 16;
         // decode_uvlc_later, and for the block's first row (lanes 0..7 of round 0) decode_uvlc(.., initial): they differ only when both u-VLCs are
         // present and the first prefix is three bits long (ht.go:756-764)
         const uint32_t t1 = (mode & 1) ? uvlc_entry(vw) : 0u;
@@ -2197,6 +2305,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
         total_bits += wave_last(ns);
     }
     if (!__any(bigu)) {                                          // (otherwise: ht_decode_block below; only zero rows have been stored so far)
+    if (!mine) return;                                           // a DUP block whose leader stays on this path: the leader stores its rows
     // MagSgn bytes -> the LDS bit string (ht_extract_fast without its u > 32 branches)
     {
         const uint32_t zw = min((uint32_t)HT_DEC_MWORDS, ((nb * 8) >> 5) + 3u);
@@ -2279,8 +2388,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
             const uint32_t it = lane + 64 * t;
             int32_t *orow = out + (4 * (it >> psh) * os + 8 * (it & (P - 1)));
             if (it < N) {
-                st_decoded(orow, vals[0], vals[1], vals[2], vals[3]);
-                st_decoded(orow + 4, vals[4], vals[5], vals[6], vals[7]);
+                st_all(orow, vals[0], vals[1], vals[2], vals[3]);
+                st_all(orow + 4, vals[4], vals[5], vals[6], vals[7]);
             }
             continue;
         }
@@ -2295,13 +2404,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
                 o[i] = (q & 1) ? b : a;
             }
             const uint32_t rg = 8 * t + drow;                              // coded row index in the block
-            if (rg < R) st_decoded(out + (4 * rg * os + 4 * q), o[0], o[1], o[2], o[3]);
+            if (rg < R) st_all(out + (4 * rg * os + 4 * q), o[0], o[1], o[2], o[3]);
         }
     }
     return;
     }   // no u above 31
     }   // lean
-    ht_decode_block<STRIDED>(S, jid, lane, jobs, stream, offs, lens, decoded, pairs, coded_rows_only_);
+    ht_decode_block<STRIDED>(S, jid, lane, jobs, stream, offs, lens, decoded, pairs, coded_rows_only_, rjid);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2317,7 +2426,9 @@ static hipError_t ht_tables_ready(hipStream_t s) {
     hipLaunchKernelGGL(ht_build_enc_table, dim3(1), dim3(128), 0, s);
     hipLaunchKernelGGL(ht_build_pair_table, dim3(64), dim3(256), 0, s);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ht_walk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ht_walk_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)sizeof(HtWalkShared))) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ht_walk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)sizeof(HtWalkShared))) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ht_front_kernel<HT_FRONT_NW>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)sizeof(HtFrontShared))) != hipSuccess) return e;
@@ -2352,6 +2463,7 @@ hipError_t launch_ht_encode_stream(hipStream_t s, const BlockJob *jobs, int njob
     return hipGetLastError();
 }
 int ht_fast_max_samples() { return HT_FAST_MAX_SAMPLES; }
+int ht_walk_max_pairs() { return HT_WALK_MAX_PAIRS; }
 
 // words of device scratch launch_ht_decode needs for njobs blocks: per-pair records + unstuffed VLC bit strings
 size_t ht_decode_scratch_words(int njobs) { return (size_t)njobs * (HT_WALK_REC + HT_VBITS_WORDS); }
@@ -2360,7 +2472,9 @@ size_t ht_decode_scratch_words(int njobs) { return (size_t)njobs * (HT_WALK_REC 
 // front: 1 = ht_front_kernel, 3 = ht_vlcprep_kernel + ht_walk_kernel (the same records either way; vbits is only used by the latter)
 hipError_t launch_ht_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, int32_t *decoded, uint32_t *scratch, int coded_rows_only, const BlockJob *placed_jobs, int lean,
-                            int front) {
+                            int front, const int32_t *dedup_rep, const int32_t *dedup_fol) {
+    // ht_vlcprep_dedup_kernel and the DEDUP instantiations (byte-identical blocks decoded once): dense blocks, the two-launch front end and the lean kernel only -- nobody else knows HT_PAIR_DUP
+    const bool dedup = dedup_rep && dedup_fol && !placed_jobs && lean && front != 1;
     if (njobs <= 0) return hipSuccess;
     hipError_t e;
     if ((e = ht_tables_ready(s)) != hipSuccess) return e;
@@ -2370,16 +2484,25 @@ hipError_t launch_ht_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
         hipLaunchKernelGGL(ht_front_kernel<HT_FRONT_NW>, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(64 * HT_FRONT_NW), sizeof(HtFrontShared), s, jobs, njobs, stream, offs, lens, pairs);
     } else {
         for (int rep_ = 0; rep_ < dev_reps(32); rep_++)
+        if (dedup) hipLaunchKernelGGL(ht_vlcprep_dedup_kernel, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, vbits, pairs, dedup_rep);
+        else
         hipLaunchKernelGGL(ht_vlcprep_kernel, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, vbits, pairs);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         for (int rep_ = 0; rep_ < dev_reps(64); rep_++)
-        hipLaunchKernelGGL(ht_walk_kernel, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(256), sizeof(HtWalkShared), s, jobs, njobs, vbits, pairs);
+        if (dedup) hipLaunchKernelGGL(ht_walk_kernel<true>, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(256), sizeof(HtWalkShared), s, jobs, njobs, vbits, pairs);
+        else
+        hipLaunchKernelGGL(ht_walk_kernel<false>, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(256), sizeof(HtWalkShared), s, jobs, njobs, vbits, pairs);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     for (int rep_ = 0; rep_ < dev_reps(128); rep_++)
-    if (placed_jobs) hipLaunchKernelGGL(lean ? ht_decode_lean_kernel<true> : ht_decode_kernel<true>, dim3((njobs + 3) / 4), dim3(256), 0, s, placed_jobs, njobs, stream, offs, lens, decoded, pairs, 1);
+    if (dedup) hipLaunchKernelGGL((ht_decode_lean_kernel<false, true>), dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, decoded, pairs, coded_rows_only, dedup_fol);
+    else if (placed_jobs) {
+        if (lean) hipLaunchKernelGGL((ht_decode_lean_kernel<true, false>), dim3((njobs + 3) / 4), dim3(256), 0, s, placed_jobs, njobs, stream, offs, lens, decoded, pairs, 1, (const int32_t *)nullptr);
+        else hipLaunchKernelGGL(ht_decode_kernel<true>, dim3((njobs + 3) / 4), dim3(256), 0, s, placed_jobs, njobs, stream, offs, lens, decoded, pairs, 1);
+    }
     else
-    hipLaunchKernelGGL(lean ? ht_decode_lean_kernel<false> : ht_decode_kernel<false>, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, decoded, pairs, coded_rows_only);
+    if (lean) hipLaunchKernelGGL((ht_decode_lean_kernel<false, false>), dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, decoded, pairs, coded_rows_only, (const int32_t *)nullptr);
+    else hipLaunchKernelGGL(ht_decode_kernel<false>, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, decoded, pairs, coded_rows_only);
     return hipGetLastError();
 }
 

@@ -46,6 +46,7 @@ static const std::vector<CtxOption> &ctx_options() {
         OPT("ht_enc_waves", v == 1 || v == 4, c->ht_enc_waves = (int)v),
         OPT("ht_dec_lean", v == 0 || v == 1, c->ht_dec_lean = (int)v),
         OPT("ht_dec_front", v == 1 || v == 3, c->ht_dec_front = (int)v),
+        OPT("ht_dec_dedup", v == 0 || v == 1, c->ht_dec_dedup = (int)v),
         OPT("l0_inv_wpe", v >= 5 && v <= 7, c->l0_inv_wpe = (int)v),
         OPT("l0_wg_inv", v == 0 || v == 1, c->l0_wg_inv = v != 0),
         OPT("l0_wg_invw", v == 0 || v == 4 || v == 8, c->l0_wg_invw = (int)v),

@@ -491,3 +491,11 @@ extern "C" int j2k_plan_get_decoded_offsets(const j2k_plan *P, uint64_t *offs, s
     return J2K_OK;
 }
 
+extern "C" int j2k_plan_get_ht_decode_leaders(const j2k_plan *P, int32_t *leaders, size_t cap) {
+    if (!P || !leaders) return J2K_ERR_INVALID_ARG;
+    if (P->spec.coder != J2K_CODER_HT) return J2K_ERR_UNSUPPORTED;
+    if (cap < P->ht_dec_rep.size()) return J2K_ERR_CAPACITY;
+    if (!P->ht_dec_rep.empty()) memcpy(leaders, P->ht_dec_rep.data(), P->ht_dec_rep.size() * sizeof(int32_t));
+    return J2K_OK;
+}
+

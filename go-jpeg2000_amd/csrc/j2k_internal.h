@@ -53,6 +53,9 @@ struct HtUJob {
     int32_t pad_;
 };
 
+// HT decode, byte-identical blocks once (j2k_plan.h d_ht_dec_fol: a count and this many ids per job): jobs that may follow one leader
+#define J2K_HT_DEC_MAX_FOLLOWERS 7
+
 // One tile-component for the fused "tail" kernels: decomposition levels l0..l0+nlev-1 run inside LDS.
 struct TailPlane {
     int64_t scr_off;      // forward: level-l0 input prefix in scratch; inverse: where X_{l0} is written

@@ -717,6 +717,36 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                 if (r == J2K_OK) r = upload(ctx, &P->d_bjobs_alias, aj);
             }
         }
+        if (r == J2K_OK && S.coder == J2K_CODER_HT) {
+            // The same fact for the decoder (option ht_dec_dedup; whatever ht_alias says): jobs with the same window carry the same bytes in any
+            // stream this encoder wrote, so one decode can serve them all.  These tables only NAME candidates -- ht_vlcprep_kernel compares the
+            // bytes of every call's stream and a job that differs decodes itself.  Leader = the lowest job of the window.  A job follows it only
+            // on static facts of the pair: same w and h, a lean width (8, 16, 32, 64), the geometry on the parallel path (ht_vlc_head's `fast`),
+            // both decoded blocks 16-byte aligned (ht_decode_lean_kernel's own condition), and the leader's list not yet full.
+            const size_t nj = bj.size();
+            std::map<std::tuple<int64_t, int32_t, int32_t, int32_t>, int> lead;
+            P->ht_dec_rep.resize(nj);
+            std::vector<int32_t> fol(nj * (size_t)(J2K_HT_DEC_MAX_FOLLOWERS + 1), 0);
+            bool any = false;
+            for (size_t i = 0; i < nj; i++) {
+                P->ht_dec_rep[i] = (int32_t)i;
+                auto ins = lead.emplace(std::make_tuple(bj[i].src_off, bj[i].stride, bj[i].w, bj[i].h), (int)i);
+                if (ins.second) continue;
+                const int L = ins.first->second, w = bj[i].w, h = bj[i].h;
+                const int R = (h + 3) / 4, Np = R * (((w + 3) / 4 + 1) / 2);
+                const bool fast = (size_t)R * (size_t)w <= (size_t)ht_fast_max_samples() && Np <= ht_walk_max_pairs();
+                int32_t *row = &fol[(size_t)L * (J2K_HT_DEC_MAX_FOLLOWERS + 1)];
+                if (bj[L].w != w || bj[L].h != h || !(w == 8 || w == 16 || w == 32 || w == 64) || !fast) continue;
+                if ((P->dec_off[i] & 3) || (P->dec_off[L] & 3) || row[0] >= J2K_HT_DEC_MAX_FOLLOWERS) continue;
+                row[++row[0]] = (int32_t)i;
+                P->ht_dec_rep[i] = L;
+                any = true;
+            }
+            if (any) {
+                r = upload(ctx, &P->d_ht_dec_rep, P->ht_dec_rep);
+                if (r == J2K_OK) r = upload(ctx, &P->d_ht_dec_fol, fol);
+            }
+        }
         for (size_t i = 0; i < bj.size(); i++) bj[i].out_off = (int64_t)P->dec_off[i];   // decode table: dense decoded blocks
         if (r == J2K_OK) r = upload(ctx, &P->d_djobs, bj);
         if (r == J2K_OK && P->spec.closed_loop && P->spec.coder == J2K_CODER_HT) {
@@ -874,7 +904,7 @@ extern "C" void j2k_plan_destroy(j2k_plan *P) {
         if (cls == 0 && P->d_bigsym_off) { (void)hipFree(P->d_bigsym_off); P->d_bigsym_off = nullptr; }
         for (auto &T : P->inv[cls]) { if (T.d_planes) (void)hipFree(T.d_planes); if (T.d_jobs) (void)hipFree(T.d_jobs); if (T.d_pjobs) (void)hipFree(T.d_pjobs); }
     }
-    void *ptrs[] = {P->d_deep_jobs_inv, P->d_mega_fwd_jobs, P->d_mega_inv_jobs, P->d_fwd_top_jobs, P->d_inv_top_jobs, P->d_inv_wg_jobs, P->d_deep_planes, P->d_deep_jobs, P->d_tile_job0, P->d_scrA, P->d_scrB, P->d_tail, P->d_bjobs, P->d_djobs, P->d_djobs_placed, P->d_frame, P->d_coeff, P->d_slots, P->d_stream, P->d_lens, P->d_numbps, P->d_offs, P->d_status, P->d_fwd_pix_jobs, P->d_fwd_wg2_jobs, P->d_fwd_wg_rest_jobs, P->d_fwd_wg_jobs, P->d_fwd97_wg_jobs, P->d_inv97_wg_jobs, P->d_ht_ujobs, P->d_ht_alias_next, P->d_bjobs_alias, P->d_maglens, P->d_mels, P->d_toffs,
+    void *ptrs[] = {P->d_deep_jobs_inv, P->d_mega_fwd_jobs, P->d_mega_inv_jobs, P->d_fwd_top_jobs, P->d_inv_top_jobs, P->d_inv_wg_jobs, P->d_deep_planes, P->d_deep_jobs, P->d_tile_job0, P->d_scrA, P->d_scrB, P->d_tail, P->d_bjobs, P->d_djobs, P->d_djobs_placed, P->d_frame, P->d_coeff, P->d_slots, P->d_stream, P->d_lens, P->d_numbps, P->d_offs, P->d_status, P->d_fwd_pix_jobs, P->d_fwd_wg2_jobs, P->d_fwd_wg_rest_jobs, P->d_fwd_wg_jobs, P->d_fwd97_wg_jobs, P->d_inv97_wg_jobs, P->d_ht_ujobs, P->d_ht_alias_next, P->d_ht_dec_rep, P->d_ht_dec_fol, P->d_bjobs_alias, P->d_maglens, P->d_mels, P->d_toffs,
                     P->d_t2_packets, P->d_tile_packet0, P->d_t2_cbs, P->d_t2_poffs, P->d_t2_ptile, P->d_t2_ws, P->d_t2_chains, P->d_t2_body_base, P->d_t2_par, P->d_frame_status,
                     P->d_cl_decoded, P->d_cl_coeff, P->d_cl_coeff_dec, P->d_cl_numbps, P->d_cl_offs, P->d_cl_lens, P->d_host_io, P->d_host_pix,
                     P->d_rate_wj, P->d_rate_ws, P->d_cl_rate, P->d_cl_dense, P->d_cl_lfloors,

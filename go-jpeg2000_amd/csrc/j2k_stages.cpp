@@ -911,8 +911,13 @@ int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const u
     if (P->spec.coder == J2K_CODER_HT) {
         int r = stage_reserve(ctx, 2, ht_decode_scratch_words(n) * 4 + 256);
         if (r != J2K_OK) return r;
+        // byte-identical blocks once (ht_dec_dedup): the plan's tables name jobs of its whole dense list, and only the two-launch front end
+        // and the lean kernel know the tag -- every other combination gets no tables
+        const bool dedup = ctx->ht_dec_dedup && d_djobs == P->d_djobs && n == (int)P->blocks.size() && !d_placed && ctx->ht_dec_lean == 1 &&
+                           ctx->ht_dec_front == 3 && P->d_ht_dec_rep && P->d_ht_dec_fol;
         HIPCHK(ctx, launch_ht_decode(ctx->stream, d_djobs, n, d_stream, d_offs, d_lens, d_decoded, (uint32_t *)ctx->stage[2],
-                                     (d_placed || P->dec_coded_rows_only) ? 1 : 0, d_placed, ctx->ht_dec_lean, ctx->ht_dec_front));
+                                     (d_placed || P->dec_coded_rows_only) ? 1 : 0, d_placed, ctx->ht_dec_lean, ctx->ht_dec_front,
+                                     dedup ? P->d_ht_dec_rep : nullptr, dedup ? P->d_ht_dec_fol : nullptr));
     } else {
         size_t wpj = 0;                                  // the one-block decoder's workspace holds the flags only
         int max_dim = 0;

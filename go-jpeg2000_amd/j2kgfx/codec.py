@@ -107,6 +107,13 @@ class FramePlan:
         self.ctx.check(self.ctx.L.j2k_plan_get_decoded_offsets(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n)))
         return out[:n]
 
+    def ht_decode_leaders(self):
+        """(n,) int32, HT plans: the job whose decode may serve job j too under the option ht_dec_dedup (j itself: none)."""
+        n = int(self.info.blocks)
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        self.ctx.check(self.ctx.L.j2k_plan_get_ht_decode_leaders(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n)))
+        return out[:n]
+
     # ---- device buffers -----------------------------------------------------------
     def empty(self, n, dtype):
         t = _torch()

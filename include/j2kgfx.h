@@ -62,7 +62,8 @@ const char *j2k_version(void);
  * are identical under every setting -- tests/test_gpu_knobs.py).  Set BEFORE plans are created on the context.  Names (csrc/j2k_ctx.cpp,
  * ctx_options): "t1_dec_split" (MQ decode plane by plane from this many blocks on; -1 automatic), "t1_lanes", "t1_dec_lanes",
  * "t1_sym_mb" (cap of the MQ encoder's symbol workspace, MiB), "pix_fuse", "l0_wg", "l0_wg_inv", "l0_fuse", "plane_wg", "deep", "mega",
- * ...  An unknown name or a value out of range is J2K_ERR_INVALID_ARG.  The ENVIRONMENT sets none of this unless J2K_TUNING=1 is in
+ * "ht_dec_front" (3 | 1), "ht_dec_lean" (0 | 1), "ht_dec_dedup" (0 | 1, default 1: HT block decode skips a job whose bytes equal its leader's,
+ * j2k_plan_get_ht_decode_leaders), ...  An unknown name or a value out of range is J2K_ERR_INVALID_ARG.  The ENVIRONMENT sets none of this unless J2K_TUNING=1 is in
  * it (then J2K_<NAME> is read for every option at j2k_ctx_create: the tests' and tools' A/B switch); J2K_RCCL_LIB, the path of the
  * RCCL library, is the one variable that is always read. */
 int j2k_ctx_set_option(j2k_ctx *ctx, const char *name, long value);
@@ -313,6 +314,12 @@ int j2k_plan_set_decode_coded_rows_only(j2k_plan *plan, int on);
 int j2k_plan_set_dequantize(j2k_plan *plan, int on);
 /* job j's offset (in int32 elements) into d_decoded */
 int j2k_plan_get_decoded_offsets(const j2k_plan *plan, uint64_t *offs, size_t cap);
+/* HT plans only (J2K_ERR_UNSUPPORTED otherwise): leaders[j] = the job whose decode may serve job j as well under the context option ht_dec_dedup
+ * (0 | 1, default 1; J2K_HT_DEC_DEDUP with J2K_TUNING=1) -- the lowest job with the same window of the same width and height, when the width is 8, 16,
+ * 32 or 64, the block is on the parallel path, both decoded offsets are multiples of 4 and the leader has fewer than 7 followers so far; j itself
+ * otherwise.  A candidate only: j2k_plan_decode_blocks compares the bytes of the two blocks in every call and decodes job j on its own unless
+ * they are equal, so the option never changes a result.  It applies with ht_dec_front = 3 and ht_dec_lean = 1 (the defaults). */
+int j2k_plan_get_ht_decode_leaders(const j2k_plan *plan, int32_t *leaders, size_t cap);
 
 /* ---- the multi-GPU exchange -------------------------------------------------------------------------------
  * One process per GPU, each with its own j2k_ctx; a frame's tiles are sharded by j2k_params.tile_first / tile_count and coded
