@@ -391,7 +391,7 @@ extern "C" int j2k_plan_decode_frame_pixels_coarse(j2k_plan *P, const uint8_t *d
 int cl_rate_workspace(j2k_plan *P, ClRate &W) {
     j2k_ctx *ctx = P->ctx;
     const size_t n = P->blocks.size(), nr = (n + 255) & ~size_t(255);
-    const size_t bytes = nr * 32 * 8 + nr * 32 * 4 + 3 * nr + 256;
+    const size_t bytes = nr * 32 * 8 + nr * 32 * 4 + 3 * nr + 256 + 256;
     if (!P->d_cl_rate) {
         if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the frame codec's workspaces are made at its first call");
         HIPCHK(ctx, hipMalloc(&P->d_cl_rate, bytes));
@@ -401,6 +401,7 @@ int cl_rate_workspace(j2k_plan *P, ClRate &W) {
     W.rate = (uint32_t *)b; b += nr * 32 * 4;
     W.chosen = (uint64_t *)b; b += 256;
     W.kept = b; W.floors = b + nr; W.floors_r = b + 2 * nr;
+    W.achieved = (double *)(b + 3 * nr);                             // (nr is a multiple of 256: aligned)
     return J2K_OK;
 }
 
@@ -421,6 +422,23 @@ int plan_encode_frame_from_coeff_rate(j2k_plan *P, const int32_t *d_coeff, uint3
     }
     if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, roi, roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
     if (r == J2K_OK) r = j2k_plan_rate_allocate(P, W.rate, W.dist, d_numbps, max_body_bytes, W.kept, W.chosen);
+    if (r == J2K_OK) r = encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, W.kept, W.rate);
+    return r;
+}
+
+// ... with the allocation's dual in its place (j2k_plan_encode_frame_pixels_quality with one target and no layer ends): every other launch is the same
+int plan_encode_frame_from_coeff_quality(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, double target, int sop, int eph, uint8_t *d_out,
+                                         size_t cap, uint64_t *d_tile_offs, const j2k_rect *roi, int roi_gain, double *d_achieved) {
+    j2k_ctx *ctx = P->ctx;
+    ClRate W{};
+    int r = cl_prepare(P);
+    if (r == J2K_OK) r = cl_rate_workspace(P, W);
+    if (r == J2K_OK && !P->d_slots) {
+        if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: run the same calls once before j2k_ctx_capture_begin");
+        HIPCHK(ctx, hipMalloc(&P->d_slots, (size_t)P->bytes_cap + 64));
+    }
+    if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, roi, roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
+    if (r == J2K_OK) r = j2k_plan_rate_allocate_quality(P, W.rate, W.dist, d_numbps, &target, 1, W.kept, W.chosen, d_achieved ? d_achieved : W.achieved);
     if (r == J2K_OK) r = encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, W.kept, W.rate);
     return r;
 }

@@ -52,6 +52,13 @@ hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate, 
                                 uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen);
 hipError_t launch_rate_allocate_layers(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
                                        const uint64_t *budgets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen);
+// the dual (rate.hip): per layer the fewest bytes whose weighted distortion stays within targets[l]; achieved[l] = that distortion
+hipError_t launch_rate_allocate_quality(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+                                        const double *targets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved);
+// per-channel sums of squared sample differences of two frames in one Pix layout (pixels.hip)
+size_t pixels_sse_workspace();
+hipError_t launch_pixels_sse(hipStream_t s, const uint8_t *a, size_t stride_a, const uint8_t *b, size_t stride_b, size_t rowbytes, int h, bool wide, int channels,
+                             uint64_t *partial, uint64_t *sums);
 // quality layers (t2dev.hip, t2dec.hip)
 hipError_t launch_t2_fill_layer_cbs(hipStream_t s, long n, int nlayers, const uint64_t *offs, const BlockJob *slot_jobs, const uint32_t *lens, const uint8_t *numbps,
                                     int mb, const uint8_t *kept, const uint32_t *rate, j2k_t2_dev_cb *cbs, uint64_t *reset);
@@ -137,12 +144,13 @@ void free_layer_tabs(j2k_plan *P);           // j2k_layers.cpp
 // the closed-loop frame codec's tables and workspaces, made at first use (j2k_frame.cpp)
 int cl_prepare(j2k_plan *P);
 int cl_workspaces(j2k_plan *P);
-struct ClRate { uint32_t *rate; uint64_t *dist; uint8_t *kept; uint64_t *chosen; uint8_t *floors, *floors_r; };
+struct ClRate { uint32_t *rate; uint64_t *dist; uint8_t *kept; uint64_t *chosen; uint8_t *floors, *floors_r; double *achieved; };   // chosen, achieved: 32 words, one per layer
 int cl_rate_workspace(j2k_plan *P, ClRate &W);
 int plan_decode_frame_tables(j2k_plan *P, const uint8_t *d_data, j2k::ReducedTab *R, int reduce, int skip_planes, const uint8_t *d_floors, uint8_t *d_floors_r,
                              void *d_pix, size_t stride);
 int rate_check(j2k_plan *P, const char *who);    // what every rate call needs of its plan (j2k_rate.cpp)
 int rate_upload_weights(j2k_plan *P);            // the per-job weights and the allocation workspace on the device (j2k_rate.cpp)
+int targets_check(j2k_ctx *ctx, const double *targets, int nlayers, const char *who);   // distortion targets: finite, >= 0, none above the one before (j2k_rate.cpp)
 // the plan data of area_blocks_kernel (and of the region-of-interest kernels), uploaded at first use; frame: also the staging frame of a region
 // decode (j2k_area.cpp)
 int area_tables(j2k_plan *P, bool frame);
@@ -166,6 +174,10 @@ int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *
                                  uint64_t *d_tile_offs);
 int plan_encode_frame_from_coeff_rate(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int64_t max_body_bytes, int sop, int eph,
                                       uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, const j2k_rect *roi = nullptr, int roi_gain = 1);   // roi: checked by the caller
+// the same with the allocation swapped for its dual: the fewest bytes whose weighted distortion is at most `target` (the caller has checked
+// plan, target and roi); d_achieved (device, or null): that distortion
+int plan_encode_frame_from_coeff_quality(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, double target, int sop, int eph, uint8_t *d_out,
+                                         size_t cap, uint64_t *d_tile_offs, const j2k_rect *roi, int roi_gain, double *d_achieved);
 // guard (device, or null): the launches that write d_frame write nothing if *guard != 0 -- the frame decoder's status word
 int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix = PixIO(), const int *guard = nullptr);
 int plan_inverse_pixels_impl(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride, const int *guard);

@@ -163,9 +163,12 @@ extern "C" int j2k_plan_decode_tile_parts_layers(j2k_plan *P, const uint8_t *d_c
 }
 
 // coefficients -> layered tile-parts: block coding into the plan's slots with the tables, the allocation of the L budgets in one launch, then every
-// block's increments from its slot into its L packets (d_lens / d_numbps: the caller's tables, filled with the UNCUT lengths and plane counts)
+// block's increments from its slot into its L packets (d_lens / d_numbps: the caller's tables, filled with the UNCUT lengths and plane counts).
+// targets != NULL (the _quality calls): the L distortion targets in the place of the budgets -- the allocation launch is the only one that differs;
+// d_achieved (device, or null): the weighted distortion of every layer's choice
 static int encode_frame_from_coeff_layers(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, const uint64_t *budgets, int L, int sop, int eph,
-                                          uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs, const j2k_rect *roi = nullptr, int roi_gain = 1) {
+                                          uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs, const j2k_rect *roi = nullptr, int roi_gain = 1,
+                                          const double *targets = nullptr, double *d_achieved = nullptr) {
     j2k_ctx *ctx = P->ctx;
     ClRate W{};
     LayerTab *T = nullptr;
@@ -180,7 +183,11 @@ static int encode_frame_from_coeff_layers(j2k_plan *P, const int32_t *d_coeff, u
     if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, roi, roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
     if (r == J2K_OK) r = rate_upload_weights(P);
     if (r != J2K_OK) return r;
-    HIPCHK(ctx, launch_rate_allocate_layers(ctx->stream, (int)P->blocks.size(), W.rate, W.dist, d_numbps, P->d_rate_wj, budgets, L, P->d_rate_ws, T->d_kept, W.chosen));      // (W.chosen: 32 words, one per layer)
+    if (targets)
+        HIPCHK(ctx, launch_rate_allocate_quality(ctx->stream, (int)P->blocks.size(), W.rate, W.dist, d_numbps, P->d_rate_wj, targets, L, P->d_rate_ws, T->d_kept, W.chosen,
+                                                 d_achieved ? d_achieved : W.achieved));
+    else
+        HIPCHK(ctx, launch_rate_allocate_layers(ctx->stream, (int)P->blocks.size(), W.rate, W.dist, d_numbps, P->d_rate_wj, budgets, L, P->d_rate_ws, T->d_kept, W.chosen));      // (W.chosen: 32 words, one per layer)
     return encode_tile_parts_layers_impl(P, *T, L, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, T->d_kept, W.rate, sop, eph, d_out, cap, d_tile_offs, d_layer_offs);
 }
 
@@ -228,6 +235,35 @@ extern "C" int j2k_plan_encode_frame_pixels_roi(j2k_plan *P, int format, const v
     return encode_frame_from_coeff_layers(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, budgets, nlayers, sop, eph, d_out, cap, d_tile_offs, d_layer_offs, roi, roi_gain);
 }
 
+// Quality-targeted encode, one call for both forms as the _roi call: nlayers = 1 with d_layer_offs == NULL writes the kept-stream format of
+// j2k_plan_encode_frame_pixels_rate, anything else the layered stream; the distortion launch (roi or not), the packets and the tile-parts are
+// theirs.  Every refusal comes before the first launch.
+static int quality_frame_check(j2k_plan *P, const double *targets, int nlayers, bool layered, const j2k_rect *roi, int roi_gain, const char *who) {
+    int r = layers_check(P, nlayers, who);
+    if (r == J2K_OK && roi) r = roi_check(P, roi, roi_gain, who);
+    if (r == J2K_OK) r = targets_check(P->ctx, targets, nlayers, who);
+    if (r == J2K_OK && !layered && nlayers != 1) r = fail(P->ctx, J2K_ERR_INVALID_ARG, (std::string(who) + ": more than one target needs the layer ends (layer_offs)").c_str());
+    return r;
+}
+extern "C" int j2k_plan_encode_frame_pixels_quality(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, const double *targets, int nlayers,
+                                                    const j2k_rect *roi, int roi_gain, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs,
+                                                    double *d_achieved) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    if (!d_out || !d_tile_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    int r = quality_frame_check(P, targets, nlayers, d_layer_offs != nullptr, roi, roi_gain, "j2k_plan_encode_frame_pixels_quality");
+    if (r != J2K_OK) return r;
+    r = cl_prepare(P);
+    if (r == J2K_OK) r = cl_workspaces(P);
+    if (r == J2K_OK && roi) r = area_tables(P, false);
+    if (r == J2K_OK) r = j2k_plan_forward_pixels(P, format, d_pix, stride, P->d_cl_coeff);
+    if (r != J2K_OK) return r;
+    if (!d_layer_offs)
+        return plan_encode_frame_from_coeff_quality(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, targets[0], sop, eph, d_out, cap, d_tile_offs, roi, roi_gain, d_achieved);
+    return encode_frame_from_coeff_layers(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, nullptr, nlayers, sop, eph, d_out, cap, d_tile_offs, d_layer_offs, roi, roi_gain, targets,
+                                          d_achieved);
+}
+
 // the first `layers` layers of every tile-part -> pixels: the LAYERED packet read, the blocks' segments gathered into the plan's dense buffer, then
 // the decode of j2k_plan_decode_frame_pixels_rate on that buffer in the place of the codestream
 extern "C" int j2k_plan_decode_frame_pixels_layers(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int layers, int reduce,
@@ -262,13 +298,15 @@ extern "C" int j2k_plan_decode_frame_pixels_layers(j2k_plan *P, const uint8_t *d
 // with_roi: j2k_encode_pixels_host_roi, whose layer_offs == NULL asks for the single-budget (_rate) stream
 static int encode_pixels_host_layers_impl(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
                                           bool with_roi, const j2k_rect *roi, int roi_gain, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs,
-                                          uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, const char *who) {
+                                          uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, const char *who, const double *targets = nullptr,
+                                          double *achieved = nullptr) {          // targets: the _quality form (roi nullable), achieved: nlayers doubles or null
     if (!P || !pix || !out_len) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
     uint64_t budgets[J2K_MAX_LAYERS];
     int r;
-    if (with_roi) r = roi_frame_check(P, layer_bytes, nlayers, layer_offs != nullptr, roi, roi_gain, budgets, who);
+    if (targets) r = quality_frame_check(P, targets, nlayers, layer_offs != nullptr, roi, roi_gain, who);
+    else if (with_roi) r = roi_frame_check(P, layer_bytes, nlayers, layer_offs != nullptr, roi, roi_gain, budgets, who);
     else {
         r = layers_check(P, nlayers, who);
         if (r == J2K_OK) r = budgets_check(ctx, layer_bytes, nlayers, budgets, who);
@@ -284,10 +322,13 @@ static int encode_pixels_host_layers_impl(j2k_plan *P, int format, const void *p
     const size_t bound = with_roi ? std::max(j2k_plan_frame_bound_layers(P, nlayers), j2k_plan_frame_bound(P)) : j2k_plan_frame_bound_layers(P, nlayers);
     const size_t toff_at = (bound + 64 + 15) & ~size_t(15);                                  // the tile-parts, and behind them their offsets and the layer ends
     if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, (size_t)S.H * stride)) != J2K_OK) return r;
-    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, toff_at + (nt + 1 + nl + 2) * 8)) != J2K_OK) return r;
+    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, toff_at + (nt + 1 + nl + 2 + J2K_MAX_LAYERS) * 8)) != J2K_OK) return r;
     uint64_t *d_toffs = reinterpret_cast<uint64_t *>((uint8_t *)P->d_host_io + toff_at), *d_loffs = d_toffs + nt + 1;
+    double *d_ach = reinterpret_cast<double *>(d_loffs + nl + 2);                            // (the _quality form: every layer's weighted distortion)
     HIPCHK(ctx, hipMemcpyAsync(P->d_host_pix, pix, (size_t)S.H * stride, hipMemcpyHostToDevice, ctx->stream));
-    if (with_roi) r = j2k_plan_encode_frame_pixels_roi(P, format, P->d_host_pix, stride, sop, eph, layer_bytes, nlayers, roi, roi_gain, (uint8_t *)P->d_host_io, bound, d_toffs,
+    if (targets) r = j2k_plan_encode_frame_pixels_quality(P, format, P->d_host_pix, stride, sop, eph, targets, nlayers, roi, roi_gain, (uint8_t *)P->d_host_io, bound, d_toffs,
+                                                          layer_offs ? d_loffs : nullptr, d_ach);
+    else if (with_roi) r = j2k_plan_encode_frame_pixels_roi(P, format, P->d_host_pix, stride, sop, eph, layer_bytes, nlayers, roi, roi_gain, (uint8_t *)P->d_host_io, bound, d_toffs,
                                                        layer_offs ? d_loffs : nullptr);
     else r = j2k_plan_encode_frame_pixels_layers(P, format, P->d_host_pix, stride, sop, eph, layer_bytes, nlayers, (uint8_t *)P->d_host_io, bound, d_toffs, d_loffs);
     if (r != J2K_OK) return r;
@@ -296,6 +337,7 @@ static int encode_pixels_host_layers_impl(j2k_plan *P, int format, const void *p
     HIPCHK(ctx, hipMemcpyAsync(offs.data(), d_toffs, offs.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (lens && nb) HIPCHK(ctx, hipMemcpyAsync(lens, P->d_cl_lens, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (numbps && nb) HIPCHK(ctx, hipMemcpyAsync(numbps, P->d_cl_numbps, nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (targets && achieved) HIPCHK(ctx, hipMemcpyAsync(achieved, d_ach, (size_t)nlayers * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if ((r = check_fault(ctx)) != J2K_OK) return r;
     if ((r = j2k_plan_frame_status(P)) != J2K_OK) return r;
@@ -320,6 +362,16 @@ extern "C" int j2k_encode_pixels_host_roi(j2k_plan *P, int format, const void *p
     if (!P) return J2K_ERR_INVALID_ARG;
     return encode_pixels_host_layers_impl(P, format, pix, stride, sop, eph, layer_bytes, nlayers, true, roi, roi_gain, out, cap, out_len, tile_offs, layer_offs, lens, numbps,
                                           "j2k_encode_pixels_host_roi");
+}
+
+// the synchronous host-memory form of j2k_plan_encode_frame_pixels_quality (layer_offs == NULL with nlayers = 1: the kept-stream format; roi nullable)
+extern "C" int j2k_encode_pixels_host_quality(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const double *targets, int nlayers,
+                                              const j2k_rect *roi, int roi_gain, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs,
+                                              uint32_t *lens, uint8_t *numbps, double *achieved) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    if (!targets) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_encode_pixels_host_quality: no targets");
+    return encode_pixels_host_layers_impl(P, format, pix, stride, sop, eph, nullptr, nlayers, true, roi, roi_gain, out, cap, out_len, tile_offs, layer_offs, lens, numbps,
+                                          "j2k_encode_pixels_host_quality", targets, achieved);
 }
 
 extern "C" int j2k_decode_pixels_host_layers(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int layers, int reduce, int skip_planes, void *pix,

@@ -181,6 +181,46 @@ extern "C" int j2k_plan_rate_allocate(j2k_plan *P, const uint32_t *d_rate, const
     return J2K_OK;
 }
 
+// ---- the dual: a distortion target in the place of a byte budget (tests/quality_cases.py) ----------------------------------------
+// T = N * peak^2 * q^2 / 10^(dB / 10): N samples, peak = 2^precision - 1, q = the plan's quality where it quantises (its coefficients are the
+// transform times quality), else 1.  Host only.
+extern "C" int j2k_plan_psnr_distortion(const j2k_plan *P, double db, double *T) {
+    if (!P || !T || !std::isfinite(db)) return J2K_ERR_INVALID_ARG;
+    const PlanSpec &S = P->spec;
+    const double peak = (double)((1u << S.precision) - 1u), q = S.quant != Q_NONE ? (double)S.quality : 1.0;
+    const double t = (double)S.W * (double)S.H * (double)S.C * peak * peak * q * q / std::pow(10.0, db / 10.0);
+    if (!std::isfinite(t)) return J2K_ERR_INVALID_ARG;
+    *T = t;
+    return J2K_OK;
+}
+
+// distortion targets: finite, none negative, none above the one before
+int targets_check(j2k_ctx *ctx, const double *targets, int nlayers, const char *who) {
+    if (!targets) return fail(ctx, J2K_ERR_INVALID_ARG, (std::string(who) + ": no targets").c_str());
+    for (int l = 0; l < nlayers; l++) {
+        if (!std::isfinite(targets[l]) || targets[l] < 0.0) return fail(ctx, J2K_ERR_INVALID_ARG, (std::string(who) + ": a target is a finite distortion >= 0").c_str());
+        if (l && targets[l] > targets[l - 1]) return fail(ctx, J2K_ERR_INVALID_ARG, (std::string(who) + ": the targets fall layer by layer -- none may be above the one before").c_str());
+    }
+    return J2K_OK;
+}
+
+extern "C" int j2k_plan_rate_allocate_quality(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, const double *targets, int nlayers,
+                                              uint8_t *d_kept, uint64_t *d_chosen, double *d_achieved) {
+    if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen || !d_achieved) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    int r = rate_check(P, "j2k_plan_rate_allocate_quality");
+    if (r != J2K_OK) return r;
+    if (nlayers < 1 || nlayers > J2K_MAX_LAYERS) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_rate_allocate_quality: the layer count is 1 ... 32");
+    r = targets_check(ctx, targets, nlayers, "j2k_plan_rate_allocate_quality");
+    if (r != J2K_OK) return r;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    r = rate_upload_weights(P);
+    if (r != J2K_OK) return r;
+    HIPCHK(ctx, launch_rate_allocate_quality(ctx->stream, (int)P->blocks.size(), d_rate, d_dist, d_numbps, P->d_rate_wj, targets, nlayers, P->d_rate_ws, d_kept, d_chosen,
+                                             d_achieved));
+    return J2K_OK;
+}
+
 int rate_upload_weights(j2k_plan *P) {
     j2k_ctx *ctx = P->ctx;
     const size_t n = P->blocks.size();

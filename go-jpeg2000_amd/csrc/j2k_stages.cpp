@@ -312,6 +312,20 @@ extern "C" int j2k_unpack_pixels(j2k_ctx *ctx, int format, const void *d_pix, si
     return J2K_OK;
 }
 
+// per-channel sums of squared sample differences of two device frames in one Pix layout: d_sums[c], c < the channels as stored (1, or 4 with
+// alpha), exact in uint64; asynchronous on the context's stream
+extern "C" int j2k_pixels_sse(j2k_ctx *ctx, int format, const void *d_a, size_t stride_a, const void *d_b, size_t stride_b, int w, int h, uint64_t *d_sums) {
+    int r = pix_args_ok(ctx, format, d_a, stride_a, w, h, 0);
+    if (r == J2K_OK) r = pix_args_ok(ctx, format, d_b, stride_b, w, h, 0);
+    if (r != J2K_OK || !d_sums) return ctx ? fail(ctx, J2K_ERR_INVALID_ARG, "j2k_pixels_sse: bad argument") : J2K_ERR_INVALID_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    r = stage_reserve(ctx, 1, pixels_sse_workspace());
+    if (r != J2K_OK) return r;
+    HIPCHK(ctx, launch_pixels_sse(ctx->stream, (const uint8_t *)d_a, stride_a, (const uint8_t *)d_b, stride_b, (size_t)w * kPixBytes[format], h, kPixPrec[format] > 8,
+                                  kPixComp[format] == 1 ? 1 : 4, (uint64_t *)ctx->stage[1], d_sums));
+    return J2K_OK;
+}
+
 extern "C" int j2k_pack_pixels(j2k_ctx *ctx, const int32_t *d_planes, int ncomp, int precision, int w, int h, void *d_pix, size_t stride) {
     if (!ctx || !d_planes || !d_pix || w < 0 || h < 0 || precision < 1 || precision > 16) return J2K_ERR_INVALID_ARG;
     if (ncomp != 1 && ncomp != 3 && ncomp != 4) return fail(ctx, J2K_ERR_UNSUPPORTED, "unsupported number of components");   // decoder.go:583-585

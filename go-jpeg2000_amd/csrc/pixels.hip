@@ -130,6 +130,80 @@ __global__ __launch_bounds__(256) void pack_pixels_window_kernel(const int32_t *
     }
 }
 
+// ---- sum of squared sample differences of two frames in the same Pix layout, per channel as stored (alpha included) -------------------------
+// One streaming pass: a row is cut into pieces of 16 bytes, 64 consecutive pieces are one item, and the wavefronts of the grid stride over the
+// items (row, chunk).  A piece never splits a pixel's channels apart from their place: 16 is a multiple of every pixel size, so byte i of a piece
+// (8-bit samples) or sample i (16-bit, big-endian) belongs to channel i % channels.  Rows whose two pointers are 16-byte aligned take one
+// 16-byte load per frame and piece; any other row, and the ragged piece at a row's end, is read byte by byte (bytes past the row count as
+// equal).  Every wavefront leaves 4 partial sums; sse_reduce_kernel adds them.  Integer sums, exact in uint64: no order to define, no atomics.
+#define SSE_MAX_WAVES 1024
+union SsePiece { uint4 v; uint8_t b[16]; };
+__global__ __launch_bounds__(256) void sse_partial_kernel(const uint8_t *__restrict__ a, size_t stride_a, const uint8_t *__restrict__ b, size_t stride_b,
+                                                          size_t rowbytes, int h, int wide, int nch, uint64_t *__restrict__ partial) {
+    const int lane = threadIdx.x & 63;
+    const size_t wave = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * 4;
+    const size_t chunks = (rowbytes + 1023) / 1024, items = chunks * (size_t)h;
+    uint64_t acc[4] = {0, 0, 0, 0};
+    for (size_t it = wave; it < items; it += nwaves) {
+        const size_t y = it / chunks, off = (it - y * chunks) * 1024 + (size_t)lane * 16;
+        if (off >= rowbytes) continue;
+        const uint8_t *pa = a + y * stride_a + off, *pb = b + y * stride_b + off;
+        const int nbytes = (int)(rowbytes - off < 16 ? rowbytes - off : 16);
+        SsePiece A, B;
+        if (nbytes == 16 && ((((uintptr_t)pa) | ((uintptr_t)pb)) & 15) == 0) {
+            A.v = *reinterpret_cast<const uint4 *>(pa);
+            B.v = *reinterpret_cast<const uint4 *>(pb);
+        } else {
+            A.v = make_uint4(0, 0, 0, 0); B.v = A.v;
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+                if (i < nbytes) { A.b[i] = pa[i]; B.b[i] = pb[i]; }
+        }
+        if (wide) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const int d = be16(A.b + 2 * i) - be16(B.b + 2 * i);
+                acc[i & 3] += (uint64_t)((uint32_t)(d < 0 ? -d : d) * (uint32_t)(d < 0 ? -d : d));       // 65535^2 < 2^32
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int d = (int)A.b[i] - (int)B.b[i];
+                acc[i & 3] += (uint64_t)(uint32_t)(d * d);
+            }
+        }
+    }
+    if (nch == 1) { acc[0] += acc[1] + acc[2] + acc[3]; acc[1] = acc[2] = acc[3] = 0; }     // one channel: the four phases are the same one
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        uint64_t s = acc[c];
+        for (int o = 32; o > 0; o >>= 1) s += (uint64_t)__shfl_xor((unsigned long long)s, o);
+        if (lane == 0) partial[wave * 4 + c] = s;
+    }
+}
+// one workgroup of 4 wavefronts: wavefront c adds channel c's partial sums
+__global__ __launch_bounds__(256) void sse_reduce_kernel(const uint64_t *__restrict__ partial, int nwaves, int nch, uint64_t *__restrict__ sums) {
+    const int lane = threadIdx.x & 63, c = threadIdx.x >> 6;
+    uint64_t s = 0;
+    for (int i = lane; i < nwaves; i += 64) s += partial[(size_t)i * 4 + c];
+    for (int o = 32; o > 0; o >>= 1) s += (uint64_t)__shfl_xor((unsigned long long)s, o);
+    if (lane == 0 && c < nch) sums[c] = s;
+}
+
+size_t pixels_sse_workspace() { return (size_t)SSE_MAX_WAVES * 4 * sizeof(uint64_t); }
+// channels: 1 or 4 as stored; partial: pixels_sse_workspace() bytes; sums: `channels` words, always written
+hipError_t launch_pixels_sse(hipStream_t s, const uint8_t *a, size_t stride_a, const uint8_t *b, size_t stride_b, size_t rowbytes, int h, bool wide, int channels,
+                             uint64_t *partial, uint64_t *sums) {
+    if (channels != 1 && channels != 4) return hipErrorInvalidValue;
+    const size_t items = ((rowbytes + 1023) / 1024) * (size_t)(h > 0 ? h : 0);
+    const int blocks = (int)std::max<size_t>(1, std::min<size_t>((items + 3) / 4, SSE_MAX_WAVES / 4));
+    hipLaunchKernelGGL(sse_partial_kernel, dim3(blocks), dim3(256), 0, s, a, stride_a, b, stride_b, rowbytes, h > 0 ? h : 0, wide ? 1 : 0, channels, partial);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sse_reduce_kernel, dim3(1), dim3(256), 0, s, partial, blocks * 4, channels, sums);
+    return hipGetLastError();
+}
+
 hipError_t launch_unpack_pixels(hipStream_t s, const uint8_t *pix, size_t stride, int format, int w, int h, int src_max, int dst_max,
                                 int32_t *planes) {
     const size_t n = (size_t)w * h;

@@ -245,6 +245,73 @@ __global__ __launch_bounds__(RATE_WG) void rate_allocate_layers_kernel(int njobs
     }
 }
 
+// ---- the dual: the fewest bytes whose weighted distortion stays within a target (tests/quality_cases.py is the definition) ------------------
+// The sum of float64 terms over the workgroup in the definition's FIXED order: `v` is the thread's own sum (its terms in order, from 0.0),
+// then six butterfly steps inside the wavefront, then the 16 wavefront values in order from 0.0.  The same value in every thread.
+__device__ __forceinline__ double wg_sum_f64(double v, double *sh) {
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
+    __syncthreads();                                     // the previous sum has been read
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int i = 0; i < RATE_WG / 64; i++) t = t + sh[i];
+    return t;
+}
+// The LARGEST bit pattern of a non-negative double whose choice has S <= target: bisection over the patterns, 64 steps, the midpoint rounded
+// up.  Pattern 0 always fits (lambda = +0.0 takes every hull to its last point, where D = 0), so `lo` is a fitting pattern throughout.
+// Writes that choice to kept[0 ... njobs), its bytes to *bytes (every thread), and returns its S.
+__device__ __forceinline__ double quality_search(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist, const double *__restrict__ weights,
+                                                 const RateWs &W, double target, uint64_t *sh, double *shf, uint8_t *__restrict__ kept, uint64_t *bytes) {
+    const int tid = threadIdx.x;
+    uint64_t lo = 0, hi = 0x7FFFFFFFFFFFFFFFull;
+    for (int step = 0; step < 64; step++) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        const double lam = __longlong_as_double((long long)mid);
+        double s = 0.0;
+        for (int j = tid; j < njobs; j += RATE_WG) s = s + weights[j] * (double)dist[(size_t)j * RATE_STRIDE + rate_pick(W, j, lam)];
+        s = wg_sum_f64(s, shf);                          // every thread takes every step: wg_sum_f64 has barriers
+        if (s <= target) lo = mid; else hi = mid - 1;
+    }
+    const double lam = __longlong_as_double((long long)lo);
+    uint64_t b = 0;
+    double s = 0.0;
+    for (int j = tid; j < njobs; j += RATE_WG) {
+        const int p = rate_pick(W, j, lam);
+        kept[j] = (uint8_t)p;
+        b += rate[(size_t)j * RATE_STRIDE + p];
+        s = s + weights[j] * (double)dist[(size_t)j * RATE_STRIDE + p];
+    }
+    *bytes = wg_sum(b, sh);
+    return wg_sum_f64(s, shf);
+}
+
+struct RateTargets { double t[32]; };
+// One workgroup, a sibling of rate_allocate_layers_kernel: layer l is the search for targets.t[l] -- kept[l * njobs + j], chosen[l] (body bytes),
+// achieved[l] (S).  The hulls are built once.  Targets fall with l, "the largest lambda that fits" then makes kept monotone in l.
+__global__ __launch_bounds__(RATE_WG) void rate_allocate_quality_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
+                                                                        const uint8_t *__restrict__ numbps, const double *__restrict__ weights,
+                                                                        const RateTargets targets, int nlayers, void *__restrict__ ws,
+                                                                        uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen, double *__restrict__ achieved) {
+    __shared__ uint64_t sh[RATE_WG / 64];
+    __shared__ double shf[RATE_WG / 64];
+    const RateWs W = rate_ws(ws, (size_t)njobs);
+    rate_hulls(njobs, rate, dist, numbps, weights, W);
+    for (int l = 0; l < nlayers; l++) {
+        uint64_t b = 0;
+        const double s = quality_search(njobs, rate, dist, weights, W, targets.t[l], sh, shf, kept + (size_t)l * njobs, &b);
+        if (threadIdx.x == 0) { chosen[l] = b; achieved[l] = s; }
+    }
+}
+
+// targets: nlayers <= 32 values on the host (a kernel argument); kept: nlayers x njobs bytes; chosen: nlayers x uint64; achieved: nlayers x double
+hipError_t launch_rate_allocate_quality(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+                                        const double *targets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved) {
+    RateTargets T{};
+    for (int l = 0; l < nlayers && l < 32; l++) T.t[l] = targets[l];
+    hipLaunchKernelGGL(rate_allocate_quality_kernel, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, T, std::min(nlayers, 32), ws, kept, chosen, achieved);
+    return hipGetLastError();
+}
+
 hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, uint64_t *dist) {
     if (njobs <= 0) return hipSuccess;
     hipLaunchKernelGGL(rate_distortion_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, numbps, dist);

@@ -76,6 +76,7 @@ SYMBOLS = [
     "j2k_tile_parts_keep_layers",
     "j2k_plan_area_shape", "j2k_plan_area_blocks", "j2k_plan_decode_frame_pixels_area", "j2k_decode_pixels_host_area",
     "j2k_plan_roi_windows", "j2k_plan_encode_blocks_planes_roi", "j2k_plan_encode_frame_pixels_roi", "j2k_encode_pixels_host_roi",
+    "j2k_plan_psnr_distortion", "j2k_plan_rate_allocate_quality", "j2k_plan_encode_frame_pixels_quality", "j2k_encode_pixels_host_quality", "j2k_pixels_sse",
     "j2k_plan_pack_bound", "j2k_plan_pack_stream", "j2k_plan_unpack_stream", "j2k_plan_unpack_streams",
     "j2k_comm_load_error", "j2k_comm_get_unique_id", "j2k_comm_create", "j2k_comm_destroy", "j2k_comm_last_error", "j2k_comm_stream", "j2k_gather_streams", "j2k_comm_wait",
 ]
@@ -168,6 +169,11 @@ def lib():
             "j2k_plan_encode_blocks_planes_roi": (I, [V, V, V, V, V, V, V, C.POINTER(Rect), I]),
             "j2k_plan_encode_frame_pixels_roi": (I, [V, I, V, S, I, I, I64P, I, C.POINTER(Rect), I, V, S, V, V]),
             "j2k_encode_pixels_host_roi": (I, [V, I, V, S, I, I, I64P, I, C.POINTER(Rect), I, V, S, C.POINTER(S), V, V, V, V]),
+            "j2k_plan_psnr_distortion": (I, [V, C.c_double, DP]),
+            "j2k_plan_rate_allocate_quality": (I, [V, V, V, V, DP, I, V, V, V]),
+            "j2k_plan_encode_frame_pixels_quality": (I, [V, I, V, S, I, I, DP, I, C.POINTER(Rect), I, V, S, V, V, V]),
+            "j2k_encode_pixels_host_quality": (I, [V, I, V, S, I, I, DP, I, C.POINTER(Rect), I, V, S, C.POINTER(S), V, V, V, V, V]),
+            "j2k_pixels_sse": (I, [V, I, V, S, V, S, I, I, V]),
         }
         for name, (res, args) in sigs.items():
             if partial and not hasattr(L, name):

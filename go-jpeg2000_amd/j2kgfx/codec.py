@@ -271,6 +271,52 @@ class FramePlan:
         self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_layers(self.h, self._p(rate), self._p(dist), self._p(numbps), arr, L, self._p(kept), self._p(chosen)))
         return kept[:L * n].view(L, n), chosen[:L]
 
+    # ---- quality targets: the dual of the byte budgets (j2k_*_quality; tests/quality_cases.py is the definition) -------
+    def psnr_distortion(self, db):
+        """the weighted-distortion target T of a PSNR in dB: width * height * ncomp * peak^2 * q^2 / 10^(dB / 10), peak = 2^precision - 1,
+        q = the plan's quality on a lossy plan, 1 on a lossless one (j2k_plan_psnr_distortion; host only)"""
+        T = C.c_double(0.0)
+        self.ctx.check(self.ctx.L.j2k_plan_psnr_distortion(self.h, C.c_double(float(db)), C.byref(T)))
+        return float(T.value)
+
+    @staticmethod
+    def _targets(targets):
+        t = [float(x) for x in targets]
+        return (C.c_double * max(len(t), 1))(*t), len(t)
+
+    def _quality_args(self, who, max_body_bytes, layer_bytes, min_psnr, max_distortion, layer_psnr, layer_distortion):
+        """the one quality argument of an encode call -> (targets, layered), or None without one"""
+        given = [k for k, v in (("min_psnr", min_psnr), ("max_distortion", max_distortion), ("layer_psnr", layer_psnr), ("layer_distortion", layer_distortion))
+                 if v is not None]
+        if not given:
+            return None
+        if len(given) > 1:
+            raise ValueError("%s: %s together -- one quality argument" % (who, " and ".join(given)))
+        if max_body_bytes is not None or layer_bytes is not None:
+            raise ValueError("%s: %s together with a byte budget -- ask for bytes or for quality" % (who, given[0]))
+        if min_psnr is not None:
+            return [self.psnr_distortion(min_psnr)], False
+        if max_distortion is not None:
+            return [float(max_distortion)], False
+        if layer_psnr is not None:
+            return [self.psnr_distortion(d) for d in layer_psnr], True
+        return [float(t) for t in layer_distortion], True
+
+    @_stage
+    def rate_allocate_quality(self, rate, dist, numbps, targets, kept=None, chosen=None, achieved=None):
+        """the planes to keep of every block so that the weighted distortion sum_j w_j * dist[j, kept_j] (float64, in the fixed order of
+        tests/quality_cases.py) is at most targets[l], in as few body bytes as the hulls allow; targets fall (or stay) layer by layer:
+        (kept uint8 [L, blocks], chosen int64 [L] = body bytes, achieved float64 [L] = that sum)  (j2k_plan_rate_allocate_quality)"""
+        t = _torch()
+        n = int(self.info.blocks)
+        arr, L = self._targets(targets)
+        kept = kept if kept is not None else self.empty(max(L, 1) * n, t.uint8)
+        chosen = chosen if chosen is not None else t.zeros(max(L, 1), dtype=t.int64, device=self.device)
+        achieved = achieved if achieved is not None else t.zeros(max(L, 1), dtype=t.float64, device=self.device)
+        self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_quality(self.h, self._p(rate), self._p(dist), self._p(numbps), arr, L, self._p(kept), self._p(chosen),
+                                                                 self._p(achieved)))
+        return kept[:L * n].view(L, n), chosen[:L], achieved[:L]
+
     def frame_bound_layers(self, nlayers):
         return int(self.ctx.L.j2k_plan_frame_bound_layers(self.h, int(nlayers)))
 
@@ -486,7 +532,8 @@ class FramePlan:
         return int(n.value)
 
     @_stage
-    def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16):
+    def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16,
+                            min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None):
         """pixels (a Go Pix layout, device uint8 [H, stride]) -> tile-parts: (out uint8, tile_offs int64[tiles + 1]).  max_body_bytes (closed-loop
         MQ plans): at most that many bytes of code-block bodies -- packet and tile-part headers come on top, tile_offs[-1] says what the frame took
         (j2k_plan_encode_frame_pixels_rate); decode with truncated=True.  layer_bytes = [B_0 <= B_1 <= ...] (the same plans; not together with
@@ -495,8 +542,28 @@ class FramePlan:
         roi=(x0, y0, x1, y1) with either budget (Mallat plans): a region of interest -- the distortion of the coefficients that reconstruct that
         rectangle counts roi_gain times (an integer 1 ... 65535, a weight on energy: 4^s is about s bit planes of priority), so the budget
         goes there first.  The stream and its decoders are as without it; decode with area=roi for the rectangle alone
-        (j2k_plan_encode_frame_pixels_roi).  roi=None takes the calls it took before"""
+        (j2k_plan_encode_frame_pixels_roi).  roi=None takes the calls it took before.
+        Quality in the place of bytes (the same plans; one of them, and no byte budget beside it -- ValueError): min_psnr = dB or max_distortion = T
+        -> (out, tile_offs, achieved float64 [1]), the stream of max_body_bytes for the fewest body bytes whose weighted distortion estimate is at
+        most T = psnr_distortion(dB); layer_psnr = [rising dB] or layer_distortion = [falling T] -> (out, tile_offs, layer_offs, achieved [L]), the
+        layered stream.  achieved: the estimate of every layer's choice, <= its target.  An ESTIMATE in the coefficient domain:
+        measure the decoded frame with pixels.psnr.  roi= / roi_gain= weigh the rectangle as with a budget (j2k_plan_encode_frame_pixels_quality)"""
         t = _torch()
+        q = self._quality_args("encode_frame_pixels", max_body_bytes, layer_bytes, min_psnr, max_distortion, layer_psnr, layer_distortion)
+        if q is not None:
+            targets, layered = q
+            arr, L = self._targets(targets)
+            nt = int(self.info.tiles)
+            r = self._rect(roi) if roi is not None else None
+            out = out if out is not None else self.empty((self.frame_bound_layers(L) or 64) if layered else self.frame_bound(), t.uint8)
+            tile_offs = tile_offs if tile_offs is not None else self.empty(nt + 1, t.int64)[:nt + 1]
+            layer_offs = self.empty(nt * max(L, 1), t.int64)[:nt * max(L, 1)] if layered else None
+            achieved = t.zeros(max(L, 1), dtype=t.float64, device=self.device)
+            self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_quality(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
+                                                                           arr, L, C.byref(r) if r is not None else None, int(roi_gain), self._p(out),
+                                                                           C.c_size_t(int(out.numel())), self._p(tile_offs), self._p(layer_offs) if layered else None,
+                                                                           self._p(achieved)))
+            return (out, tile_offs, layer_offs, achieved[:L]) if layered else (out, tile_offs, achieved[:L])
         if roi is not None:
             if max_body_bytes is None and layer_bytes is None:
                 raise ValueError("encode_frame_pixels: roi= shifts a budget -- give max_body_bytes= or layer_bytes=")
@@ -574,13 +641,37 @@ class FramePlan:
         return pix
 
     # ---- host memory in, host memory out: the one-call forms (j2k_encode_pixels_host / j2k_decode_pixels_host) -------------------
-    def encode_pixels_host(self, fmt, pix, sop=False, eph=False, cap=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16):
+    def encode_pixels_host(self, fmt, pix, sop=False, eph=False, cap=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16,
+                           min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None):
         """pix: numpy uint8 [H, stride] (a Go Pix layout) -> dict(bytes, tile_offs, lens, numbps): every tile as a tile-part.  max_body_bytes: as
         encode_frame_pixels (j2k_encode_pixels_host_rate; lens / numbps are the uncut ones); layer_bytes: as encode_frame_pixels, the dict also
         holds layer_offs uint64 [tiles * L] (j2k_encode_pixels_host_layers); roi, roi_gain with either budget: as encode_frame_pixels
-        (j2k_encode_pixels_host_roi)"""
+        (j2k_encode_pixels_host_roi); min_psnr / max_distortion / layer_psnr / layer_distortion: as encode_frame_pixels, the dict also holds
+        achieved float64 [L] (j2k_encode_pixels_host_quality)"""
         L = self.ctx.L
         n, nt = int(self.info.blocks), int(self.info.tiles)
+        q = self._quality_args("encode_pixels_host", max_body_bytes, layer_bytes, min_psnr, max_distortion, layer_psnr, layer_distortion)
+        if q is not None:
+            targets, layered = q
+            arr, nl = self._targets(targets)
+            r = self._rect(roi) if roi is not None else None
+            cap = int(cap) if cap is not None else max(self.frame_bound_layers(nl) or 64, self.frame_bound()) + 64
+            pix = np.ascontiguousarray(pix, dtype=np.uint8)
+            out = np.zeros(max(cap, 1), np.uint8)
+            toffs = np.zeros(nt + 1, np.uint64); loffs = np.zeros(max(nt * nl, 1), np.uint64)
+            lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
+            ach = np.zeros(max(nl, 1), np.float64)
+            olen = C.c_size_t(0)
+            st = L.j2k_encode_pixels_host_quality(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)), arr, nl,
+                                                  C.byref(r) if r is not None else None, int(roi_gain), out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen),
+                                                  toffs.ctypes.data_as(C.c_void_p), loffs.ctypes.data_as(C.c_void_p) if layered else None,
+                                                  lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p), ach.ctypes.data_as(C.c_void_p))
+            self.encoded_len = olen.value
+            self.ctx.check(st)
+            res = dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy(), achieved=ach[:nl].copy())
+            if layered:
+                res["layer_offs"] = loffs[:nt * nl].copy()
+            return res
         if roi is not None:
             if max_body_bytes is None and layer_bytes is None:
                 raise ValueError("encode_pixels_host: roi= shifts a budget -- give max_body_bytes= or layer_bytes=")

@@ -52,6 +52,37 @@ def create_image(planes, prec, stride=None, ctx=None):
     return pix
 
 
+# ---- what came out: squared error and PSNR of two DEVICE frames (j2k_pixels_sse) ---------------------------------------------
+def sse(fmt, a, b, w, h, ctx=None):
+    """a, b: torch uint8 [h, stride] on the context's device, the same Pix layout (strides may differ).  Returns numpy uint64 [channels as
+    stored: 1 for the gray formats, 4 with alpha for the others]: the exact sum of squared sample differences of every channel.  The frames
+    stay on the device; synchronises the context (what torch has queued on its current stream is waited for first)."""
+    import torch
+    ctx = ctx or default_context()
+    assert a.dim() == 2 and b.dim() == 2 and a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.is_contiguous() and b.is_contiguous()
+    if int(a.shape[0]) < int(h) or int(b.shape[0]) < int(h):
+        raise _lib.J2KError(_lib.ERR_INVALID_ARG, "pixels.sse: fewer than h rows")
+    nch = 1 if components(fmt) == 1 else 4
+    sums = torch.zeros(4, dtype=torch.int64, device=a.device)
+    torch.cuda.current_stream(a.device).synchronize()
+    ctx.check(ctx.L.j2k_pixels_sse(ctx.h, int(fmt), C.c_void_p(a.data_ptr()), C.c_size_t(int(a.shape[1])), C.c_void_p(b.data_ptr()), C.c_size_t(int(b.shape[1])),
+                                   int(w), int(h), C.c_void_p(sums.data_ptr())))
+    ctx.sync()
+    return sums.cpu().numpy().view(np.uint64)[:nch].copy()
+
+
+def psnr(fmt, a, b, w, h, ctx=None):
+    """10 log10(peak^2 * samples / squared error) of two device frames over the gray or the three colour channels (alpha is left out), peak =
+    2^precision(fmt) - 1; inf for equal frames"""
+    s = sse(fmt, a, b, w, h, ctx=ctx)
+    nch = min(len(s), 3)
+    total = int(s[:nch].astype(object).sum())
+    if total == 0:
+        return float("inf")
+    peak = float((1 << precision(fmt)) - 1)
+    return 10.0 * float(np.log10(peak * peak * float(int(w) * int(h) * nch) / float(total)))
+
+
 # ---- the default branch (encoder.go:178-195): Go's *image.YCbCr, *image.CMYK, *image.Paletted by their fields -----------------
 # Planes are 1-D uint8 buffers -- numpy arrays (host calls) or torch tensors (device calls) -- with Go's strides and lengths;
 # rect = image.Rect(min_x, min_y, max_x, max_y).

@@ -888,6 +888,43 @@ int j2k_encode_pixels_host_roi(j2k_plan *plan, int format, const void *pix, size
                                int nlayers, const j2k_rect *roi, int roi_gain, uint8_t *out, size_t cap, size_t *out_len,
                                uint64_t *tile_offs, uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps);
 
+/* Quality-targeted encode (the library's own): the dual of the rate calls above -- "at least this good, in as few bytes as that takes".  The
+ * tables, the band weights, the hulls and the rule "block j keeps the last hull point whose slope is >= lambda" are those of
+ * j2k_plan_rate_allocate; the search runs on the weighted distortion S = sum_j w_j * float64(d_dist[j * 32 + kept_j]) instead of the byte sum:
+ * lambda is the float64 with the LARGEST bit pattern in 0 ... 2^63 - 1 whose choice has S <= target (64 bisection steps).  S is a float64 sum in
+ * a FIXED order (the allocation's one workgroup of 1024 threads: thread i adds its blocks i, i + 1024, ... from 0.0, six butterfly steps inside
+ * each wavefront, the 16 wavefront values in order); tests/quality_cases.py is the definition the device agrees with bit for bit.  lambda = +0.0
+ * keeps everything that lowers a block's distortion, where S = 0: no target is infeasible.  A target at or above the distortion of coding nothing
+ * codes nothing.
+ *   S is an ESTIMATE of the squared error of the frame, not a bound: the weights are synthesis energy gains, so it measures the colour-transformed
+ * components (not RGB), in the coefficient domain, without the rounding of the 5-3, the clamp to the sample range or the cross terms between
+ * blocks.  Measure what came out with j2k_pixels_sse; docs/KERNEL_NOTES.md has a table of targets against measured PSNR.  Body bytes only: no
+ * header bytes are counted or minimised, and cuts are at whole bit planes.
+ *   j2k_plan_psnr_distortion           HOST ONLY: *T = N * peak^2 * q^2 / 10^(dB / 10), N = width * height * components, peak = 2^precision - 1,
+ *                                      q = the plan's quality on a lossy plan (its coefficients are the transform times quality), 1 on a lossless one
+ *   j2k_plan_rate_allocate_quality     targets[l] (host, non-increasing, 1 <= nlayers <= 32) -> d_kept[l * blocks + j], d_chosen[l] = the body
+ *                                      bytes, d_achieved[l] = S of layer l's choice (float64, <= targets[l]); one launch
+ *   j2k_plan_encode_frame_pixels_quality  the frame call: j2k_plan_encode_frame_pixels_rate (nlayers = 1, d_layer_offs = NULL) or
+ *                                      j2k_plan_encode_frame_pixels_layers with that allocation in the place of theirs; roi (nullable) and
+ *                                      roi_gain as j2k_plan_encode_frame_pixels_roi; d_achieved (device, nullable): nlayers float64.  Decode with the
+ *                                      _rate / _layers decode calls
+ *   j2k_encode_pixels_host_quality     its synchronous host-memory form (achieved: host, nullable)
+ * Refusals, all before the first launch: what j2k_plan_rate_allocate / the _layers / the _roi calls refuse, with their codes; a target that is
+ * negative, NaN or infinite, targets that rise, nlayers outside 1 ... 32, more than one target without d_layer_offs: J2K_ERR_INVALID_ARG. */
+int j2k_plan_psnr_distortion(const j2k_plan *plan, double db, double *T);
+int j2k_plan_rate_allocate_quality(j2k_plan *plan, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, const double *targets,
+                                   int nlayers, uint8_t *d_kept, uint64_t *d_chosen, double *d_achieved);
+int j2k_plan_encode_frame_pixels_quality(j2k_plan *plan, int format, const void *d_pix, size_t stride, int sop, int eph, const double *targets,
+                                         int nlayers, const j2k_rect *roi, int roi_gain, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs,
+                                         uint64_t *d_layer_offs, double *d_achieved);
+int j2k_encode_pixels_host_quality(j2k_plan *plan, int format, const void *pix, size_t stride, int sop, int eph, const double *targets,
+                                   int nlayers, const j2k_rect *roi, int roi_gain, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs,
+                                   uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, double *achieved);
+/* Per-channel sum of squared sample differences of two DEVICE frames in the same pixel format (J2K_PIX_*; 16-bit samples big-endian):
+ * d_sums[c] for every channel as stored -- 1 for the gray formats, 4 (alpha included) for the others -- exact in uint64.  Two launches on the
+ * context's stream, no atomics; asynchronous. */
+int j2k_pixels_sse(j2k_ctx *ctx, int format, const void *d_a, size_t stride_a, const void *d_b, size_t stride_b, int w, int h, uint64_t *d_sums);
+
 /* The block coder's outputs as those tables.  j2k_plan_t2_packets (host table out): one packet per (tile, component,
  * resolution) of the plan in job order (encoder.go:616-673: tile, component, resolution, band, block row, block column), its
  * code-blocks = the plan's jobs of that resolution, tree widths = block columns of its first band; layer as given.
