@@ -486,7 +486,8 @@ class FramePlan:
         return out, tile_offs
 
     @_stage
-    def decode_tile_parts(self, cs, length, tile_offs=None, sop=False, eph=False, offs=None, lens=None, numbps=None, floors=None, layers=None):
+    def decode_tile_parts(self, cs, length, tile_offs=None, sop=False, eph=False, offs=None, lens=None, numbps=None, floors=None, layers=None, dense=None,
+                          dense_cap=None):
         """tile-parts cs[:length] -> (offs, lens, numbps) as decode_blocks takes them (offsets into cs).  floors = True or a device uint8
         [blocks] tensor (MQ plans): also every block's floor, for streams cut at bit planes -- returns (offs, lens, numbps, floors) with
         numbps counted from each block's top plane down to bit 0 (j2k_plan_decode_tile_parts_floors)"""
@@ -497,11 +498,16 @@ class FramePlan:
         numbps = numbps if numbps is not None else self.empty(n, t.uint8)
         if layers is not None:
             # the first `layers` layers of a layered stream: every block's segments gathered into a dense buffer -- returns (dense, offs, lens,
-            # numbps, floors), offsets into dense; decode_blocks(dense, offs, lens, numbps, floors=floors) (j2k_plan_decode_tile_parts_layers)
+            # numbps, floors), offsets into dense; decode_blocks(dense, offs, lens, numbps, floors=floors) (j2k_plan_decode_tile_parts_layers).
+            # dense: a caller-owned device uint8 buffer in the place of one of length + 64 bytes, dense_cap: how many of its bytes the call may
+            # use (default: all) -- blocks that do not fit are dropped and frame_status() raises J2K_ERR_CAPACITY
             floors = self.empty(n, t.uint8) if floors is None or floors is True or floors is False else floors
-            dense = self.empty(int(length) + 64, t.uint8)
+            dense = dense if dense is not None else self.empty(int(length) + 64, t.uint8)
+            cap = int(dense.numel()) if dense_cap is None else int(dense_cap)
+            if cap < 0 or cap > int(dense.numel()):
+                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "decode_tile_parts: dense_cap is not within dense")
             self.ctx.check(self.ctx.L.j2k_plan_decode_tile_parts_layers(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
-                                                                        int(bool(sop)), int(bool(eph)), int(layers), self._p(dense), C.c_size_t(int(dense.numel())),
+                                                                        int(bool(sop)), int(bool(eph)), int(layers), self._p(dense), C.c_size_t(cap),
                                                                         self._p(offs), self._p(lens), self._p(numbps), self._p(floors)))
             return dense, offs, lens, numbps, floors
         if floors is not None and floors is not False:

@@ -20,8 +20,9 @@ bodies at the first inclusion only), so the header walk is restated here on t2re
 first comes from layer 0's unary where layer 0's packet holds data; a layer-0 packet WITHOUT data (presence bit 0) carries no unary at all, so
 the rule that covers both is: at l > 0, ZeroBitPlanes follows the "contributes" bit iff the block has not contributed in an earlier layer --
 on every stream the composer writes that is exactly l == first.  A unary value >= the layers being read just means "not in what is read".
-Passes and lengths accumulate; every contributing (layer, block) is one body segment; floor and plane count are
-rate_cases.floors_from_header on the sums."""
+Passes and lengths accumulate; every contributing (layer, block) is one body segment; a contribution of length 0, which no writer makes, counts
+for the ZeroBitPlanes rule and adds neither a segment nor its passes; floor and plane count are rate_cases.floors_from_header on the sums.
+tests/stream_reader_cases.py has the same reader with a verdict per tile in the place of an exception."""
 import rate_cases as rc
 
 MAX_LAYERS = 32
@@ -142,8 +143,10 @@ def read_layers(t2ref, stream, tile_offs, tiles, k, sop, eph, tile_first=0):
                             continue
                         if s["zbp"] is None:                         # its first contribution: ZeroBitPlanes
                             s["zbp"] = dec.decode_tag_tree_value()
-                        s["passes"] += dec.decode_num_passes()
+                        npass = dec.decode_num_passes()
                         lens.append((j, dec.decode_length()))
+                        if lens[-1][1]:                              # a contribution of length 0 (no writer makes one) adds no passes: DESIGN.md 7
+                            s["passes"] += npass
                 dec.pos = dec.bio.rpos
                 if eph and dec.pos + 2 <= len(dec.buf) and dec.buf[dec.pos] == 0xFF and dec.buf[dec.pos + 1] == 0x92:
                     dec.pos += 2

@@ -191,16 +191,17 @@ _SLOT_CACHE = {}
 
 def plan_slot_offset(plan, j):
     """byte offset of job j's coding slot (the slots are the blocks' bounds rounded up to 16, in job order)"""
+    import weakref
     from j2kgfx import entropy
-    key = id(plan)
-    if key not in _SLOT_CACHE:
-        _SLOT_CACHE.clear()
+    # (the entry is its plan's while that very object lives: a later plan may get a closed one's id(), and with it another geometry's offsets)
+    ref, offs = _SLOT_CACHE.get("plan", (None, None))
+    if ref is None or ref() is not plan:
         offs, pos = [], 0
         for b in plan.blocks():
             offs.append(pos)
             pos += (entropy.block_bound(0, int(b["w"]), int(b["h"])) + 15) & ~15
-        _SLOT_CACHE[key] = offs
-    return _SLOT_CACHE[key][j]
+        _SLOT_CACHE["plan"] = (weakref.ref(plan), offs)
+    return offs[j]
 
 
 def test_cut_stream_without_truncated_keeps_the_old_rule(env):
