@@ -1346,18 +1346,36 @@ __global__ __launch_bounds__(256) void ht_vlcprep_kernel(const BlockJob *__restr
 // only when they are equal does it write HT_PAIR_DUP and stop -- no unstuffing, no bit string, no walk, no decode; ht_decode_lean_kernel<false, true>'s leader
 // wavefront stores its rows to the follower's block as well.  On any difference the block goes on exactly as in ht_vlcprep_kernel and decodes itself.
 //
-// What is compared: the lengths, and EVERY byte [0, len) of the two blocks.  That is a superset of what any decode path reads -- the parallel paths read
-// the MagSgn segment [0, len - scup) (ht_extract_fast and the lean path, whole, in 1 KB batches), the at most four bytes at the MEL start (init_mel_ok),
-// the VLC bytes [len - 2 - ht_vlc_nbytes, len - 2) (ht_vlc_load4) and the two trailer bytes (ht_vlc_head); the serial path of ht_decode_block reads the
-// same segments byte by byte; nothing reads the interior of the MEL run, which is a few bytes and rides along rather than being cut out of the loop.
-// Same bytes, same w, h and len give the same tag, records and samples, on whichever path the leader ends up; nothing else enters the decision.
-// (A block shorter than four bytes is never a follower: the compare works in 4-byte pieces, the last one pulled back to end at len.)
-// Round trips: rep[jid] rides with the job, offs[rep] / lens[rep] with the trailer bytes, the first 1 KB of both blocks with the VLC bytes: four, as before.
-// A block longer than 1 KB takes one more per KB, and stops at the first batch that differs.
+// What is compared: the lengths, and exactly the bytes a decode path can read (with nvlc = ht_vlc_nbytes, the bytes the prep's string takes):
+//   A = [0, min(len, len - scup + 4))   the MagSgn segment and the MEL start;      B = [len - 2 - nvlc, len)   the VLC reach and the trailer;
+// when A reaches B, [0, len).  The readers, each with the lowest and the highest byte of the block it can touch:
+//   ht_vlc_head                 data[len - 2], data[len - 1] (b0, SCUP)                                                      -- B (the trailer)
+//   init_mel_ok                 data[len - scup + i], i < min(4 - ((len - scup) & 3), scup - 1), below len                   -- A (its last four bytes)
+//   ht_vlc_load4 / ht_vlc_unstuff   [len - 2 - nvlc, len - 3]; a group the segment ends in loads the segment's first four bytes, nothing below them -- B
+//   the lean path's 1 KB batches, ht_extract_fast   aligned dwords over [-(d), len - scup + 3) with d = address & 3 of the block: up to three bytes
+//                               BEFORE the block and up to three past the segment are loaded, and every one of them gets width 0 (`valid`), is kept out
+//                               of `plain` (k0 >= 1 && k0 + 4 <= nb) and is deposited nowhere; the byte before the segment is looked at only for k > 0.
+//                               They reach no result (and only the leader's own are loaded: nothing is decoded for a verified follower) -- A covers the rest
+//   the serial path of ht_decode_block   MagSgn: data[0 .. len - scup) (FwdStream, size len - scup) -- A; the trailer and init_mel_ok as above; VLC: data[len - 2]
+//                               and then downwards, four bytes at a time while its 64-bit window holds 32 bits or fewer.  It walks the same code words as the
+//                               walk kernel, so what it CONSUMES lies in the string the prep made, i.e. in B; its window can hold bytes below B, which no
+//                               code word reaches.  (That is the parent's own assumption: a block whose code words reached past nvlc bytes would be walked
+//                               on a string that ends early, with or without this option.)
+// Nothing reads the rest -- the interior of the MEL run, [len - scup + 4, len - 2 - nvlc).  That is not "a few bytes": the reference writes max(64, 2 w h) / 4
+// zero bytes of MEL per block (ht.go:978, 1019; mel_bytes in compact.hip), and on three tiles of the headline frame (477 non-empty blocks) a block is
+// 2 792 bytes on average, of which 467 are MagSgn, 633 the VLC reach and 1 686 (60 %) this interior: 3.4 batches of 1 KB per follower with it, 1.8 without.
+// Same read set, same w, h and len give the same tag, records and samples, on whichever path the leader ends up; nothing else enters the decision.
+// (A block shorter than four bytes is never a follower: the compare works in 4-byte pieces, the last one pulled back to end at the range's end; A is
+// never shorter than four bytes because scup <= len.)
+// Round trips: rep[jid] and walk_pos[jid] ride with the job, offs[rep] / lens[rep] with the trailer bytes; then ONE for the follower's VLC bytes (pre[], its
+// side of B), the leader's (the same ht_vlc_load4 on the leader's bytes), the 4-byte piece that ends at len of both (the trailer) and the first 1 KB of A of
+// both.  Only a MagSgn segment longer than 1 KB takes further batches, one per KB, and stops at the first that differs.
+// The bit string of a block that does unstuff goes to row walk_pos[jid] of vbits: the walk's order (leaders first), not the job order.
 __global__ __launch_bounds__(256) void ht_vlcprep_dedup_kernel(const BlockJob *__restrict__ jobs, int njobs,
                                                                const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offs,
                                                                const uint32_t *__restrict__ lens, uint32_t *__restrict__ vbits,
-                                                               uint32_t *__restrict__ pairs, const int32_t *__restrict__ rep) {
+                                                               uint32_t *__restrict__ pairs, const int32_t *__restrict__ rep,
+                                                               const int32_t *__restrict__ walk_pos) {
     __shared__ uint32_t vb4[4][HT_VBITS_WORDS + 8];
     uint32_t *vb = vb4[threadIdx.x >> 6];
     const int jid = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1365,6 +1383,7 @@ __global__ __launch_bounds__(256) void ht_vlcprep_dedup_kernel(const BlockJob *_
     const int lane = threadIdx.x & 63;
     uint32_t *rec = pairs + (size_t)jid * HT_WALK_REC;
     const int ldr = rep[jid];
+    const int slot = walk_pos[jid];
     const uint64_t loff = offs[ldr];
     const uint32_t llen = lens[ldr];
     const HtVlcHead H = ht_vlc_head(jobs, jid, stream, offs, lens);
@@ -1374,26 +1393,42 @@ __global__ __launch_bounds__(256) void ht_vlcprep_dedup_kernel(const BlockJob *_
     for (int c = 0; c < HT_VLC_STEPS; c++) pre[c] = ht_vlc_load4(H.data, (long)H.len, nb, 1 + 256 * c + 4 * lane);
     if (ldr != jid && H.tag == 0 && llen == H.len && H.len >= 4) {       // wave-uniform
         const uint8_t *mine = H.data, *theirs = stream + loff;
-        const uint32_t len = H.len, nd = (len + 3) >> 2;
-        bool same = true;
-        for (uint32_t j0 = 0; j0 < nd && same; j0 += 256) {
-            uint32_t x[4], y[4];
+        const uint32_t len = H.len;
+        uint32_t aend = min(len, len - H.scup + 4);                      // A = [0, aend), at least four bytes
+        if (aend >= len - 2 - (uint32_t)nb) aend = len;                  // A meets B: the whole block (B rides along)
+        const uint32_t nd = (aend + 3) >> 2;
+        uint32_t x[4], y[4], lb[HT_VLC_STEPS], tx, ty;
+#pragma unroll
+        for (int c = 0; c < HT_VLC_STEPS; c++) lb[c] = ht_vlc_load4(theirs, (long)len, nb, 1 + 256 * c + 4 * lane);
+        __builtin_memcpy(&tx, mine + (len - 4), 4);
+        __builtin_memcpy(&ty, theirs + (len - 4), 4);
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const uint32_t p = min(4 * (64 * c + lane), aend - 4);       // piece j of both blocks; past the end: the last piece again
+            __builtin_memcpy(&x[c], mine + p, 4);
+            __builtin_memcpy(&y[c], theirs + p, 4);
+        }
+        bool eq = tx == ty;
+#pragma unroll
+        for (int c = 0; c < HT_VLC_STEPS; c++) eq &= pre[c] == lb[c];
+        bool same = __all(eq & (x[0] == y[0]) & (x[1] == y[1]) & (x[2] == y[2]) & (x[3] == y[3]));
+        for (uint32_t j0 = 256; j0 < nd && same; j0 += 256) {
 #pragma unroll
             for (int c = 0; c < 4; c++) {
-                const uint32_t p = min(4 * (j0 + 64 * c + lane), len - 4);   // piece j of both blocks; past the end: the last piece again
+                const uint32_t p = min(4 * (j0 + 64 * c + lane), aend - 4);
                 __builtin_memcpy(&x[c], mine + p, 4);
                 __builtin_memcpy(&y[c], theirs + p, 4);
             }
             same = __all((x[0] == y[0]) & (x[1] == y[1]) & (x[2] == y[2]) & (x[3] == y[3]));
         }
         if (same) {
-            if (lane == 0) { rec[0] = HT_PAIR_DUP; rec[1] = (uint32_t)ldr; rec[HT_WALK_MAX_PAIRS] = H.scup; }   // (the leader: for the decode kernel)
+            if (lane == 0) { rec[0] = HT_PAIR_DUP; rec[1] = (uint32_t)ldr; rec[HT_WALK_MAX_PAIRS] = H.scup; }   // (the leader's id: for whoever reads the records)
             return;
         }
     }
     ht_vlc_unstuff(H, lane, vb, rec, pre);
     if (H.tag) return;
-    uint32_t *dst = vbits + (size_t)jid * HT_VBITS_WORDS;
+    uint32_t *dst = vbits + (size_t)slot * HT_VBITS_WORDS;
     for (int i = lane; i < HT_VBITS_WORDS; i += 64) dst[i] = vb[i];
 }
 
@@ -1495,16 +1530,31 @@ __device__ __forceinline__ uint32_t ht_walk_lane(const uint32_t *row, const uint
     return pos;
 }
 
-// DEDUP (behind ht_vlcprep_dedup_kernel): a lane whose block is tagged HT_PAIR_DUP idles (the chain per block is what the kernel costs, so nothing else changes)
+// DEDUP (behind ht_vlcprep_dedup_kernel): a lane whose block is tagged HT_PAIR_DUP idles, and the lanes are dealt in the plan's walk order, not in job
+// order: slot s = 64 blockIdx.x + lane belongs to job walk_order[s] and its bit string is row s of vbits (the prep wrote it there), so the staging is the
+// same contiguous batch of loads and walk_order rides with it; the tag, w, h and the records follow from the job id.  The first nlead slots are the jobs
+// that lead themselves -- they fill whole workgroups -- and a workgroup that starts at or behind slot nlead holds static followers only: it looks at its 64
+// tags first and leaves, with nothing staged, unless a follower failed the prep's compare (then it goes on as any other workgroup, one round trip late).
+// The workgroup in which the leaders end counts as a leader workgroup.
 template <bool DEDUP>
 __global__ __launch_bounds__(256) void ht_walk_kernel(const BlockJob *__restrict__ jobs, int njobs,
-                                                     const uint32_t *__restrict__ vbits, uint32_t *__restrict__ pairs) {
+                                                     const uint32_t *__restrict__ vbits, uint32_t *__restrict__ pairs,
+                                                     const int32_t *__restrict__ walk_order, int nlead) {
     extern __shared__ __align__(16) unsigned char walk_smem[];
     HtWalkShared &S = *reinterpret_cast<HtWalkShared *>(walk_smem);
     const int tid = threadIdx.x, lane = tid & 63;
     const int jid0 = blockIdx.x * HT_WALK_BLOCKS;
-    const int jid = jid0 + lane;
-    const bool have = lane < HT_WALK_BLOCKS && jid < njobs;
+    const bool have = lane < HT_WALK_BLOCKS && jid0 + lane < njobs;
+    int jid = jid0 + lane;
+    if constexpr (DEDUP) {
+        jid = walk_order[min(jid0 + lane, njobs - 1)];         // (clamped, not branched around: nothing waits for it here)
+        if (jid0 >= nlead) {                                   // followers only: every wavefront looks at the same 64 tags and decides alike
+            int fj = jid;
+            asm volatile("" : "+v"(fj));                       // (this path's address arithmetic stays its own: shared with the one below it is hoisted to the top, where the staging then waits for walk_order)
+            const uint32_t t = pairs[(size_t)fj * HT_WALK_REC];
+            if (!__any(have && t != HT_PAIR_SERIAL && t != HT_PAIR_ZERO && t != HT_PAIR_DUP)) return;
+        }
+    }
 #ifdef J2K_WALK_STAMP
     const long long st0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1513,9 +1563,10 @@ __global__ __launch_bounds__(256) void ht_walk_kernel(const BlockJob *__restrict
     // = 12 x 16 B per thread, the two 1 KiB tables.  Afterwards only wavefront 0 walks.
     const int nblk = min(HT_WALK_BLOCKS, njobs - jid0);
     // the walking wavefront's own inputs ride along with the staging loads
-    uint32_t *rec = pairs + (size_t)jid * HT_WALK_REC;
+    uint32_t *rec = DEDUP ? nullptr : pairs + (size_t)jid * HT_WALK_REC;
     uint32_t tag = HT_PAIR_ZERO;
     int w = 0, h = 0;
+    if constexpr (!DEDUP)
     if (tid < 64 && have) { tag = rec[0]; w = jobs[jid].w; h = jobs[jid].h; }
     {
         constexpr int NV = HT_WALK_BLOCKS * 48 / 256;          // 16-byte pieces of bit string per thread
@@ -1527,6 +1578,11 @@ __global__ __launch_bounds__(256) void ht_walk_kernel(const BlockJob *__restrict
             const int q = j * 256 + tid;                      // 16-byte piece q: block q / 48, words 4 * (q % 48) ..
             const int bsel = min(q / 48, nblk - 1);
             v[j] = reinterpret_cast<const uint4 *>(vbits + (size_t)(jid0 + bsel) * HT_VBITS_WORDS)[q % 48];
+        }
+        if constexpr (DEDUP) {                                // behind the staging loads (these wait for walk_order, the staging does not), by every
+            // thread and of a clamped slot: no branch, nothing waits for them before the barrier
+            rec = pairs + (size_t)jid * HT_WALK_REC;
+            tag = rec[0]; w = jobs[jid].w; h = jobs[jid].h;
         }
         if (tid < 64) reinterpret_cast<uint4 *>(S.tbl0)[tid] = reinterpret_cast<const uint4 *>(c_vlc_tbl0)[tid];   // contexts 0..3 = 1 KiB
         else if (tid < 128) reinterpret_cast<uint4 *>(S.tbl1)[tid - 64] = reinterpret_cast<const uint4 *>(c_vlc_tbl1)[tid - 64];
@@ -1544,6 +1600,9 @@ __global__ __launch_bounds__(256) void ht_walk_kernel(const BlockJob *__restrict
     const long long st1 = __builtin_amdgcn_s_memtime();
 #endif
     if (tid >= 64) return;
+    if constexpr (DEDUP) {
+        if (!have) { tag = HT_PAIR_ZERO; w = 0; h = 0; }
+    }
     const uint32_t pos = ht_walk_lane<DEDUP>(&S.vb[lane][0], S.tbl0, S.tbl1, S.pair1, rec, w, h, have, tag);
     (void)pos;
 #ifdef J2K_WALK_STAMP
@@ -2472,9 +2531,9 @@ size_t ht_decode_scratch_words(int njobs) { return (size_t)njobs * (HT_WALK_REC 
 // front: 1 = ht_front_kernel, 3 = ht_vlcprep_kernel + ht_walk_kernel (the same records either way; vbits is only used by the latter)
 hipError_t launch_ht_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, int32_t *decoded, uint32_t *scratch, int coded_rows_only, const BlockJob *placed_jobs, int lean,
-                            int front, const int32_t *dedup_rep, const int32_t *dedup_fol) {
+                            int front, const int32_t *dedup_rep, const int32_t *dedup_fol, const int32_t *walk_order, const int32_t *walk_pos, int walk_nlead) {
     // ht_vlcprep_dedup_kernel and the DEDUP instantiations (byte-identical blocks decoded once): dense blocks, the two-launch front end and the lean kernel only -- nobody else knows HT_PAIR_DUP
-    const bool dedup = dedup_rep && dedup_fol && !placed_jobs && lean && front != 1;
+    const bool dedup = dedup_rep && dedup_fol && walk_order && walk_pos && !placed_jobs && lean && front != 1;
     if (njobs <= 0) return hipSuccess;
     hipError_t e;
     if ((e = ht_tables_ready(s)) != hipSuccess) return e;
@@ -2484,14 +2543,14 @@ hipError_t launch_ht_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
         hipLaunchKernelGGL(ht_front_kernel<HT_FRONT_NW>, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(64 * HT_FRONT_NW), sizeof(HtFrontShared), s, jobs, njobs, stream, offs, lens, pairs);
     } else {
         for (int rep_ = 0; rep_ < dev_reps(32); rep_++)
-        if (dedup) hipLaunchKernelGGL(ht_vlcprep_dedup_kernel, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, vbits, pairs, dedup_rep);
+        if (dedup) hipLaunchKernelGGL(ht_vlcprep_dedup_kernel, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, vbits, pairs, dedup_rep, walk_pos);
         else
         hipLaunchKernelGGL(ht_vlcprep_kernel, dim3((njobs + 3) / 4), dim3(256), 0, s, jobs, njobs, stream, offs, lens, vbits, pairs);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         for (int rep_ = 0; rep_ < dev_reps(64); rep_++)
-        if (dedup) hipLaunchKernelGGL(ht_walk_kernel<true>, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(256), sizeof(HtWalkShared), s, jobs, njobs, vbits, pairs);
+        if (dedup) hipLaunchKernelGGL(ht_walk_kernel<true>, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(256), sizeof(HtWalkShared), s, jobs, njobs, vbits, pairs, walk_order, walk_nlead);
         else
-        hipLaunchKernelGGL(ht_walk_kernel<false>, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(256), sizeof(HtWalkShared), s, jobs, njobs, vbits, pairs);
+        hipLaunchKernelGGL(ht_walk_kernel<false>, dim3((njobs + HT_WALK_BLOCKS - 1) / HT_WALK_BLOCKS), dim3(256), sizeof(HtWalkShared), s, jobs, njobs, vbits, pairs, (const int32_t *)nullptr, 0);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     for (int rep_ = 0; rep_ < dev_reps(128); rep_++)

@@ -517,3 +517,12 @@ extern "C" int j2k_plan_get_ht_decode_leaders(const j2k_plan *P, int32_t *leader
     return J2K_OK;
 }
 
+extern "C" int j2k_plan_get_ht_decode_walk_order(const j2k_plan *P, int32_t *order, size_t cap, int32_t *n_leaders) {
+    if (!P || !order) return J2K_ERR_INVALID_ARG;
+    if (P->spec.coder != J2K_CODER_HT) return J2K_ERR_UNSUPPORTED;
+    if (cap < P->ht_walk_order.size()) return J2K_ERR_CAPACITY;
+    if (!P->ht_walk_order.empty()) memcpy(order, P->ht_walk_order.data(), P->ht_walk_order.size() * sizeof(int32_t));
+    if (n_leaders) *n_leaders = (int32_t)P->ht_walk_nlead;
+    return J2K_OK;
+}
+

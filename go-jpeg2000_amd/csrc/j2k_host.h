@@ -31,7 +31,8 @@ hipError_t launch_ht_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
                             const int *alias_ids = nullptr, int waves = 1);
 hipError_t launch_ht_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, int32_t *decoded, uint32_t *scratch, int coded_rows_only = 0, const BlockJob *placed_jobs = nullptr, int lean = 1, int front = 3,
-                            const int32_t *dedup_rep = nullptr, const int32_t *dedup_fol = nullptr);
+                            const int32_t *dedup_rep = nullptr, const int32_t *dedup_fol = nullptr, const int32_t *walk_order = nullptr,
+                            const int32_t *walk_pos = nullptr, int walk_nlead = 0);
 int ht_walk_max_pairs();
 size_t ht_decode_scratch_words(int njobs);
 hipError_t launch_ht_encode_stream(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *stream,

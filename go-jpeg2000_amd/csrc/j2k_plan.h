@@ -31,7 +31,8 @@ struct j2k_ctx {
     int ht_dec_front = 3;      // HT block decode, kernels 1 + 2 (J2K_HT_DEC_FRONT: 3 = ht_vlcprep_kernel + ht_walk_kernel, two launches; 1 = ht_front_kernel, the workgroup unstuffs the strings it walks)
     int ht_dec_lean = 1;       // HT block decode, third kernel (J2K_HT_DEC_LEAN: 1 = ht_decode_lean_kernel, the 64-wide common case written out and everything else out of line; 0 = ht_decode_kernel)
     int ht_dec_dedup = 1;      // HT block decode (J2K_HT_DEC_DEDUP, with ht_dec_front = 3 and ht_dec_lean = 1 only): 1 = a job whose bytes ht_vlcprep_kernel finds equal to its leader's
-                               // (the plan's candidate table, d_ht_dec_rep) is not decoded; the leader stores its rows to both places.  Measured: docs/KERNEL_NOTES.md 4aa
+                               // (the plan's candidate table, d_ht_dec_rep) is not decoded; the leader stores its rows to both places.  Equal: in every byte a
+                               // decode path can read.  The walk then takes the jobs in d_ht_walk_order (leaders first).  Measured: docs/KERNEL_NOTES.md 4aa
     int l0_inv_wpe = 5;        // its occupancy variant (J2K_L0_INV_WPE: 5 = all in registers, 26.4 us; 6 = odd row parked in LDS for 6 waves per SIMD, measured slower: 33.6 us)
     bool l0_wg_inv = true;     // the inverse level 0 to RGBA8 in workgroup form too (J2K_L0_WG_INV=0: the general kernel)
     int l0_store = 1;          // its final-coefficient store flavour (J2K_L0_STORE: 0 plain, 1 nt, 2 sc1, 4 sc1 nt)
@@ -239,6 +240,12 @@ struct j2k_plan {
     // d_ht_dec_fol[8 j + 1 ..] = their ids.  Both null when no job has a follower (closed-loop plans: the windows partition the plane).
     std::vector<int32_t> ht_dec_rep;        // the host's copy of d_ht_dec_rep (every HT plan; j2k_plan_get_ht_decode_leaders)
     int32_t *d_ht_dec_rep = nullptr, *d_ht_dec_fol = nullptr;
+    // The walk's static order under the same option: slot s of the bit-string scratch (and lane s % 64 of walk workgroup s / 64) belongs to job
+    // ht_walk_order[s] -- the ht_walk_nlead jobs that are their own leader first, in ascending job order, the static followers behind them, ascending;
+    // d_ht_walk_pos is the inverse (job -> slot).  Uploaded with d_ht_dec_rep; the identity, and null, when no job has a follower.
+    std::vector<int32_t> ht_walk_order;     // the host's copy (every HT plan; j2k_plan_get_ht_decode_walk_order)
+    int32_t *d_ht_walk_order = nullptr, *d_ht_walk_pos = nullptr;
+    int ht_walk_nlead = 0;
     j2k::DwtJob *d_fwd97_wg_jobs = nullptr; // 9-7: one job per workgroup = (plane, component, band) of dwt97_fwd_rgb_wg_kernel
     int fwd97_wg_njobs = 0, fwd97_wg_waves = 0;
     j2k::DwtJob *d_inv97_wg_jobs = nullptr; // 9-7 inverse: one job per workgroup = (plane, band) of dwt97_inv_rgb_wg_kernel

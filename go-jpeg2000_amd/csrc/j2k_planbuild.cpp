@@ -742,9 +742,19 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
                 P->ht_dec_rep[i] = L;
                 any = true;
             }
+            // The walk's order (ht_walk_kernel<true>): one block per lane, and only a job that is its own leader is sure to walk -- those first, ascending,
+            // so that they fill whole workgroups; the static followers behind them, in workgroups that leave at once when every follower verifies.
+            P->ht_walk_order.clear();
+            for (size_t i = 0; i < nj; i++) if (P->ht_dec_rep[i] == (int32_t)i) P->ht_walk_order.push_back((int32_t)i);
+            P->ht_walk_nlead = (int)P->ht_walk_order.size();
+            for (size_t i = 0; i < nj; i++) if (P->ht_dec_rep[i] != (int32_t)i) P->ht_walk_order.push_back((int32_t)i);
             if (any) {
+                std::vector<int32_t> pos(nj);
+                for (size_t s = 0; s < nj; s++) pos[(size_t)P->ht_walk_order[s]] = (int32_t)s;
                 r = upload(ctx, &P->d_ht_dec_rep, P->ht_dec_rep);
                 if (r == J2K_OK) r = upload(ctx, &P->d_ht_dec_fol, fol);
+                if (r == J2K_OK) r = upload(ctx, &P->d_ht_walk_order, P->ht_walk_order);
+                if (r == J2K_OK) r = upload(ctx, &P->d_ht_walk_pos, pos);
             }
         }
         for (size_t i = 0; i < bj.size(); i++) bj[i].out_off = (int64_t)P->dec_off[i];   // decode table: dense decoded blocks
@@ -904,7 +914,7 @@ extern "C" void j2k_plan_destroy(j2k_plan *P) {
         if (cls == 0 && P->d_bigsym_off) { (void)hipFree(P->d_bigsym_off); P->d_bigsym_off = nullptr; }
         for (auto &T : P->inv[cls]) { if (T.d_planes) (void)hipFree(T.d_planes); if (T.d_jobs) (void)hipFree(T.d_jobs); if (T.d_pjobs) (void)hipFree(T.d_pjobs); }
     }
-    void *ptrs[] = {P->d_deep_jobs_inv, P->d_mega_fwd_jobs, P->d_mega_inv_jobs, P->d_fwd_top_jobs, P->d_inv_top_jobs, P->d_inv_wg_jobs, P->d_deep_planes, P->d_deep_jobs, P->d_tile_job0, P->d_scrA, P->d_scrB, P->d_tail, P->d_bjobs, P->d_djobs, P->d_djobs_placed, P->d_frame, P->d_coeff, P->d_slots, P->d_stream, P->d_lens, P->d_numbps, P->d_offs, P->d_status, P->d_fwd_pix_jobs, P->d_fwd_wg2_jobs, P->d_fwd_wg_rest_jobs, P->d_fwd_wg_jobs, P->d_fwd97_wg_jobs, P->d_inv97_wg_jobs, P->d_ht_ujobs, P->d_ht_alias_next, P->d_ht_dec_rep, P->d_ht_dec_fol, P->d_bjobs_alias, P->d_maglens, P->d_mels, P->d_toffs,
+    void *ptrs[] = {P->d_deep_jobs_inv, P->d_mega_fwd_jobs, P->d_mega_inv_jobs, P->d_fwd_top_jobs, P->d_inv_top_jobs, P->d_inv_wg_jobs, P->d_deep_planes, P->d_deep_jobs, P->d_tile_job0, P->d_scrA, P->d_scrB, P->d_tail, P->d_bjobs, P->d_djobs, P->d_djobs_placed, P->d_frame, P->d_coeff, P->d_slots, P->d_stream, P->d_lens, P->d_numbps, P->d_offs, P->d_status, P->d_fwd_pix_jobs, P->d_fwd_wg2_jobs, P->d_fwd_wg_rest_jobs, P->d_fwd_wg_jobs, P->d_fwd97_wg_jobs, P->d_inv97_wg_jobs, P->d_ht_ujobs, P->d_ht_alias_next, P->d_ht_dec_rep, P->d_ht_dec_fol, P->d_ht_walk_order, P->d_ht_walk_pos, P->d_bjobs_alias, P->d_maglens, P->d_mels, P->d_toffs,
                     P->d_t2_packets, P->d_tile_packet0, P->d_t2_cbs, P->d_t2_poffs, P->d_t2_ptile, P->d_t2_ws, P->d_t2_chains, P->d_t2_body_base, P->d_t2_par, P->d_frame_status,
                     P->d_cl_decoded, P->d_cl_coeff, P->d_cl_coeff_dec, P->d_cl_numbps, P->d_cl_offs, P->d_cl_lens, P->d_host_io, P->d_host_pix,
                     P->d_rate_wj, P->d_rate_ws, P->d_cl_rate, P->d_cl_dense, P->d_cl_lfloors,

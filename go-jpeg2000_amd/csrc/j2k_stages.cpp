@@ -928,10 +928,11 @@ int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const u
         // byte-identical blocks once (ht_dec_dedup): the plan's tables name jobs of its whole dense list, and only the two-launch front end
         // and the lean kernel know the tag -- every other combination gets no tables
         const bool dedup = ctx->ht_dec_dedup && d_djobs == P->d_djobs && n == (int)P->blocks.size() && !d_placed && ctx->ht_dec_lean == 1 &&
-                           ctx->ht_dec_front == 3 && P->d_ht_dec_rep && P->d_ht_dec_fol;
+                           ctx->ht_dec_front == 3 && P->d_ht_dec_rep && P->d_ht_dec_fol && P->d_ht_walk_order && P->d_ht_walk_pos;
         HIPCHK(ctx, launch_ht_decode(ctx->stream, d_djobs, n, d_stream, d_offs, d_lens, d_decoded, (uint32_t *)ctx->stage[2],
                                      (d_placed || P->dec_coded_rows_only) ? 1 : 0, d_placed, ctx->ht_dec_lean, ctx->ht_dec_front,
-                                     dedup ? P->d_ht_dec_rep : nullptr, dedup ? P->d_ht_dec_fol : nullptr));
+                                     dedup ? P->d_ht_dec_rep : nullptr, dedup ? P->d_ht_dec_fol : nullptr, dedup ? P->d_ht_walk_order : nullptr,
+                                     dedup ? P->d_ht_walk_pos : nullptr, dedup ? P->ht_walk_nlead : 0));
     } else {
         size_t wpj = 0;                                  // the one-block decoder's workspace holds the flags only
         int max_dim = 0;

@@ -114,6 +114,14 @@ class FramePlan:
         self.ctx.check(self.ctx.L.j2k_plan_get_ht_decode_leaders(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n)))
         return out[:n]
 
+    def ht_decode_walk_order(self):
+        """((n,) int32, leaders): HT plans: the job of every slot of the decoder's walk stage -- the `leaders` jobs that lead themselves first."""
+        n = int(self.info.blocks)
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        nl = C.c_int32(0)
+        self.ctx.check(self.ctx.L.j2k_plan_get_ht_decode_walk_order(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n), C.byref(nl)))
+        return out[:n], int(nl.value)
+
     # ---- device buffers -----------------------------------------------------------
     def empty(self, n, dtype):
         t = _torch()

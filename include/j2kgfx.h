@@ -320,6 +320,10 @@ int j2k_plan_get_decoded_offsets(const j2k_plan *plan, uint64_t *offs, size_t ca
  * otherwise.  A candidate only: j2k_plan_decode_blocks compares the bytes of the two blocks in every call and decodes job j on its own unless
  * they are equal, so the option never changes a result.  It applies with ht_dec_front = 3 and ht_dec_lean = 1 (the defaults). */
 int j2k_plan_get_ht_decode_leaders(const j2k_plan *plan, int32_t *leaders, size_t cap);
+/* HT plans only: the order in which the walk stage of j2k_plan_decode_blocks takes the jobs under ht_dec_dedup -- order[s] = the job of slot s: the
+ * *n_leaders (may be NULL) jobs with leaders[j] == j first, in ascending order, then every other job, ascending.  Like the leaders it is static and
+ * never changes a result. */
+int j2k_plan_get_ht_decode_walk_order(const j2k_plan *plan, int32_t *order, size_t cap, int32_t *n_leaders);
 
 /* ---- the multi-GPU exchange -------------------------------------------------------------------------------
  * One process per GPU, each with its own j2k_ctx; a frame's tiles are sharded by j2k_params.tile_first / tile_count and coded
