@@ -88,6 +88,7 @@ extern "C" int j2k_plan_decode_frame_pixels_area(j2k_plan *P, const uint8_t *d_c
     if (r != J2K_OK) return r;
     if (layers < 0 || layers > J2K_MAX_LAYERS) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_decode_frame_pixels_area: the layer count is 1 ... 32 (0: not a layered stream)");
     if (layers > 0 && (r = rate_check(P, "j2k_plan_decode_frame_pixels_area")) != J2K_OK) return r;
+    if (truncated && (r = raw_magref_refuse(P, "j2k_plan_decode_frame_pixels_area (truncated)")) != J2K_OK) return r;
     if (!d_cs || !d_pix) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     // decoder.createImage's formats, as j2k_pack_pixels checks them
     if (S.precision < 1 || S.precision > 16 || (S.C != 1 && S.C != 3 && S.C != 4)) return fail(ctx, J2K_ERR_UNSUPPORTED, "unsupported number of components / precision");

@@ -195,6 +195,7 @@ extern "C" int j2k_plan_decode_tile_parts_floors(j2k_plan *P, const uint8_t *d_c
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!d_floors) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     if (P->spec.coder != J2K_CODER_MQ) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_decode_tile_parts_floors: per-block floors need the MQ coder");
+    { const int rr = raw_magref_refuse(P, "j2k_plan_decode_tile_parts_floors"); if (rr != J2K_OK) return rr; }
     return decode_tile_parts_impl(P, d_cs, len, d_tile_offs, sop, eph, d_offs, d_lens, d_numbps, d_floors);
 }
 static int decode_tile_parts_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
@@ -469,6 +470,7 @@ extern "C" int j2k_plan_decode_frame_pixels_rate(j2k_plan *P, const uint8_t *d_c
     int r = check_skip_planes(ctx, P->spec.coder, skip_planes, "j2k_plan_decode_frame_pixels_rate");
     if (r != J2K_OK) return r;
     if (P->spec.coder != J2K_CODER_MQ) return fail(ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_decode_frame_pixels_rate: per-block floors need the MQ coder");
+    if ((r = raw_magref_refuse(P, "j2k_plan_decode_frame_pixels_rate")) != J2K_OK) return r;
     if (!d_pix) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     ReducedTab *R = nullptr;
     if (reduce != 0) { r = plan_reduced(P, reduce, &R); if (r != J2K_OK) return r; }

@@ -41,7 +41,9 @@ int ht_fast_max_samples();
 hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots,
                             uint32_t *lens, uint8_t *numbps, uint8_t *work, size_t work_per_job, int *fault, int max_dim,
                             uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint8_t *bigsym = nullptr, const uint64_t *bigsym_off = nullptr,
-                            uint32_t *bignsyms = nullptr, uint32_t *rate = nullptr);   // rate: 32 words per job, the rate tables (blocks <= 64 x 64 only)
+                            uint32_t *bignsyms = nullptr, uint32_t *rate = nullptr,    // rate: 32 words per job, the rate tables (blocks <= 64 x 64 only)
+                            uint32_t *rawst = nullptr);   // rawst: the raw-MagRef style -- t1_raw_stage_bytes() per job of staging (blocks <= 64 x 64, no rate tables)
+size_t t1_raw_stage_bytes();
 // rate control (rate.hip): plane distortions of every block; the allocation of a byte budget over the blocks' rate / distortion tables
 hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, uint64_t *dist);
 // region of interest (area.hip, rate.hip): every block's footprint of a rectangle; the distortions with that footprint weighted `gain` times
@@ -71,8 +73,9 @@ size_t t1_sym_stride(int planes);
 hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, const uint8_t *numbps, int32_t *decoded, uint8_t *work,
                             size_t work_per_job, int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput = 0, int skip_planes = 0,
-                            const uint8_t *floors = nullptr);   // floors (device, one byte per job): job j stops at max(skip_planes, floors[j])
-size_t t1_dec_split_bytes(size_t njobs);
+                            const uint8_t *floors = nullptr,    // floors (device, one byte per job): job j stops at max(skip_planes, floors[j])
+                            int raw_magref = 0);                // the bodies are H | MQ | RAW (blocks <= 64 x 64, no floors)
+size_t t1_dec_split_bytes(size_t njobs, bool raw_magref = false);    // raw_magref: with the un-stuffed RAW strings of the style's blocks
 hipError_t launch_mq_encode(hipStream_t s, const uint8_t *ctxs, const uint8_t *decs, size_t n, uint8_t *out, size_t cap, uint32_t *out_len, int *fault);
 hipError_t launch_mq_decode(hipStream_t s, const uint8_t *data, size_t len, const uint8_t *ctxs, size_t n, uint8_t *decs, int *fault);
 hipError_t launch_raw_encode(hipStream_t s, const uint8_t *bits, size_t n, uint8_t *out, size_t cap, uint32_t *out_len, int *fault);
@@ -150,6 +153,7 @@ int cl_rate_workspace(j2k_plan *P, ClRate &W);
 int plan_decode_frame_tables(j2k_plan *P, const uint8_t *d_data, j2k::ReducedTab *R, int reduce, int skip_planes, const uint8_t *d_floors, uint8_t *d_floors_r,
                              void *d_pix, size_t stride);
 int rate_check(j2k_plan *P, const char *who);    // what every rate call needs of its plan (j2k_rate.cpp)
+int raw_magref_refuse(const j2k_plan *P, const char *who);    // J2K_ERR_UNSUPPORTED on a plan in the raw-MagRef style (j2k_stages.cpp): the calls that cut bodies or read cut ones
 int rate_upload_weights(j2k_plan *P);            // the per-job weights and the allocation workspace on the device (j2k_rate.cpp)
 int targets_check(j2k_ctx *ctx, const double *targets, int nlayers, const char *who);   // distortion targets: finite, >= 0, none above the one before (j2k_rate.cpp)
 // the plan data of area_blocks_kernel (and of the region-of-interest kernels), uploaded at first use; frame: also the staging frame of a region

@@ -439,6 +439,7 @@ extern "C" int j2k_encode_pixels_host_rate(j2k_plan *P, int format, const void *
     if (!P) return J2K_ERR_INVALID_ARG;
     if (max_body_bytes < 0) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_encode_pixels_host_rate: a negative budget");
     if (!P->spec.closed_loop) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_encode_pixels_host_rate: needs a closed-loop plan");
+    { const int rr = raw_magref_refuse(P, "j2k_encode_pixels_host_rate"); if (rr != J2K_OK) return rr; }
     return encode_pixels_host_impl(P, format, pix, stride, sop, eph, max_body_bytes, out, cap, out_len, tile_offs, lens, numbps);
 }
 static int encode_pixels_host_impl(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes, uint8_t *out, size_t cap,
@@ -521,6 +522,7 @@ extern "C" int j2k_decode_pixels_host_rate(j2k_plan *P, const uint8_t *cs, size_
     int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_decode_pixels_host_rate");
     if (r != J2K_OK) return r;
     if (P->spec.coder != J2K_CODER_MQ) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_decode_pixels_host_rate: per-block floors need the MQ coder");
+    if ((r = raw_magref_refuse(P, "j2k_decode_pixels_host_rate")) != J2K_OK) return r;
     if (reduce != 0) {
         int32_t wr = 0, hr = 0;
         r = j2k_plan_reduced_size(P, reduce, &wr, &hr);

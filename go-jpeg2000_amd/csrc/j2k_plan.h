@@ -285,5 +285,6 @@ struct j2k_plan {
     j2k_block *d_area_blocks = nullptr;
     j2k::AreaPlane *d_area_planes = nullptr;
     int32_t *d_area_frame = nullptr;
+    bool raw_magref = false;                // j2k_plan_set_raw_magref: MQ block bodies are H | MQ | RAW, the MagRef decisions bypass the MQ coder
     bool dequantize = false;                // j2k_plan_set_dequantize: the 9-7 inverse kernels multiply every int32 coefficient by 1.0 / Quality at their load (dwt.go:514-520)
 };

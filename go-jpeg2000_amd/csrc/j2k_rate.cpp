@@ -77,6 +77,7 @@ int rate_check(j2k_plan *P, const char *who) {
     if (S.coder != J2K_CODER_MQ) why = "needs the MQ coder (the HT coder's one pass has no planes to cut between)";
     else if (!S.closed_loop) why = "needs a closed-loop plan (only its packets can say where a block was cut)";
     else if (S.frame_h != S.H) why = "a batch plan (frame_rows): not built";
+    else if (P->raw_magref) why = "the plan codes in the raw-MagRef style (j2k_plan_set_raw_magref): a two-stream body cannot be cut at bit planes";
     else
         for (const j2k_block &b : P->blocks)
             if (b.w > 64 || b.h > 64) { why = "blocks above 64 x 64: not built"; break; }

@@ -678,7 +678,9 @@ int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slot
         for (const j2k_block &b : P->blocks) max_dim = std::max(max_dim, std::max(b.w, b.h));
         const size_t wpj = max_dim > 64 ? t1_work_per_job(P) : 0;     // only the serial kernel (blocks > 64) needs a workspace
         const T1Workspace W = t1_workspace(ctx, (size_t)n, wpj);
-        r = stage_reserve(ctx, 2, W.total);
+        if (P->raw_magref && d_rate) return fail(ctx, J2K_ERR_UNSUPPORTED, "rate tables of a plan in the raw-MagRef style");     // (rate_check refuses first)
+        const size_t raw_off = (W.total + 255) & ~size_t(255);         // the raw-MagRef style: a staging record per job behind the workspace
+        r = stage_reserve(ctx, 2, P->raw_magref ? raw_off + (size_t)n * j2k::t1_raw_stage_bytes() + 256 : W.total);
         if (r != J2K_OK) return r;
         uint8_t *ws = (uint8_t *)ctx->stage[2];
         // blocks of 65 ... 256 columns or rows: symbol lists for the two-kernel form (t1_big.inc) -- 16 symbols of room per sample
@@ -709,7 +711,8 @@ int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slot
         }
         HIPCHK(ctx, launch_t1_encode(ctx->stream, P->d_bjobs, n, d_coeff, d_slots, d_lens, d_numbps, ws, wpj, d_fault, max_dim,
                                      W.stride ? ws + W.off_sym : nullptr, W.stride, (uint32_t *)(ws + W.off_nsyms),
-                                     ctx->t1_lanes > 0 ? ctx->t1_lanes : (mq_throughput_mode() ? -1 : 0), bigsym, P->d_bigsym_off, bignsyms, d_rate));
+                                     ctx->t1_lanes > 0 ? ctx->t1_lanes : (mq_throughput_mode() ? -1 : 0), bigsym, P->d_bigsym_off, bignsyms, d_rate,
+                                     P->raw_magref ? (uint32_t *)(ws + raw_off) : nullptr));
     }
     return J2K_OK;
 }
@@ -883,6 +886,26 @@ extern "C" int j2k_plan_set_dequantize(j2k_plan *P, int on) {
     return J2K_OK;
 }
 
+// The raw-MagRef coding style: plan state, like the setters above; the block coder's launches read it, nothing above the block
+// body does.  Built for MQ plans whose blocks are all <= 64 x 64.
+extern "C" int j2k_plan_set_raw_magref(j2k_plan *P, int on) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_set_raw_magref: plan state cannot change while a graph is being captured");
+    if (P->spec.coder != J2K_CODER_MQ) return fail(ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_set_raw_magref: the style is the MQ coder's (the HT coder has no MagRef pass to divert)");
+    for (const j2k_block &b : P->blocks)
+        if (b.w > 64 || b.h > 64) return fail(ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_set_raw_magref: blocks above 64 x 64: not built");
+    P->raw_magref = on != 0;
+    return J2K_OK;
+}
+extern "C" int j2k_plan_get_raw_magref(const j2k_plan *P) { return P && P->raw_magref ? 1 : 0; }
+// the calls that cut or layer block bodies, or read bodies that were: a two-stream body has no prefix property
+int raw_magref_refuse(const j2k_plan *P, const char *who) {
+    if (P && P->raw_magref)
+        return fail(P->ctx, J2K_ERR_UNSUPPORTED, (std::string(who) + ": the plan codes in the raw-MagRef style (j2k_plan_set_raw_magref): its bodies cannot be cut at bit planes").c_str());
+    return J2K_OK;
+}
+
 extern "C" int j2k_plan_decode_blocks(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
                                       const uint8_t *d_numbps, int32_t *d_decoded) {
     if (!P || !d_stream || !d_offs || !d_lens || !d_numbps || !d_decoded) return J2K_ERR_INVALID_ARG;
@@ -914,12 +937,14 @@ extern "C" int j2k_plan_decode_blocks_floors(j2k_plan *P, const uint8_t *d_strea
     const int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_plan_decode_blocks_floors");
     if (r != J2K_OK) return r;
     if (d_floors && P->spec.coder == J2K_CODER_HT) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_decode_blocks_floors: per-block floors need the MQ coder");
+    if (d_floors) { const int rr = raw_magref_refuse(P, "j2k_plan_decode_blocks_floors"); if (rr != J2K_OK) return rr; }
     return plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_stream, d_offs, d_lens, d_numbps, d_decoded, nullptr, skip_planes, d_floors);
 }
 
 int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
                             const uint8_t *d_numbps, int32_t *d_decoded, const BlockJob *d_placed, int skip_planes, const uint8_t *d_floors) {
     j2k_ctx *ctx = P->ctx;
+    if (d_floors) { const int rr = raw_magref_refuse(P, "block decode with per-block floors"); if (rr != J2K_OK) return rr; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!n) return J2K_OK;
     if (P->spec.coder == J2K_CODER_HT) {
@@ -947,12 +972,13 @@ int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const u
         // The lanes decoder's workspace is T1DS_STRIDE + 3.5 KB of row masks + 16 KB of plane words per block (0.55 GB for an 8K frame of
         // 27 000 blocks); if the device cannot give it, the one-launch kernels decode the frame with gen_bytes alone
         // rather than the call failing.
-        int r = stage_reserve(ctx, 2, gen_bytes + 256 + (split ? j2k::t1_dec_split_bytes((size_t)n) : 0));
+        int r = stage_reserve(ctx, 2, gen_bytes + 256 + (split ? j2k::t1_dec_split_bytes((size_t)n, P->raw_magref) : 0));
         if (r != J2K_OK && split) { (void)hipGetLastError(); split = false; r = stage_reserve(ctx, 2, gen_bytes + 256); }
         if (r != J2K_OK) return r;
         HIPCHK(ctx, launch_t1_decode(ctx->stream, d_djobs, n, d_stream, d_offs, d_lens, d_numbps, d_decoded,
                                      (uint8_t *)ctx->stage[2], wpj, max_dim, ctx->t1_dec_general,
-                                     split ? (uint8_t *)ctx->stage[2] + gen_bytes : nullptr, ctx->t1_dec_lanes, mq_throughput_mode() ? 1 : 0, skip_planes, d_floors));
+                                     split ? (uint8_t *)ctx->stage[2] + gen_bytes : nullptr, ctx->t1_dec_lanes, mq_throughput_mode() ? 1 : 0, skip_planes, d_floors,
+                                     P->raw_magref ? 1 : 0));
     }
     return J2K_OK;
 }

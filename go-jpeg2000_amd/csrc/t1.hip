@@ -136,6 +136,20 @@ __device__ __forceinline__ void mq_byte_out(MqEnc &e) {   // t1_fast.go:11-34
     mq_advance(e, e.C >> 19); e.C &= 0x7FFFF; e.CT = 8;
 }
 
+// setbits + Flush (mqc.go:313-341 as t1_fast5.go:878-898 restates it) and the byte still in `cur`: returns endPos -- the codeword is
+// buf[1 .. endPos - 1] = out[0 .. endPos - 2], a trailing 0xFF dropped
+__device__ __forceinline__ long mq_flush(MqEnc &e) {
+    const uint32_t tempC = e.C + e.A;
+    e.C |= 0xFFFF;
+    if (e.C >= tempC) e.C -= 0x8000;
+    e.C <<= e.CT; mq_byte_out(e);
+    e.C <<= e.CT; mq_byte_out(e);
+    long end = e.bp + 1;                       // endPos
+    if (e.cur == 0xFF) end--;                  // drop a trailing 0xFF
+    else if (e.bp >= 1) { if (e.bp - 1 < e.cap) e.out[e.bp - 1] = (uint8_t)e.cur; else e.overflow = 1; }
+    return end;
+}
+
 __device__ __forceinline__ void mq_encode(MqEnc &e, T1Tables &T, int ctx, int d) {   // mqc.go:224-255
     const uint32_t st = T.ctx[ctx];
     const uint32_t ent = T.mq[st];
@@ -356,15 +370,7 @@ __global__ __launch_bounds__(64) void t1_encode_kernel(const BlockJob *__restric
         }
     }
     // ---- flush (t1_fast5.go:878-898) ----
-    const uint32_t tempC = e.C + e.A;
-    e.C |= 0xFFFF;
-    if (e.C >= tempC) e.C -= 0x8000;
-    e.C <<= e.CT; mq_byte_out(e);
-    e.C <<= e.CT; mq_byte_out(e);
-    // bytes buf[1..bp]; the last one is still in `cur`
-    long end = e.bp + 1;                       // endPos
-    if (e.cur == 0xFF) end--;                  // drop a trailing 0xFF
-    else if (e.bp >= 1) { if (e.bp - 1 < e.cap) out[e.bp - 1] = (uint8_t)e.cur; else e.overflow = 1; }
+    const long end = mq_flush(e);
     if (e.overflow) atomicMax(fault, 2);
     lens[jid] = end > 1 ? (uint32_t)(end - 1) : 0;
     numbps[jid] = (uint8_t)numBPS;
@@ -461,6 +467,83 @@ __device__ __forceinline__ void mq_run(MqEnc &e, const uint32_t *mqtab, uint32_t
     e.A = A; e.C = C; e.CT = CT;
 }
 
+// ---- the raw-MagRef coding style (j2k_plan_set_raw_magref): a block's refinement bits bypass the MQ coder -------------------------------
+// Body = H | MQ | RAW: H = len(MQ) in three 7-bit groups, RAW = the refinement decisions of all planes in coding order as the reference's
+// RawEncoder writes them (mqc.go:564-600: MSB first, a 7-bit byte after every 0xFF, Flush as written).  While a block is coded its bits
+// collect, unstuffed, in a staging record in the workspace: word 0 = the bit count, words 4 ... = the bits MSB first, zero behind the last one
+// and one zero word after them (the packer reads 64-bit windows).
+#define T1_RAW_HDR 3u
+#define T1_RAWST_WORDS (4u + 31u * 4096u / 32u + 4u)      /* 31 planes of 64 x 64 refinements at most */
+__device__ __forceinline__ uint32_t t1_ld_l2(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // written by this launch: L2, not this CU's L1
+// wave-uniform writer of the staging record: appends up to 64 bits at a time
+struct T1RawStage {
+    uint32_t *st;
+    uint64_t acc;          // pending bits, left-aligned; zero behind them
+    uint32_t pend, words;  // pend < 32
+    __device__ __forceinline__ void start(uint32_t *rec) { st = rec; acc = 0; pend = 0; words = 0; }
+    // v: cnt bits (1 ... 64), the first one in bit 63, zero behind them
+    __device__ __forceinline__ void append(uint64_t v, uint32_t cnt, int lane) {
+        uint64_t hi = acc | (pend ? v >> pend : v);
+        uint64_t lo = pend ? v << (64u - pend) : 0ull;
+        uint32_t tot = pend + cnt;                         // <= 95
+        while (tot >= 32u) {
+            if (lane == 0) st[4u + words] = (uint32_t)(hi >> 32);
+            words++;
+            hi = hi << 32 | lo >> 32; lo <<= 32; tot -= 32u;
+        }
+        acc = hi; pend = tot;
+    }
+    __device__ __forceinline__ void finish(int lane) {
+        if (lane == 0) {
+            st[0] = words * 32u + pend;
+            uint32_t wn = words;
+            if (pend) st[4u + wn++] = (uint32_t)(acc >> 32);
+            st[4u + wn] = 0u;
+        }
+    }
+};
+// All 64 lanes: header, then the staged bits stuffed behind the m bytes of MQ codeword already at out + 3.  A byte's width (8 bits, 7 after an
+// 0xFF) depends only on the byte before it, so every lane cuts the byte it would own if no 0xFF came before it in this trip, and a trip keeps
+// the bytes up to and including the first 0xFF: 64 bytes per trip, fewer only where the string holds 0xFF bytes.  Returns the body's length;
+// ovf: it did not fit `cap`.
+__device__ __forceinline__ uint32_t t1_raw_pack(uint8_t *out, uint32_t cap, uint32_t m, const uint32_t *st, int lane, bool &ovf) {
+    const uint32_t nbits = t1_ld_l2(st);
+    const uint32_t *words = st + 4;
+    ovf = T1_RAW_HDR + m > cap;
+    if (ovf) return 0;
+    if (lane < (int)T1_RAW_HDR) out[lane] = (uint8_t)((m >> (7 * (2 - lane))) & 0x7Fu);
+    uint8_t *dst = out + T1_RAW_HDR + m;
+    const uint32_t room = cap - T1_RAW_HDR - m;
+    uint32_t p = 0, k = 0;
+    bool first7 = false;
+    while (p < nbits) {
+        const uint32_t s = p + (first7 ? (lane ? 7u + 8u * (uint32_t)(lane - 1) : 0u) : 8u * (uint32_t)lane);
+        const uint32_t wd = (first7 && lane == 0) ? 7u : 8u;
+        const bool act = s < nbits;
+        uint32_t byte = 0;
+        if (act) {
+            const uint32_t wi = s >> 5, sh = s & 31u;
+            const uint64_t two = (uint64_t)t1_ld_l2(words + wi) << 32 | t1_ld_l2(words + wi + 1);
+            byte = (uint32_t)(two >> (64u - wd - sh)) & ((1u << wd) - 1u);
+        }
+        const uint64_t ffm = __ballot(act && byte == 0xFFu);
+        const uint32_t nact = (uint32_t)__popcll(__ballot(act));
+        const uint32_t take = ffm ? (uint32_t)__ffsll((long long)ffm) : nact;       // lanes 0 ... take - 1 hold bytes of the string
+        if ((uint32_t)lane < take) {
+            if (k + (uint32_t)lane < room) dst[k + lane] = (uint8_t)byte;
+        }
+        k += take;
+        p += first7 ? 7u + 8u * (take - 1u) : 8u * take;
+        first7 = ffm != 0;
+    }
+    if (first7) {                                           // the string ends behind an 0xFF: ct = 7 < 8, Flush appends the empty byte (mqc.go:595-600)
+        if (lane == 0 && k < room) dst[k] = 0;
+        k++;
+    }
+    ovf = k > room;
+    return T1_RAW_HDR + m + k;
+}
+
 // SPLIT = false: contexts + MQ coder in this kernel (lane 0 codes each chunk of symbols).  only_skipped != null: just the
 //                 blocks the split path marked T1F_SKIPPED.
 // SPLIT = true : the symbols go to `gsym` (job j at j * sym_stride, chunks padded to 16 with no-op symbols, count in
@@ -472,7 +555,11 @@ __device__ __forceinline__ void mq_run(MqEnc &e, const uint32_t *mqtab, uint32_t
 //                replaces each mark by the byte count when its lane passes it.
 #define T1_RATE_STRIDE 32
 #define T1_RATE_MARGIN 5u   /* bytes past the coder's byte index that hold everything the registers held at a plane end */
-template <bool SPLIT, bool PLANES = false>
+// RAWMR: the raw-MagRef coding style (j2k_plan_set_raw_magref): the MagRef decisions never become symbols -- they go, in coding
+//                order, to the block's raw bit string in `rate` (not a rate table here: PLANES and RAWMR exclude each other), job j at
+//                j * T1_RAWST_WORDS; the MQ codeword starts three bytes into the slot.  SPLIT = false packs the body (t1_raw_pack) itself,
+//                SPLIT = true leaves that to t1_raw_pack_kernel behind the lanes kernel.
+template <bool SPLIT, bool PLANES = false, bool RAWMR = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void t1_encode64_kernel(const BlockJob *__restrict__ jobs, int njobs, const int32_t *__restrict__ coef,
                                                          uint8_t *__restrict__ slots, uint32_t *__restrict__ lens,
                                                          uint8_t *__restrict__ numbps, int *__restrict__ fault,
@@ -555,7 +642,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
     const uint64_t lt = (1ull << lane) - 1;         // columns before this lane's column
     uint64_t S = 0, REF = 0;
     uint8_t *out = slots + J.out_off;
-    MqEnc e{0x8000, 0, 12, 0, 0, out, (long)t1_mqbuf_bytes(n), 0};
+    MqEnc e{0x8000, 0, 12, 0, 0, RAWMR ? out + T1_RAW_HDR : out, (long)t1_mqbuf_bytes(n) - (RAWMR ? (long)T1_RAW_HDR : 0), 0};
+    T1RawStage rs;
+    if (RAWMR) rs.start(rate + (size_t)jid * T1_RAWST_WORDS);
     const int x = lane;
     uint32_t nsym = 0;
 #define T1F_DRAIN()                                           \
@@ -640,6 +729,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
             if (lane == 63) Dn2 = 0;
             const uint64_t ANY = spread3(Up) | spread3(Dn2) | (Snew << 1) | (Snew >> 1);
             uint64_t rows = __ballot(S != 0);
+            while (RAWMR && rows) {
+                // the row's decisions in column order = the plane's bits compressed under the member mask: member lanes send their bit to
+                // the lane of their rank, the others to the lanes behind (a permutation), a ballot collects the string
+                const int r = __ffsll((long long)rows) - 1;
+                rows &= rows - 1;
+                const uint64_t M = rl64(S, r), Bm = rl64(B, r);
+                const uint32_t cnt = (uint32_t)__popcll(M), below = (uint32_t)__popcll(M & lt);
+                const uint32_t to = bit_at(M, x) ? below : cnt + ((uint32_t)lane - below);
+                const int got = __builtin_amdgcn_ds_permute((int)(to << 2), (int)bit_at(Bm, x));
+                const uint64_t cm = __ballot(got != 0 && (uint32_t)lane < cnt);
+                rs.append(__brevll(cm), cnt, lane);
+            }
             while (rows) {
                 const int r = __ffsll((long long)rows) - 1;
                 rows &= rows - 1;
@@ -737,6 +838,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
     T1F_DRAIN();
 #undef T1F_DRAIN
 #undef T1F_ROOM
+    if (RAWMR) {
+        rs.finish(lane);
+        if (!SPLIT) {                                       // flush the codeword (t1_fast5.go:878-898), then H | MQ | RAW
+            uint32_t m = 0;
+            int mqovf = 0;
+            if (lane == 0) {
+                const long end = mq_flush(e);
+                m = end > 1 ? (uint32_t)(end - 1) : 0u;
+                mqovf = e.overflow;
+            }
+            m = (uint32_t)__shfl((int)m, 0);
+            mqovf = __shfl(mqovf, 0);
+            __syncthreads();                                // the staging record and the codeword are in memory
+            bool ovf = false;
+            const uint32_t len = mqovf ? 0u : t1_raw_pack(out, (uint32_t)t1_mqbuf_bytes(n), m, rs.st, lane, ovf);
+            if (lane == 0) {
+                if (mqovf || ovf) atomicMax(fault, 2);
+                lens[jid] = (mqovf || ovf) ? 0u : len;
+                numbps[jid] = (uint8_t)numBPS;
+            }
+            return;
+        }
+    }
     if (lane != 0) return;
     if (SPLIT) {
         if (govf) atomicMax(fault, 2);
@@ -750,14 +874,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
         return;
     }
     // ---- flush (t1_fast5.go:878-898) ----
-    const uint32_t tempC = e.C + e.A;
-    e.C |= 0xFFFF;
-    if (e.C >= tempC) e.C -= 0x8000;
-    e.C <<= e.CT; mq_byte_out(e);
-    e.C <<= e.CT; mq_byte_out(e);
-    long end = e.bp + 1;                       // endPos
-    if (e.cur == 0xFF) end--;                  // drop a trailing 0xFF
-    else if (e.bp >= 1) { if (e.bp - 1 < e.cap) out[e.bp - 1] = (uint8_t)e.cur; else e.overflow = 1; }
+    const long end = mq_flush(e);
     if (e.overflow) atomicMax(fault, 2);
     lens[jid] = end > 1 ? (uint32_t)(end - 1) : 0;
     numbps[jid] = (uint8_t)numBPS;
@@ -800,7 +917,8 @@ __device__ __forceinline__ void t1_wave_sync() {       // LDS written by this wa
 // list has ended are fed the no-op symbol (context 31: Qe = 0, never renormalises).
 // PLANES: `rate` holds every block's plane-end marks (t1_encode64_kernel<true, true>); a lane that has coded the symbols up to its next
 // mark replaces the mark by its byte index + T1_RATE_MARGIN, and after the flush clamps the table to the codeword's length.
-template <bool PLANES = false>
+// RAWMR (the raw-MagRef style): the codeword starts three bytes into the slot; lens[] holds its length until t1_raw_pack_kernel has packed the body.
+template <bool PLANES = false, bool RAWMR = false>
 __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const BlockJob *__restrict__ jobs, int njobs, int K, const uint8_t *__restrict__ gsym,
                                                          size_t sym_stride, const uint32_t *__restrict__ nsyms, uint8_t *__restrict__ slots,
                                                          uint32_t *__restrict__ lens, int *__restrict__ fault, const uint32_t *__restrict__ perm,
@@ -830,8 +948,8 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const Bl
     if (nmax == 0) return;
     const BlockJob J = jobs[live ? jid : 0];
     const uint8_t *src = gsym + (size_t)(live ? jid : 0) * sym_stride;
-    uint8_t *const out = slots + J.out_off;
-    const uint32_t cap = (uint32_t)t1_mqbuf_bytes((size_t)J.w * J.h);
+    uint8_t *const out = slots + J.out_off + (RAWMR ? T1_RAW_HDR : 0u);
+    const uint32_t cap = (uint32_t)t1_mqbuf_bytes((size_t)J.w * J.h) - (RAWMR ? T1_RAW_HDR : 0u);
     uint32_t A = 0x8000, C = 0, CT = 12;
     uint32_t curb = 0, bp = 0, ovf = 0;            // pending byte buf[bp]; byte k >= 1 goes to out[k - 1] (t1_fast.go:11-34)
     // One byte leaves C (mqc.go:270-299 as t1_fast.go restates it), select-only: the pending byte takes the carry unless it
@@ -931,10 +1049,35 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const Bl
     if (curb == 0xFF) end--;
     else if (bp >= 1) { if (bp - 1 < cap) out[bp - 1] = (uint8_t)curb; else ovf = 1; }
     if (ovf) atomicMax(fault, 2);
-    lens[jid] = end > 1 ? (uint32_t)(end - 1) : 0;
+    lens[jid] = (RAWMR && ovf) ? 0xFFFFFFFFu : (end > 1 ? (uint32_t)(end - 1) : 0);      // (the style: the mark makes t1_raw_pack_kernel leave lens = 0)
     if (PLANES) {
         const uint32_t len = end > 1 ? end - 1 : 0u;
         for (uint32_t p = 1; p < T1_RATE_STRIDE; p++) rrow[p] = p < nbl ? min(rrow[p], len) : len;
+    }
+}
+
+// The raw-MagRef style behind t1_mq_lanes_kernel<false, true>: one wavefront per block writes H and stuffs RAW behind the codeword the lanes
+// kernel left (its length in lens[]).  Blocks without symbols (no bit planes, or a list that overflowed) and the blocks left to the
+// one-kernel form (T1F_SKIPPED), which packs its own, are not touched.
+__global__ __launch_bounds__(64) void t1_raw_pack_kernel(const BlockJob *__restrict__ jobs, int njobs, uint8_t *__restrict__ slots, uint32_t *__restrict__ lens,
+                                                         const uint32_t *__restrict__ nsyms, const uint32_t *__restrict__ rawst, int *__restrict__ fault) {
+    const int jid = blockIdx.x;
+    if (jid >= njobs) return;
+    const uint32_t ns = nsyms[jid];
+    if (ns == 0 || ns == T1F_SKIPPED) return;
+    const BlockJob J = jobs[jid];
+    if (J.w > 64 || J.h > 64) return;
+    const int lane = threadIdx.x;
+    const uint32_t m = lens[jid];
+    if (m == 0xFFFFFFFFu) {                                     // the codeword overflowed its slot (the fault word is set): a faulted block has no length
+        if (lane == 0) lens[jid] = 0;
+        return;
+    }
+    bool ovf = false;
+    const uint32_t len = t1_raw_pack(slots + J.out_off, (uint32_t)t1_mqbuf_bytes((size_t)J.w * J.h), m, rawst + (size_t)jid * T1_RAWST_WORDS, lane, ovf);
+    if (lane == 0) {
+        if (ovf) atomicMax(fault, 2);
+        lens[jid] = ovf ? 0u : len;
     }
 }
 
@@ -1029,6 +1172,62 @@ __device__ __forceinline__ void t1_dec_magref_wave(T1DecLane &L, int32_t bit, ui
                 *f = (uint8_t)(fv | T1Refine);
             }
             __syncthreads();
+        }
+}
+// ---- the raw-MagRef style's decoder side: RawDecoder (mqc.go:516-562) and the body split ----
+// A total function of the bytes: past the end, and at an 0xFF followed by a byte above 0x8F, the reader stays at 0xFF and returns ones.
+struct RawRd {
+    const uint8_t *data;
+    uint32_t pos, len, c, ct;
+    __device__ __forceinline__ void start(const uint8_t *d, uint32_t n) { data = d; pos = 0; len = n; c = 0; ct = 0; }
+    // the next n <= 64 bits, the first one in bit 0
+    __device__ __forceinline__ uint64_t take(uint32_t n) {
+        uint64_t out = 0;
+        uint32_t got = 0;
+        while (got < n) {
+            if (ct == 0) {
+                const bool more = pos < len;
+                const uint32_t nx = more ? data[pos] : 0xFFu;
+                if (c == 0xFF) {
+                    if (more && nx <= 0x8F) { c = nx; pos++; ct = 7; }
+                    else { c = 0xFF; ct = 8; }
+                } else if (more) { c = nx; pos++; ct = 8; }
+                else { c = 0xFF; ct = 8; }
+            }
+            const uint32_t t = min(ct, n - got);
+            const uint32_t chunk = (c >> (ct - t)) & ((1u << t) - 1u);          // t bits, the first one on top
+            out |= (uint64_t)(__brev(chunk) >> (32u - t)) << got;
+            ct -= t; got += t;
+        }
+        return out;
+    }
+};
+// body = H | MQ | RAW: a body shorter than the header has neither part; m is clamped to what the body holds
+__device__ __forceinline__ void t1_raw_split(const uint8_t *body, uint32_t len, uint32_t &m, uint32_t &rawlen) {
+    m = 0; rawlen = 0;
+    if (len < T1_RAW_HDR) return;
+    m = min((uint32_t)body[0] << 14 | (uint32_t)body[1] << 7 | (uint32_t)body[2], len - T1_RAW_HDR);
+    rawlen = len - T1_RAW_HDR - m;
+}
+// MagRef in the raw style: the members of a row take the next popcount(members) bits of the raw string, in column order.  rd: lane 0's reader.
+__device__ __forceinline__ void t1_dec_magref_raw_wave(T1DecLane &L, RawRd &rd, int32_t bit, int lane) {
+    const int w = L.w, h = L.h, stride = L.stride;
+    const uint64_t lt_lane = (1ull << lane) - 1;
+    for (int y = 0; y < h; y++)
+        for (int x0 = 0; x0 < w; x0 += 64) {
+            const int x = x0 + lane;
+            uint8_t *const f = L.flags + (size_t)(y + 1) * stride + T1D_XO + x;
+            const uint32_t fv = x < w ? *f : 0u;
+            const bool member = (fv & T1Sig) && !(fv & T1Visit);
+            const uint64_t mask = __ballot(member);
+            if (mask == 0) continue;
+            uint64_t bits = 0;
+            if (lane == 0) bits = rd.take((uint32_t)__popcll(mask));
+            bits = (uint64_t)__shfl((int)(bits >> 32), 0) << 32 | (uint32_t)__shfl((int)bits, 0);
+            if (member) {
+                if ((bits >> __popcll(mask & lt_lane)) & 1) atomicOr(&L.data[(size_t)y * w + x], bit);
+                *f = (uint8_t)(fv | T1Refine);
+            }
         }
 }
 // SigProp (t1.go:1295-1319).  Per row (64 columns at a time) all lanes find the candidates (not significant, a significant
@@ -1167,10 +1366,14 @@ __device__ __forceinline__ int32_t t1_coarse_finish(int32_t mag, uint32_t mid, b
 }
 // One block, one wavefront; all lanes call this.  Only the MQ decisions and what depends on them run on lane 0.
 // skip: the quality floor (j2k_*_coarse): the planes below it are left undecoded.
-__device__ __forceinline__ void t1_decode_block_wave(T1DecLane &L, int numBPS, int skip, uint8_t *mrctx, int lane) {
+// RAWMR (the raw-MagRef style): MagRef takes its decisions from rd, lane 0's reader of the body's RAW part.
+template <bool RAWMR = false>
+__device__ __forceinline__ void t1_decode_block_wave(T1DecLane &L, int numBPS, int skip, uint8_t *mrctx, int lane, RawRd *rd = nullptr) {
     for (int bp = numBPS - 1; bp >= skip; bp--) {
         const int32_t bit = bp < 32 ? (int32_t)(1u << bp) : 0;
         t1_dec_sigprop_wave(L, bit, mrctx, mrctx + 64, lane);
+        if (RAWMR) t1_dec_magref_raw_wave(L, *rd, bit, lane);
+        else
         t1_dec_magref_wave(L, bit, mrctx, lane);
         t1_dec_cleanup_wave(L, bit, mrctx, lane);
     }
@@ -1249,6 +1452,8 @@ struct T1Dec64Shared {
     uint8_t mrctx[128];                          // per-column context lists of the wave-level passes (two of 64 bytes)
 };
 static_assert(sizeof(T1Dec64Shared) <= 5120, "t1_decode64_kernel: LDS per block above 10 granules (32 blocks per CU)");
+// RAWMR: the raw-MagRef style (j2k_plan_set_raw_magref): the body is H | MQ | RAW, the MQ decoder runs on MQ, MagRef reads RAW.
+template <bool RAWMR = false>
 __global__ __launch_bounds__(64) void t1_decode64_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                          const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
                                                          const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded, int min_bps, int skip_uniform, const uint8_t *__restrict__ floors) {
@@ -1282,8 +1487,20 @@ __global__ __launch_bounds__(64) void t1_decode64_kernel(const BlockJob *__restr
     __syncthreads();
     {
         T1DecLane L;                                              // L.d is lane 0's decoder
+        RawRd rd;
+        if (RAWMR) {
+            if (lane == 0) {
+                const uint8_t *body = stream + offs[jid];
+                uint32_t m, rawlen;
+                t1_raw_split(body, lens[jid], m, rawlen);
+                mq_dec_init(L.d, body + T1_RAW_HDR, (long)m);      // (m = 0: no byte is read)
+                rd.start(body + T1_RAW_HDR + m, rawlen);
+            }
+        } else
         if (lane == 0) mq_dec_init(L.d, stream + offs[jid], (long)lens[jid]);
         L.ent = S.ent; L.mq = c_mq94.v; L.zcsc = S.zcsc; L.flags = S.flags; L.data = out; L.w = w; L.h = h; L.stride = stride;
+        if (RAWMR) t1_decode_block_wave<true>(L, __shfl((int)numbps[jid], 0), skip_planes + vzero, S.mrctx, lane, &rd);
+        else
         t1_decode_block_wave(L, __shfl((int)numbps[jid], 0), skip_planes + vzero, S.mrctx, lane);
     }
     __syncthreads();                                                      // includes the wait for lane 0's stores and atomics
@@ -1631,7 +1848,7 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_magref_lanes_kernel(
 }
 
 #include "t1_lanes.inc"
-size_t t1_dec_split_bytes(size_t njobs) { return t1_dec_lanes_bytes(njobs); }
+size_t t1_dec_split_bytes(size_t njobs, bool raw_magref) { return raw_magref ? t1_dec_lanes_bytes_raw(njobs) : t1_dec_lanes_bytes(njobs); }
 
 // ---- stand-alone coders: the reference's MQEncoder / MQDecoder / RawEncoder / RawDecoder as batch calls ----
 // mqc.go:169-349: NewMQEncoder, n x Encode(ctx, decision), Flush.  One wavefront, the coder on lane 0 (a single chain).
@@ -1647,14 +1864,7 @@ __global__ __launch_bounds__(64) void mq_encode_kernel(const uint8_t *__restrict
         if (c >= NumContexts) { atomicMax(fault, 3); *out_len = 0; return; }      // Go: index out of range panic
         mq_encode(e, T, c, decs[i]);                                              // uint8(decision) == mps: a decision > 1 never matches
     }
-    const uint32_t tempC = e.C + e.A;                                             // setbits + Flush, mqc.go:313-341
-    e.C |= 0xFFFF;
-    if (e.C >= tempC) e.C -= 0x8000;
-    e.C <<= e.CT; mq_byte_out(e);
-    e.C <<= e.CT; mq_byte_out(e);
-    long end = e.bp + 1;
-    if (e.cur == 0xFF) end--;
-    else if (e.bp >= 1) { if (e.bp - 1 < e.cap) out[e.bp - 1] = (uint8_t)e.cur; else e.overflow = 1; }
+    const long end = mq_flush(e);
     if (e.overflow) atomicMax(fault, 2);
     *out_len = end > 1 ? (uint32_t)(end - 1) : 0;
 }
@@ -1753,62 +1963,64 @@ static int lds_for(size_t work_per_job, size_t limit = T1_LDS_LIMIT) {
 // symbol workspace of the split path: bytes per job for blocks up to 64x64 with `planes` bit planes.  A block emits at
 // most one decision per sample and plane, one sign per sample, and two extra symbols per run-length hit (a 4-sample
 // column can be hit once): (planes + 1.5) * 4096, plus the padding of each drained chunk.
+size_t t1_raw_stage_bytes() { return (size_t)T1_RAWST_WORDS * 4; }      // per job: the raw-MagRef style's staging record
 size_t t1_sym_stride(int planes) { return ((size_t)(planes + 2) * 4096 + 1024 + 15) & ~size_t(15); }
+
+// The launches for blocks up to 64 x 64, one sequence for every instantiation: PLANES (aux = the rate tables), RAWMR (the raw-MagRef style, aux = the
+// staging records; t1_raw_pack_kernel assembles the bodies behind the lanes kernel), or neither (aux = null).
+// sym != null: context formation and MQ coding as two kernels through the symbol workspace; otherwise the one-kernel form.
+template <bool PLANES, bool RAWMR>
+static void launch_t1_encode64(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots, uint32_t *lens, uint8_t *numbps, int *fault,
+                               uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint32_t *aux) {
+    if (!(sym && nsyms)) {
+        hipLaunchKernelGGL((t1_encode64_kernel<false, PLANES, RAWMR>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
+                           (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nullptr, aux);
+        return;
+    }
+    int planes = (int)((sym_stride - 1024) / 4096) - 2;
+    if (planes > 31) planes = 31;
+    hipLaunchKernelGGL((t1_encode64_kernel<true, PLANES, RAWMR>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
+                       sym, sym_stride, nsyms, planes, (const uint32_t *)nullptr, aux);
+    // blocks per wavefront: the kernel runs at the latency of one chain whatever K is, so K decides how much of the
+    // device a frame's chains occupy while they run.  Measured on a 4K 12-bit frame (7005 blocks): one frame alone
+    // 15.8 ms at K = 4, 18.0 at K = 32 (each wavefront waits for its slowest lane); three or more frames in flight
+    // 34.8 ms per frame at K = 4, 28.3 at K = 32 -- the chains of one frame then run beside the other frames' decode
+    // kernels, which are issue-bound.  lanes > 0: as given (J2K_T1_LANES); 0: latency (blocks / 2048); < 0: throughput
+    // (blocks / 256, at most 64) -- the caller passes < 0 while several contexts code with the MQ coder.
+    // The lanes are ordered by symbol count (t1_order_kernel; measured in round 3 and kept): a wavefront's chains end together, and the
+    // throughput setting fills all 64 lanes.
+    int K = lanes > 0 ? lanes : (lanes < 0 ? std::min(64, (njobs + 255) / 256) : (njobs + 2047) / 2048);
+    K = std::min(64, std::max(1, K));
+    uint32_t *perm = nsyms + njobs;       // njobs + 64 words behind nsyms (t1_workspace in j2k_stages.cpp)
+    hipLaunchKernelGGL(t1_order_kernel, dim3(1), dim3(1024), 0, s, jobs, njobs, (const uint8_t *)nullptr, (const uint32_t *)nsyms, 1, perm,
+                       (uint32_t *)nullptr, njobs);
+    const dim3 lgrid(((njobs + K - 1) / K + T1_LANES_WPW - 1) / T1_LANES_WPW);
+    hipLaunchKernelGGL((t1_mq_lanes_kernel<PLANES, RAWMR>), lgrid, dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, K, sym, sym_stride, nsyms,
+                       slots, lens, fault, (const uint32_t *)perm, PLANES ? aux : (uint32_t *)nullptr, PLANES ? (const uint8_t *)numbps : (const uint8_t *)nullptr);
+    if (RAWMR) hipLaunchKernelGGL(t1_raw_pack_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, slots, lens, (const uint32_t *)nsyms, (const uint32_t *)aux, fault);
+    if (planes < 31)        // the lists are shorter than the deepest block can be: the blocks marked T1F_SKIPPED take the one-kernel form
+        hipLaunchKernelGGL((t1_encode64_kernel<false, PLANES, RAWMR>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
+                           (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nsyms, aux);
+}
 
 // max_dim: largest block width or height among the jobs (<= 64: every block takes the wave-parallel kernels).
 // sym != null: context formation and MQ coding as two kernels through the symbol workspace (sym_stride bytes per job,
 // nsyms = njobs words); blocks with more bit planes than the stride allows fall back to the one-kernel path.
 hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots,
                             uint32_t *lens, uint8_t *numbps, uint8_t *work, size_t work_per_job, int *fault, int max_dim,
-                            uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint8_t *bigsym, const uint64_t *bigsym_off, uint32_t *bignsyms, uint32_t *rate) {
+                            uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint8_t *bigsym, const uint64_t *bigsym_off, uint32_t *bignsyms, uint32_t *rate,
+                            uint32_t *rawst) {
     if (njobs <= 0) return hipSuccess;
+    if (rawst) {     // the raw-MagRef style (j2k_plan_set_raw_magref; blocks <= 64 x 64, no rate tables): the RAWMR instantiations, same sequence
+        launch_t1_encode64<false, true>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rawst);
+        return hipGetLastError();
+    }
     static int serial_only = -1;   // J2K_T1_SERIAL=1: A/B against the serial kernel
     if (serial_only < 0) serial_only = 0;          // (round 1's A/B switch J2K_T1_SERIAL: gone, the serial kernel only takes what the others leave)
     if (!serial_only) {
-        if (sym && nsyms) {
-            int planes = (int)((sym_stride - 1024) / 4096) - 2;
-            if (planes > 31) planes = 31;
-            // rate != null (j2k_plan_encode_blocks_planes): the PLANES instantiations of the <= 64 x 64 kernels; the others are launched as before
-            if (rate) hipLaunchKernelGGL((t1_encode64_kernel<true, true>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                                         sym, sym_stride, nsyms, planes, (const uint32_t *)nullptr, rate);
-            else
-            hipLaunchKernelGGL(t1_encode64_kernel<true>, dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                               sym, sym_stride, nsyms, planes, (const uint32_t *)nullptr, (uint32_t *)nullptr);
-            // blocks per wavefront: the kernel runs at the latency of one chain whatever K is, so K decides how much of the
-            // device a frame's chains occupy while they run.  Measured on a 4K 12-bit frame (7005 blocks): one frame alone
-            // 15.8 ms at K = 4, 18.0 at K = 32 (each wavefront waits for its slowest lane); three or more frames in flight
-            // 34.8 ms per frame at K = 4, 28.3 at K = 32 -- the chains of one frame then run beside the other frames' decode
-            // kernels, which are issue-bound.  lanes > 0: as given (J2K_T1_LANES); 0: latency (blocks / 2048); < 0: throughput
-            // (blocks / 256, at most 32) -- the caller passes < 0 while several contexts code with the MQ coder.
-            // With the lanes ordered by symbol count (t1_order_kernel; `lane_order`, J2K_T1_ENC_ORDER=0 turns it off) a wavefront's
-            // chains end together, and the throughput setting fills all 64 lanes.
-            static int lane_order = -1;
-            if (lane_order < 0) lane_order = 1;            // (J2K_T1_ENC_ORDER: measured in round 3, ordered lanes kept)
-            int K = lanes > 0 ? lanes : (lanes < 0 ? std::min(lane_order ? 64 : 32, (njobs + 255) / 256) : (njobs + 2047) / 2048);
-            K = std::min(64, std::max(1, K));
-            uint32_t *perm = lane_order ? nsyms + njobs : nullptr;       // njobs + 64 words behind nsyms (t1_workspace in j2k_stages.cpp)
-            if (perm) hipLaunchKernelGGL(t1_order_kernel, dim3(1), dim3(1024), 0, s, jobs, njobs, (const uint8_t *)nullptr, (const uint32_t *)nsyms, 1, perm,
-                                         (uint32_t *)nullptr, njobs);
-            const dim3 lgrid(((njobs + K - 1) / K + T1_LANES_WPW - 1) / T1_LANES_WPW);
-            if (rate) hipLaunchKernelGGL(t1_mq_lanes_kernel<true>, lgrid, dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, K, sym, sym_stride, nsyms,
-                                         slots, lens, fault, (const uint32_t *)perm, rate, (const uint8_t *)numbps);
-            else
-            hipLaunchKernelGGL(t1_mq_lanes_kernel<false>, lgrid, dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, K, sym, sym_stride, nsyms,
-                               slots, lens, fault, (const uint32_t *)perm, (uint32_t *)nullptr, (const uint8_t *)nullptr);
-            if (planes < 31) {
-                if (rate) hipLaunchKernelGGL((t1_encode64_kernel<false, true>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                                             (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nsyms, rate);
-                else
-                hipLaunchKernelGGL(t1_encode64_kernel<false>, dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                                   (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nsyms, (uint32_t *)nullptr);
-            }
-        } else if (rate) {
-            hipLaunchKernelGGL((t1_encode64_kernel<false, true>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                               (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nullptr, rate);
-        } else {
-            hipLaunchKernelGGL(t1_encode64_kernel<false>, dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                               (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nullptr, (uint32_t *)nullptr);
-        }
+        // rate != null (j2k_plan_encode_blocks_planes): the PLANES instantiations of the <= 64 x 64 kernels; the others are launched as before
+        if (rate) launch_t1_encode64<true, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rate);
+        else launch_t1_encode64<false, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, (uint32_t *)nullptr);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || max_dim <= 64) return e;
         // blocks above 64 x 64, up to 256 x 256 (the reference's default size): wave-parallel context formation (t1_big.inc)
@@ -1861,8 +2073,37 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
 // general_only: every block on the general kernel (A/B knob); otherwise blocks up to 64x64 take t1_decode64_kernel
 hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, const uint8_t *numbps, int32_t *decoded, uint8_t *work, size_t work_per_job,
-                            int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput, int skip_planes, const uint8_t *floors) {
+                            int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput, int skip_planes, const uint8_t *floors, int raw_magref) {
     if (njobs <= 0) return hipSuccess;
+    if (raw_magref) {
+        // the raw-MagRef style (blocks <= 64 x 64, no per-block floors: the setter and the floors calls have refused everything else): the
+        // plane-stepped lanes path where the plain style would take a plane-stepped path (split_ws; its workspace is t1_dec_split_bytes(njobs,
+        // true)) -- as one launch per group (sig_lanes = 2) or as two launches per plane (sig_lanes = 1, and 0: round 2's step kernels have no
+        // instantiation for the style) with NO MagRef lanes launch -- and the one-launch kernel for everything else, t1_dec_general included
+        if (split_ws) {
+            uint64_t *masks = reinterpret_cast<uint64_t *>(split_ws + t1_dec_lanes_mask_offset((size_t)njobs));
+            uint64_t *planes = reinterpret_cast<uint64_t *>(split_ws + t1_dec_lanes_planes_offset((size_t)njobs));
+            const int ngroups = (njobs + 63) / 64;
+            const int nwg = (ngroups + T1_LANES_WPW - 1) / T1_LANES_WPW;
+            uint32_t *perm = reinterpret_cast<uint32_t *>(split_ws + t1_dec_lanes_perm_offset((size_t)njobs)), *slot_of = perm + (size_t)ngroups * 64;
+            hipLaunchKernelGGL(t1_order_kernel, dim3(1), dim3(1024), 0, s, jobs, njobs, numbps, lens, 0, perm, slot_of, ngroups * 64);
+            if (sig_lanes >= 2) {
+                hipLaunchKernelGGL((t1_dec_sig_lanes_kernel<true, true>), dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, lens, numbps,
+                                   split_ws, masks, (const uint32_t *)perm, planes, 0, skip_planes, (const uint8_t *)nullptr);
+            } else
+            for (int k = 0; k <= T1DS_MAXP; k++) {
+                hipLaunchKernelGGL((t1_dec_sig_lanes_kernel<false, true>), dim3(nwg), dim3(64 * T1_LANES_WPW), 0, s, jobs, njobs, stream, offs, lens, numbps,
+                                   split_ws, masks, (const uint32_t *)perm, planes, k, skip_planes, (const uint8_t *)nullptr);
+                hipLaunchKernelGGL(t1_dec_plane_raw_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, split_ws, masks,
+                                   (const uint32_t *)slot_of, planes, k, skip_planes, (const uint8_t *)nullptr);
+            }
+            hipLaunchKernelGGL(t1_dec_assemble_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, numbps, decoded, (const uint64_t *)masks,
+                               (const uint32_t *)slot_of, (const uint64_t *)planes, skip_planes, (const uint8_t *)nullptr);
+        }
+        hipLaunchKernelGGL(t1_decode64_kernel<true>, dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, decoded,
+                           split_ws ? T1DS_MAXP + 1 : 0, skip_planes, (const uint8_t *)nullptr);
+        return hipGetLastError();
+    }
     if (!general_only) {
         if (split_ws) {
             // plane-stepped path for blocks of at most 31 planes; the one-launch kernel keeps the deeper ones
@@ -1898,7 +2139,7 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
                                reinterpret_cast<const uint64_t *>(split_ws + t1_dec_lanes_mask_offset((size_t)njobs)),
                                reinterpret_cast<const uint32_t *>(split_ws + t1_dec_lanes_perm_offset((size_t)njobs)) + (size_t)((njobs + 63) / 64) * 64,
                                reinterpret_cast<const uint64_t *>(split_ws + t1_dec_lanes_planes_offset((size_t)njobs)), skip_planes, floors);
-        hipLaunchKernelGGL(t1_decode64_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, decoded,
+        hipLaunchKernelGGL(t1_decode64_kernel<false>, dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, decoded,
                            split_ws ? T1DS_MAXP + 1 : 0, skip_planes, floors);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || max_dim <= 64) return e;

@@ -36,6 +36,15 @@ size_t t1_dec_lanes_perm_offset(size_t njobs) { return t1_dec_lanes_mask_offset(
 size_t t1_dec_lanes_planes_offset(size_t njobs) { return (t1_dec_lanes_perm_offset(njobs) + (((njobs + 63) / 64) * 64 + njobs) * 4 + 255) & ~size_t(255); }
 #define T1L_PLANE_WORDS ((size_t)32 * 64)               /* per block: one 64-bit row mask per bit plane and row, [plane][row] */
 size_t t1_dec_lanes_bytes(size_t njobs) { return t1_dec_lanes_planes_offset(njobs) + njobs * T1L_PLANE_WORDS * 8 + 256; }
+// The raw-MagRef style (j2k_plan_set_raw_magref): behind the plane words, per block the un-stuffed RAW part of its body as a linear bit string
+// (decision r of the block = bit r & 31 of word r >> 5; ones from the string's end on, as RawDecoder.DecodeBit returns them) -- room for the
+// 31 x 4096 decisions a plane-stepped block can have and the words a trip of t1l_raw_unstuff may run over.  The running offset of the next
+// plane's decisions is the first word of the record's T1DS_BITS area, which the style does not use otherwise.
+#define T1L_RAWB_WORDS ((size_t)31 * 4096 / 32 + 32)
+size_t t1_dec_lanes_bytes_raw(size_t njobs) { return t1_dec_lanes_bytes(njobs) + njobs * T1L_RAWB_WORDS * 4 + 256; }
+__device__ __forceinline__ uint32_t *t1l_rawbits(uint64_t *planes, int njobs, long jid) {
+    return reinterpret_cast<uint32_t *>(planes + (size_t)njobs * T1L_PLANE_WORDS + 32) + (size_t)jid * T1L_RAWB_WORDS;
+}
 
 // x's bits at the set positions of m, packed to the low end (compress) and the inverse (expand), 64 bits wide: Hacker's Delight
 // 7-4 / 7-5.  The six move masks depend on m only and serve any number of words.
@@ -142,10 +151,57 @@ __device__ __forceinline__ uint64_t t1l_sel4(uint32_t i, uint64_t a, uint64_t b,
     return i1 ? hi : lo;
 }
 
+// RawDecoder (mqc.go:516-562) over a whole RAW part at once, all 64 lanes: the first `need` decisions (and up to a trip more) as a linear bit
+// string in dst.  A byte carries 8 bits, 7 behind an 0xFF -- its width depends on the byte before it only -- so a trip places 64 bytes with one
+// prefix sum of the widths: every lane ORs its byte, first bit lowest, into a 20-word LDS stage that starts with the partial word the trip
+// before left, the full words go to dst.  At an 0xFF followed by a byte above 0x8F, and at the end of the bytes, the reader stays at 0xFF:
+// ones from there to the end of the record.  stage: 20 words of LDS owned by the calling wavefront.
+__device__ __forceinline__ void t1l_raw_unstuff(int lane, const uint8_t *raw, uint32_t rawlen, uint32_t need, uint32_t *dst, uint32_t *stage) {
+    const uint32_t needw = (need + 31u) / 32u + 3u;
+    uint32_t P = 0, carry = 0, prev_last = 0;
+    bool stuck = false;
+    for (uint32_t base = 0; base < rawlen && P < need && !stuck; base += 64) {
+        const uint32_t i = base + (uint32_t)lane;
+        const bool in = i < rawlen;
+        const uint32_t v = in ? raw[i] : 0u;
+        uint32_t pv = (uint32_t)__shfl_up((int)v, 1);
+        if (lane == 0) pv = prev_last;
+        const uint64_t stopm = __ballot(in && pv == 0xFFu && v > 0x8Fu);
+        const uint32_t nin = min(rawlen - base, 64u);
+        const uint32_t nval = stopm ? (uint32_t)__ffsll((long long)stopm) - 1u : nin;
+        stuck = stopm != 0;
+        const bool val = (uint32_t)lane < nval;
+        const uint32_t wd = val ? (pv == 0xFFu ? 7u : 8u) : 0u;
+        uint32_t incl = wd;
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)incl, o); if (lane >= o) incl += t; }
+        const uint32_t total = (uint32_t)__shfl((int)incl, 63);
+        if (lane < 20) stage[lane] = lane == 0 ? carry : 0u;
+        t1_wave_sync();
+        if (val) {
+            const uint32_t rev = __brev(v & ((1u << wd) - 1u)) >> (32u - wd);       // the byte's first bit lowest
+            const uint32_t pos = (P & 31u) + incl - wd, w = pos >> 5, sh = pos & 31u;
+            atomicOr(&stage[w], rev << sh);
+            if (sh + wd > 32u) atomicOr(&stage[w + 1], rev >> (32u - sh));
+        }
+        t1_wave_sync();
+        const uint32_t T = P + total, W0 = P >> 5, nfull = (T >> 5) - W0;              // nfull <= 16
+        if ((uint32_t)lane < nfull) dst[W0 + lane] = stage[lane];
+        carry = stage[nfull];
+        t1_wave_sync();
+        P = T;
+        prev_last = (uint32_t)__shfl((int)v, 63);
+    }
+    const uint32_t W0 = P >> 5, first = carry | (0xFFFFFFFFu << (P & 31u));
+    for (uint32_t w = W0 + (uint32_t)lane; w < needw; w += 64) dst[w] = w == W0 ? first : 0xFFFFFFFFu;
+}
+
 // The work of one block and one launch k >= 1 (see above), all 64 lanes = the block's rows.  l = the block's lane in its group;
 // stage = 2 x 132 words of LDS owned by the calling wavefront.  Returns the length of MagRef(p)'s list (0 at p = -1).
+// RAWMR (the raw-MagRef style): the decisions of MagRef(p + 1) are not what a chain left in the record but the next popcount(members) bits of
+// the block's un-stuffed raw string `rawwords`, from the running offset on; the context list of MagRef(p) is still written (nobody reads it).
+template <bool RAWMR = false>
 __device__ __forceinline__ uint32_t t1l_plane_work(int lane, int w, int h, int p, int k, uint8_t *rec, uint64_t *masks, long group, int l,
-                                                   uint64_t *pl, uint32_t (*stage)[132]) {
+                                                   uint64_t *pl, uint32_t (*stage)[132], const uint32_t *rawwords = nullptr) {
     auto row_ptr = [&](int arr) -> uint64_t * { return t1l_row(masks, group, arr, lane) + l; };     // lane = row
     const bool inrow = lane < h;
     const uint64_t S = inrow ? *row_ptr(T1L_S) : 0ull, VIS = inrow ? *row_ptr(T1L_VIS) : 0ull, REF = inrow ? *row_ptr(T1L_REF) : 0ull;
@@ -163,8 +219,15 @@ __device__ __forceinline__ uint32_t t1l_plane_work(int lane, int w, int h, int p
     {
         const uint32_t cnt = (uint32_t)__popcll(MEMBP);
         uint32_t total;
-        const uint32_t off = excl_sum(cnt, total);
-        const uint32_t *bits = reinterpret_cast<const uint32_t *>(rec + T1DS_BITS);
+        uint32_t off = excl_sum(cnt, total);
+        const uint32_t *bits = RAWMR ? rawwords : reinterpret_cast<const uint32_t *>(rec + T1DS_BITS);
+        if (RAWMR) {
+            uint32_t *const roffp = reinterpret_cast<uint32_t *>(rec + T1DS_BITS);
+            const uint32_t roff = *roffp;
+            off += roff;
+            t1_wave_sync();
+            if (lane == 0) *roffp = roff + total;
+        }
         uint64_t d = 0;
         if (cnt) {
             const uint32_t w0 = off >> 5, sh = off & 31;
@@ -226,6 +289,10 @@ __device__ __attribute__((noinline)) uint32_t t1l_plane_work_call(int lane, int 
                                                                   uint64_t *pl, uint32_t (*stage)[132]) {
     return t1l_plane_work(lane, w, h, p, k, rec, masks, group, l, pl, stage);
 }
+__device__ __attribute__((noinline)) uint32_t t1l_plane_work_raw_call(int lane, int w, int h, int p, int k, uint8_t *rec, uint64_t *masks, long group, int l,
+                                                                      uint64_t *pl, uint32_t (*stage)[132], const uint32_t *rawwords) {
+    return t1l_plane_work<true>(lane, w, h, p, k, rec, masks, group, l, pl, stage, rawwords);
+}
 
 // PERSIST = false: launch k of the sequence above (Cleanup(p + 1), SigProp(p)).  PERSIST = true: the WHOLE plane-stepped decode of
 // the wavefront's 64 blocks in one launch -- initialisation, then for k = 1 .. 31 the significance passes, the plane work of each of
@@ -233,7 +300,9 @@ __device__ __attribute__((noinline)) uint32_t t1l_plane_work_call(int lane, int 
 // decoder, its ring and the context entries staying where they are.  Nothing crosses wavefronts: no launch boundary makes a
 // wavefront wait for the slowest one of another group, 3 launches per frame instead of 96, and the plane work runs at the lanes
 // kernels' priority instead of queueing behind other frames' kernels.
-template <bool PERSIST>
+// RAWMR (the raw-MagRef style): the MQ decoder runs on the MQ part of the body H | MQ | RAW; PERSIST un-stuffs every block's RAW part before the
+// first plane and has no MagRef chains.
+template <bool PERSIST, bool RAWMR = false>
 __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                               const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
                                                               const uint8_t *__restrict__ numbps, uint8_t *__restrict__ ws,
@@ -266,6 +335,11 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(con
         }
         if (live0) {
             MqDec d;
+            if (RAWMR) {
+                uint32_t m, rawlen;
+                t1_raw_split(stream + offs[jid], lens[jid], m, rawlen);
+                mq_dec_init(d, stream + offs[jid] + T1_RAW_HDR, (long)m);
+            } else
             mq_dec_init(d, stream + offs[jid], (long)lens[jid]);
             T1DecState t; t.C = d.C; t.A = d.A; t.CT = d.CT; t.nmr = 0; t.bp = d.bp; t.len = d.len;
             *stp = t;
@@ -321,6 +395,11 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(con
         st = T1DecState{0, 0x8000u, 0, 0, 0, 0};
         if (live) {
             MqDec d;
+            if (RAWMR) {
+                uint32_t m, rawlen;
+                t1_raw_split(stream + offs[jid], lens[jid], m, rawlen);
+                mq_dec_init(d, stream + offs[jid] + T1_RAW_HDR, (long)m);
+            } else
             mq_dec_init(d, stream + offs[jid], (long)lens[jid]);
             st.C = d.C; st.A = d.A; st.CT = d.CT; st.bp = d.bp; st.len = d.len;
         }
@@ -332,8 +411,24 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(con
 
     // ---- this lane's MQ decoder ----
     MqLaneDec mq;
-    mq.start(stream + offs[live ? jid : 0], st, live, L.ring, lane);
+    mq.start(stream + offs[live ? jid : 0] + (RAWMR ? T1_RAW_HDR : 0u), st, live, L.ring, lane);
     t1_wave_sync();
+    if (PERSIST && RAWMR) {                                     // every block's RAW part, un-stuffed once (lanes = bytes of one block at a time)
+        uint64_t todo = __ballot(live);
+        while (todo) {
+            const int l = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const uint32_t jl = (uint32_t)__builtin_amdgcn_readlane((int)pj, l);
+            const uint32_t need = (uint32_t)(__builtin_amdgcn_readlane(nb0, l) * __builtin_amdgcn_readlane(w, l) * __builtin_amdgcn_readlane(h, l));
+            const uint8_t *body = stream + offs[jl];
+            uint32_t m, rawlen;
+            t1_raw_split(body, lens[jl], m, rawlen);
+            t1l_raw_unstuff(lane, body + T1_RAW_HDR + m, rawlen, need, t1l_rawbits(planes, njobs, (long)jl), &L.stage[0][0]);
+            if (lane == 0) *reinterpret_cast<uint32_t *>(ws + (size_t)jl * T1DS_STRIDE + T1DS_BITS) = 0u;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        t1_wave_sync();
+    }
     uint32_t nact = 0;
     // one decision of every lane that has one (`act`) in context ctx; b0 / b1 from mq.peek() at the top of the trip
     auto mq_step = [&](uint32_t ctx, bool act, uint32_t b0, uint32_t b1) -> uint32_t {
@@ -506,14 +601,16 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_dec_sig_lanes_kernel(con
             todo &= todo - 1;
             const int wl = __builtin_amdgcn_readlane(w, l), hl = __builtin_amdgcn_readlane(h, l), pl_ = __builtin_amdgcn_readlane(p, l);
             const uint32_t jl = (uint32_t)__builtin_amdgcn_readlane((int)pj, l);
-            const uint32_t n_l = t1l_plane_work_call(lane, wl, hl, pl_, k, ws + (size_t)jl * T1DS_STRIDE, masks, group, l,
+            const uint32_t n_l = RAWMR ? t1l_plane_work_raw_call(lane, wl, hl, pl_, k, ws + (size_t)jl * T1DS_STRIDE, masks, group, l,
+                                                                 planes + (size_t)jl * T1L_PLANE_WORDS + lane, L.stage, t1l_rawbits(planes, njobs, (long)jl))
+                                       : t1l_plane_work_call(lane, wl, hl, pl_, k, ws + (size_t)jl * T1DS_STRIDE, masks, group, l,
                                                 planes + (size_t)jl * T1L_PLANE_WORDS + lane, L.stage);
             if (lane == l) nmr_mine = n_l;
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");     // lists and masks written by rows are read by the blocks' own lanes
         t1_wave_sync();
         // ---- MagRef(p) ----
-        const uint32_t n = dosig ? nmr_mine : 0u;
+        const uint32_t n = (dosig && !RAWMR) ? nmr_mine : 0u;          // (the style: MagRef(p) is read from the raw string by the next plane work)
         uint32_t nmax = n;
         for (int o = 32; o > 0; o >>= 1) nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, o));
         if (nmax) {
@@ -578,6 +675,44 @@ __global__ __launch_bounds__(64) void t1_dec_plane_kernel(const BlockJob *__rest
         return;
     }
     const uint32_t nmr = t1l_plane_work(lane, w, h, p, k, rec, masks, group, l, pl, stage);
+    if (lane == 0 && p >= 0) stp->nmr = nmr;
+}
+
+// t1_dec_plane_kernel in the raw-MagRef style: k = 0 also un-stuffs the block's RAW part (t1l_raw_unstuff) and clears the running offset; the
+// later launches read MagRef's decisions from that string, and no t1_dec_magref_lanes_kernel runs between them.
+__global__ __launch_bounds__(64) void t1_dec_plane_raw_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
+                                                              const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens, const uint8_t *__restrict__ numbps,
+                                                              uint8_t *__restrict__ ws, uint64_t *__restrict__ masks, const uint32_t *__restrict__ slot_of,
+                                                              uint64_t *__restrict__ planes, int k, int skip_uniform, const uint8_t *__restrict__ floors) {
+    __shared__ uint32_t stage[2][132];
+    const int jid = blockIdx.x;
+    if (jid >= njobs) return;
+    const int skip_planes = t1_floor_of(skip_uniform, floors, jid);
+    const int nb0 = (int)numbps[jid];
+    const int nb = max(nb0 - skip_planes, 0);
+    const int p = nb - 1 - k;
+    if (nb0 > T1DS_MAXP || p < -1) return;
+    const BlockJob J = jobs[jid];
+    const int w = J.w, h = J.h;
+    if (w > 64 || h > 64) return;
+    const int lane = threadIdx.x;
+    const uint32_t slot = slot_of[jid];
+    const long group = slot >> 6;
+    const int l = slot & 63;
+    uint8_t *const rec = ws + (size_t)jid * T1DS_STRIDE;
+    T1DecState *const stp = reinterpret_cast<T1DecState *>(rec + T1DS_STATE);
+    uint64_t *const pl = planes + (size_t)jid * T1L_PLANE_WORDS + lane;
+    uint32_t *const rawwords = t1l_rawbits(planes, njobs, jid);
+    if (k == 0) {
+        t1l_row(masks, group, T1L_REF, lane)[l] = 0; t1l_row(masks, group, T1L_MEMB, lane)[l] = 0;
+        if (lane == 0) { stp->nmr = 0; *reinterpret_cast<uint32_t *>(rec + T1DS_BITS) = 0u; }
+        const uint8_t *body = stream + offs[jid];
+        uint32_t m, rawlen;
+        t1_raw_split(body, lens[jid], m, rawlen);
+        t1l_raw_unstuff(lane, body + T1_RAW_HDR + m, rawlen, (uint32_t)(nb0 * w * h), rawwords, &stage[0][0]);
+        return;
+    }
+    const uint32_t nmr = t1l_plane_work<true>(lane, w, h, p, k, rec, masks, group, l, pl, stage, rawwords);
     if (lane == 0 && p >= 0) stp->nmr = nmr;
 }
 

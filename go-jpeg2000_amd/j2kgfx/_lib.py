@@ -50,7 +50,7 @@ SYMBOLS = [
     "j2k_decompose_multilevel97", "j2k_reconstruct_multilevel97",
     "j2k_tcd_apply_forward_dwt", "j2k_tcd_apply_inverse_dwt", "j2k_quantize", "j2k_dequantize",
     "j2k_encode_blocks", "j2k_decode_blocks", "j2k_block_bound",
-    "j2k_plan_set_decode_coded_rows_only", "j2k_plan_set_dequantize", "j2k_plan_create", "j2k_plan_destroy", "j2k_plan_get_info", "j2k_plan_get_blocks", "j2k_plan_get_planes",
+    "j2k_plan_set_decode_coded_rows_only", "j2k_plan_set_dequantize", "j2k_plan_set_raw_magref", "j2k_plan_get_raw_magref", "j2k_plan_create", "j2k_plan_destroy", "j2k_plan_get_info", "j2k_plan_get_blocks", "j2k_plan_get_planes",
     "j2k_plan_forward", "j2k_plan_inverse", "j2k_plan_encode_blocks", "j2k_plan_compact", "j2k_plan_encode_stream",
     "j2k_plan_decode_blocks", "j2k_plan_get_decoded_offsets", "j2k_plan_get_ht_decode_leaders", "j2k_plan_get_ht_decode_walk_order", "j2k_encode_frame",
     "j2k_mq_encode", "j2k_mq_decode", "j2k_raw_encode", "j2k_raw_decode",
@@ -136,6 +136,7 @@ def lib():
             "j2k_plan_pack_bound": (S, [V]), "j2k_ctx_set_option": (I, [V, C.c_char_p, C.c_long]),
             "j2k_quantize": (I, [V, DP, S, C.c_double, C.POINTER(C.c_int32)]), "j2k_dequantize": (I, [V, C.POINTER(C.c_int32), S, C.c_double, DP]),
             "j2k_plan_set_dequantize": (I, [V, I]),
+            "j2k_plan_set_raw_magref": (I, [V, I]), "j2k_plan_get_raw_magref": (I, [V]),
             "j2k_decode_blocks_coarse": (I, [V, I, V, V, V, V, V, S, I, V, V]),
             "j2k_plan_decode_blocks_coarse": (I, [V, V, V, V, V, I, V]),
             "j2k_plan_decode_frame_pixels_coarse": (I, [V, V, S, V, I, I, I, I, V, S]),

@@ -45,7 +45,7 @@ def _stage(fn):
 class FramePlan:
     def __init__(self, width, height, ncomp, precision=8, lossless=True, quality=0, num_resolutions=6,
                  cb=(64, 64), tile=(0, 0), coder=_lib.CODER_MQ, is_signed=False, tile_first=0, tile_count=0,
-                 ctx=None, track_streams=True, frame_rows=0, closed_loop=False, dequantize=False, mallat=False):
+                 ctx=None, track_streams=True, frame_rows=0, closed_loop=False, dequantize=False, mallat=False, raw_magref=False):
         self.ctx = ctx or default_context()
         self.track_streams = bool(track_streams)
         self._ext_stream = None
@@ -71,6 +71,8 @@ class FramePlan:
         register_plan(self)                     # closed by the package's atexit hook if the caller never does
         if dequantize:
             self.set_dequantize(True)
+        if raw_magref:
+            self.set_raw_magref(True)
 
     def close(self):
         if getattr(self, "h", None):
@@ -355,6 +357,18 @@ class FramePlan:
         coefficient by 1.0 / Quality first (dwt.Dequantize, fused into the inverse kernels' loads), so that a lossy frame decodes
         to the picture; off (the default) is tcd.ApplyInverseDWT as the reference wrote it (j2k_plan_set_dequantize)."""
         self.ctx.check(self.ctx.L.j2k_plan_set_dequantize(self.h, int(bool(on))))
+
+    def set_raw_magref(self, on=True):
+        """MQ plans with blocks of at most 64 x 64: the raw-MagRef coding style for every later block coder call of the plan -- block bodies are
+        H | MQ | RAW, the magnitude-refinement decisions bypass the MQ coder (tests/raw_magref_cases.py is the definition).  encode_blocks,
+        encode_stream, decode_blocks (skip_planes=), encode_frame_pixels / decode_frame_pixels (reduce=, skip_planes=, area=), encode_frame_image,
+        the host forms and captures of the frame calls follow it; planes=True, byte budgets, layers, quality targets, roi=, truncated=, floors=
+        and layers= raise J2K_ERR_UNSUPPORTED on such a plan.  Decode a stream with the setting it was coded with (j2k_plan_set_raw_magref)."""
+        self.ctx.check(self.ctx.L.j2k_plan_set_raw_magref(self.h, int(bool(on))))
+
+    @property
+    def raw_magref(self):
+        return bool(self.ctx.L.j2k_plan_get_raw_magref(self.h))
 
     @_stage
     def forward_pixels(self, fmt, pix, coeff=None):

@@ -312,6 +312,24 @@ int j2k_plan_set_decode_coded_rows_only(j2k_plan *plan, int on);
  * fused into the load of the inverse kernels.  Applies to every later call on the plan, and to what is captured into a
  * graph from then on; a graph captured earlier keeps the setting it was captured with. */
 int j2k_plan_set_dequantize(j2k_plan *plan, int on);
+/* The raw-MagRef coding style (this library's; the reference declares its parts -- RawEncoder / RawDecoder mqc.go:516-600, CodeBlockBypass
+ * markers.go:140 -- and never connects them).  MQ plans whose code-blocks are all at most 64 x 64; J2K_ERR_UNSUPPORTED on an HT plan and on a
+ * plan with a larger block; J2K_ERR_INVALID_ARG while the context captures a graph.  Default off.  On: every later block coder call of the plan
+ * (j2k_plan_encode_blocks / _encode_stream / _decode_blocks / _decode_blocks_coarse, the frame calls j2k_plan_encode_frame_pixels / _image,
+ * j2k_plan_decode_frame_pixels / _reduced / _coarse / _area, their host forms and captures of them) codes and reads block bodies H | MQ | RAW:
+ * the decisions, their order, numBPS and every context that is not a magnitude refinement are the plain codec's; the decisions of contexts
+ * Mag0 / Mag1 / Mag2 bypass the MQ coder and are written, in coding order across all planes, as one RawEncoder string RAW (MSB first, a 7-bit
+ * byte after every 0xFF, Flush as written); MQ is the codeword of the remaining symbols; H = len(MQ) in three 7-bit groups, most significant
+ * first.  A block without bit planes has an empty body.  Nothing above the body changes (packet headers, lens, numbps, SOP / EPH, tile-parts).
+ * The decoder is a total function of (bytes, numbps): a body shorter than 3 bytes has empty MQ and RAW, len(MQ) is clamped to the body, past the
+ * end of MQ the MQ decoder reads what the reference's reads, past the end of RAW and behind an 0xFF followed by a byte above 0x8F the raw reader
+ * returns ones (RawDecoder.DecodeBit).  A two-stream body has no prefix property: on a plan in the style the calls that cut bodies at bit planes
+ * or read cut bodies return J2K_ERR_UNSUPPORTED before anything is launched -- j2k_plan_encode_blocks_planes(_roi), every _rate / _layers / _roi /
+ * _quality / _kept encode and allocation call, and the decode calls with per-block floors, truncated streams or layers.  A stream is decoded by a
+ * plan with the setting it was coded with; nothing in the stream says which. */
+int j2k_plan_set_raw_magref(j2k_plan *plan, int on);
+/* 1 if the plan codes in the raw-MagRef style, else 0 (j2k_plan_info keeps its layout) */
+int j2k_plan_get_raw_magref(const j2k_plan *plan);
 /* job j's offset (in int32 elements) into d_decoded */
 int j2k_plan_get_decoded_offsets(const j2k_plan *plan, uint64_t *offs, size_t cap);
 /* HT plans only (J2K_ERR_UNSUPPORTED otherwise): leaders[j] = the job whose decode may serve job j as well under the context option ht_dec_dedup
