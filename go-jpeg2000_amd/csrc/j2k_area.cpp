@@ -1,13 +1,11 @@
 // j2k_area.cpp -- region decode behind the C ABI (include/j2kgfx.h: j2k_plan_area_shape, j2k_plan_area_blocks, j2k_plan_decode_frame_pixels_area,
 // j2k_decode_pixels_host_area): the pixels of a rectangle, decoding only the code-blocks it needs.  The need set is computed on the device from the
-// rectangle (area.hip; definition: tests/area_cases.py, rule: DESIGN.md 7); everything else is the frame decoder's own stages: the packet parse of
-// the call without `area`, the MQ block decoders on tables in which the other blocks are empty, the whole-frame inverse into a staging frame of the
-// plan, and a pack of the window (pixels.hip).
+// rectangle (area.hip; definition: tests/area_cases.py, rule: DESIGN.md 7); everything else is the frame decoder's own stages (plan_decode_frame,
+// j2k_frame.cpp, with DecodeRequest.area): the packet parse of the call without `area`, the MQ block decoders on tables in which the other blocks
+// are empty, the whole-frame inverse into a staging frame of the plan, and a pack of the window (pixels.hip).  Here: the refusals and the tables.
 #include "j2k_host.h"
 
 using namespace j2k;
-
-struct AreaOut { int x0, y0, w, h; };      // the rectangle of the reduced frame the call returns
 
 // every refusal of an area call that its plan, `reduce` and rectangle decide (host only)
 static int area_check(const j2k_plan *P, const j2k_rect *area, int reduce, AreaOut &out, const char *who) {
@@ -59,7 +57,7 @@ int area_tables(j2k_plan *P, bool frame) {
     return r;
 }
 
-static int area_launch(j2k_plan *P, const j2k_rect *area, int reduce, uint8_t *d_need, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors) {
+int area_launch(j2k_plan *P, const j2k_rect *area, int reduce, uint8_t *d_need, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors) {
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, launch_area_blocks(ctx->stream, P->d_area_blocks, (int)P->blocks.size(), P->d_area_planes, area->x0, area->y0, area->x1, area->y1, reduce,
                                    P->spec.wavelet == W97 ? 2 : 1, d_need, d_lens, d_numbps, d_floors));
@@ -95,77 +93,20 @@ extern "C" int j2k_plan_decode_frame_pixels_area(j2k_plan *P, const uint8_t *d_c
     const size_t bpp = (size_t)(S.C == 1 ? 1 : 4) * (S.precision > 8 ? 2 : 1);
     if (stride < (size_t)o.w * bpp) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_decode_frame_pixels_area: stride smaller than a row of the rectangle");
     if (S.C != 1 && S.precision <= 8 && (((uintptr_t)d_pix | stride) & 3)) return fail(ctx, J2K_ERR_INVALID_ARG, "RGBA rows must be 4-byte aligned");
-    ReducedTab *R = nullptr;
-    if (reduce != 0 && (r = plan_reduced(P, reduce, &R)) != J2K_OK) return r;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    r = cl_prepare(P);
-    if (r == J2K_OK) r = cl_workspaces(P);
-    if (r == J2K_OK) r = area_tables(P, true);
-    if (r != J2K_OK) return r;
-
-    // 1. the packet parse of the call without `area`: block tables (and floors, where the stream's blocks may be cut) into the plan's workspaces
-    const size_t n = P->blocks.size(), nr = (n + 255) & ~size_t(255);
-    const uint8_t *d_data = d_cs;
-    uint8_t *d_floors = nullptr, *d_floors_r = nullptr;
-    if (layers > 0) {
-        if (!P->d_cl_dense || P->cl_dense_bytes < len + 64 || !P->d_cl_lfloors) {
-            if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the dense buffer grows with the stream -- run the call once on a stream at least as long before j2k_ctx_capture_begin");
-            if ((r = ensure_sized(ctx, &P->d_cl_dense, &P->cl_dense_bytes, len + 64)) != J2K_OK) return r;
-            if (!P->d_cl_lfloors) HIPCHK(ctx, hipMalloc((void **)&P->d_cl_lfloors, 2 * nr + 64));
-        }
-        d_floors = P->d_cl_lfloors; d_floors_r = P->d_cl_lfloors + nr;
-        d_data = (const uint8_t *)P->d_cl_dense;
-        r = j2k_plan_decode_tile_parts_layers(P, d_cs, len, d_tile_offs, sop, eph, layers, (uint8_t *)P->d_cl_dense, P->cl_dense_bytes, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps,
-                                              d_floors);
-    } else if (truncated) {
-        ClRate W{};
-        if ((r = cl_rate_workspace(P, W)) != J2K_OK) return r;
-        d_floors = W.floors; d_floors_r = W.floors_r;
-        r = j2k_plan_decode_tile_parts_floors(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, d_floors);
-    } else {
-        r = j2k_plan_decode_tile_parts(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps);
-    }
-    if (r != J2K_OK) return r;
-
-    // 2. the need set: the entries of every other block emptied
-    if ((r = area_launch(P, area, reduce, nullptr, P->d_cl_lens, P->d_cl_numbps, d_floors)) != J2K_OK) return r;
-
-    // 3. block decode and placement as plan_decode_frame_tables runs them (reduce > 0: the jobs of the resolutions it keeps)
-    if (reduce == 0) {
-        r = plan_decode_blocks_jobs(P, P->d_djobs, (int)n, d_data, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, P->d_cl_decoded, nullptr, skip_planes, d_floors);
-        if (r == J2K_OK) r = j2k_plan_place_blocks(P, P->d_cl_decoded, P->d_cl_coeff);
-    } else {
-        if (d_floors) HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, d_floors, R->d_offs, R->d_lens, d_floors_r));
-        HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, R->d_offs, R->d_lens, R->d_numbps));
-        r = plan_decode_blocks_jobs(P, R->d_djobs, R->njobs, d_data, R->d_offs, R->d_lens, R->d_numbps, P->d_cl_decoded, nullptr, skip_planes, d_floors ? d_floors_r : nullptr);
-        if (r == J2K_OK) HIPCHK(ctx, launch_place_blocks(ctx->stream, R->d_bjobs, R->d_djobs, R->njobs, R->max_block_h, P->d_cl_decoded, P->d_cl_coeff));
-    }
-    if (r != J2K_OK) return r;
-
-    // 4. the inverse transform of the whole (reduced) frame into the staging frame, then the window (guarded by the status word)
-    r = j2k_plan_inverse_reduced(P, P->d_cl_coeff, reduce, P->d_area_frame);
-    if (r != J2K_OK) return r;
-    const int Wr = (int)(((int64_t)S.W + ((1 << reduce) - 1)) >> reduce), Hr = (int)(((int64_t)S.H + ((1 << reduce) - 1)) >> reduce);
-    HIPCHK(ctx, launch_pack_pixels_window(ctx->stream, P->d_area_frame, S.C, S.precision, Wr, Hr, o.x0, o.y0, o.w, o.h, (uint8_t *)d_pix, stride, P->d_frame_status));
-    return J2K_OK;
+    DecodeRequest q;
+    q.layers = layers; q.truncated = truncated != 0; q.reduce = reduce; q.skip_planes = skip_planes; q.area = area;
+    return plan_decode_frame(P, d_cs, len, d_tile_offs, sop, eph, q, &o, d_pix, stride);
 }
 
 extern "C" int j2k_decode_pixels_host_area(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int layers, int truncated, int reduce, int skip_planes,
                                            const j2k_rect *area, void *pix, size_t stride) {
-    if (!P || !cs || !pix) return J2K_ERR_INVALID_ARG;
-    j2k_ctx *ctx = P->ctx;
-    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
+    const int c = host_call_check(P, cs, pix);
+    if (c != J2K_OK) return c;
     AreaOut o{};
-    int r = area_check(P, area, reduce, o, "j2k_decode_pixels_host_area");
+    const int r = area_check(P, area, reduce, o, "j2k_decode_pixels_host_area");
     if (r != J2K_OK) return r;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t pixbytes = (size_t)o.h * stride;
-    if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, pixbytes)) != J2K_OK) return r;
-    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, len + 64)) != J2K_OK) return r;
-    HIPCHK(ctx, hipMemcpyAsync(P->d_host_io, cs, len, hipMemcpyHostToDevice, ctx->stream));
-    r = j2k_plan_decode_frame_pixels_area(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, layers, truncated, reduce, skip_planes, area, P->d_host_pix, stride);
-    if (r != J2K_OK) return r;
-    if ((r = j2k_plan_frame_status(P)) != J2K_OK) return r;            // (synchronises; a refused stream wrote nothing: pix stays as it is)
-    HIPCHK(ctx, hipMemcpy(pix, P->d_host_pix, pixbytes, hipMemcpyDeviceToHost));
-    return J2K_OK;
+    // (the status is read before the copy back -- it synchronises; a refused stream wrote nothing: pix stays as it is)
+    return decode_host(P, cs, len, (size_t)o.h * stride, pix, true, [&](const uint8_t *d_cs, void *d_pix) {
+        return j2k_plan_decode_frame_pixels_area(P, d_cs, len, nullptr, sop, eph, layers, truncated, reduce, skip_planes, area, d_pix, stride);
+    });
 }

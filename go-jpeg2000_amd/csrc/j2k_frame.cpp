@@ -1,4 +1,6 @@
-// j2k_frame.cpp -- Tier-2 on device buffers and the closed-loop frame codec (packets, tile-parts, decode body) (C ABI of libj2kgfx.so, include/j2kgfx.h; shared declarations: j2k_host.h)
+// j2k_frame.cpp -- Tier-2 on device buffers and the closed-loop frame codec (C ABI of libj2kgfx.so, include/j2kgfx.h; shared declarations: j2k_host.h): the packet
+// and tile-part stage calls, the ONE frame encoder (plan_encode_frame_from_coeff: every encode form is an EncodeRequest) and the ONE frame decoder
+// (plan_decode_frame: every decode form is a DecodeRequest), and the device entry points of both -- each checks, fills its request and calls them
 #include "j2k_host.h"
 
 using namespace j2k;
@@ -111,7 +113,7 @@ int cl_prepare(j2k_plan *P) {
         for (int q = tp0[t]; q < tp0[t + 1]; q++) ptile[(size_t)q] = t;
     int r = upload(ctx, &P->d_tile_packet0, tp0);
     if (r == J2K_OK) r = upload(ctx, &P->d_t2_ptile, ptile);
-    auto alloc = [&](void **p, size_t bytes) { if (r == J2K_OK) { hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 64)); if (e != hipSuccess) r = fail_hip(ctx, e, "hipMalloc (frame codec)"); } };
+    auto alloc = [&](void **p, size_t bytes) { first_use_alloc(ctx, r, p, bytes, "hipMalloc (frame codec)"); };
     alloc((void **)&P->d_t2_cbs, n * sizeof(j2k_t2_dev_cb));
     alloc((void **)&P->d_t2_poffs, (np + 1) * 8);
     alloc(&P->d_t2_ws, ((j2k::t2_dev_workspace((long)np) + 15) & ~size_t(15)) + 64);
@@ -162,9 +164,6 @@ extern "C" int j2k_plan_encode_tile_parts(j2k_plan *P, const uint8_t *d_stream, 
     return encode_tile_parts_impl(P, d_stream, d_offs, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs);
 }
 
-// what every rate call needs of its plan (j2k_rate.cpp)
-int rate_check(j2k_plan *P, const char *who);
-
 // j2k_plan_encode_tile_parts with every block cut after its first d_kept[j] bit planes (j2k_plan_rate_allocate): its bytes are the prefix
 // d_rate[j * 32 + d_kept[j]] of what the block coder wrote, its passes the 3 p - 2 of those planes (none, and no bytes, for p = 0), ZeroBitPlanes
 // as before.  Compaction, bodies, tile-parts, SOP and EPH are unchanged; d_kept[j] = numBPS everywhere gives j2k_plan_encode_tile_parts' bytes.
@@ -181,8 +180,27 @@ extern "C" int j2k_plan_encode_tile_parts_kept(j2k_plan *P, const uint8_t *d_str
     return encode_tile_parts_impl(P, d_stream, d_offs, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, d_kept, d_rate);
 }
 
+// the tile-part chains and the packet read (t2dec.hip); d_floors (or null): also every block's floor (the _floors calls)
+static int decode_tile_parts_launch(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, uint64_t *d_offs, uint32_t *d_lens,
+                                    uint8_t *d_numbps, uint8_t *d_floors) {
+    j2k_ctx *ctx = P->ctx;
+    HIPCHK(ctx, j2k::launch_t2_tile_chains(ctx->stream, d_cs, (uint64_t)len, d_tile_offs, P->tile_count, P->tile_first, P->d_tile_packet0, P->d_t2_chains));
+    // (SOP + EPH streams: a tile's packets side by side, checked against the serial rule and redone by it where a guess was off -- t2dec.hip)
+    HIPCHK(ctx, j2k::launch_t2_decode_tiles(ctx->stream, P->d_t2_chains, P->tile_count, P->d_tile_packet0, P->d_t2_packets, P->t2_npackets, P->d_t2_cbs,
+                                            (uint64_t)P->blocks.size(), d_cs, (uint64_t)len, sop, eph, P->d_t2_body_base, P->d_frame_status, ctx->t2_parallel ? P->d_t2_par : nullptr,
+                                            P->spec.coder == J2K_CODER_HT ? 1 : 0, 31, d_offs, d_lens, d_numbps, d_floors));
+    return J2K_OK;
+}
 static int decode_tile_parts_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
-                                  uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors);
+                                  uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    if (!d_cs || !d_offs || !d_lens || !d_numbps) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int r = cl_prepare(P);
+    if (r != J2K_OK) return r;
+    return decode_tile_parts_launch(P, d_cs, len, d_tile_offs, sop, eph, d_offs, d_lens, d_numbps, d_floors);
+}
 extern "C" int j2k_plan_decode_tile_parts(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
                                           uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps) {
     return decode_tile_parts_impl(P, d_cs, len, d_tile_offs, sop, eph, d_offs, d_lens, d_numbps, nullptr);
@@ -197,22 +215,6 @@ extern "C" int j2k_plan_decode_tile_parts_floors(j2k_plan *P, const uint8_t *d_c
     if (P->spec.coder != J2K_CODER_MQ) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_decode_tile_parts_floors: per-block floors need the MQ coder");
     { const int rr = raw_magref_refuse(P, "j2k_plan_decode_tile_parts_floors"); if (rr != J2K_OK) return rr; }
     return decode_tile_parts_impl(P, d_cs, len, d_tile_offs, sop, eph, d_offs, d_lens, d_numbps, d_floors);
-}
-static int decode_tile_parts_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
-                                  uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors) {
-    if (!P) return J2K_ERR_INVALID_ARG;
-    j2k_ctx *ctx = P->ctx;
-    if (!d_cs || !d_offs || !d_lens || !d_numbps) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int r = cl_prepare(P);
-    if (r != J2K_OK) return r;
-    const long n = (long)P->blocks.size();
-    HIPCHK(ctx, j2k::launch_t2_tile_chains(ctx->stream, d_cs, (uint64_t)len, d_tile_offs, P->tile_count, P->tile_first, P->d_tile_packet0, P->d_t2_chains));
-    // (SOP + EPH streams: a tile's packets side by side, checked against the serial rule and redone by it where a guess was off -- t2dec.hip)
-    HIPCHK(ctx, j2k::launch_t2_decode_tiles(ctx->stream, P->d_t2_chains, P->tile_count, P->d_tile_packet0, P->d_t2_packets, P->t2_npackets, P->d_t2_cbs, (uint64_t)n, d_cs,
-                                            (uint64_t)len, sop, eph, P->d_t2_body_base, P->d_frame_status, ctx->t2_parallel ? P->d_t2_par : nullptr,
-                                            P->spec.coder == J2K_CODER_HT ? 1 : 0, 31, d_offs, d_lens, d_numbps, d_floors));
-    return J2K_OK;
 }
 
 extern "C" int j2k_plan_frame_parallel_tiles(j2k_plan *P, long *tiles) {
@@ -262,13 +264,13 @@ int cl_workspaces(j2k_plan *P) {
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the frame codec's workspaces are made at its first call");
     int r = J2K_OK;
     const size_t n = P->blocks.size();
-    auto alloc = [&](void **p, size_t bytes) { if (r == J2K_OK) { hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 64)); if (e != hipSuccess) r = fail_hip(ctx, e, "hipMalloc (frame codec)"); } };
+    auto alloc = [&](void **p, size_t bytes) { first_use_alloc(ctx, r, p, bytes, "hipMalloc (frame codec)"); };
     if (P->spec.coder != J2K_CODER_HT) alloc((void **)&P->d_cl_decoded, (size_t)P->decoded_elems * 4);     // (HT: decoded in place, below)
     alloc((void **)&P->d_cl_offs, (n + 1) * 8);
     alloc((void **)&P->d_cl_lens, n * 4 + 16);
     alloc((void **)&P->d_cl_numbps, n + 16);
     // HT plans: the decoder's coefficient planes, its own (the encoder's forward transform writes d_cl_coeff) and zeroed once --
-    // j2k_plan_decode_frame_pixels relies on it
+    // the frame decoder relies on it
     if (P->spec.coder == J2K_CODER_HT) {
         alloc((void **)&P->d_cl_coeff_dec, (size_t)P->coeff_elems * 4);
         if (r == J2K_OK) { hipError_t e = hipMemsetAsync(P->d_cl_coeff_dec, 0, std::max<size_t>((size_t)P->coeff_elems * 4, 64), ctx->stream); if (e != hipSuccess) r = fail_hip(ctx, e, "hipMemsetAsync"); }
@@ -277,118 +279,7 @@ int cl_workspaces(j2k_plan *P) {
     return r;
 }
 
-// coefficients -> tile-parts with one copy of every block's bytes (the closed-loop one-call forms; d_lens / d_numbps: the caller's tables, filled)
-int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int sop, int eph, uint8_t *d_out, size_t cap,
-                                 uint64_t *d_tile_offs) {
-    int r = cl_prepare(P);
-    // block coding into the plan's slots, then every block's bytes ONCE: from its slot to its place in its packet in its tile-part (the stage
-    // calls j2k_plan_encode_stream + j2k_plan_encode_tile_parts copy them twice: dense stream, tile-parts)
-    if (r == J2K_OK) r = plan_encode_private_slots(P, d_coeff, d_lens, d_numbps);
-    if (r == J2K_OK) r = encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs);
-    return r;
-}
-
-extern "C" int j2k_plan_encode_frame_pixels(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, uint8_t *d_out, size_t cap,
-                                            uint64_t *d_tile_offs) {
-    if (!P) return J2K_ERR_INVALID_ARG;
-    if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
-    int r = cl_prepare(P);
-    if (r == J2K_OK) r = cl_workspaces(P);
-    if (r == J2K_OK) r = j2k_plan_forward_pixels(P, format, d_pix, stride, P->d_cl_coeff);
-    if (r == J2K_OK) r = plan_encode_frame_from_coeff(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, sop, eph, d_out, cap, d_tile_offs);
-    return r;
-}
-
-// the same chain from an image.YCbCr / CMYK / Paletted (j2k_image.cpp): a palette index >= npal is the frame status's J2K_ERR_GO_PANIC
-extern "C" int j2k_plan_encode_frame_image(j2k_plan *P, const j2k_image *d_img, int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
-    if (!P || !d_img) return J2K_ERR_INVALID_ARG;
-    if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
-    int r = cl_prepare(P);
-    if (r == J2K_OK) r = cl_workspaces(P);
-    if (r == J2K_OK) r = plan_forward_image_impl(P, d_img, P->d_cl_coeff, P->d_frame_status);
-    if (r == J2K_OK) r = plan_encode_frame_from_coeff(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, sop, eph, d_out, cap, d_tile_offs);
-    return r;
-}
-
-static int decode_frame_pixels_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int skip_planes, void *d_pix,
-                                    size_t stride);
-static int decode_frame_pixels_reduced_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
-                                            int skip_planes, void *d_pix, size_t stride);
-extern "C" int j2k_plan_decode_frame_pixels(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, void *d_pix,
-                                            size_t stride) {
-    return decode_frame_pixels_impl(P, d_cs, len, d_tile_offs, sop, eph, 0, d_pix, stride);
-}
-// skip_planes: the quality floor of j2k_plan_decode_frame_pixels_coarse (0: the full decode; > 0: MQ plans only, checked by the caller)
-static int decode_frame_pixels_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int skip_planes, void *d_pix,
-                                    size_t stride) {
-    if (!P) return J2K_ERR_INVALID_ARG;
-    int r = cl_prepare(P);
-    if (r == J2K_OK) r = cl_workspaces(P);
-    if (r == J2K_OK) r = j2k_plan_decode_tile_parts(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps);
-    if (r != J2K_OK) return r;
-    if (P->spec.coder == J2K_CODER_HT) {
-        // The reference's HT decoder writes one row in four and the other rows of a fresh decoder's block are zero.  The
-        // coefficient planes here are the plan's own, zeroed when they were made, and nothing else writes them (the inverse transform reads
-        // its input only; the encoder's forward transform has planes of its own): the block decoder writes the coded rows straight into each
-        // block's window (closed-loop windows partition the plane) -- a quarter of the stores, no dense blocks, no placement copy.
-        j2k_ctx *ctx = P->ctx;
-        const int n = (int)P->blocks.size();
-        r = stage_reserve(ctx, 2, ht_decode_scratch_words(n) * 4 + 256);
-        if (r != J2K_OK) return r;
-        HIPCHK(ctx, launch_ht_decode(ctx->stream, P->d_djobs, n, d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_coeff_dec, (uint32_t *)ctx->stage[2], 1, P->d_djobs_placed, ctx->ht_dec_lean, ctx->ht_dec_front));
-        return plan_inverse_pixels_impl(P, P->d_cl_coeff_dec, d_pix, stride, P->d_frame_status);
-    } else {
-        r = j2k_plan_decode_blocks_coarse(P, d_cs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, skip_planes, P->d_cl_decoded);
-        if (r == J2K_OK) r = j2k_plan_place_blocks(P, P->d_cl_decoded, P->d_cl_coeff);
-    }
-    // (the status word as the guard of the launches that write d_pix: a stream that was refused leaves the caller's frame alone)
-    if (r == J2K_OK) r = plan_inverse_pixels_impl(P, P->d_cl_coeff, d_pix, stride, P->d_frame_status);
-    return r;
-}
-
-// j2k_plan_decode_frame_pixels to a reduced resolution (Mallat plans).  Every packet is parsed as before -- a tile's packets are in component ->
-// resolution order, the later ones cannot be found otherwise -- but the block decoder and the placement run the jobs of the resolutions
-// <= num_resolutions - 1 - reduce only (with the MQ coder that is where the decode time is), and the inverse transform stops at level `reduce`.
-extern "C" int j2k_plan_decode_frame_pixels_reduced(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
-                                                    void *d_pix, size_t stride) {
-    return decode_frame_pixels_reduced_impl(P, d_cs, len, d_tile_offs, sop, eph, reduce, 0, d_pix, stride);
-}
-static int decode_frame_pixels_reduced_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
-                                            int skip_planes, void *d_pix, size_t stride) {
-    if (!P) return J2K_ERR_INVALID_ARG;
-    j2k_ctx *ctx = P->ctx;
-    ReducedTab *R = nullptr;
-    int r = plan_reduced(P, reduce, &R);
-    if (r != J2K_OK) return r;
-    if (reduce == 0) return decode_frame_pixels_impl(P, d_cs, len, d_tile_offs, sop, eph, skip_planes, d_pix, stride);
-    if (!d_pix) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
-    r = cl_prepare(P);
-    if (r == J2K_OK) r = cl_workspaces(P);
-    if (r == J2K_OK) r = j2k_plan_decode_tile_parts(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps);
-    if (r != J2K_OK) return r;
-    HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, R->d_offs, R->d_lens, R->d_numbps));
-    const bool ht = P->spec.coder == J2K_CODER_HT;
-    int32_t *coeff = ht ? P->d_cl_coeff_dec : P->d_cl_coeff;
-    // (HT: straight into the windows of the plan's zeroed planes, coded rows only, as the full decode; the windows left out keep what an earlier
-    //  full decode wrote -- no level >= reduce reads them)
-    r = plan_decode_blocks_jobs(P, R->d_djobs, R->njobs, d_cs, R->d_offs, R->d_lens, R->d_numbps, ht ? coeff : P->d_cl_decoded, ht ? R->d_placed : nullptr, skip_planes);
-    if (r == J2K_OK && !ht) HIPCHK(ctx, launch_place_blocks(ctx->stream, R->d_bjobs, R->d_djobs, R->njobs, R->max_block_h, P->d_cl_decoded, coeff));
-    if (r == J2K_OK) r = plan_inverse_pixels_reduced_impl(P, coeff, reduce, d_pix, stride, P->d_frame_status);
-    return r;
-}
-
-// Both scalability axes in one call: resolution (`reduce`, the rules of j2k_plan_decode_frame_pixels_reduced; 0 on any closed-loop plan) and
-// quality (`skip_planes`: every MQ block decoder stops after that bit plane).  A refusal comes before the first launch: d_pix is left alone.
-extern "C" int j2k_plan_decode_frame_pixels_coarse(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
-                                                   int skip_planes, void *d_pix, size_t stride) {
-    if (!P) return J2K_ERR_INVALID_ARG;
-    const int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_plan_decode_frame_pixels_coarse");
-    if (r != J2K_OK) return r;
-    if (reduce == 0) return decode_frame_pixels_impl(P, d_cs, len, d_tile_offs, sop, eph, skip_planes, d_pix, stride);
-    return decode_frame_pixels_reduced_impl(P, d_cs, len, d_tile_offs, sop, eph, reduce, skip_planes, d_pix, stride);
-}
-
-// ---- rate-limited frames: j2k_plan_encode_frame_pixels with a budget of code-block body bytes, and the decode of what it writes -------------
+// the rate tables, the cuts and the floors of a frame, one allocation made at the first rate-limited call
 int cl_rate_workspace(j2k_plan *P, ClRate &W) {
     j2k_ctx *ctx = P->ctx;
     const size_t n = P->blocks.size(), nr = (n + 255) & ~size_t(255);
@@ -406,61 +297,221 @@ int cl_rate_workspace(j2k_plan *P, ClRate &W) {
     return J2K_OK;
 }
 
-// coefficients -> rate-limited tile-parts: block coding into the plan's slots with the tables, the allocation, then every block's kept prefix once
-// from its slot into its packet (d_lens / d_numbps: the caller's tables, filled with the UNCUT lengths and plane counts)
-int plan_encode_frame_from_coeff_rate(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int64_t max_body_bytes, int sop, int eph,
-                                      uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, const j2k_rect *roi, int roi_gain) {
+// ---- the one frame encoder --------------------------------------------------------------------------------------------------------------------
+// Block coding into the plan's slots, then every block's bytes ONCE: from its slot to its place in its packet in its tile-part (the stage calls
+// j2k_plan_encode_stream + j2k_plan_encode_tile_parts copy them twice: dense stream, tile-parts).  A request that cuts: the block coder also fills
+// the rate tables, the distortion launch (with the rectangle, if there is one) the distortion tables, ONE allocation launch chooses every block's
+// planes -- the only launch that differs between the forms -- and the packets hold the kept prefixes, or per layer the increments.
+int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, const EncodeRequest &q, int sop, int eph, uint8_t *d_out,
+                                 size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs) {
     j2k_ctx *ctx = P->ctx;
-    int r = rate_check(P, "rate-limited frame encode");
-    if (r != J2K_OK) return r;
-    if (max_body_bytes < 0) return fail(ctx, J2K_ERR_INVALID_ARG, "rate-limited frame encode: a negative budget");
+    int r;
+    if (q.kind == EncodeRequest::NONE) {
+        r = cl_prepare(P);
+        if (r == J2K_OK) r = plan_encode_private_slots(P, d_coeff, d_lens, d_numbps);
+        if (r == J2K_OK) r = encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs);
+        return r;
+    }
+    if ((r = rate_check(P, "rate-limited frame encode")) != J2K_OK) return r;     // (j2k_encode_pixels_host_rate has not asked)
     ClRate W{};
+    LayerTab *T = nullptr;
     r = cl_prepare(P);
     if (r == J2K_OK) r = cl_rate_workspace(P, W);
-    if (r == J2K_OK && !P->d_slots) {
+    if (r == J2K_OK && q.layered) r = layer_tab(P, q.nlayers, &T);
+    if (r == J2K_OK && (!P->d_slots || (T && !T->d_kept))) {
         if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: run the same calls once before j2k_ctx_capture_begin");
-        HIPCHK(ctx, hipMalloc(&P->d_slots, (size_t)P->bytes_cap + 64));
+        if (!P->d_slots) HIPCHK(ctx, hipMalloc(&P->d_slots, (size_t)P->bytes_cap + 64));
+        if (T && !T->d_kept) HIPCHK(ctx, hipMalloc((void **)&T->d_kept, std::max<size_t>(P->blocks.size() * (size_t)q.nlayers, 64)));
     }
-    if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, roi, roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
-    if (r == J2K_OK) r = j2k_plan_rate_allocate(P, W.rate, W.dist, d_numbps, max_body_bytes, W.kept, W.chosen);
-    if (r == J2K_OK) r = encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, W.kept, W.rate);
-    return r;
+    if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, q.roi, q.roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
+    if (r == J2K_OK) r = rate_upload_weights(P);
+    if (r != J2K_OK) return r;
+    const int n = (int)P->blocks.size();
+    uint8_t *d_kept = T ? T->d_kept : W.kept;
+    if (q.kind == EncodeRequest::DISTORTION)
+        HIPCHK(ctx, launch_rate_allocate_quality(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.targets, q.nlayers, P->d_rate_ws, d_kept, W.chosen,
+                                                 q.d_achieved ? q.d_achieved : W.achieved));
+    else if (q.layered)
+        HIPCHK(ctx, launch_rate_allocate_layers(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.budgets, q.nlayers, P->d_rate_ws, d_kept, W.chosen));      // (W.chosen: 32 words, one per layer)
+    else
+        HIPCHK(ctx, launch_rate_allocate(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.budgets[0], P->d_rate_ws, d_kept, W.chosen));
+    if (T) return encode_tile_parts_layers_launch(P, *T, q.nlayers, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, d_kept, W.rate, sop, eph, d_out, cap, d_tile_offs, d_layer_offs);
+    return encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, d_kept, W.rate);
 }
 
-// ... with the allocation's dual in its place (j2k_plan_encode_frame_pixels_quality with one target and no layer ends): every other launch is the same
-int plan_encode_frame_from_coeff_quality(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, double target, int sop, int eph, uint8_t *d_out,
-                                         size_t cap, uint64_t *d_tile_offs, const j2k_rect *roi, int roi_gain, double *d_achieved) {
-    j2k_ctx *ctx = P->ctx;
-    ClRate W{};
+int plan_encode_frame_cl(j2k_plan *P, const EncodeRequest &q, const std::function<int(int32_t *)> &forward, int sop, int eph, uint8_t *d_out, size_t cap,
+                         uint64_t *d_tile_offs, uint64_t *d_layer_offs) {
     int r = cl_prepare(P);
-    if (r == J2K_OK) r = cl_rate_workspace(P, W);
-    if (r == J2K_OK && !P->d_slots) {
-        if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: run the same calls once before j2k_ctx_capture_begin");
-        HIPCHK(ctx, hipMalloc(&P->d_slots, (size_t)P->bytes_cap + 64));
-    }
-    if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, roi, roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
-    if (r == J2K_OK) r = j2k_plan_rate_allocate_quality(P, W.rate, W.dist, d_numbps, &target, 1, W.kept, W.chosen, d_achieved ? d_achieved : W.achieved);
-    if (r == J2K_OK) r = encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, W.kept, W.rate);
+    if (r == J2K_OK) r = cl_workspaces(P);
+    if (r == J2K_OK && q.roi) r = area_tables(P, false);
+    if (r == J2K_OK) r = forward(P->d_cl_coeff);
+    if (r == J2K_OK) r = plan_encode_frame_from_coeff(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, q, sop, eph, d_out, cap, d_tile_offs, d_layer_offs);
     return r;
 }
 
-// j2k_plan_encode_frame_pixels with at most max_body_bytes of code-block bodies (packet and tile-part headers come on top: the last entry of
-// d_tile_offs says what the frame took).  A budget that cuts nothing gives j2k_plan_encode_frame_pixels' bytes.
+// the device forms of the pixel encode: their own refusals (before the first launch), their request, the one encoder
+static int encode_frame_pixels(j2k_plan *P, int format, const void *d_pix, size_t stride, const EncodeRequest &q, int sop, int eph, uint8_t *d_out, size_t cap,
+                               uint64_t *d_tile_offs, uint64_t *d_layer_offs) {
+    return plan_encode_frame_cl(P, q, [&](int32_t *d_coeff) { return j2k_plan_forward_pixels(P, format, d_pix, stride, d_coeff); }, sop, eph, d_out, cap, d_tile_offs, d_layer_offs);
+}
+extern "C" int j2k_plan_encode_frame_pixels(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, uint8_t *d_out, size_t cap,
+                                            uint64_t *d_tile_offs) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    return encode_frame_pixels(P, format, d_pix, stride, EncodeRequest(), sop, eph, d_out, cap, d_tile_offs, nullptr);
+}
+// the same chain from an image.YCbCr / CMYK / Paletted (j2k_image.cpp): a palette index >= npal is the frame status's J2K_ERR_GO_PANIC
+extern "C" int j2k_plan_encode_frame_image(j2k_plan *P, const j2k_image *d_img, int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+    if (!P || !d_img) return J2K_ERR_INVALID_ARG;
+    if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    return plan_encode_frame_cl(P, EncodeRequest(), [&](int32_t *d_coeff) { return plan_forward_image_impl(P, d_img, d_coeff, P->d_frame_status); }, sop, eph, d_out, cap,
+                                d_tile_offs, nullptr);
+}
+// ... with at most max_body_bytes of code-block bodies (packet and tile-part headers come on top: the last entry of d_tile_offs says what the
+// frame took).  A budget that cuts nothing gives j2k_plan_encode_frame_pixels' bytes.
 extern "C" int j2k_plan_encode_frame_pixels_rate(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, int64_t max_body_bytes,
                                                  uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
     if (!P) return J2K_ERR_INVALID_ARG;
-    j2k_ctx *ctx = P->ctx;
-    if (!d_out || !d_tile_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
-    int r = rate_check(P, "j2k_plan_encode_frame_pixels_rate");
+    if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    EncodeRequest q;
+    const int r = encode_request(P, "j2k_plan_encode_frame_pixels_rate", &max_body_bytes, nullptr, 1, false, false, nullptr, 1, nullptr, q);
     if (r != J2K_OK) return r;
-    if (max_body_bytes < 0) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_encode_frame_pixels_rate: a negative budget");
-    r = cl_prepare(P);
-    if (r == J2K_OK) r = cl_workspaces(P);
-    if (r == J2K_OK) r = j2k_plan_forward_pixels(P, format, d_pix, stride, P->d_cl_coeff);
-    if (r == J2K_OK) r = plan_encode_frame_from_coeff_rate(P, P->d_cl_coeff, P->d_cl_lens, P->d_cl_numbps, max_body_bytes, sop, eph, d_out, cap, d_tile_offs);
-    return r;
+    return encode_frame_pixels(P, format, d_pix, stride, q, sop, eph, d_out, cap, d_tile_offs, nullptr);
+}
+extern "C" int j2k_plan_encode_frame_pixels_layers(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
+                                                   uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    if (!d_out || !d_tile_offs || !d_layer_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    EncodeRequest q;
+    const int r = encode_request(P, "j2k_plan_encode_frame_pixels_layers", layer_bytes, nullptr, nlayers, true, false, nullptr, 1, nullptr, q);
+    if (r != J2K_OK) return r;
+    return encode_frame_pixels(P, format, d_pix, stride, q, sop, eph, d_out, cap, d_tile_offs, d_layer_offs);
+}
+// Region-of-interest encode, one call for both budget forms: nlayers = 1 with d_layer_offs == NULL is j2k_plan_encode_frame_pixels_rate with
+// max_body_bytes = layer_bytes[0], anything else j2k_plan_encode_frame_pixels_layers; the only new step is the distortion launch, which takes the
+// rectangle and the gain (rate.hip).
+extern "C" int j2k_plan_encode_frame_pixels_roi(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
+                                                const j2k_rect *roi, int roi_gain, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    EncodeRequest q;
+    const int r = encode_request(P, "j2k_plan_encode_frame_pixels_roi", layer_bytes, nullptr, nlayers, d_layer_offs != nullptr, true, roi, roi_gain, nullptr, q);
+    if (r != J2K_OK) return r;
+    return encode_frame_pixels(P, format, d_pix, stride, q, sop, eph, d_out, cap, d_tile_offs, d_layer_offs);
+}
+// Quality-targeted encode, one call for both forms as the _roi call: distortion targets in the place of the budgets, roi nullable
+extern "C" int j2k_plan_encode_frame_pixels_quality(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, const double *targets, int nlayers,
+                                                    const j2k_rect *roi, int roi_gain, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs,
+                                                    double *d_achieved) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    EncodeRequest q;
+    const int r = encode_request(P, "j2k_plan_encode_frame_pixels_quality", nullptr, targets, nlayers, d_layer_offs != nullptr, roi != nullptr, roi, roi_gain, d_achieved, q);
+    if (r != J2K_OK) return r;
+    return encode_frame_pixels(P, format, d_pix, stride, q, sop, eph, d_out, cap, d_tile_offs, d_layer_offs);
 }
 
+// ---- the one frame decoder --------------------------------------------------------------------------------------------------------------------
+// (a) the packet parse into the plan's block tables: plain, with every block's floor (a kept-prefix stream), or the LAYERED read, which also
+// gathers the blocks' segments into the plan's dense buffer -- the block decoder then reads that in the place of the codestream.  (b) with a
+// rectangle: the entries of the blocks it does not need emptied.  (c) block decode and placement: the plan's jobs, or (reduce > 0) the subset of
+// the resolutions it keeps -- every packet was parsed, a tile's later ones cannot be found otherwise -- down to max(skip_planes, floor).  (d) the
+// inverse transform to pixels, stopped at level `reduce`; with a rectangle into the plan's staging frame, whose window is packed.  The status
+// word guards the launches that write d_pix: a stream that was refused leaves the caller's frame alone.
+int plan_decode_frame(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, const DecodeRequest &q, const AreaOut *out, void *d_pix,
+                      size_t stride) {
+    j2k_ctx *ctx = P->ctx;
+    const PlanSpec &S = P->spec;
+    ReducedTab *R = nullptr;
+    int r;
+    if (q.reduce != 0 && (r = plan_reduced(P, q.reduce, &R)) != J2K_OK) return r;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LayerTab *T = nullptr;
+    r = cl_prepare(P);
+    if (r == J2K_OK) r = cl_workspaces(P);
+    if (r == J2K_OK && q.area) r = area_tables(P, true);
+    if (r == J2K_OK && q.layers > 0) r = layer_tab(P, q.layers, &T);
+    if (r != J2K_OK) return r;
+    if (!d_cs || !d_pix) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    // (a)
+    const size_t n = P->blocks.size(), nr = (n + 255) & ~size_t(255);
+    const uint8_t *d_data = d_cs;
+    uint8_t *d_floors = nullptr, *d_floors_r = nullptr;
+    if (T) {
+        if (!P->d_cl_dense || P->cl_dense_bytes < len + 64 || !P->d_cl_lfloors) {
+            if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the dense buffer grows with the stream -- run the call once on a stream at least as long before j2k_ctx_capture_begin");
+            if ((r = ensure_sized(ctx, &P->d_cl_dense, &P->cl_dense_bytes, len + 64)) != J2K_OK) return r;
+            if (!P->d_cl_lfloors) HIPCHK(ctx, hipMalloc((void **)&P->d_cl_lfloors, 2 * nr + 64));
+        }
+        d_floors = P->d_cl_lfloors; d_floors_r = P->d_cl_lfloors + nr;
+        d_data = (const uint8_t *)P->d_cl_dense;
+        r = decode_tile_parts_layers_launch(P, *T, q.layers, d_cs, len, d_tile_offs, sop, eph, (uint8_t *)P->d_cl_dense, P->cl_dense_bytes, P->d_cl_offs, P->d_cl_lens,
+                                            P->d_cl_numbps, d_floors);
+    } else {
+        if (q.truncated) {
+            ClRate W{};
+            if ((r = cl_rate_workspace(P, W)) != J2K_OK) return r;
+            d_floors = W.floors; d_floors_r = W.floors_r;
+        }
+        r = decode_tile_parts_launch(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, d_floors);
+    }
+    if (r != J2K_OK) return r;
+    // (b)
+    if (q.area && (r = area_launch(P, q.area, q.reduce, nullptr, P->d_cl_lens, P->d_cl_numbps, d_floors)) != J2K_OK) return r;
+    // (c)  HT plans: straight into the windows of the decoder's own zeroed planes, coded rows only (the reference's HT decoder writes one row in four,
+    // SURVEY fact 3; closed-loop windows partition the plane, and nothing else writes those planes): a quarter of the stores, no placement copy.
+    // The windows a reduced decode leaves out keep what an earlier full decode wrote -- no level >= reduce reads them.
+    const bool ht = S.coder == J2K_CODER_HT;
+    int32_t *coeff = ht ? P->d_cl_coeff_dec : P->d_cl_coeff;
+    const BlockJob *bjobs = P->d_bjobs, *djobs = P->d_djobs, *placed = P->d_djobs_placed;
+    const uint64_t *offs = P->d_cl_offs;
+    const uint32_t *lens = P->d_cl_lens;
+    const uint8_t *numbps = P->d_cl_numbps, *floors = d_floors;
+    int njobs = (int)n, max_h = P->max_block_h;
+    if (R) {
+        // the subset's tables, and (the same kernel, the floors in the place of the plane counts) its floors
+        if (d_floors) HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, d_floors, R->d_offs, R->d_lens, d_floors_r));
+        HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, R->d_offs, R->d_lens, R->d_numbps));
+        bjobs = R->d_bjobs; djobs = R->d_djobs; placed = R->d_placed; njobs = R->njobs; max_h = R->max_block_h;
+        offs = R->d_offs; lens = R->d_lens; numbps = R->d_numbps; floors = d_floors ? d_floors_r : nullptr;
+    }
+    r = plan_decode_blocks_jobs(P, djobs, njobs, d_data, offs, lens, numbps, ht ? coeff : P->d_cl_decoded, ht ? placed : nullptr, q.skip_planes, floors);
+    if (r != J2K_OK) return r;
+    if (!ht) HIPCHK(ctx, launch_place_blocks(ctx->stream, bjobs, djobs, njobs, max_h, P->d_cl_decoded, coeff));
+    // (d)
+    if (!q.area) return R ? plan_inverse_pixels_reduced_impl(P, coeff, q.reduce, d_pix, stride, P->d_frame_status) : plan_inverse_pixels_impl(P, coeff, d_pix, stride, P->d_frame_status);
+    if ((r = j2k_plan_inverse_reduced(P, coeff, q.reduce, P->d_area_frame)) != J2K_OK) return r;
+    const int Wr = (int)reduced_rows(S.W, q.reduce), Hr = (int)reduced_rows(S.H, q.reduce);
+    HIPCHK(ctx, launch_pack_pixels_window(ctx->stream, P->d_area_frame, S.C, S.precision, Wr, Hr, out->x0, out->y0, out->w, out->h, (uint8_t *)d_pix, stride, P->d_frame_status));
+    return J2K_OK;
+}
+
+// the device forms of the decode: their own refusals, in their own order (before the first launch), their request, the one decoder
+extern "C" int j2k_plan_decode_frame_pixels(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, void *d_pix,
+                                            size_t stride) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    return plan_decode_frame(P, d_cs, len, d_tile_offs, sop, eph, DecodeRequest(), nullptr, d_pix, stride);
+}
+// Both scalability axes in one call: resolution (`reduce`: Mallat plans; 0 on any closed-loop plan) and quality (`skip_planes`: every MQ block
+// decoder stops after that bit plane)
+extern "C" int j2k_plan_decode_frame_pixels_coarse(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
+                                                   int skip_planes, void *d_pix, size_t stride) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    const int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_plan_decode_frame_pixels_coarse");
+    if (r != J2K_OK) return r;
+    DecodeRequest q;
+    q.reduce = reduce; q.skip_planes = skip_planes;
+    return plan_decode_frame(P, d_cs, len, d_tile_offs, sop, eph, q, nullptr, d_pix, stride);
+}
+// ... to a reduced resolution alone (reduce = 0 too asks for a Mallat plan)
+extern "C" int j2k_plan_decode_frame_pixels_reduced(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
+                                                    void *d_pix, size_t stride) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    ReducedTab *R = nullptr;
+    const int r = plan_reduced(P, reduce, &R);
+    if (r != J2K_OK) return r;
+    return j2k_plan_decode_frame_pixels_coarse(P, d_cs, len, d_tile_offs, sop, eph, reduce, 0, d_pix, stride);
+}
 // j2k_plan_decode_frame_pixels_coarse for streams whose blocks may be cut at bit planes: every block runs from its own top plane down to
 // max(skip_planes, its floor from the packet header).  An uncut stream decodes as with the _coarse call.
 extern "C" int j2k_plan_decode_frame_pixels_rate(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
@@ -472,36 +523,22 @@ extern "C" int j2k_plan_decode_frame_pixels_rate(j2k_plan *P, const uint8_t *d_c
     if (P->spec.coder != J2K_CODER_MQ) return fail(ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_decode_frame_pixels_rate: per-block floors need the MQ coder");
     if ((r = raw_magref_refuse(P, "j2k_plan_decode_frame_pixels_rate")) != J2K_OK) return r;
     if (!d_pix) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
-    ReducedTab *R = nullptr;
-    if (reduce != 0) { r = plan_reduced(P, reduce, &R); if (r != J2K_OK) return r; }
-    ClRate W{};
-    r = cl_prepare(P);
-    if (r == J2K_OK) r = cl_workspaces(P);
-    if (r == J2K_OK) r = cl_rate_workspace(P, W);
-    if (r == J2K_OK) r = decode_tile_parts_impl(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, W.floors);
-    if (r != J2K_OK) return r;
-    return plan_decode_frame_tables(P, d_cs, R, reduce, skip_planes, W.floors, W.floors_r, d_pix, stride);
+    DecodeRequest q;
+    q.truncated = true; q.reduce = reduce; q.skip_planes = skip_planes;
+    return plan_decode_frame(P, d_cs, len, d_tile_offs, sop, eph, q, nullptr, d_pix, stride);
 }
-
-// the block tables of a frame (the plan's d_cl_offs / d_cl_lens / d_cl_numbps, offsets into d_data) and every block's floor -> pixels: MQ block
-// decode down to max(skip_planes, floor), placement, inverse transform; reduce > 0 (R = its tables): the subset of the resolutions it needs
-int plan_decode_frame_tables(j2k_plan *P, const uint8_t *d_data, ReducedTab *R, int reduce, int skip_planes, const uint8_t *d_floors, uint8_t *d_floors_r, void *d_pix,
-                             size_t stride) {
+// the first `layers` layers of every tile-part of a layered stream
+extern "C" int j2k_plan_decode_frame_pixels_layers(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int layers, int reduce,
+                                                   int skip_planes, void *d_pix, size_t stride) {
+    if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
-    int r;
-    if (reduce == 0) {
-        r = plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_data, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, P->d_cl_decoded, nullptr, skip_planes, d_floors);
-        if (r == J2K_OK) r = j2k_plan_place_blocks(P, P->d_cl_decoded, P->d_cl_coeff);
-        if (r == J2K_OK) r = plan_inverse_pixels_impl(P, P->d_cl_coeff, d_pix, stride, P->d_frame_status);
-        return r;
-    }
-    // the subset's tables, and (the same kernel, the floors in the place of the plane counts) its floors
-    HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, d_floors, R->d_offs, R->d_lens, d_floors_r));
-    HIPCHK(ctx, launch_select_blocks(ctx->stream, R->d_ids, R->njobs, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, R->d_offs, R->d_lens, R->d_numbps));
-    r = plan_decode_blocks_jobs(P, R->d_djobs, R->njobs, d_data, R->d_offs, R->d_lens, R->d_numbps, P->d_cl_decoded, nullptr, skip_planes, d_floors_r);
-    if (r == J2K_OK) HIPCHK(ctx, launch_place_blocks(ctx->stream, R->d_bjobs, R->d_djobs, R->njobs, R->max_block_h, P->d_cl_decoded, P->d_cl_coeff));
-    if (r == J2K_OK) r = plan_inverse_pixels_reduced_impl(P, P->d_cl_coeff, reduce, d_pix, stride, P->d_frame_status);
-    return r;
+    int r = check_skip_planes(ctx, P->spec.coder, skip_planes, "j2k_plan_decode_frame_pixels_layers");
+    if (r == J2K_OK) r = layers_check(P, layers, "j2k_plan_decode_frame_pixels_layers");
+    if (r != J2K_OK) return r;
+    if (!d_cs || !d_pix) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    DecodeRequest q;
+    q.layers = layers; q.reduce = reduce; q.skip_planes = skip_planes;
+    return plan_decode_frame(P, d_cs, len, d_tile_offs, sop, eph, q, nullptr, d_pix, stride);
 }
 
 extern "C" int j2k_plan_get_decoded_offsets(const j2k_plan *P, uint64_t *offs, size_t cap) {

@@ -1,6 +1,7 @@
-// j2k_host.h -- what the host-side files of the C ABI share (j2k_ctx.cpp, j2k_planbuild.cpp, j2k_stages.cpp, j2k_frame.cpp,
-// j2k_hostcalls.cpp; round 4 had all of it in one 2 200-line j2k_abi.cpp): the kernels' launch wrappers, the status helpers, the
-// context's staging slots and the plan builder.  Host-side orchestration only: geometry -> device job tables, launches on the
+// j2k_host.h -- what the host-side files of the C ABI share (j2k_ctx.cpp, j2k_planbuild.cpp, j2k_stages.cpp, j2k_frame.cpp, j2k_rate.cpp,
+// j2k_layers.cpp, j2k_area.cpp, j2k_hostcalls.cpp; round 4 had all of it in one 2 200-line j2k_abi.cpp): the kernels' launch wrappers, the
+// status helpers, the context's staging slots, the plan builder, and the requests, the one encoder / decoder and the two host drivers of the
+// closed-loop frame codec.  Host-side orchestration only: geometry -> device job tables, launches on the
 // context's HIP stream, host <-> device staging.  All arithmetic lives in the .hip kernels; there is no CPU fallback.
 #pragma once
 #include <algorithm>
@@ -8,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <tuple>
 
@@ -145,13 +147,76 @@ void plan_t2_packets(const j2k_plan *P, int layer, std::vector<j2k_t2_dev_packet
 // include/j2kgfx.h: J2K_ERR_UNSUPPORTED on any other plan, J2K_ERR_INVALID_ARG for a `reduce` the geometry does not allow
 int plan_reduced(j2k_plan *P, int reduce, j2k::ReducedTab **out);
 void free_layer_tabs(j2k_plan *P);           // j2k_layers.cpp
+// a device buffer of a first-use table set: allocated if nothing failed before it (r carries the first failure; at least 64 bytes)
+static inline void first_use_alloc(j2k_ctx *ctx, int &r, void **p, size_t bytes, const char *what) {
+    if (r != J2K_OK) return;
+    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 64));
+    if (e != hipSuccess) r = fail_hip(ctx, e, what);
+}
 // the closed-loop frame codec's tables and workspaces, made at first use (j2k_frame.cpp)
 int cl_prepare(j2k_plan *P);
 int cl_workspaces(j2k_plan *P);
 struct ClRate { uint32_t *rate; uint64_t *dist; uint8_t *kept; uint64_t *chosen; uint8_t *floors, *floors_r; double *achieved; };   // chosen, achieved: 32 words, one per layer
 int cl_rate_workspace(j2k_plan *P, ClRate &W);
-int plan_decode_frame_tables(j2k_plan *P, const uint8_t *d_data, j2k::ReducedTab *R, int reduce, int skip_planes, const uint8_t *d_floors, uint8_t *d_floors_r,
-                             void *d_pix, size_t stride);
+int layer_tab(j2k_plan *P, int L, j2k::LayerTab **out);     // the tables of layer count L, made at its first use (j2k_layers.cpp)
+
+// ---- the closed-loop frame codec: one encoder, one decoder (j2k_frame.cpp) ----
+// How a frame's blocks are cut.  NONE: every block whole.  BYTES: the cumulative budgets[0 .. nlayers) of body bytes.  DISTORTION: the falling
+// targets[0 .. nlayers) of weighted distortion, d_achieved (device, or null) = what every layer's choice reached.  layered: the layer-major
+// stream with its layer ends (else nlayers = 1 and the kept-prefix stream of the _rate calls).  roi (or null): the rectangle whose footprint
+// counts roi_gain times in the distortion tables.
+struct EncodeRequest {
+    enum Kind { NONE, BYTES, DISTORTION } kind = NONE;
+    int nlayers = 1;
+    bool layered = false;
+    uint64_t budgets[J2K_MAX_LAYERS] = {};
+    double targets[J2K_MAX_LAYERS] = {};
+    const j2k_rect *roi = nullptr;
+    int roi_gain = 1;
+    double *d_achieved = nullptr;
+};
+// an entry point's arguments -> its request, or the refusal (through fail(), naming `who`), in this order: the plan (rate_check), the layer count,
+// the rectangle and gain (check_roi), the budgets or targets (targets != NULL: DISTORTION), more than one of them without the layered stream
+int encode_request(j2k_plan *P, const char *who, const int64_t *layer_bytes, const double *targets, int nlayers, bool layered, bool check_roi, const j2k_rect *roi,
+                   int roi_gain, double *d_achieved, EncodeRequest &q);
+int layers_check(j2k_plan *P, int nlayers, const char *who);     // what every layer call needs: the plan rate_check accepts, a layer count 1 ... 32 (j2k_layers.cpp)
+// coefficients -> tile-parts, THE stage order of every encode form: block coding into the plan's slots (with the rate / distortion tables unless
+// NONE), the allocation, the packets of the kept-prefix or of the layered stream (d_layer_offs: its layer ends).  d_lens / d_numbps: the caller's
+// tables, filled with the UNCUT lengths and plane counts.  The callers have checked the request.
+int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, const EncodeRequest &q, int sop, int eph, uint8_t *d_out,
+                                 size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs);
+// ... from whatever `forward` puts into the plan's closed-loop coefficient buffer (its argument), with that set's tables
+int plan_encode_frame_cl(j2k_plan *P, const EncodeRequest &q, const std::function<int(int32_t *)> &forward, int sop, int eph, uint8_t *d_out, size_t cap,
+                         uint64_t *d_tile_offs, uint64_t *d_layer_offs);
+// What a frame decode reads and how far: layers > 0: the first `layers` layers of a layered stream; truncated: a kept-prefix stream (per-block
+// floors); reduce: resolutions left out (Mallat plans); skip_planes: the uniform quality floor; area (or null): only that rectangle.
+struct DecodeRequest { int layers = 0; bool truncated = false; int reduce = 0, skip_planes = 0; const j2k_rect *area = nullptr; };
+struct AreaOut { int x0, y0, w, h; };      // the rectangle of the reduced frame an area call returns (j2k_area.cpp: area_check)
+// tile-parts -> pixels, THE stage order of every decode form: parse, need set, block decode + placement, inverse transform.  out: area != NULL.
+// The callers have checked the request; refuses a `reduce` the plan does not allow, null d_cs / d_pix, and first use while capturing.
+int plan_decode_frame(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, const DecodeRequest &q, const AreaOut *out, void *d_pix,
+                      size_t stride);
+int area_launch(j2k_plan *P, const j2k_rect *area, int reduce, uint8_t *d_need, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors);   // j2k_area.cpp
+int decode_tile_parts_layers_launch(j2k_plan *P, j2k::LayerTab &T, int layers, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                    uint8_t *d_dense, size_t dense_cap, uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors);   // j2k_layers.cpp
+int encode_tile_parts_layers_launch(j2k_plan *P, j2k::LayerTab &T, int L, const uint8_t *d_data, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,
+                                    const uint8_t *d_kept, const uint32_t *d_rate, int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs,
+                                    uint64_t *d_layer_offs);   // j2k_layers.cpp
+// ---- host memory in, host memory out (j2k_hostcalls.cpp) ----
+int host_call_check(j2k_plan *P, const void *in, const void *out);   // J2K_ERR_INVALID_ARG for a null one; the refusal of a synchronising call while the context captures
+int pix_format_bytes(int format);                                    // bytes per pixel of a J2K_PIX_* format, 0 for anything else
+// THE host encode driver: `forward` (host image -> device -> forward transform into the buffer it is given), the one encoder, offsets / lens /
+// numbps / achieved back, synchronise, fault and status, then the tile-parts at their exact length.  cl_set: the plan's closed-loop buffers
+// (the layered, roi and quality forms), else P->d_coeff / d_lens / d_numbps; bound: what d_host_io holds of tile-parts, and the device call's cap
+int encode_host(j2k_plan *P, const EncodeRequest &q, bool cl_set, size_t bound, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs,
+                uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, double *achieved, const std::function<int(int32_t *)> &forward);
+// ... for image.*.Pix in host memory: the format / stride refusal, the pixels' staging buffer, the H2D copy and j2k_plan_forward_pixels as `forward`
+int encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, const EncodeRequest &q, bool cl_set, size_t bound, int sop, int eph, uint8_t *out,
+                       size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, double *achieved);
+// THE host decode driver: H2D, `decode` (a device frame decode of d_host_io into d_host_pix), D2H of pixbytes, the frame status; status_first
+// (the area call): the status is read before the copy back, so that a refused stream leaves pix alone
+int decode_host(j2k_plan *P, const uint8_t *cs, size_t len, size_t pixbytes, void *pix, bool status_first, const std::function<int(const uint8_t *, void *)> &decode);
+static inline size_t reduced_rows(int H, int reduce) { return reduce > 0 ? (size_t)(((int64_t)H + (((int64_t)1 << reduce) - 1)) >> reduce) : (size_t)H; }
 int rate_check(j2k_plan *P, const char *who);    // what every rate call needs of its plan (j2k_rate.cpp)
 int raw_magref_refuse(const j2k_plan *P, const char *who);    // J2K_ERR_UNSUPPORTED on a plan in the raw-MagRef style (j2k_stages.cpp): the calls that cut bodies or read cut ones
 int rate_upload_weights(j2k_plan *P);            // the per-job weights and the allocation workspace on the device (j2k_rate.cpp)
@@ -175,14 +240,6 @@ struct PixIO { int stride = 0, single = 0, triple = 0; j2k::YccSrc ycc{}; };   /
 int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix = PixIO());
 int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate);
 int plan_encode_private_slots(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps);
-int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int sop, int eph, uint8_t *d_out, size_t cap,
-                                 uint64_t *d_tile_offs);
-int plan_encode_frame_from_coeff_rate(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, int64_t max_body_bytes, int sop, int eph,
-                                      uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, const j2k_rect *roi = nullptr, int roi_gain = 1);   // roi: checked by the caller
-// the same with the allocation swapped for its dual: the fewest bytes whose weighted distortion is at most `target` (the caller has checked
-// plan, target and roi); d_achieved (device, or null): that distortion
-int plan_encode_frame_from_coeff_quality(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps, double target, int sop, int eph, uint8_t *d_out,
-                                         size_t cap, uint64_t *d_tile_offs, const j2k_rect *roi, int roi_gain, double *d_achieved);
 // guard (device, or null): the launches that write d_frame write nothing if *guard != 0 -- the frame decoder's status word
 int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix = PixIO(), const int *guard = nullptr);
 int plan_inverse_pixels_impl(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride, const int *guard);

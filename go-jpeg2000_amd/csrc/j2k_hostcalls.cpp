@@ -1,4 +1,5 @@
-// j2k_hostcalls.cpp -- the host (unit) calls: one per reference function, caller-owned host buffers (C ABI of libj2kgfx.so, include/j2kgfx.h; shared declarations: j2k_host.h)
+// j2k_hostcalls.cpp -- the host (unit) calls: one per reference function, caller-owned host buffers (C ABI of libj2kgfx.so, include/j2kgfx.h; shared declarations:
+// j2k_host.h), and the two drivers of the one-call frame forms: encode_host (every j2k_encode_*_host entry point) and decode_host (every j2k_decode_pixels_host*)
 #include "j2k_host.h"
 
 using namespace j2k;
@@ -371,93 +372,108 @@ int ensure_sized(j2k_ctx *ctx, void **p, size_t *cur, size_t need) {
 // image.*.Pix (host) -> H2D at native width (4 x fewer bytes than int32 planes) -> forward transform -> block coder -> tile-parts
 // (reference-mode plan: SOT | SOD | the tile's concatenated block bytes, encoder.createTileHeader of encodeTile's output; closed-loop
 // plan: SOT | SOD | packets) -> D2H at the exact length.  Synchronous; bench.py --io host shows what pipelining adds on top.
-// what follows the pixels' H2D copy in the one-call encode (j2k_encode_pixels_host, j2k_encode_image_host): `forward` puts the host
-// image on the device and runs the forward transform into P->d_coeff (after every other buffer is sized)
-template <typename Fwd>
-static int encode_host_tail(j2k_plan *P, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint32_t *lens,
-                            uint8_t *numbps, const Fwd &forward, int64_t max_body_bytes = -1) {    // max_body_bytes >= 0: the rate-limited frame encode
+int host_call_check(j2k_plan *P, const void *in, const void *out) {
+    if (!P || !in || !out) return J2K_ERR_INVALID_ARG;
+    if (P->ctx->capturing) return fail(P->ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
+    return J2K_OK;
+}
+int pix_format_bytes(int format) {
+    return format == J2K_PIX_GRAY8 ? 1 : format == J2K_PIX_GRAY16 ? 2 : (format == J2K_PIX_RGBA8 || format == J2K_PIX_NRGBA8) ? 4 :
+           (format == J2K_PIX_RGBA64 || format == J2K_PIX_NRGBA64) ? 8 : 0;
+}
+
+int encode_host(j2k_plan *P, const EncodeRequest &request, bool cl_set, size_t bound, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs,
+                uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, double *achieved, const std::function<int(int32_t *)> &forward) {
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nb = P->blocks.size(), nt = (size_t)P->tile_count;
-    const size_t bound = S.closed_loop ? j2k_plan_frame_bound(P) : j2k_plan_tile_parts_bound(P);
+    size_t nl = cl_set ? nt * (size_t)request.nlayers : 0;
     int r;
-    if ((r = ensure(ctx, &P->d_coeff, (size_t)P->coeff_elems * 4)) != J2K_OK) return r;
+    if (!cl_set && (r = ensure(ctx, &P->d_coeff, (size_t)P->coeff_elems * 4)) != J2K_OK) return r;
     if (!S.closed_loop && (r = ensure(ctx, &P->d_stream, (size_t)P->bytes_cap)) != J2K_OK) return r;
-    const size_t toff_at = (bound + 64 + 15) & ~size_t(15);                                              // the tile-parts, and behind them their offsets / the length word
-    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, toff_at + (nt + 2) * 8)) != J2K_OK) return r;
-    if ((r = ensure(ctx, &P->d_lens, nb * 4 + 16)) != J2K_OK) return r;
-    if ((r = ensure(ctx, &P->d_numbps, nb + 16)) != J2K_OK) return r;
+    // the tile-parts, and behind them their offsets (reference mode: the length word) and, for the closed-loop set, the layer ends and the layers' distortions
+    const size_t toff_at = (bound + 64 + 15) & ~size_t(15);
+    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, toff_at + (cl_set ? nt + 1 + nl + 2 + J2K_MAX_LAYERS : nt + 2) * 8)) != J2K_OK) return r;
+    if (!cl_set && (r = ensure(ctx, &P->d_lens, nb * 4 + 16)) != J2K_OK) return r;
+    if (!cl_set && (r = ensure(ctx, &P->d_numbps, nb + 16)) != J2K_OK) return r;
     if (!S.closed_loop && (r = ensure(ctx, &P->d_offs, (nb + 1) * 8)) != J2K_OK) return r;
-    uint64_t *d_toffs = reinterpret_cast<uint64_t *>((uint8_t *)P->d_host_io + toff_at);
-    if ((r = forward()) != J2K_OK) return r;
-    std::vector<uint64_t> toffs(nt + 1, 0);
-    if (S.closed_loop) {                                     // (blocks gathered from their coding slots straight into the tile-parts: no dense stream)
-        if (max_body_bytes >= 0) r = plan_encode_frame_from_coeff_rate(P, (int32_t *)P->d_coeff, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps, max_body_bytes, sop, eph, (uint8_t *)P->d_host_io, bound, d_toffs);
-        else r = plan_encode_frame_from_coeff(P, (int32_t *)P->d_coeff, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps, sop, eph, (uint8_t *)P->d_host_io, bound, d_toffs);
-        if (r != J2K_OK) return r;
-        HIPCHK(ctx, hipMemcpyAsync(toffs.data(), d_toffs, (nt + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else {
+    uint64_t *d_toffs = reinterpret_cast<uint64_t *>((uint8_t *)P->d_host_io + toff_at), *d_loffs = d_toffs + nt + 1;
+    EncodeRequest q = request;
+    if (q.kind == EncodeRequest::DISTORTION) q.d_achieved = reinterpret_cast<double *>(d_loffs + nl + 2);
+    if (!q.layered) nl = 0;                                                                  // (the kept-prefix stream has no layer ends)
+    std::vector<uint64_t> offs(nt + 1 + nl, 0), boffs;
+    if (cl_set) r = plan_encode_frame_cl(P, q, forward, sop, eph, (uint8_t *)P->d_host_io, bound, d_toffs, q.layered ? d_loffs : nullptr);
+    else r = forward((int32_t *)P->d_coeff);
+    if (r != J2K_OK) return r;
+    if (!S.closed_loop) {                                    // reference mode: the dense stream, then SOT | SOD | a tile's blocks
         if ((r = j2k_plan_encode_stream(P, (int32_t *)P->d_coeff, (uint8_t *)P->d_stream, (uint64_t *)P->d_offs, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps)) != J2K_OK) return r;
         if ((r = j2k_plan_assemble_tiles_device(P, (uint8_t *)P->d_stream, (uint64_t *)P->d_offs, (uint8_t *)P->d_host_io, d_toffs + nt)) != J2K_OK) return r;
-        HIPCHK(ctx, hipMemcpyAsync(&toffs[nt], d_toffs + nt, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&offs[nt], d_toffs + nt, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else {                                                 // (blocks gathered from their coding slots straight into the tile-parts: no dense stream)
+        if (!cl_set && (r = plan_encode_frame_from_coeff(P, (int32_t *)P->d_coeff, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps, q, sop, eph, (uint8_t *)P->d_host_io, bound, d_toffs, nullptr)) != J2K_OK) return r;
+        HIPCHK(ctx, hipMemcpyAsync(offs.data(), d_toffs, offs.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (lens && nb) HIPCHK(ctx, hipMemcpyAsync(lens, P->d_lens, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (numbps && nb) HIPCHK(ctx, hipMemcpyAsync(numbps, P->d_numbps, nb, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<uint64_t> boffs;
+    if (lens && nb) HIPCHK(ctx, hipMemcpyAsync(lens, cl_set ? P->d_cl_lens : P->d_lens, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (numbps && nb) HIPCHK(ctx, hipMemcpyAsync(numbps, cl_set ? P->d_cl_numbps : P->d_numbps, nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (q.d_achieved && achieved) HIPCHK(ctx, hipMemcpyAsync(achieved, q.d_achieved, (size_t)q.nlayers * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (!S.closed_loop && tile_offs) { boffs.resize(nb + 1); if (nb) HIPCHK(ctx, hipMemcpyAsync(boffs.data(), P->d_offs, (nb + 1) * 8, hipMemcpyDeviceToHost, ctx->stream)); }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if ((r = check_fault(ctx)) != J2K_OK) return r;
     if (S.closed_loop && (r = j2k_plan_frame_status(P)) != J2K_OK) return r;
-    const size_t total = (size_t)toffs[nt];
+    const size_t total = (size_t)offs[nt];
     *out_len = total;
-    if (tile_offs) {
-        if (S.closed_loop) memcpy(tile_offs, toffs.data(), (nt + 1) * 8);
-        else {                                             // tile-part t starts 14 t bytes behind its tile's first block (SOT + SOD per tile before it)
-            size_t j = 0;
-            for (size_t t = 0; t < nt; t++) {
-                while (j < nb && (size_t)P->block_tile[j] < t) j++;
-                tile_offs[t] = (j < nb ? boffs[j] : boffs[nb]) + 14 * t;
-            }
-            tile_offs[nt] = total;
+    if (tile_offs && S.closed_loop) memcpy(tile_offs, offs.data(), (nt + 1) * 8);
+    else if (tile_offs) {                                  // tile-part t starts 14 t bytes behind its tile's first block (SOT + SOD per tile before it)
+        size_t j = 0;
+        for (size_t t = 0; t < nt; t++) {
+            while (j < nb && (size_t)P->block_tile[j] < t) j++;
+            tile_offs[t] = (j < nb ? boffs[j] : boffs[nb]) + 14 * t;
         }
+        tile_offs[nt] = total;
     }
+    if (layer_offs && nl) memcpy(layer_offs, offs.data() + nt + 1, nl * 8);
     if (total > cap || (total && !out)) return fail(ctx, J2K_ERR_CAPACITY, "out too small (*out_len says what the tile-parts take)");
     if (total) HIPCHK(ctx, hipMemcpy(out, P->d_host_io, total, hipMemcpyDeviceToHost));
     return J2K_OK;
 }
 
-static int encode_pixels_host_impl(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes, uint8_t *out, size_t cap,
-                                   size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps);
+int encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, const EncodeRequest &q, bool cl_set, size_t bound, int sop, int eph, uint8_t *out,
+                       size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, double *achieved) {
+    j2k_ctx *ctx = P->ctx;
+    const PlanSpec &S = P->spec;
+    const int pb = pix_format_bytes(format);
+    if (!pb || stride < (size_t)S.W * pb) return fail(ctx, J2K_ERR_INVALID_ARG, "pixel format / stride");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, (size_t)S.H * stride);
+    if (r != J2K_OK) return r;
+    return encode_host(P, q, cl_set, bound, sop, eph, out, cap, out_len, tile_offs, layer_offs, lens, numbps, achieved, [&](int32_t *d_coeff) {
+        HIPCHK(ctx, hipMemcpyAsync(P->d_host_pix, pix, (size_t)S.H * stride, hipMemcpyHostToDevice, ctx->stream));
+        return j2k_plan_forward_pixels(P, format, P->d_host_pix, stride, d_coeff);
+    });
+}
+static size_t plain_bound(const j2k_plan *P) { return P->spec.closed_loop ? j2k_plan_frame_bound(P) : j2k_plan_tile_parts_bound(P); }
+
 extern "C" int j2k_encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, uint8_t *out, size_t cap,
                                       size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
-    return encode_pixels_host_impl(P, format, pix, stride, sop, eph, -1, out, cap, out_len, tile_offs, lens, numbps);
+    const int r = host_call_check(P, pix, out_len);
+    if (r != J2K_OK) return r;
+    return encode_pixels_host(P, format, pix, stride, EncodeRequest(), false, plain_bound(P), sop, eph, out, cap, out_len, tile_offs, nullptr, lens, numbps, nullptr);
 }
 // ... with at most max_body_bytes of code-block bodies (j2k_plan_encode_frame_pixels_rate); lens / numbps: the UNCUT lengths and plane counts
+// (what else the plan must be, the encoder refuses after the forward transform: MQ coder, no batch, blocks <= 64 x 64)
 extern "C" int j2k_encode_pixels_host_rate(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes, uint8_t *out,
                                            size_t cap, size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
     if (!P) return J2K_ERR_INVALID_ARG;
     if (max_body_bytes < 0) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_encode_pixels_host_rate: a negative budget");
     if (!P->spec.closed_loop) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_encode_pixels_host_rate: needs a closed-loop plan");
-    { const int rr = raw_magref_refuse(P, "j2k_encode_pixels_host_rate"); if (rr != J2K_OK) return rr; }
-    return encode_pixels_host_impl(P, format, pix, stride, sop, eph, max_body_bytes, out, cap, out_len, tile_offs, lens, numbps);
-}
-static int encode_pixels_host_impl(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes, uint8_t *out, size_t cap,
-                                   size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
-    if (!P || !pix || !out_len) return J2K_ERR_INVALID_ARG;
-    j2k_ctx *ctx = P->ctx;
-    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
-    const PlanSpec &S = P->spec;
-    const int pb = format == J2K_PIX_GRAY8 ? 1 : format == J2K_PIX_GRAY16 ? 2 : (format == J2K_PIX_RGBA8 || format == J2K_PIX_NRGBA8) ? 4 :
-                   (format == J2K_PIX_RGBA64 || format == J2K_PIX_NRGBA64) ? 8 : 0;
-    if (!pb || stride < (size_t)S.W * pb) return fail(ctx, J2K_ERR_INVALID_ARG, "pixel format / stride");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int r;
-    if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, (size_t)S.H * stride)) != J2K_OK) return r;
-    return encode_host_tail(P, sop, eph, out, cap, out_len, tile_offs, lens, numbps, [&]() {
-        HIPCHK(ctx, hipMemcpyAsync(P->d_host_pix, pix, (size_t)S.H * stride, hipMemcpyHostToDevice, ctx->stream));
-        return j2k_plan_forward_pixels(P, format, P->d_host_pix, stride, (int32_t *)P->d_coeff);
-    }, max_body_bytes);
+    int r = raw_magref_refuse(P, "j2k_encode_pixels_host_rate");
+    if (r == J2K_OK) r = host_call_check(P, pix, out_len);
+    if (r != J2K_OK) return r;
+    EncodeRequest q;
+    q.kind = EncodeRequest::BYTES;
+    q.budgets[0] = (uint64_t)max_body_bytes;
+    return encode_pixels_host(P, format, pix, stride, q, false, plain_bound(P), sop, eph, out, cap, out_len, tile_offs, nullptr, lens, numbps, nullptr);
 }
 
 // image.YCbCr / CMYK / Paletted in Go memory (encoder.go:178-195): each plane crosses PCIe at its native size -- the bytes the rectangle
@@ -465,12 +481,12 @@ static int encode_pixels_host_impl(j2k_plan *P, int format, const void *pix, siz
 // level-0 kernel), then j2k_plan_forward_image; a palette index >= npal returns J2K_ERR_GO_PANIC before anything is written.
 extern "C" int j2k_encode_image_host(j2k_plan *P, const j2k_image *img, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len,
                                      uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
-    if (!P || !img || !out_len) return J2K_ERR_INVALID_ARG;
+    int r = host_call_check(P, img, out_len);
+    if (r != J2K_OK) return r;
     j2k_ctx *ctx = P->ctx;
-    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
     const PlanSpec &S = P->spec;
     if (S.C != 3) return fail(ctx, J2K_ERR_INVALID_ARG, "an image.YCbCr / CMYK / Paletted is 3 components (encoder.go:178-195): the plan has another count");
-    int r = j2k_image_validate(img, S.W, S.H);
+    r = j2k_image_validate(img, S.W, S.H);
     if (r == J2K_ERR_GO_PANIC) return fail(ctx, r, "image: a plane shorter than the rectangle reaches, or an empty palette (Go panics in At)");
     if (r != J2K_OK) return fail(ctx, r, "image: unknown kind / ratio, a stride shorter than a row, or dims other than the plan's");
     uint64_t need[3];
@@ -479,18 +495,46 @@ extern "C" int j2k_encode_image_host(j2k_plan *P, const j2k_image *img, int sop,
     const size_t total = image_layout(img, need, off);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, total + 64)) != J2K_OK) return r;
-    return encode_host_tail(P, sop, eph, out, cap, out_len, tile_offs, lens, numbps, [&]() {
+    return encode_host(P, EncodeRequest(), false, plain_bound(P), sop, eph, out, cap, out_len, tile_offs, nullptr, lens, numbps, nullptr, [&](int32_t *d_coeff) {
         j2k_image d_img;
         const int u = image_upload(ctx, img, need, (uint8_t *)P->d_host_pix, off, &d_img);
         if (u != J2K_OK) return u;
-        return plan_forward_image_impl(P, &d_img, (int32_t *)P->d_coeff, nullptr);
+        return plan_forward_image_impl(P, &d_img, d_coeff, nullptr);
     });
 }
 
-static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride, int skip_planes = 0, bool cut = false);
+int decode_host(j2k_plan *P, const uint8_t *cs, size_t len, size_t pixbytes, void *pix, bool status_first, const std::function<int(const uint8_t *, void *)> &decode) {
+    j2k_ctx *ctx = P->ctx;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int r;
+    if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, pixbytes)) != J2K_OK) return r;
+    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, len + 64)) != J2K_OK) return r;
+    HIPCHK(ctx, hipMemcpyAsync(P->d_host_io, cs, len, hipMemcpyHostToDevice, ctx->stream));
+    if ((r = decode((const uint8_t *)P->d_host_io, P->d_host_pix)) != J2K_OK) return r;
+    if (status_first) {
+        if ((r = j2k_plan_frame_status(P)) != J2K_OK) return r;
+        HIPCHK(ctx, hipMemcpy(pix, P->d_host_pix, pixbytes, hipMemcpyDeviceToHost));
+        return J2K_OK;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(pix, P->d_host_pix, pixbytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return j2k_plan_frame_status(P);
+}
+
 // closed-loop plans: tile-parts (host) -> H2D -> parse -> block decode -> placement -> inverse transform -> image.*.Pix (host), one
 // synchronous call.  The pixel format is the plan's: components 1 / 3 / 4, precision <= 8 -> Gray / RGBA, else Gray16 / RGBA64
-// (decoder.createImage, decoder.go:417-588).
+// (decoder.createImage, decoder.go:417-588).  reduce < 0: the call without `reduce` (which any closed-loop plan takes); cut: the _rate call
+static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride, int skip_planes = 0, bool cut = false) {
+    const int r = host_call_check(P, cs, pix);
+    if (r != J2K_OK) return r;
+    if (!P->spec.closed_loop) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "the plan was not made with j2k_params.closed_loop: the reference has no decode body to mirror");
+    return decode_host(P, cs, len, reduced_rows(P->spec.H, reduce) * stride, pix, false, [&](const uint8_t *d_cs, void *d_pix) {
+        return cut ? j2k_plan_decode_frame_pixels_rate(P, d_cs, len, nullptr, sop, eph, std::max(reduce, 0), skip_planes, d_pix, stride)
+             : skip_planes ? j2k_plan_decode_frame_pixels_coarse(P, d_cs, len, nullptr, sop, eph, std::max(reduce, 0), skip_planes, d_pix, stride)
+             : reduce >= 0 ? j2k_plan_decode_frame_pixels_reduced(P, d_cs, len, nullptr, sop, eph, reduce, d_pix, stride)
+                           : j2k_plan_decode_frame_pixels(P, d_cs, len, nullptr, sop, eph, d_pix, stride);
+    });
+}
 extern "C" int j2k_decode_pixels_host(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, void *pix, size_t stride) {
     return decode_pixels_host_impl(P, cs, len, sop, eph, -1, pix, stride);
 }
@@ -507,12 +551,9 @@ extern "C" int j2k_decode_pixels_host_coarse(j2k_plan *P, const uint8_t *cs, siz
                                              size_t stride) {
     if (!P) return J2K_ERR_INVALID_ARG;
     int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_decode_pixels_host_coarse");
+    int32_t wr = 0, hr = 0;
+    if (r == J2K_OK && reduce != 0) r = j2k_plan_reduced_size(P, reduce, &wr, &hr);
     if (r != J2K_OK) return r;
-    if (reduce != 0) {
-        int32_t wr = 0, hr = 0;
-        r = j2k_plan_reduced_size(P, reduce, &wr, &hr);
-        if (r != J2K_OK) return r;
-    }
     return decode_pixels_host_impl(P, cs, len, sop, eph, reduce != 0 ? reduce : -1, pix, stride, skip_planes);
 }
 // ... of a stream whose blocks may be cut at bit planes (j2k_plan_decode_frame_pixels_rate)
@@ -522,33 +563,9 @@ extern "C" int j2k_decode_pixels_host_rate(j2k_plan *P, const uint8_t *cs, size_
     int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_decode_pixels_host_rate");
     if (r != J2K_OK) return r;
     if (P->spec.coder != J2K_CODER_MQ) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_decode_pixels_host_rate: per-block floors need the MQ coder");
-    if ((r = raw_magref_refuse(P, "j2k_decode_pixels_host_rate")) != J2K_OK) return r;
-    if (reduce != 0) {
-        int32_t wr = 0, hr = 0;
-        r = j2k_plan_reduced_size(P, reduce, &wr, &hr);
-        if (r != J2K_OK) return r;
-    }
-    return decode_pixels_host_impl(P, cs, len, sop, eph, reduce != 0 ? reduce : -1, pix, stride, skip_planes, true);
-}
-static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride, int skip_planes, bool cut) {
-    if (!P || !cs || !pix) return J2K_ERR_INVALID_ARG;
-    j2k_ctx *ctx = P->ctx;
-    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
-    const PlanSpec &S = P->spec;
-    if (!S.closed_loop) return fail(ctx, J2K_ERR_UNSUPPORTED, "the plan was not made with j2k_params.closed_loop: the reference has no decode body to mirror");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int r;
-    const size_t rows = reduce > 0 ? (size_t)(((int64_t)S.H + (((int64_t)1 << reduce) - 1)) >> reduce) : (size_t)S.H;
-    const size_t pixbytes = rows * stride;
-    if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, pixbytes)) != J2K_OK) return r;
-    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, len + 64)) != J2K_OK) return r;
-    HIPCHK(ctx, hipMemcpyAsync(P->d_host_io, cs, len, hipMemcpyHostToDevice, ctx->stream));
-    r = cut ? j2k_plan_decode_frame_pixels_rate(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, std::max(reduce, 0), skip_planes, P->d_host_pix, stride)
-        : skip_planes ? j2k_plan_decode_frame_pixels_coarse(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, std::max(reduce, 0), skip_planes, P->d_host_pix, stride)
-        : reduce >= 0 ? j2k_plan_decode_frame_pixels_reduced(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, reduce, P->d_host_pix, stride)
-                      : j2k_plan_decode_frame_pixels(P, (const uint8_t *)P->d_host_io, len, nullptr, sop, eph, P->d_host_pix, stride);
+    int32_t wr = 0, hr = 0;
+    r = raw_magref_refuse(P, "j2k_decode_pixels_host_rate");
+    if (r == J2K_OK && reduce != 0) r = j2k_plan_reduced_size(P, reduce, &wr, &hr);
     if (r != J2K_OK) return r;
-    HIPCHK(ctx, hipMemcpyAsync(pix, P->d_host_pix, pixbytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return j2k_plan_frame_status(P);
+    return decode_pixels_host_impl(P, cs, len, sop, eph, reduce != 0 ? reduce : -1, pix, stride, skip_planes, true);
 }

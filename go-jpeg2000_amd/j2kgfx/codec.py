@@ -559,6 +559,34 @@ class FramePlan:
         self.ctx.check(self.ctx.L.j2k_plan_frame_parallel_tiles(self.h, ctypes.byref(n)))
         return int(n.value)
 
+    # ---- the frame calls: one resolver from keywords to the C entry point, one block of outputs, one call site per signature -------------------------
+    def _encode_form(self, who, max_body_bytes, layer_bytes, roi, min_psnr, max_distortion, layer_psnr, layer_distortion):
+        """the cut an encode call asks for -> (entry-point suffix, budgets / targets array (or the one budget), L, layered, roi rectangle or None)"""
+        q = self._quality_args(who, max_body_bytes, layer_bytes, min_psnr, max_distortion, layer_psnr, layer_distortion)
+        if q is not None:
+            arr, L = self._targets(q[0])
+            return "_quality", arr, L, q[1], self._rect(roi) if roi is not None else None
+        if roi is not None and max_body_bytes is None and layer_bytes is None:
+            raise ValueError("%s: roi= shifts a budget -- give max_body_bytes= or layer_bytes=" % who)
+        if max_body_bytes is not None and layer_bytes is not None:
+            raise _lib.J2KError(_lib.ERR_INVALID_ARG, "%s: layer_bytes and max_body_bytes together" % who)
+        layered = layer_bytes is not None
+        if roi is not None:
+            arr, L = self._layer_bytes(layer_bytes if layered else [max_body_bytes])
+            return "_roi", arr, L, layered, self._rect(roi)
+        if layered:
+            arr, L = self._layer_bytes(layer_bytes)
+            return "_layers", arr, L, True, None
+        if max_body_bytes is not None:
+            return "_rate", C.c_int64(int(max_body_bytes)), 1, False, None
+        return "", None, 1, False, None
+
+    @staticmethod
+    def _encode_args(form, arr, L, rect, roi_gain):
+        """what an encode entry point takes between eph and out"""
+        rect = C.byref(rect) if rect is not None else None
+        return {"": [], "_rate": [arr], "_layers": [arr, L], "_roi": [arr, L, rect, int(roi_gain)], "_quality": [arr, L, rect, int(roi_gain)]}[form]
+
     @_stage
     def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16,
                             min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None):
@@ -577,57 +605,32 @@ class FramePlan:
         layered stream.  achieved: the estimate of every layer's choice, <= its target.  An ESTIMATE in the coefficient domain:
         measure the decoded frame with pixels.psnr.  roi= / roi_gain= weigh the rectangle as with a budget (j2k_plan_encode_frame_pixels_quality)"""
         t = _torch()
-        q = self._quality_args("encode_frame_pixels", max_body_bytes, layer_bytes, min_psnr, max_distortion, layer_psnr, layer_distortion)
-        if q is not None:
-            targets, layered = q
-            arr, L = self._targets(targets)
-            nt = int(self.info.tiles)
-            r = self._rect(roi) if roi is not None else None
-            out = out if out is not None else self.empty((self.frame_bound_layers(L) or 64) if layered else self.frame_bound(), t.uint8)
-            tile_offs = tile_offs if tile_offs is not None else self.empty(nt + 1, t.int64)[:nt + 1]
-            layer_offs = self.empty(nt * max(L, 1), t.int64)[:nt * max(L, 1)] if layered else None
-            achieved = t.zeros(max(L, 1), dtype=t.float64, device=self.device)
-            self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_quality(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
-                                                                           arr, L, C.byref(r) if r is not None else None, int(roi_gain), self._p(out),
-                                                                           C.c_size_t(int(out.numel())), self._p(tile_offs), self._p(layer_offs) if layered else None,
-                                                                           self._p(achieved)))
-            return (out, tile_offs, layer_offs, achieved[:L]) if layered else (out, tile_offs, achieved[:L])
-        if roi is not None:
-            if max_body_bytes is None and layer_bytes is None:
-                raise ValueError("encode_frame_pixels: roi= shifts a budget -- give max_body_bytes= or layer_bytes=")
-            if max_body_bytes is not None and layer_bytes is not None:
-                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "encode_frame_pixels: layer_bytes and max_body_bytes together")
-            layered = layer_bytes is not None
-            arr, L = self._layer_bytes(layer_bytes if layered else [max_body_bytes])
-            nt = int(self.info.tiles)
-            r = self._rect(roi)
-            out = out if out is not None else self.empty((self.frame_bound_layers(L) or 64) if layered else self.frame_bound(), t.uint8)
-            tile_offs = tile_offs if tile_offs is not None else self.empty(nt + 1, t.int64)[:nt + 1]
-            layer_offs = self.empty(nt * max(L, 1), t.int64)[:nt * max(L, 1)] if layered else None
-            self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_roi(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
-                                                                       arr, L, C.byref(r), int(roi_gain), self._p(out), C.c_size_t(int(out.numel())),
-                                                                       self._p(tile_offs), self._p(layer_offs) if layered else None))
-            return (out, tile_offs, layer_offs) if layered else (out, tile_offs)
-        if layer_bytes is not None:
-            if max_body_bytes is not None:
-                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "encode_frame_pixels: layer_bytes and max_body_bytes together")
-            arr, L = self._layer_bytes(layer_bytes)
-            nt = int(self.info.tiles)
-            out = out if out is not None else self.empty(self.frame_bound_layers(L) or 64, t.uint8)
-            tile_offs = tile_offs if tile_offs is not None else self.empty(nt + 1, t.int64)[:nt + 1]
-            layer_offs = self.empty(nt * max(L, 1), t.int64)[:nt * max(L, 1)]
-            self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_layers(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
-                                                                          arr, L, self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs), self._p(layer_offs)))
-            return out, tile_offs, layer_offs
-        out = out if out is not None else self.empty(self.frame_bound(), t.uint8)
-        tile_offs = tile_offs if tile_offs is not None else self.empty(int(self.info.tiles) + 1, t.int64)[:int(self.info.tiles) + 1]
-        if max_body_bytes is not None:
-            self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_rate(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
-                                                                        C.c_int64(int(max_body_bytes)), self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs)))
-            return out, tile_offs
-        self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
-                                                               self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs)))
-        return out, tile_offs
+        form, arr, L, layered, rect = self._encode_form("encode_frame_pixels", max_body_bytes, layer_bytes, roi, min_psnr, max_distortion, layer_psnr, layer_distortion)
+        nt = int(self.info.tiles)
+        out = out if out is not None else self.empty((self.frame_bound_layers(L) or 64) if layered else self.frame_bound(), t.uint8)
+        tile_offs = tile_offs if tile_offs is not None else self.empty(nt + 1, t.int64)[:nt + 1]
+        layer_offs = self.empty(nt * max(L, 1), t.int64)[:nt * max(L, 1)] if layered else None
+        achieved = t.zeros(max(L, 1), dtype=t.float64, device=self.device) if form == "_quality" else None
+        tail = [self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs)]
+        if form in ("_layers", "_roi", "_quality"):
+            tail.append(self._p(layer_offs) if layered else None)
+        if form == "_quality":
+            tail.append(self._p(achieved))
+        self.ctx.check(getattr(self.ctx.L, "j2k_plan_encode_frame_pixels" + form)(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
+                                                                                 *(self._encode_args(form, arr, L, rect, roi_gain) + tail)))
+        return (out, tile_offs) + ((layer_offs,) if layered else ()) + ((achieved[:L],) if form == "_quality" else ())
+
+    def _decode_form(self, reduce, skip_planes, truncated, layers, area):
+        """the decode a call asks for -> (entry-point suffix, what it takes between eph and pix); `area`: a _lib.Rect or None"""
+        if area is not None:
+            return "_area", [int(layers or 0), int(bool(truncated)), int(reduce), int(skip_planes), C.byref(area)]
+        if layers is not None:                   # a layered stream, its first `layers` layers
+            return "_layers", [int(layers), int(reduce), int(skip_planes)]
+        if truncated:
+            return "_rate", [int(reduce), int(skip_planes)]
+        if skip_planes:
+            return "_coarse", [int(reduce), int(skip_planes)]
+        return ("_reduced", [int(reduce)]) if reduce else ("", [])
 
     @_stage
     def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None, area=None):
@@ -639,33 +642,12 @@ class FramePlan:
         every tile-part are read, what follows them is ignored (j2k_plan_decode_frame_pixels_layers).  area = (x0, y0, x1, y1), Mallat MQ plans,
         with any of the others: only that rectangle, pix = [h, stride] with (h, w) = area_shape(area, reduce), and only the code-blocks the
         rectangle needs are decoded (j2k_plan_decode_frame_pixels_area)"""
-        if area is not None:
-            r = self._rect(area)
-            if pix.dim() != 2 or int(pix.shape[0]) != self.area_shape(area, reduce)[0]:
-                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "decode_frame_pixels: pix is not area_shape(area, reduce) rows")
-            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_area(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
-                                                                        int(bool(sop)), int(bool(eph)), int(layers or 0), int(bool(truncated)), int(reduce), int(skip_planes),
-                                                                        C.byref(r), self._p(pix), C.c_size_t(int(pix.shape[1]))))
-            return pix
-        if layers is not None:
-            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_layers(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
-                                                                          int(bool(sop)), int(bool(eph)), int(layers), int(reduce), int(skip_planes), self._p(pix),
-                                                                          C.c_size_t(int(pix.shape[1]))))
-            return pix
-        if truncated:
-            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_rate(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
-                                                                        int(bool(sop)), int(bool(eph)), int(reduce), int(skip_planes), self._p(pix), C.c_size_t(int(pix.shape[1]))))
-            return pix
-        if skip_planes:
-            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_coarse(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
-                                                                          int(bool(sop)), int(bool(eph)), int(reduce), int(skip_planes), self._p(pix), C.c_size_t(int(pix.shape[1]))))
-            return pix
-        if reduce:
-            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_reduced(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
-                                                                           int(bool(sop)), int(bool(eph)), int(reduce), self._p(pix), C.c_size_t(int(pix.shape[1]))))
-            return pix
-        self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
-                                                               int(bool(sop)), int(bool(eph)), self._p(pix), C.c_size_t(int(pix.shape[1]))))
+        rect = self._rect(area) if area is not None else None
+        if area is not None and (pix.dim() != 2 or int(pix.shape[0]) != self.area_shape(area, reduce)[0]):
+            raise _lib.J2KError(_lib.ERR_INVALID_ARG, "decode_frame_pixels: pix is not area_shape(area, reduce) rows")
+        form, args = self._decode_form(reduce, skip_planes, truncated, layers, rect)
+        self.ctx.check(getattr(self.ctx.L, "j2k_plan_decode_frame_pixels" + form)(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
+                                                                                 int(bool(sop)), int(bool(eph)), *(args + [self._p(pix), C.c_size_t(int(pix.shape[1]))])))
         return pix
 
     # ---- host memory in, host memory out: the one-call forms (j2k_encode_pixels_host / j2k_decode_pixels_host) -------------------
@@ -678,120 +660,51 @@ class FramePlan:
         achieved float64 [L] (j2k_encode_pixels_host_quality)"""
         L = self.ctx.L
         n, nt = int(self.info.blocks), int(self.info.tiles)
-        q = self._quality_args("encode_pixels_host", max_body_bytes, layer_bytes, min_psnr, max_distortion, layer_psnr, layer_distortion)
-        if q is not None:
-            targets, layered = q
-            arr, nl = self._targets(targets)
-            r = self._rect(roi) if roi is not None else None
-            cap = int(cap) if cap is not None else max(self.frame_bound_layers(nl) or 64, self.frame_bound()) + 64
-            pix = np.ascontiguousarray(pix, dtype=np.uint8)
-            out = np.zeros(max(cap, 1), np.uint8)
-            toffs = np.zeros(nt + 1, np.uint64); loffs = np.zeros(max(nt * nl, 1), np.uint64)
-            lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
-            ach = np.zeros(max(nl, 1), np.float64)
-            olen = C.c_size_t(0)
-            st = L.j2k_encode_pixels_host_quality(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)), arr, nl,
-                                                  C.byref(r) if r is not None else None, int(roi_gain), out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen),
-                                                  toffs.ctypes.data_as(C.c_void_p), loffs.ctypes.data_as(C.c_void_p) if layered else None,
-                                                  lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p), ach.ctypes.data_as(C.c_void_p))
-            self.encoded_len = olen.value
-            self.ctx.check(st)
-            res = dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy(), achieved=ach[:nl].copy())
-            if layered:
-                res["layer_offs"] = loffs[:nt * nl].copy()
-            return res
-        if roi is not None:
-            if max_body_bytes is None and layer_bytes is None:
-                raise ValueError("encode_pixels_host: roi= shifts a budget -- give max_body_bytes= or layer_bytes=")
-            if max_body_bytes is not None and layer_bytes is not None:
-                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "encode_pixels_host: layer_bytes and max_body_bytes together")
-            layered = layer_bytes is not None
-            arr, nl = self._layer_bytes(layer_bytes if layered else [max_body_bytes])
-            r = self._rect(roi)
-            cap = int(cap) if cap is not None else max(self.frame_bound_layers(nl) or 64, self.frame_bound()) + 64
-            pix = np.ascontiguousarray(pix, dtype=np.uint8)
-            out = np.zeros(max(cap, 1), np.uint8)
-            toffs = np.zeros(nt + 1, np.uint64); loffs = np.zeros(max(nt * nl, 1), np.uint64)
-            lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
-            olen = C.c_size_t(0)
-            st = L.j2k_encode_pixels_host_roi(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)), arr, nl,
-                                              C.byref(r), int(roi_gain), out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen),
-                                              toffs.ctypes.data_as(C.c_void_p), loffs.ctypes.data_as(C.c_void_p) if layered else None,
-                                              lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p))
-            self.encoded_len = olen.value
-            self.ctx.check(st)
-            res = dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
-            if layered:
-                res["layer_offs"] = loffs[:nt * nl].copy()
-            return res
-        if layer_bytes is not None:
-            if max_body_bytes is not None:
-                raise _lib.J2KError(_lib.ERR_INVALID_ARG, "encode_pixels_host: layer_bytes and max_body_bytes together")
-            arr, nl = self._layer_bytes(layer_bytes)
-            cap = int(cap) if cap is not None else (self.frame_bound_layers(nl) or 64) + 64
-            pix = np.ascontiguousarray(pix, dtype=np.uint8)
-            out = np.zeros(max(cap, 1), np.uint8)
-            toffs = np.zeros(nt + 1, np.uint64); loffs = np.zeros(max(nt * nl, 1), np.uint64)
-            lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
-            olen = C.c_size_t(0)
-            st = L.j2k_encode_pixels_host_layers(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)), arr, nl,
-                                                 out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen), toffs.ctypes.data_as(C.c_void_p),
-                                                 loffs.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p))
-            self.encoded_len = olen.value
-            self.ctx.check(st)
-            return dict(bytes=out[:olen.value].copy(), tile_offs=toffs, layer_offs=loffs[:nt * nl].copy(), lens=lens[:n].copy(), numbps=nbps[:n].copy())
-        L.j2k_plan_tile_parts_bound.restype = C.c_size_t
-        cap = int(cap) if cap is not None else max(self.frame_bound(), int(L.j2k_plan_tile_parts_bound(self.h))) + 64
+        form, arr, nl, layered, rect = self._encode_form("encode_pixels_host", max_body_bytes, layer_bytes, roi, min_psnr, max_distortion, layer_psnr, layer_distortion)
+        if cap is None:
+            L.j2k_plan_tile_parts_bound.restype = C.c_size_t
+            cap = {"_layers": self.frame_bound_layers(nl) or 64, "_roi": max(self.frame_bound_layers(nl) or 64, self.frame_bound()),
+                   "_quality": max(self.frame_bound_layers(nl) or 64, self.frame_bound())}.get(form) or max(self.frame_bound(), int(L.j2k_plan_tile_parts_bound(self.h)))
+            cap += 64
+        cap = int(cap)
         pix = np.ascontiguousarray(pix, dtype=np.uint8)
         out = np.zeros(max(cap, 1), np.uint8)
-        toffs = np.zeros(nt + 1, np.uint64); lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
+        toffs = np.zeros(nt + 1, np.uint64); loffs = np.zeros(max(nt * nl, 1), np.uint64)
+        lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
+        ach = np.zeros(max(nl, 1), np.float64)
         olen = C.c_size_t(0)
-        if max_body_bytes is not None:
-            st = L.j2k_encode_pixels_host_rate(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
-                                               C.c_int64(int(max_body_bytes)), out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen),
-                                               toffs.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p))
-        else:
-            st = L.j2k_encode_pixels_host(self.h, int(fmt), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
-                                          out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(olen), toffs.ctypes.data_as(C.c_void_p),
-                                          lens.ctypes.data_as(C.c_void_p), nbps.ctypes.data_as(C.c_void_p))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        tail = [ptr(out), C.c_size_t(cap), C.byref(olen), ptr(toffs)]
+        if form in ("_layers", "_roi", "_quality"):
+            tail.append(ptr(loffs) if layered else None)
+        tail += [ptr(lens), ptr(nbps)] + ([ptr(ach)] if form == "_quality" else [])
+        st = getattr(L, "j2k_encode_pixels_host" + form)(self.h, int(fmt), ptr(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
+                                                        *(self._encode_args(form, arr, nl, rect, roi_gain) + tail))
         self.encoded_len = olen.value
         self.ctx.check(st)
-        return dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
+        res = dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
+        if form == "_quality":
+            res["achieved"] = ach[:nl].copy()
+        if layered:
+            res["layer_offs"] = loffs[:nt * nl].copy()
+        return res
 
     def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None, area=None, pix=None):
         """closed-loop plans: tile-parts (bytes / numpy uint8) -> numpy uint8 pixels of `shape` = (H, stride); reduce > 0: (H_r, stride);
         skip_planes > 0 (MQ plans), truncated: as decode_frame_pixels; area: as decode_frame_pixels, shape = (h, stride) with h of area_shape
         (j2k_decode_pixels_host_area; pix: a numpy uint8 array of `shape` to write instead of a new one -- a refused call leaves it alone)"""
         cs = np.ascontiguousarray(np.frombuffer(bytes(cs), np.uint8) if not isinstance(cs, np.ndarray) else cs, dtype=np.uint8)
+        rect = self._rect(area) if area is not None else None
         if area is not None:
-            r = self._rect(area)
             if len(shape) != 2 or int(shape[0]) != self.area_shape(area, reduce)[0]:
                 raise _lib.J2KError(_lib.ERR_INVALID_ARG, "decode_pixels_host: shape is not area_shape(area, reduce) rows")
             pix = pix if pix is not None else np.zeros(shape, np.uint8)
             assert pix.dtype == np.uint8 and pix.shape == tuple(shape) and pix.flags.c_contiguous
-            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_area(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
-                                                                  int(layers or 0), int(bool(truncated)), int(reduce), int(skip_planes), C.byref(r),
-                                                                  pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
-            return pix
-        pix = np.zeros(shape, np.uint8)
-        if layers is not None:                   # a layered stream, its first `layers` layers (j2k_decode_pixels_host_layers)
-            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_layers(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
-                                                                    int(layers), int(reduce), int(skip_planes), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
-            return pix
-        if truncated:
-            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_rate(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
-                                                                  int(reduce), int(skip_planes), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
-            return pix
-        if skip_planes:
-            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_coarse(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
-                                                                    int(reduce), int(skip_planes), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
-            return pix
-        if reduce:
-            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_reduced(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
-                                                                     int(reduce), pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
-            return pix
-        self.ctx.check(self.ctx.L.j2k_decode_pixels_host(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
-                                                         pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))))
+        else:
+            pix = np.zeros(shape, np.uint8)
+        form, args = self._decode_form(reduce, skip_planes, truncated, layers, rect)
+        self.ctx.check(getattr(self.ctx.L, "j2k_decode_pixels_host" + form)(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
+                                                                           *(args + [pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))])))
         return pix
 
     def pack_bound(self):
