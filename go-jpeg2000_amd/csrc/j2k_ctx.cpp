@@ -176,6 +176,10 @@ int check_fault(j2k_ctx *ctx) {
     ctx->fault_armed = false;
     if (!f) return J2K_OK;
     HIPCHK(ctx, hipMemsetAsync(ctx->stage[3], 0, sizeof(int), ctx->stream));   // ordered with the next launches on this stream
+    return fault_result(ctx, f);
+}
+int fault_result(j2k_ctx *ctx, int f) {
+    if (!f) return J2K_OK;
     if (f == 1) return fail(ctx, J2K_ERR_GO_PANIC, "block coder: input on which the reference panics (stream buffer overrun / MinInt32)");
     if (f == 4) return fail(ctx, J2K_ERR_INVALID_ARG, "unpack_stream: the pack was not made by a plan of this geometry");
     // the MQ coder ran past the reference's own mqBuf size (j2k_block_bound): the Go code indexes out of range there

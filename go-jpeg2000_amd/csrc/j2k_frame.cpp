@@ -252,6 +252,9 @@ extern "C" int j2k_plan_frame_status(j2k_plan *P) {
     HIPCHK(ctx, hipMemcpyAsync(&st, P->d_frame_status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(P->d_frame_status, 0, sizeof st, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return frame_status_result(ctx, st);
+}
+int frame_status_result(j2k_ctx *ctx, int st) {
     if (st == J2K_ERR_CAPACITY) return fail(ctx, st, "frame codec: the output buffer is smaller than the tile-parts (the last entry of d_tile_offs says what they take)");
     if (st == J2K_ERR_GO_PANIC) return fail(ctx, st, "frame codec: a palette index >= len(Palette) in the image (Go: index out of range)");
     if (st != J2K_OK) return fail(ctx, st, "frame codec: a malformed tile-part or packet (SOT fields, header bits or body bytes running out)");

@@ -1,5 +1,5 @@
 // j2k_host.h -- what the host-side files of the C ABI share (j2k_ctx.cpp, j2k_planbuild.cpp, j2k_stages.cpp, j2k_frame.cpp, j2k_rate.cpp,
-// j2k_layers.cpp, j2k_area.cpp, j2k_hostcalls.cpp; round 4 had all of it in one 2 200-line j2k_abi.cpp): the kernels' launch wrappers, the
+// j2k_layers.cpp, j2k_area.cpp, j2k_hostcalls.cpp, j2k_pipe.cpp; round 4 had all of it in one 2 200-line j2k_abi.cpp): the kernels' launch wrappers, the
 // status helpers, the context's staging slots, the plan builder, and the requests, the one encoder / decoder and the two host drivers of the
 // closed-loop frame codec.  Host-side orchestration only: geometry -> device job tables, launches on the
 // context's HIP stream, host <-> device staging.  All arithmetic lives in the .hip kernels; there is no CPU fallback.
@@ -210,6 +210,25 @@ int pix_format_bytes(int format);                                    // bytes pe
 // (the layered, roi and quality forms), else P->d_coeff / d_lens / d_numbps; bound: what d_host_io holds of tile-parts, and the device call's cap
 int encode_host(j2k_plan *P, const EncodeRequest &q, bool cl_set, size_t bound, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs,
                 uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, double *achieved, const std::function<int(int32_t *)> &forward);
+// ... its launch half, shared with the pipelined form (j2k_pipe.cpp): the plan's workspaces, `forward`, the one encoder (or the reference-mode
+// branch) writing the tile-parts and, behind them, their offsets into d_io (encode_host_io_bytes of device memory).  Nothing is copied back and
+// nothing synchronises once the plan's workspaces exist.  io: where the results lie on the device -- offs_count words at d_offs belong at
+// entry offs_at of the host's table [tile offsets (tiles + 1) | layer ends (nl)]; reference mode: the one length word, entry `tiles`
+struct HostEncodeIO {
+    EncodeRequest q;
+    size_t nl = 0, offs_at = 0, offs_count = 0;
+    const uint64_t *d_offs = nullptr;
+    const uint32_t *d_lens = nullptr;
+    const uint8_t *d_numbps = nullptr;
+};
+size_t encode_host_io_bytes(const j2k_plan *P, bool cl_set, int nlayers, size_t bound);
+int encode_host_launch(j2k_plan *P, const EncodeRequest &q, bool cl_set, size_t bound, int sop, int eph, void *d_io, const std::function<int(int32_t *)> &forward,
+                       HostEncodeIO &io);
+size_t plain_bound(const j2k_plan *P);      // `bound` of the plain forms: j2k_plan_frame_bound (closed loop) / j2k_plan_tile_parts_bound
+// reference mode: where tile-part t starts, from the dense stream's block offsets boffs (blocks + 1) -- 14 t bytes behind its tile's first block
+void reference_tile_offs(const j2k_plan *P, const uint64_t *boffs, size_t total, uint64_t *tile_offs);
+int frame_status_result(j2k_ctx *ctx, int st);      // a value of the frame status word -> what j2k_plan_frame_status returns for it (j2k_frame.cpp)
+int fault_result(j2k_ctx *ctx, int f);              // a value of the block coders' fault word -> what check_fault returns for it (j2k_ctx.cpp)
 // ... for image.*.Pix in host memory: the format / stride refusal, the pixels' staging buffer, the H2D copy and j2k_plan_forward_pixels as `forward`
 int encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, const EncodeRequest &q, bool cl_set, size_t bound, int sop, int eph, uint8_t *out,
                        size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, double *achieved);

@@ -382,40 +382,72 @@ int pix_format_bytes(int format) {
            (format == J2K_PIX_RGBA64 || format == J2K_PIX_NRGBA64) ? 8 : 0;
 }
 
+size_t encode_host_io_bytes(const j2k_plan *P, bool cl_set, int nlayers, size_t bound) {
+    const size_t nt = (size_t)P->tile_count, nl = cl_set ? nt * (size_t)nlayers : 0;
+    return ((bound + 64 + 15) & ~size_t(15)) + (cl_set ? nt + 1 + nl + 2 + J2K_MAX_LAYERS : nt + 2) * 8;
+}
+
+int encode_host_launch(j2k_plan *P, const EncodeRequest &request, bool cl_set, size_t bound, int sop, int eph, void *d_io, const std::function<int(int32_t *)> &forward,
+                       HostEncodeIO &io) {
+    j2k_ctx *ctx = P->ctx;
+    const PlanSpec &S = P->spec;
+    const size_t nb = P->blocks.size(), nt = (size_t)P->tile_count;
+    size_t nl = cl_set ? nt * (size_t)request.nlayers : 0;
+    int r;
+    if (!cl_set && (r = ensure(ctx, &P->d_coeff, (size_t)P->coeff_elems * 4)) != J2K_OK) return r;
+    if (!S.closed_loop && (r = ensure(ctx, &P->d_stream, (size_t)P->bytes_cap)) != J2K_OK) return r;
+    if (!cl_set && (r = ensure(ctx, &P->d_lens, nb * 4 + 16)) != J2K_OK) return r;
+    if (!cl_set && (r = ensure(ctx, &P->d_numbps, nb + 16)) != J2K_OK) return r;
+    if (!S.closed_loop && (r = ensure(ctx, &P->d_offs, (nb + 1) * 8)) != J2K_OK) return r;
+    // the tile-parts, and behind them their offsets (reference mode: the length word) and, for the closed-loop set, the layer ends and the layers' distortions
+    const size_t toff_at = (bound + 64 + 15) & ~size_t(15);
+    uint64_t *d_toffs = reinterpret_cast<uint64_t *>((uint8_t *)d_io + toff_at), *d_loffs = d_toffs + nt + 1;
+    io.q = request;
+    if (io.q.kind == EncodeRequest::DISTORTION) io.q.d_achieved = reinterpret_cast<double *>(d_loffs + nl + 2);
+    if (!io.q.layered) nl = 0;                                                               // (the kept-prefix stream has no layer ends)
+    io.nl = nl;
+    if (cl_set) r = plan_encode_frame_cl(P, io.q, forward, sop, eph, (uint8_t *)d_io, bound, d_toffs, io.q.layered ? d_loffs : nullptr);
+    else r = forward((int32_t *)P->d_coeff);
+    if (r != J2K_OK) return r;
+    if (!S.closed_loop) {                                    // reference mode: the dense stream, then SOT | SOD | a tile's blocks
+        if ((r = j2k_plan_encode_stream(P, (int32_t *)P->d_coeff, (uint8_t *)P->d_stream, (uint64_t *)P->d_offs, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps)) != J2K_OK) return r;
+        if ((r = j2k_plan_assemble_tiles_device(P, (uint8_t *)P->d_stream, (uint64_t *)P->d_offs, (uint8_t *)d_io, d_toffs + nt)) != J2K_OK) return r;
+        io.d_offs = d_toffs + nt; io.offs_at = nt; io.offs_count = 1;
+    } else {                                                 // (blocks gathered from their coding slots straight into the tile-parts: no dense stream)
+        if (!cl_set && (r = plan_encode_frame_from_coeff(P, (int32_t *)P->d_coeff, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps, io.q, sop, eph, (uint8_t *)d_io, bound, d_toffs, nullptr)) != J2K_OK) return r;
+        io.d_offs = d_toffs; io.offs_at = 0; io.offs_count = nt + 1 + nl;
+    }
+    io.d_lens = cl_set ? P->d_cl_lens : (const uint32_t *)P->d_lens;
+    io.d_numbps = cl_set ? P->d_cl_numbps : (const uint8_t *)P->d_numbps;
+    return J2K_OK;
+}
+
+void reference_tile_offs(const j2k_plan *P, const uint64_t *boffs, size_t total, uint64_t *tile_offs) {
+    const size_t nb = P->blocks.size(), nt = (size_t)P->tile_count;
+    size_t j = 0;
+    for (size_t t = 0; t < nt; t++) {
+        while (j < nb && (size_t)P->block_tile[j] < t) j++;
+        tile_offs[t] = (j < nb ? boffs[j] : boffs[nb]) + 14 * t;
+    }
+    tile_offs[nt] = total;
+}
+
 int encode_host(j2k_plan *P, const EncodeRequest &request, bool cl_set, size_t bound, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs,
                 uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps, double *achieved, const std::function<int(int32_t *)> &forward) {
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nb = P->blocks.size(), nt = (size_t)P->tile_count;
-    size_t nl = cl_set ? nt * (size_t)request.nlayers : 0;
     int r;
-    if (!cl_set && (r = ensure(ctx, &P->d_coeff, (size_t)P->coeff_elems * 4)) != J2K_OK) return r;
-    if (!S.closed_loop && (r = ensure(ctx, &P->d_stream, (size_t)P->bytes_cap)) != J2K_OK) return r;
-    // the tile-parts, and behind them their offsets (reference mode: the length word) and, for the closed-loop set, the layer ends and the layers' distortions
-    const size_t toff_at = (bound + 64 + 15) & ~size_t(15);
-    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, toff_at + (cl_set ? nt + 1 + nl + 2 + J2K_MAX_LAYERS : nt + 2) * 8)) != J2K_OK) return r;
-    if (!cl_set && (r = ensure(ctx, &P->d_lens, nb * 4 + 16)) != J2K_OK) return r;
-    if (!cl_set && (r = ensure(ctx, &P->d_numbps, nb + 16)) != J2K_OK) return r;
-    if (!S.closed_loop && (r = ensure(ctx, &P->d_offs, (nb + 1) * 8)) != J2K_OK) return r;
-    uint64_t *d_toffs = reinterpret_cast<uint64_t *>((uint8_t *)P->d_host_io + toff_at), *d_loffs = d_toffs + nt + 1;
-    EncodeRequest q = request;
-    if (q.kind == EncodeRequest::DISTORTION) q.d_achieved = reinterpret_cast<double *>(d_loffs + nl + 2);
-    if (!q.layered) nl = 0;                                                                  // (the kept-prefix stream has no layer ends)
+    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, encode_host_io_bytes(P, cl_set, request.nlayers, bound))) != J2K_OK) return r;
+    HostEncodeIO io;
+    if ((r = encode_host_launch(P, request, cl_set, bound, sop, eph, P->d_host_io, forward, io)) != J2K_OK) return r;
+    const size_t nl = io.nl;
+    const EncodeRequest &q = io.q;
     std::vector<uint64_t> offs(nt + 1 + nl, 0), boffs;
-    if (cl_set) r = plan_encode_frame_cl(P, q, forward, sop, eph, (uint8_t *)P->d_host_io, bound, d_toffs, q.layered ? d_loffs : nullptr);
-    else r = forward((int32_t *)P->d_coeff);
-    if (r != J2K_OK) return r;
-    if (!S.closed_loop) {                                    // reference mode: the dense stream, then SOT | SOD | a tile's blocks
-        if ((r = j2k_plan_encode_stream(P, (int32_t *)P->d_coeff, (uint8_t *)P->d_stream, (uint64_t *)P->d_offs, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps)) != J2K_OK) return r;
-        if ((r = j2k_plan_assemble_tiles_device(P, (uint8_t *)P->d_stream, (uint64_t *)P->d_offs, (uint8_t *)P->d_host_io, d_toffs + nt)) != J2K_OK) return r;
-        HIPCHK(ctx, hipMemcpyAsync(&offs[nt], d_toffs + nt, 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else {                                                 // (blocks gathered from their coding slots straight into the tile-parts: no dense stream)
-        if (!cl_set && (r = plan_encode_frame_from_coeff(P, (int32_t *)P->d_coeff, (uint32_t *)P->d_lens, (uint8_t *)P->d_numbps, q, sop, eph, (uint8_t *)P->d_host_io, bound, d_toffs, nullptr)) != J2K_OK) return r;
-        HIPCHK(ctx, hipMemcpyAsync(offs.data(), d_toffs, offs.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (lens && nb) HIPCHK(ctx, hipMemcpyAsync(lens, cl_set ? P->d_cl_lens : P->d_lens, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (numbps && nb) HIPCHK(ctx, hipMemcpyAsync(numbps, cl_set ? P->d_cl_numbps : P->d_numbps, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&offs[io.offs_at], io.d_offs, io.offs_count * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (lens && nb) HIPCHK(ctx, hipMemcpyAsync(lens, io.d_lens, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (numbps && nb) HIPCHK(ctx, hipMemcpyAsync(numbps, io.d_numbps, nb, hipMemcpyDeviceToHost, ctx->stream));
     if (q.d_achieved && achieved) HIPCHK(ctx, hipMemcpyAsync(achieved, q.d_achieved, (size_t)q.nlayers * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (!S.closed_loop && tile_offs) { boffs.resize(nb + 1); if (nb) HIPCHK(ctx, hipMemcpyAsync(boffs.data(), P->d_offs, (nb + 1) * 8, hipMemcpyDeviceToHost, ctx->stream)); }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -424,14 +456,7 @@ int encode_host(j2k_plan *P, const EncodeRequest &request, bool cl_set, size_t b
     const size_t total = (size_t)offs[nt];
     *out_len = total;
     if (tile_offs && S.closed_loop) memcpy(tile_offs, offs.data(), (nt + 1) * 8);
-    else if (tile_offs) {                                  // tile-part t starts 14 t bytes behind its tile's first block (SOT + SOD per tile before it)
-        size_t j = 0;
-        for (size_t t = 0; t < nt; t++) {
-            while (j < nb && (size_t)P->block_tile[j] < t) j++;
-            tile_offs[t] = (j < nb ? boffs[j] : boffs[nb]) + 14 * t;
-        }
-        tile_offs[nt] = total;
-    }
+    else if (tile_offs) reference_tile_offs(P, boffs.data(), total, tile_offs);   // tile-part t starts 14 t bytes behind its tile's first block (SOT + SOD per tile before it)
     if (layer_offs && nl) memcpy(layer_offs, offs.data() + nt + 1, nl * 8);
     if (total > cap || (total && !out)) return fail(ctx, J2K_ERR_CAPACITY, "out too small (*out_len says what the tile-parts take)");
     if (total) HIPCHK(ctx, hipMemcpy(out, P->d_host_io, total, hipMemcpyDeviceToHost));
@@ -452,7 +477,7 @@ int encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, 
         return j2k_plan_forward_pixels(P, format, P->d_host_pix, stride, d_coeff);
     });
 }
-static size_t plain_bound(const j2k_plan *P) { return P->spec.closed_loop ? j2k_plan_frame_bound(P) : j2k_plan_tile_parts_bound(P); }
+size_t plain_bound(const j2k_plan *P) { return P->spec.closed_loop ? j2k_plan_frame_bound(P) : j2k_plan_tile_parts_bound(P); }
 
 extern "C" int j2k_encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, uint8_t *out, size_t cap,
                                       size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {

@@ -76,6 +76,8 @@ class FramePlan:
 
     def close(self):
         if getattr(self, "h", None):
+            for pipe in list(getattr(self, "_pipes", ())):     # a j2k_pipe keeps a pointer to its plan
+                pipe.close()
             if getattr(self.ctx, "h", None):    # (a plan whose context is gone was destroyed with it)
                 self.ctx.L.j2k_plan_destroy(self.h)
             self.h = None
@@ -808,3 +810,134 @@ class FramePlan:
             nbps.ctypes.data_as(C.c_void_p)))
         return dict(bytes=out[:olen.value].copy(), lens=lens[:n].copy(), numbps=nbps[:n].copy(), tile_offs=toffs,
                     coeff=coeff)
+
+
+# ---- the pipelined host codec (j2k_pipe_*): encode_pixels_host / decode_pixels_host with frames in flight ----------------------------------
+class _PinnedBlock:
+    """j2k_host_alloc memory, freed when the last array on it goes"""
+
+    def __init__(self, nbytes):
+        self._L = _lib.lib()
+        self.ptr = self._L.j2k_host_alloc(C.c_size_t(nbytes))
+        if not self.ptr:
+            raise _lib.J2KError(_lib.ERR_HIP, "j2k_host_alloc(%d) failed" % nbytes)
+
+    def __del__(self):
+        if self.ptr and not sys.is_finalizing():
+            self._L.j2k_host_free(C.c_void_p(self.ptr))
+            self.ptr = None
+
+
+def pinned_empty(shape, dtype=np.uint8):
+    """a numpy array on pinned host memory (j2k_host_alloc), freed with the array: what a HostPipe copies from / to without staging"""
+    dtype = np.dtype(dtype)
+    shape = (int(shape),) if np.isscalar(shape) else tuple(int(x) for x in shape)
+    nbytes = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
+    block = _PinnedBlock(max(nbytes, 1))
+    raw = (C.c_uint8 * max(nbytes, 1)).from_address(block.ptr)
+    raw._pinned_block = block                      # (numpy keeps `raw` as the array's base, and `raw` the block)
+    return np.frombuffer(raw, dtype=np.uint8, count=nbytes).view(dtype).reshape(shape)
+
+
+class HostPipe:
+    """j2k_pipe on a FramePlan: submit_encode / submit_decode return tickets, wait(ticket) returns what encode_pixels_host / decode_pixels_host
+    return for that frame (or raises what they raise).  At most `depth` tickets may be un-waited.  While tickets are outstanding the plan and
+    its context belong to the pipe.  The pipe keeps references to the submitted buffers until their wait."""
+
+    def __init__(self, plan, depth=2):
+        self.plan, self.ctx, self.depth = plan, plan.ctx, int(depth)
+        self.h = None
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.L.j2k_pipe_create(plan.h, int(depth), C.byref(h)))
+        self.h = h
+        self._frames = {}
+        self.encoded_len = 0
+        if not hasattr(plan, "_pipes"):
+            import weakref
+            plan._pipes = weakref.WeakSet()
+        plan._pipes.add(self)                      # closed with the plan: a j2k_pipe keeps a pointer to its j2k_plan
+
+    @staticmethod
+    def _ptr(a):
+        return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+    def submit_encode(self, fmt, pix, sop=False, eph=False, cap=None, out=None, tables=True):
+        """pix: numpy uint8 [H, stride], pinned (pinned_empty) or not; out: the numpy uint8 array the tile-parts go to (default: a new pageable
+        one of `cap` bytes; cap default: the plan's bound); tables=False: tile_offs / lens / numbps are not asked for"""
+        plan, L = self.plan, self.ctx.L
+        n, nt = int(plan.info.blocks), int(plan.info.tiles)
+        if cap is None:
+            L.j2k_plan_tile_parts_bound.restype = C.c_size_t
+            cap = (out.size if out is not None else max(plan.frame_bound(), int(L.j2k_plan_tile_parts_bound(plan.h))) + 64)
+        cap = int(cap)
+        assert isinstance(pix, np.ndarray) and pix.dtype == np.uint8 and pix.ndim == 2 and pix.flags.c_contiguous
+        if out is None:
+            out = np.zeros(max(cap, 1), np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= cap
+        toffs = np.zeros(nt + 1, np.uint64) if tables else None
+        lens = np.zeros(max(n, 1), np.uint32) if tables else None
+        nbps = np.zeros(max(n, 1), np.uint8) if tables else None
+        t = C.c_uint64(0)
+        self.ctx.check(L.j2k_pipe_submit_encode(self.h, int(fmt), self._ptr(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)), self._ptr(out),
+                                                C.c_size_t(cap), self._ptr(toffs), self._ptr(lens), self._ptr(nbps), C.byref(t)))
+        self._frames[t.value] = ("encode", pix, out, toffs, lens, nbps)
+        return t.value
+
+    def submit_decode(self, cs, pix, sop=False, eph=False):
+        """cs: tile-parts (bytes / numpy uint8, pinned or not); pix: the numpy uint8 [H, stride] array to decode into, pinned or not"""
+        cs = np.frombuffer(bytes(cs), np.uint8) if not isinstance(cs, np.ndarray) else cs
+        assert cs.dtype == np.uint8 and cs.flags.c_contiguous
+        assert isinstance(pix, np.ndarray) and pix.dtype == np.uint8 and pix.ndim == 2 and pix.flags.c_contiguous
+        t = C.c_uint64(0)
+        self.ctx.check(self.ctx.L.j2k_pipe_submit_decode(self.h, self._ptr(cs), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)), self._ptr(pix),
+                                                         C.c_size_t(int(pix.shape[1])), C.byref(t)))
+        self._frames[t.value] = ("decode", cs, pix)
+        return t.value
+
+    def wait(self, ticket):
+        """encode: dict(bytes, tile_offs, lens, numbps) as encode_pixels_host (+ out: the caller's array); decode: the pix array.  A refused frame
+        raises J2KError (self.encoded_len then holds *out_len: what the tile-parts take, after J2K_ERR_CAPACITY)"""
+        olen = C.c_size_t(0)
+        st = self.ctx.L.j2k_pipe_wait(self.h, C.c_uint64(int(ticket)), C.byref(olen))
+        frame = self._frames.pop(int(ticket), None)
+        self.encoded_len = olen.value
+        self.ctx.check(st)
+        if frame[0] == "decode":
+            return frame[2]
+        _, _, out, toffs, lens, nbps = frame
+        n = int(self.plan.info.blocks)
+        res = dict(bytes=out[:olen.value].copy(), out=out)
+        if toffs is not None:
+            res.update(tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
+        return res
+
+    def poll(self, ticket):
+        done = C.c_int(0)
+        self.ctx.check(self.ctx.L.j2k_pipe_poll(self.h, C.c_uint64(int(ticket)), C.byref(done)))
+        return bool(done.value)
+
+    def drain(self):
+        self.ctx.check(self.ctx.L.j2k_pipe_drain(self.h))
+
+    def close(self):
+        """drains, frees the pipe; the plan is usable by the one-call forms again.  Un-waited tickets are gone."""
+        if getattr(self, "h", None):
+            if getattr(self.plan, "h", None) and getattr(self.ctx, "h", None):
+                self.ctx.L.j2k_pipe_destroy(self.h)
+            self.h = None
+            self._frames = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+        return False
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass

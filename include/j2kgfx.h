@@ -540,6 +540,47 @@ int j2k_encode_pixels_host(j2k_plan *plan, int format, const void *pix, size_t s
                            size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps);
 int j2k_decode_pixels_host(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, void *pix, size_t stride);
 
+/* ---- the pipelined host codec: the two calls above with up to `depth` frames in flight ---------------------------------------------------
+ * A submitted encode IS j2k_encode_pixels_host on the same arguments (reference-mode and closed-loop plans, either coder), a submitted decode
+ * IS j2k_decode_pixels_host (closed-loop plans; J2K_ERR_UNSUPPORTED from the submit otherwise): out, *out_len, tile_offs, lens, numbps and
+ * pix are written byte for byte as those calls write them, but one frame's H2D and D2H copies run beside another frame's kernels.  Only the
+ * plain forms: no budgets, layers, quality targets, roi, reduce, skip_planes, truncated streams, area or image sources.
+ *   How.  All kernels of all frames run on the context's one stream in submission order; each of the `depth` slots owns the device pixels,
+ * the device tile-parts with their offsets, and a snapshot of the frame's status (taken, and the plan's status word cleared, on the stream
+ * behind the frame's kernels: a refused frame never disturbs its neighbours).  The pipe owns one high-priority stream per copy direction.
+ * The small results come back first; a frame's tile-parts are copied at their exact length once that length is on the host, which happens
+ * inside a later submit, poll or wait -- the library creates no thread, reads no environment variable, and a steady-state submit allocates
+ * nothing (everything is allocated by j2k_pipe_create, or at the first frame that needs the ring for pageable memory or a larger stride).
+ *   Caller memory.  The pipe asks hipPointerGetAttributes whether pix, out and cs are pinned (j2k_host_alloc, hipHostMalloc,
+ * hipHostRegister).  Pinned input is copied from where it lies; pinned tile-part output receives the D2H copy; a pinned decode frame is
+ * stored by the inverse transform itself through its device address (no device frame, no copy) unless that address is not aligned to what
+ * the device call takes (4 bytes for RGBA rows, the sample size for gray), in which case it takes the slot's device frame and a copy.
+ * Pageable memory (Go's heap) is staged through a pinned ring owned by the pipe: memcpy in inside the submit, memcpy out inside the wait.
+ * Results are identical in every case; row padding of a decoded frame is never written.  Buffers handed to a submit stay valid and
+ * untouched by the caller until that ticket's wait returns.
+ *   Tickets are 1, 2, 3, ... per pipe; frames complete in submission order; waits may come in any order.  At most `depth` tickets may be
+ * un-waited: a further submit returns J2K_ERR_INVALID_ARG, queues nothing and consumes no ticket -- as does every refusal the one-call form
+ * decides from its arguments and the plan (NULL pointers, format / stride, a decode on a plan without closed_loop, a capturing context), with
+ * that form's code.  j2k_pipe_wait returns what the one-call form would have returned for that frame: J2K_OK; J2K_ERR_CAPACITY with *out_len
+ * = what the tile-parts take and out untouched; J2K_ERR_INVALID_ARG for a malformed stream, pix untouched in every memory case;
+ * J2K_ERR_HIP.  *out_len (may be NULL) is set for encodes.  A ticket that is unknown or was waited before: J2K_ERR_INVALID_ARG.
+ * j2k_pipe_poll never blocks: *done = 1 once the wait would not block.  j2k_pipe_drain returns when all submitted work is complete; the
+ * tickets stay waitable.  j2k_pipe_destroy drains, frees everything and leaves the plan usable by the one-call forms.
+ *   While tickets are outstanding the plan and its context belong to the pipe: no other call on either (the library does not police it).
+ * The pipe must be destroyed before its plan.  Single-threaded, like the context.
+ *   j2k_host_alloc / j2k_host_free: pinned host memory (hipHostMalloc), so that a cgo caller needs no HIP binding; NULL on failure. */
+typedef struct j2k_pipe j2k_pipe;
+int j2k_pipe_create(j2k_plan *plan, int depth, j2k_pipe **out);       /* depth 1 ... 8 frames in flight */
+void j2k_pipe_destroy(j2k_pipe *pipe);
+int j2k_pipe_submit_encode(j2k_pipe *pipe, int format, const void *pix, size_t stride, int sop, int eph, uint8_t *out, size_t cap,
+                           uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps, uint64_t *ticket);
+int j2k_pipe_submit_decode(j2k_pipe *pipe, const uint8_t *cs, size_t len, int sop, int eph, void *pix, size_t stride, uint64_t *ticket);
+int j2k_pipe_wait(j2k_pipe *pipe, uint64_t ticket, size_t *out_len);
+int j2k_pipe_poll(j2k_pipe *pipe, uint64_t ticket, int *done);
+int j2k_pipe_drain(j2k_pipe *pipe);
+void *j2k_host_alloc(size_t bytes);
+void j2k_host_free(void *p);
+
 /* ---- multi-tile codestream assembly: host calls, no device needed ------------------------------
  * j2k_create_tile_header = encoder.createTileHeader(tileIdx, tileData) (encoder.go:746-760): SOT (0xFF90) Lsot = 10,
  * Isot = uint16(tileIdx), Psot = uint32(14 + len), TPsot = 0, TNsot = 1, SOD (0xFF93), then the tile data -- 14 + len bytes.
