@@ -20,7 +20,7 @@ def step_of(quality):
     return 1.0 / float(quality if quality > 0 else 100)
 
 
-def expect_dequantized(oracle, coefs, prec, nres, quality, multiply=True):
+def expect_dequantized(oracle, coefs, prec, nres, quality, multiply=True, is_signed=False):
     """the decode side of one tile with the coefficients dequantised first: coefs int32 [C, h, w] -> frame int32 [C, h, w].
     multiply=False leaves the product out: tcd.ApplyInverseDWT as written (== lossy97_cases.expect_inverse)"""
     C, h, w = coefs.shape
@@ -32,7 +32,7 @@ def expect_dequantized(oracle, coefs, prec, nres, quality, multiply=True):
             f = f * step                                               # dwt.go:517
         f = oracle.reconstruct97(f, w, h, lc.levels_of(nres))
         planes.append(lc.go_int32(f + 0.5)[0])                         # tcd.go:433-435
-    return np.stack(oracle.postprocess(planes, prec, False))
+    return np.stack(oracle.postprocess(planes, prec, False, is_signed=is_signed))
 
 
 def expect_frame(oracle, coef_of_tile, Cn, W, H, tile, prec, nres, quality, multiply=True):

@@ -546,11 +546,12 @@ def expect_forward(oracle, crop, prec, nres):
     return np.stack(oracle.preprocess([np.ascontiguousarray(crop[c]) for c in range(C)], w, h, prec, True, nres))
 
 
-def expect_inverse(oracle, coefs, prec, nres):
-    """the decode side of one tile [C, h, w]: tcd.ApplyInverseDWT per component, the inverse RCT on the first three, the DC shift"""
+def expect_inverse(oracle, coefs, prec, nres, is_signed=False):
+    """the decode side of one tile [C, h, w]: tcd.ApplyInverseDWT per component, the inverse RCT on the first three, the DC shift (none for
+    signed components, decoder.go:344-348)"""
     C, h, w = coefs.shape
     inv = [oracle.tcd_inverse_dwt(coefs[c], w, h, levels_of(nres), 1) for c in range(C)]
-    return np.stack(oracle.postprocess(inv, prec, True, mct=C >= 3))
+    return np.stack(oracle.postprocess(inv, prec, True, mct=C >= 3, is_signed=is_signed))
 
 
 def out_of_range_rows(frame, prec):

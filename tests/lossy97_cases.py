@@ -311,11 +311,11 @@ def inverse_counts(oracle, coefs, prec, nres):
     return out, rows
 
 
-def expect_inverse(oracle, coefs, prec, nres):
+def expect_inverse(oracle, coefs, prec, nres, is_signed=False):
     """the composition tests/test_gpu_dwt97.py::test_plan_forward_lossy uses for the decode side of one tile"""
     C, h, w = coefs.shape
     inv = [oracle.tcd_inverse_dwt(coefs[c], w, h, levels_of(nres), 0) for c in range(C)]
-    return np.stack(oracle.postprocess(inv, prec, False))
+    return np.stack(oracle.postprocess(inv, prec, False, is_signed=is_signed))
 
 
 # ---- pyref's 1-D transforms on whole rows / columns at a time ----------------------------------------------------------------------------------

@@ -70,7 +70,7 @@ def forward_tile(oracle, crop, prec, nres, lossless=True, quality=0, prefix=Fals
     return np.stack(out)
 
 
-def inverse_tile(oracle, coefs, prec, nres, lossless=True, quality=0, dequantize=False, reduce=0):
+def inverse_tile(oracle, coefs, prec, nres, lossless=True, quality=0, dequantize=False, reduce=0, is_signed=False):
     """one tile's coefficients int32 [C, h, w] -> int32 [C, h_r, w_r]"""
     C, h, w = coefs.shape
     L = levels_of(nres)
@@ -91,7 +91,7 @@ def inverse_tile(oracle, coefs, prec, nres, lossless=True, quality=0, dequantize
             p[:hl, :wl] = (oracle.inv53_2d if lossless else oracle.inv97_2d)(rect, wl, hl)
         p = np.ascontiguousarray(p[:hr, :wr])
         planes.append(p if lossless else lc.go_int32(p + 0.5)[0])       # tcd.go:433-435
-    return np.stack(oracle.postprocess(planes, prec, lossless, mct=C >= 3))
+    return np.stack(oracle.postprocess(planes, prec, lossless, mct=C >= 3, is_signed=is_signed))
 
 
 # ---- frames ---------------------------------------------------------------------------------------------------------------------------------
@@ -133,14 +133,15 @@ def forward_frame(oracle, frm, tile, prec, nres, lossless=True, quality=0, frame
             for x0, y0, w, h in tiles_of(W, H, tile, frame_rows)]
 
 
-def inverse_frame(oracle, tiles, W, H, tile, prec, nres, lossless=True, quality=0, dequantize=False, reduce=0, frame_rows=0, only=None, fill=0):
+def inverse_frame(oracle, tiles, W, H, tile, prec, nres, lossless=True, quality=0, dequantize=False, reduce=0, frame_rows=0, only=None, fill=0,
+                  is_signed=False):
     """coefficient tiles -> the reduced frame int32 [C, H_r, W_r]; only: the tile numbers written (a shard), the rest holds `fill`"""
     C = tiles[0].shape[0]
     out = np.full((C, shr(H, reduce), shr(W, reduce)), fill, np.int32)
     for t, (x, y, w, h) in enumerate(reduced_rects(W, H, tile, reduce, frame_rows)):
         if only is not None and t not in only:
             continue
-        got = inverse_tile(oracle, tiles[t], prec, nres, lossless, quality, dequantize, reduce)
+        got = inverse_tile(oracle, tiles[t], prec, nres, lossless, quality, dequantize, reduce, is_signed)
         assert got.shape == (C, h, w)
         out[:, y:y + h, x:x + w] = got
     return out
