@@ -1282,7 +1282,7 @@ hipError_t launch_dwt53_tail_inv(hipStream_t s, const TailPlane *planes, int npl
 template <int NW>
 static hipError_t fwd_wg_go(hipStream_t s, const LevelLaunch &L, const int32_t *src, int32_t *out, int32_t *nxt, int dc) {
     if (L.ycc.y) {             // an image.YCbCr (j2k_plan_forward_image): no level-1 fusion, nt stores (the plan's checks)
-        if (L.njobs2 > 0 || L.wg_store != 1) return hipErrorInvalidValue;
+        if (L.njobs2 > 0 || L.wg_store != 1 || L.scr16) return hipErrorInvalidValue;
 #define J2K_YWG(R) hipExtLaunchKernelGGL((dwt53_fwd_ycc_wg_kernel<NW, 1, 6, 1 + R>), dim3(L.njobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
                                          L.jobs, L.njobs, L.planes, L.ycc, out, nxt, dc)
         switch (L.ycc.ratio) {
@@ -1295,6 +1295,15 @@ static hipError_t fwd_wg_go(hipStream_t s, const LevelLaunch &L, const int32_t *
         return hipGetLastError();
     }
     const uint32_t *pix = reinterpret_cast<const uint32_t *>(src);
+    if (L.scr16) {             // the rows of X_1 as int16: eight waves, nt stores, level 0 alone (all the plan sets the flag for)
+        if constexpr (NW == 8) {
+            if (L.njobs2 > 0 || L.wg_store != 1 || L.njobs <= 0) return hipErrorInvalidValue;
+            hipExtLaunchKernelGGL((dwt53_fwd_rgba8_wg16_kernel<8, 1, 6>), dim3(L.njobs), dim3(8 * 64), 0, s, L.ev_start, L.ev_stop, 0,
+                                  L.jobs, L.njobs, L.planes, pix, out, nxt, dc, L.pix_stride);
+            return hipGetLastError();
+        }
+        return hipErrorInvalidValue;
+    }
 #define J2K_WG(FL) hipExtLaunchKernelGGL((dwt53_fwd_rgba8_wg_kernel<NW, FL, 6>), dim3(L.njobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \
                                          L.jobs, L.njobs, L.planes, pix, out, nxt, dc, L.pix_stride)
     // with a fused part the event pair brackets both launches (start on the first, stop on the second)
@@ -1385,7 +1394,7 @@ hipError_t launch_dwt53_fwd(hipStream_t s, const LevelLaunch &L, const int32_t *
         if (L.njobs <= 0 && L.njobs2 <= 0) return hipSuccess;
         if (L.pix_stride <= 0 || L.ncomp != 3) return hipErrorInvalidValue;
         if (L.mallat) {        // a Mallat plan: eight waves, nt stores, RGBA8 pixels, level 0 alone (all the plan builds a table for)
-            if (L.wg_waves != 8 || L.wg_store != 1 || L.njobs2 > 0 || L.ycc.y || L.njobs <= 0) return hipErrorInvalidValue;
+            if (L.wg_waves != 8 || L.wg_store != 1 || L.njobs2 > 0 || L.ycc.y || L.njobs <= 0 || L.scr16) return hipErrorInvalidValue;
             hipExtLaunchKernelGGL((dwt53_fwd_rgba8_wg_kernel<8, 1, 6, true>), dim3(L.njobs), dim3(8 * 64), 0, s, L.ev_start, L.ev_stop, 0,
                                   L.jobs, L.njobs, L.planes, reinterpret_cast<const uint32_t *>(src), out, nxt, dc_shift, L.pix_stride);
             return hipGetLastError();
@@ -1428,9 +1437,15 @@ hipError_t launch_dwt53_inv(hipStream_t s, const LevelLaunch &L, const int32_t *
         if (L.pix_stride <= 0 || L.ncomp != 3 || !final_level) return hipErrorInvalidValue;
         uint32_t *pix = reinterpret_cast<uint32_t *>(dst);
         if (L.mallat) {        // a Mallat plan: four waves, everything in registers (all the plan builds a table for)
-            if (L.wg_waves != 4 || L.wg_store != 5) return hipErrorInvalidValue;
+            if (L.wg_waves != 4 || L.wg_store != 5 || L.scr16_fmt) return hipErrorInvalidValue;
             hipExtLaunchKernelGGL((dwt53_inv_rgba8_wg_kernel<4, 5, false, true>), dim3(L.njobs), dim3(4 * 64), 0, s, L.ev_start, L.ev_stop, 0,
                                   L.jobs, L.njobs, L.planes, coef, prev, pix, dc_shift, L.pix_stride, L.guard);
+            return hipGetLastError();
+        }
+        if (L.scr16_fmt) {     // behind dwt53_deep_inv16_kernel: four waves, everything in registers (all the plan sets the flag for)
+            if (L.wg_waves != 4 || L.wg_store != 5) return hipErrorInvalidValue;
+            hipExtLaunchKernelGGL((dwt53_inv_rgba8_wg16_kernel<4, 5>), dim3(L.njobs), dim3(4 * 64), 0, s, L.ev_start, L.ev_stop, 0,
+                                  L.jobs, L.njobs, L.planes, coef, prev, pix, dc_shift, L.pix_stride, L.guard, L.scr16_fmt);
             return hipGetLastError();
         }
 #define J2K_INVWG(NW, WPE) hipExtLaunchKernelGGL((dwt53_inv_rgba8_wg_kernel<NW, WPE>), dim3(L.njobs), dim3(NW * 64), 0, s, L.ev_start, L.ev_stop, 0, \

@@ -62,6 +62,17 @@ __device__ __forceinline__ void deep_st2_lds(int32_t *p, int a, int b) { *(lds_v
 #define DEEP_HAS_MID 0x10000
 #define DEEP_COMPACT 0x20000      /* inverse: the LDS levels' coefficients staged as compact runs (see dwt53_deep_inv_body) */
 extern __shared__ __attribute__((aligned(16))) int32_t deep_lds[];
+// A row of X_{l0} that dwt53_fwd_rgba8_wg16_kernel stored (st_scr16, dwt53_l0pix.inc): int16 in the first half of the row's int32-sized
+// slot, four per lane in one 8-byte load, sign-extended.  Lanes past the row end load column 0 and are zeroed, as in load_cols.
+typedef short deep_v4s __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) deep_v4s glb_v4s_t;
+__device__ __forceinline__ void deep_load_cols16(const int32_t *__restrict__ row, int c, int w, int (&x)[4]) {
+    const bool in = c < w;
+    const deep_v4s t = *(const glb_v4s_t *)(reinterpret_cast<const int16_t *>(row) + (in ? c : 0));
+    x[0] = in ? (int)t.x : 0; x[1] = in ? (int)t.y : 0; x[2] = in ? (int)t.z : 0; x[3] = in ? (int)t.w : 0;
+}
+// S16: the level-l0 input rows are 16-bit (dwt53_deep_fwd16_kernel); everything behind the load is the same
+template <bool S16 = false>
 __device__ __forceinline__ void dwt53_deep_fwd_body(const DwtJob job, const TailPlane *__restrict__ planes,
                                                     const int32_t *__restrict__ scr, int32_t *__restrict__ coef) {
     const TailPlane P = planes[job.plane];
@@ -90,7 +101,10 @@ __device__ __forceinline__ void dwt53_deep_fwd_body(const DwtJob job, const Tail
     const int qa = job.prow0 + wave * DEEP_PER;
     const bool first = wave == 0 && job.prow0 > 0;                 // needs d of the pair-row above the job
     const bool lastw = qa < q_end && qa + DEEP_PER >= q_end;       // holds the job's last pair-row: loads the even row below it
-    auto ldrow = [&](int r, int (&x)[4]) { load_cols<4, true>(src + (int64_t)min(max(r, 0), h - 1) * w, c, w, x); };
+    auto ldrow = [&](int r, int (&x)[4]) {
+        if constexpr (S16) deep_load_cols16(src + (int64_t)min(max(r, 0), h - 1) * w, c, w, x);
+        else load_cols<4, true>(src + (int64_t)min(max(r, 0), h - 1) * w, c, w, x);
+    };
     DEEP_STAMP(0, 0);
     {
         int xe[DEEP_PER][4], xo[DEEP_PER][4], xa[4] = {0, 0, 0, 0}, xb[4] = {0, 0, 0, 0}, xn[4] = {0, 0, 0, 0};
@@ -205,9 +219,22 @@ __global__ __launch_bounds__(64 * DEEP_WAVES) __attribute__((amdgpu_waves_per_eu
     if (job.plane < 0) return;
     dwt53_deep_fwd_body(job, planes, scr, coef);
 }
+// ... behind dwt53_fwd_rgba8_wg16_kernel: the rows of X_{l0} are int16 (deep_load_cols16)
+__global__ __launch_bounds__(64 * DEEP_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void dwt53_deep_fwd16_kernel(const DwtJob *__restrict__ jobs, const TailPlane *__restrict__ planes,
+                                                                           const int32_t *__restrict__ scr, int32_t *__restrict__ coef) {
+    const DwtJob job = jobs[blockIdx.x];
+    if (job.plane < 0) return;
+    dwt53_deep_fwd_body<true>(job, planes, scr, coef);
+}
 
+// S16 (dwt53_deep_inv16_kernel; option l0_scr16 bit 1): a wave that stores a row of X_{l0} -- it holds the whole row, four columns per lane --
+// votes on "every value of the row fits int16".  If so the row goes out as int16 in the first half of its int32-sized slot (8 bytes per
+// lane), else as int32 as ever; either way lane 0 writes the row's format byte (1 = int16) to fmt[(scr_off + row * w) >> 3] -- rows start
+// at least 8 elements apart (w >= 8), so no two rows share a byte -- with an ordinary byte store.  Every row is stored once per call by one
+// wave, so the table is rewritten whole on every call.  Exact for every input: a narrow row is one whose sign extension gives it back.
+template <bool S16 = false>
 __device__ __forceinline__ void dwt53_deep_inv_body(const DwtJob job, const TailPlane *__restrict__ planes,
-                                                    const int32_t *__restrict__ coef, int32_t *__restrict__ scr) {
+                                                    const int32_t *__restrict__ coef, int32_t *__restrict__ scr, uint8_t *__restrict__ fmt = nullptr) {
     const TailPlane P = planes[job.plane];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int w = P.w, h = P.h;
@@ -307,6 +334,19 @@ __device__ __forceinline__ void dwt53_deep_inv_body(const DwtJob job, const Tail
     };
     // pair-rows [p0, p0 + np) of level l0: every row they need requested at once, the vertical steps with one LDS exchange (e of
     // the pair-row below), then the horizontal inverse of each row
+    [[maybe_unused]] auto st_row = [&](int r, const int (&x)[4]) {      // (S16 only: the int32 form keeps its own statements below)
+        {
+            const bool wide = active && ((x[0] != (int)(short)x[0]) | (x[1] != (int)(short)x[1]) | (x[2] != (int)(short)x[2]) | (x[3] != (int)(short)x[3]));
+            const bool narrow = __builtin_amdgcn_ballot_w64(wide) == 0;       // wave-uniform
+            if (narrow) {
+                if (active) {
+                    const unsigned lo = __builtin_amdgcn_perm((unsigned)x[1], (unsigned)x[0], 0x05040100u), hi = __builtin_amdgcn_perm((unsigned)x[3], (unsigned)x[2], 0x05040100u);
+                    *(glb_v2i_t *)(reinterpret_cast<int16_t *>(dst + (int64_t)r * w) + c) = (deep_v2i){(int)lo, (int)hi};
+                }
+            } else if (active) *reinterpret_cast<int4 *>(dst + (int64_t)r * w + c) = make_int4(x[0], x[1], x[2], x[3]);
+            if (lane == 0) fmt[(P.scr_off + (int64_t)r * w) >> 3] = narrow ? 1 : 0;
+        }
+    };
     auto level0_rows = [&](int p0, int np) {
         const int q_end = min(p0 + np, halfH);
         const int qa = p0 + wave * DEEP_PER;
@@ -351,7 +391,8 @@ __device__ __forceinline__ void dwt53_deep_inv_body(const DwtJob job, const Tail
             const bool inner = (i + 1 < DEEP_PER) && (q + 1 < q_end);
             int x[4];
             hinv<4>(Sl[i], Sh[i], c, w, x);
-            if (active) *reinterpret_cast<int4 *>(dst + (int64_t)(2 * q) * w + c) = make_int4(x[0], x[1], x[2], x[3]);
+            if constexpr (S16) st_row(2 * q, x);
+            else if (active) *reinterpret_cast<int4 *>(dst + (int64_t)(2 * q) * w + c) = make_int4(x[0], x[1], x[2], x[3]);
             if (2 * q + 1 < h) {
                 int ol[2], oh[2];
 #pragma unroll
@@ -361,7 +402,8 @@ __device__ __forceinline__ void dwt53_deep_inv_body(const DwtJob job, const Tail
                     oh[j] = wadd(Dh[i][j], has_next ? avg1(Sh[i][j], nh) : Sh[i][j]);
                 }
                 hinv<4>(ol, oh, c, w, x);
-                if (active) *reinterpret_cast<int4 *>(dst + (int64_t)(2 * q + 1) * w + c) = make_int4(x[0], x[1], x[2], x[3]);
+                if constexpr (S16) st_row(2 * q + 1, x);
+                else if (active) *reinterpret_cast<int4 *>(dst + (int64_t)(2 * q + 1) * w + c) = make_int4(x[0], x[1], x[2], x[3]);
             }
         }
     };
@@ -422,6 +464,13 @@ __global__ __launch_bounds__(64 * DEEP_WAVES) __attribute__((amdgpu_waves_per_eu
     if (job.plane < 0) return;
     dwt53_deep_inv_body(job, planes, coef, scr);
 }
+// ... in front of dwt53_inv_rgba8_wg16_kernel: rows of X_{l0} that fit are stored as int16, fmt says which (the body's st_row)
+__global__ __launch_bounds__(64 * DEEP_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void dwt53_deep_inv16_kernel(const DwtJob *__restrict__ jobs, const TailPlane *__restrict__ planes,
+                                                                           const int32_t *__restrict__ coef, int32_t *__restrict__ scr, uint8_t *__restrict__ fmt) {
+    const DwtJob job = jobs[blockIdx.x];
+    if (job.plane < 0) return;
+    dwt53_deep_inv_body<true>(job, planes, coef, scr, fmt);
+}
 
 // ================================================================================================================
 // The deep levels and HALF OF LEVEL 0 in one launch (packed RGBA8 frames).  The deep workgroups' chain (memory -> level 1 ->
@@ -466,8 +515,18 @@ extern "C" int j2k_dev_deep_wstamps(unsigned long long *out) { return (int)hipMe
 #endif
 
 hipError_t launch_dwt53_deep_fwd(hipStream_t s, const DwtJob *jobs, int njobs, const TailPlane *planes, size_t lds_bytes, const int32_t *scr,
-                                 int32_t *coef, hipEvent_t ev0, hipEvent_t ev1) {
+                                 int32_t *coef, hipEvent_t ev0, hipEvent_t ev1, int scr16) {
     if (njobs <= 0) return hipSuccess;
+    if (scr16) {               // the level-0 launch of this call stored the rows of `scr` as int16 (dwt53_fwd_rgba8_wg16_kernel)
+        static bool attr16_done = false;
+        if (!attr16_done) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dwt53_deep_fwd16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            if (e != hipSuccess) return e;
+            attr16_done = true;
+        }
+        hipExtLaunchKernelGGL(dwt53_deep_fwd16_kernel, dim3(njobs), dim3(64 * DEEP_WAVES), lds_bytes, s, ev0, ev1, 0, jobs, planes, scr, coef);
+        return hipGetLastError();
+    }
     static bool attr_done = false;
     if (!attr_done) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dwt53_deep_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
@@ -478,8 +537,18 @@ hipError_t launch_dwt53_deep_fwd(hipStream_t s, const DwtJob *jobs, int njobs, c
     return hipGetLastError();
 }
 hipError_t launch_dwt53_deep_inv(hipStream_t s, const DwtJob *jobs, int njobs, const TailPlane *planes, size_t lds_bytes, const int32_t *coef,
-                                 int32_t *scr, hipEvent_t ev0, hipEvent_t ev1) {
+                                 int32_t *scr, hipEvent_t ev0, hipEvent_t ev1, uint8_t *scr16_fmt) {
     if (njobs <= 0) return hipSuccess;
+    if (scr16_fmt) {           // the level-0 launch of this call is dwt53_inv_rgba8_wg16_kernel: rows that fit go out as int16, scr16_fmt says which
+        static bool attr16_done = false;
+        if (!attr16_done) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dwt53_deep_inv16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            if (e != hipSuccess) return e;
+            attr16_done = true;
+        }
+        hipExtLaunchKernelGGL(dwt53_deep_inv16_kernel, dim3(njobs), dim3(64 * DEEP_WAVES), lds_bytes, s, ev0, ev1, 0, jobs, planes, coef, scr, scr16_fmt);
+        return hipGetLastError();
+    }
     static bool attr_done = false;
     if (!attr_done) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dwt53_deep_inv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);

@@ -39,6 +39,21 @@ __device__ __forceinline__ void st_final(v4i *p, const v4i &v) {
     else *p = v;
 }
 
+// The 16-bit hand-off to the deep launch (option l0_scr16; dwt53_fwd_rgba8_wg16_kernel -> dwt53_deep_fwd16_kernel).  What level 0 of a
+// packed 8-bit frame sends to `nxt` is bounded whatever the pixels are.  With raw bytes R, G, B the lifted inputs are Y + c =
+// (R + 2G + B) >> 2 in [0, 255] and U = B - G, V = R - G in [-255, 255]: |x| <= M = 255.  One 1-D lifting step of values |x| <= M gives
+//     d = x_odd - ((x_e + x_e') >> 1),  |d| <= 2M;      s = x_e + ((d + d' + 2) >> 2),  |s| <= M + ((4M + 2) >> 2) = 2M,
+// so after the horizontal and the vertical step every L / H half-row element is within 4M = 1020, and the LL quadrant of Y has the DC
+// shift c subtracted once more: |value| <= 4 * 255 + 3 + c (the + 3 is slack, not needed), 1151 for c = 128 -- 12 bits of int16's 16.
+// The plan checks J2K_SCR16_BOUND + dc_shift against INT16_MAX before it chooses these kernels (j2k_planbuild.cpp), so the
+// truncation below drops only copies of the sign bit and the reader's sign extension gives the int32 back.
+// p = the row's slot + 2 * lane int32s, i.e. int16 element 4 * lane of the row: one 8-byte store instead of a 16-byte one.
+__device__ __forceinline__ void st_scr16(int32_t *p, const v4i &v) {
+    const unsigned lo = __builtin_amdgcn_perm((unsigned)v.y, (unsigned)v.x, 0x05040100u);      // low halves of x | y << 16
+    const unsigned hi = __builtin_amdgcn_perm((unsigned)v.w, (unsigned)v.z, 0x05040100u);
+    *reinterpret_cast<v2i *>(p) = (v2i){(int)lo, (int)hi};
+}
+
 
 // ================================================================================================================
 // Workgroup form (round 2, the one the plan launches): NO recomputation.  A workgroup of NW wavefronts owns NW-1
@@ -62,6 +77,7 @@ __device__ __forceinline__ void dwt53_fwd_rgba8_wg_body(v4i (&slot)[NW][6][64], 
                                                         const uint32_t *__restrict__ pix, int32_t *__restrict__ out, int32_t *__restrict__ nxt,
                                                         int dc_shift, int pix_stride) {
     constexpr bool MAL = false;                    // (the merged launch is not built for Mallat plans)
+    constexpr bool S16 = false;                    // (... nor for the 16-bit hand-off)
 #include "dwt53_l0pix_fwd_body.inc"
 }
 // MAL: the level 0 of a Mallat plan (the body's store_row)
@@ -73,6 +89,20 @@ void dwt53_fwd_rgba8_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
     __shared__ v4i slot[NW][6][64];
     const DwtJob job = jobs[blockIdx.x];           // uniform: scalar loads
     if (job.plane < 0) return;                     // padding entry of the XCD-aware job order (whole workgroup, before any barrier)
+    constexpr bool S16 = false;
+#include "dwt53_l0pix_fwd_body.inc"
+}
+// The same workgroup with the rows of X_1 stored as int16 (st_scr16; option l0_scr16): a kernel of its own name, so that the one above
+// stays what it was.  Prefix plans only, and only when dwt53_deep_fwd16_kernel reads the scratch next (plan_forward_impl).
+template <int NW, int NT, int WPE>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
+void dwt53_fwd_rgba8_wg16_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
+                                 const uint32_t *__restrict__ pix, int32_t *__restrict__ out, int32_t *__restrict__ nxt,
+                                 int dc_shift, int pix_stride) {
+    __shared__ v4i slot[NW][6][64];
+    const DwtJob job = jobs[blockIdx.x];
+    if (job.plane < 0) return;
+    constexpr bool MAL = false, S16 = true;
 #include "dwt53_l0pix_fwd_body.inc"
 }
 // The same workgroup over an image.YCbCr (encoder.go:178-195, the default branch; j2k_plan_forward_image): SRC = 1 + J2K_YCBCR_444 /
@@ -88,6 +118,7 @@ void dwt53_fwd_ycc_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
     const DwtJob job = jobs[blockIdx.x];
     if (job.plane < 0) return;
     constexpr bool MAL = false;                    // (prefix plans only: plan_rgba8_wg_fusable)
+    constexpr bool S16 = false;                    // (the YCbCr source keeps the int32 hand-off)
 #include "dwt53_l0pix_fwd_body.inc"
 }
 #undef J2K_L0_YCC
@@ -108,10 +139,15 @@ void dwt53_fwd_ycc_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const D
 // ================================================================================================================
 // MAL: the level 0 of a Mallat plan -- load_row routes as inv_load_row<MAL> does: LL (the low half of a low-pass row, while there is a coarser
 // level) from its dense (w/2) x ceil(h/2) result, every other half-row from the plane at row * coef_stride + column.
-template <int NW, bool PARK, bool MAL = false>
+// S16 (dwt53_inv_rgba8_wg16_kernel, behind dwt53_deep_inv16_kernel; option l0_scr16 bit 1): a half-row of `prev` is int16 in the first half of its
+// slot when its format byte says so (fmt[(nxt_off + row start) >> 3] = 1), else int32.  The 8-byte load of the narrow form and the byte are issued
+// with the coefficient loads, addressed from the plane table alone -- neither waits for the other, so a narrow row costs no round trip more
+// than before; only a row marked wide (a wave-uniform branch: one byte per half-row) pays a second one for its 16-byte load.
+template <int NW, bool PARK, bool MAL = false, bool S16 = false>
 __device__ __forceinline__ void dwt53_inv_rgba8_wg_body(v4i (&slot)[NW][PARK ? 8 : 6][64], const DwtJob job, const DwtPlane *__restrict__ planes,
                                                         const int32_t *__restrict__ coef, const int32_t *__restrict__ prev, uint32_t *__restrict__ pix,
-                                                        int dc_shift, int pix_stride) {
+                                                        int dc_shift, int pix_stride, const uint8_t *__restrict__ fmt = nullptr) {
+    static_assert(!(S16 && MAL), "the 16-bit hand-off is not built for Mallat plans");
     constexpr int NR = NW - 1;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -149,6 +185,45 @@ __device__ __forceinline__ void dwt53_inv_rgba8_wg_body(v4i (&slot)[NW][PARK ? 8
             v[2 * k + 1] = *reinterpret_cast<const v4i *>((finH ? coef + P.src_off[k] : prev + P.nxt_off[k]) + idxH);
         }
     };
+    // S16, a low-pass row (the only rows with halves below n_next): the loads ...
+    [[maybe_unused]] auto load_row16 = [&](int ro, v4i (&v)[6], int (&f)[6]) {
+        const int rowL = ro * w, rowH = rowL + halfW;
+        const bool finL = rowL >= P.n_next, finH = rowH >= P.n_next;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+#pragma unroll
+            for (int hf = 0; hf < 2; hf++) {
+                const int row = hf ? rowH : rowL;
+                if (hf ? finH : finL) {
+                    v[2 * k + hf] = *reinterpret_cast<const v4i *>(coef + P.src_off[k] + row + lo4);
+                    f[2 * k + hf] = 1;
+                } else {
+                    const v2i t = *reinterpret_cast<const v2i *>(prev + P.nxt_off[k] + row + (lo4 >> 1));      // int16 element 4 * lane
+                    v[2 * k + hf] = (v4i){t.x, t.y, 0, 0};
+                    f[2 * k + hf] = fmt[(P.nxt_off[k] + row) >> 3];
+                }
+            }
+        }
+    };
+    // ... and what they mean: a narrow half-row is sign-extended, one marked wide is loaded again as int32
+    [[maybe_unused]] auto fix_row16 = [&](int ro, v4i (&v)[6], const int (&f)[6]) {
+        const int rowL = ro * w, rowH = rowL + halfW;
+        const bool finL = rowL >= P.n_next, finH = rowH >= P.n_next;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+#pragma unroll
+            for (int hf = 0; hf < 2; hf++) {
+                if (hf ? finH : finL) continue;
+                const int row = hf ? rowH : rowL;
+                if (__builtin_amdgcn_readfirstlane(f[2 * k + hf])) {
+                    const int a = v[2 * k + hf].x, b = v[2 * k + hf].y;
+                    v[2 * k + hf] = (v4i){(int)(short)a, a >> 16, (int)(short)b, b >> 16};
+                } else {
+                    v[2 * k + hf] = *reinterpret_cast<const v4i *>(prev + P.nxt_off[k] + row + lo4);
+                }
+            }
+        }
+    };
     v4i S[6], D[6];
     const v4i two = {2, 2, 2, 2};
     if (helper) {
@@ -162,11 +237,25 @@ __device__ __forceinline__ void dwt53_inv_rgba8_wg_body(v4i (&slot)[NW][PARK ? 8
             for (int v = 0; v < 6; v++) slot[0][v][lane] = Da[v];
         }
         asm volatile("" ::: "memory");
+        if constexpr (S16) {
+            int f[6];
+            load_row16(min(q0 + NR, halfH - 1), S, f);
+            load_row(halfH + min(q0 + NR, max(nhigh - 1, 0)), D);
+            fix_row16(min(q0 + NR, halfH - 1), S, f);
+        } else {
         load_row(min(q0 + NR, halfH - 1), S);
         load_row(halfH + min(q0 + NR, max(nhigh - 1, 0)), D);
+        }
     } else if (live) {
+        if constexpr (S16) {
+            int f[6];
+            load_row16(q, S, f);
+            load_row(halfH + min(q, max(nhigh - 1, 0)), D);
+            fix_row16(q, S, f);
+        } else {
         load_row(q, S);
         load_row(halfH + min(q, max(nhigh - 1, 0)), D);      // odd height: the last pair-row has no d row (clamped, unused)
+        }
 #pragma unroll
         for (int v = 0; v < 6; v++) slot[wv + 1][v][lane] = D[v];
     }
@@ -273,6 +362,19 @@ void dwt53_inv_rgba8_wg_kernel(const DwtJob *__restrict__ jobs, int njobs, const
     const DwtJob job = jobs[blockIdx.x];
     if (job.plane < 0) return;
     dwt53_inv_rgba8_wg_body<NW, PARK, MAL>(slot, job, planes, coef, prev, pix, dc_shift, pix_stride);
+}
+// The same workgroup behind dwt53_deep_inv16_kernel: the half-rows of `prev` are int16 where fmt says so (the body's S16).  A kernel of its own
+// name, so that the one above stays what it was; four waves, everything in registers (the default shape, all the plan sets the flag for).
+template <int NW, int WPE>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
+void dwt53_inv_rgba8_wg16_kernel(const DwtJob *__restrict__ jobs, int njobs, const DwtPlane *__restrict__ planes,
+                                 const int32_t *__restrict__ coef, const int32_t *__restrict__ prev, uint32_t *__restrict__ pix,
+                                 int dc_shift, int pix_stride, const int *__restrict__ guard, const uint8_t *__restrict__ fmt) {
+    __shared__ v4i slot[NW][6][64];
+    if (guard && *guard) return;
+    const DwtJob job = jobs[blockIdx.x];
+    if (job.plane < 0) return;
+    dwt53_inv_rgba8_wg_body<NW, false, false, true>(slot, job, planes, coef, prev, pix, dc_shift, pix_stride, fmt);
 }
 
 // ================================================================================================================

@@ -1,7 +1,8 @@
 // dwt53_l0pix_fwd_body.inc -- the statements of one workgroup of the packed-RGBA8 level-0 forward transform (see dwt53_l0pix.inc),
 // included TEXTUALLY by dwt53_fwd_rgba8_wg_kernel (its own static LDS array) and by dwt53_fwd_rgba8_wg_body (dynamic LDS of
 // dwt53_mega_fwd_kernel): as a function call the kernel lost two registers to the inliner's different schedule and spilled.
-// Names it expects in scope: NW, NT (template parameters), MAL (a compile-time bool: Mallat routing of the stores, see store_row), slot
+// Names it expects in scope: NW, NT (template parameters), MAL (a compile-time bool: Mallat routing of the stores, see store_row), S16 (a
+// compile-time bool: the rows of X_1 as int16, see store_row; never with MAL), slot
 // (v4i [NW][6][64] in LDS), job (DwtJob), planes, pix, out, nxt, dc_shift, pix_stride.
 
     constexpr int NR = NW - 1;                     // regular waves = pair-rows per workgroup
@@ -100,15 +101,21 @@
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const v4i vl = (k == 0) ? v[0] - ysub : v[2 * k];
+            // S16 (dwt53_fwd_rgba8_wg16_kernel): a half-row below n_next -- a row of X_1, read back by the deep launch alone -- goes out
+            // as four int16 per lane in the first half of its int32-sized slot (st_scr16: the bound, and why nothing is lost)
             if (finL) {
                 v4i *bl = reinterpret_cast<v4i *>(out + P.out_off[k] + idxL);
                 st_final<NT>(bl, vl);
+            } else if constexpr (S16) {
+                st_scr16(nxt + P.nxt_off[k] + idxL - lane * 2, vl);
             } else {
                 *reinterpret_cast<v4i *>(nxt + P.nxt_off[k] + idxL) = vl;
             }
             if (finH) {
                 v4i *bh = reinterpret_cast<v4i *>(out + P.out_off[k] + idxH);
                 st_final<NT>(bh, v[2 * k + 1]);
+            } else if constexpr (S16) {
+                st_scr16(nxt + P.nxt_off[k] + idxH - lane * 2, v[2 * k + 1]);
             } else {
                 *reinterpret_cast<v4i *>(nxt + P.nxt_off[k] + idxH) = v[2 * k + 1];
             }

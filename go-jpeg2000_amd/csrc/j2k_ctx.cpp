@@ -52,6 +52,7 @@ static const std::vector<CtxOption> &ctx_options() {
         OPT("l0_wg_invw", v == 0 || v == 4 || v == 8, c->l0_wg_invw = (int)v),
         OPT("l0_xcd_group", v >= 0 && v <= 4096, c->l0_xcd_group = (int)v),
         OPT("l0_store", v == 0 || v == 1 || v == 2 || v == 4, c->l0_store = (int)v),
+        OPT("l0_scr16", v >= 0 && v <= 3, c->l0_scr16 = (int)v),
         OPT("fuse_compact", v == 0 || v == 1, c->fuse_compact = v != 0),
         OPT("deep", v == 0 || v == 1, c->use_deep = v != 0),
         OPT("deep_min_planes", v >= 0 && v <= 1000000, c->deep_min_planes = (int)v),

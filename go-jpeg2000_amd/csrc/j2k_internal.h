@@ -118,7 +118,12 @@ struct LevelLaunch {
     YccSrc ycc;           // ycc.y non-null: level 0 of the workgroup form reads this YCbCr image instead of packed RGBA8
     const int *guard;     // inverse: non-null = a device word; the launch writes nothing if it is not 0 (the frame decoder's status, j2k_frame.cpp)
     int mallat;           // 1: a level of a Mallat plan (DwtPlane::coef_stride): the MAL instantiation of the general kernels
+    const uint8_t *scr16_fmt;   // inverse, non-null: the workgroup form of the packed RGBA8 level 0 reads the half-rows of X_1 as int16 where this table says so
+                                // (dwt53_inv_rgba8_wg16_kernel behind dwt53_deep_inv16_kernel; j2k_plan::d_scr16_fmt)
+    int scr16;            // 1: the workgroup form of the packed RGBA8 level 0 stores the rows of X_1 as int16 (dwt53_fwd_rgba8_wg16_kernel; j2k_plan::scr16_fwd)
 };
+// |element of X_1| <= J2K_SCR16_BOUND + dc_shift after level 0 of a packed 8-bit frame (derived at st_scr16, dwt53_l0pix.inc)
+#define J2K_SCR16_BOUND (4 * 255 + 3)
 
 hipError_t launch_dwt53_fwd(hipStream_t s, const LevelLaunch &L, const int32_t *src, int32_t *out,
                             int32_t *nxt, int dc_shift);
@@ -130,10 +135,11 @@ hipError_t launch_dwt53_tail_inv(hipStream_t s, const TailPlane *planes, int npl
                                  int32_t *scr, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 // every level below level 0 in one launch (dwt53_deep.inc); ev0 / ev1: optional begin / end events stamped by the dispatch
+// scr16: the rows of `scr` are int16 in the first half of their slots (the level-0 launch was dwt53_fwd_rgba8_wg16_kernel)
 hipError_t launch_dwt53_deep_fwd(hipStream_t s, const DwtJob *jobs, int njobs, const TailPlane *planes, size_t lds_bytes, const int32_t *scr,
-                                 int32_t *coef, hipEvent_t ev0, hipEvent_t ev1);
+                                 int32_t *coef, hipEvent_t ev0, hipEvent_t ev1, int scr16 = 0);
 hipError_t launch_dwt53_deep_inv(hipStream_t s, const DwtJob *jobs, int njobs, const TailPlane *planes, size_t lds_bytes, const int32_t *coef,
-                                 int32_t *scr, hipEvent_t ev0, hipEvent_t ev1);
+                                 int32_t *scr, hipEvent_t ev0, hipEvent_t ev1, uint8_t *scr16_fmt = nullptr);   // scr16_fmt: dwt53_deep_inv16_kernel and its format table
 
 hipError_t launch_dwt53_mega_fwd(hipStream_t s, const DwtJob *jobs, int njobs, const TailPlane *tplanes, const DwtPlane *l0planes, size_t lds_bytes,
                                  const int32_t *scr, int32_t *coef, const uint32_t *pix, int32_t *nxt0, int dc_shift, int pix_stride,

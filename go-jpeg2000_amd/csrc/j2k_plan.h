@@ -36,6 +36,9 @@ struct j2k_ctx {
     int l0_inv_wpe = 5;        // its occupancy variant (J2K_L0_INV_WPE: 5 = all in registers, 26.4 us; 6 = odd row parked in LDS for 6 waves per SIMD, measured slower: 33.6 us)
     bool l0_wg_inv = true;     // the inverse level 0 to RGBA8 in workgroup form too (J2K_L0_WG_INV=0: the general kernel)
     int l0_store = 1;          // its final-coefficient store flavour (J2K_L0_STORE: 0 plain, 1 nt, 2 sc1, 4 sc1 nt)
+    int l0_scr16 = 1;          // J2K_L0_SCR16 (bit 0 forward, bit 1 inverse; 0 ... 3): packed RGBA8 forward, level 0 hands X_1 to the deep launch as int16 rows (dwt53_fwd_rgba8_wg16_kernel ->
+                               // dwt53_deep_fwd16_kernel; j2k_plan::scr16_fwd says when; 0 = int32 rows, the kernels as they were).  Measured: level 0
+                               // 23.0 -> 21.0 us solo, headline 82.2-83.0 -> 84.7-85.0 Gpixel/s (docs/KERNEL_NOTES.md 4ae)
     int band_prows_pix = 3;    // packed-pixel level-0 forward (J2K_BAND_PROWS_PIX)
     int band_prows_97 = 8;     // 9-7 kernels: 7 halo rows per band, so taller bands (J2K_BAND_PROWS_97)
     int band_prows_inv = 0;    // 0: same as band_prows (J2K_BAND_PROWS_INV)
@@ -183,6 +186,10 @@ struct j2k_plan {
     size_t tail_lds_fwd = 0, tail_lds_inv = 0;
     // every level below level 0 in one launch per direction (dwt53_deep.inc): levels deep_l0 .. levels-1; -1 = not used
     int deep_l0 = -1;
+    bool scr16_inv = false;                     // inverse_rgba8 of this plan may: rows of X_1 that fit int16 are stored so, d_scr16_fmt[(element offset of the row) >> 3] = 1 says which
+    uint8_t *d_scr16_fmt = nullptr;
+    bool last_fwd_scr16 = false, last_inv_scr16 = false;   // what the plan's last forward / inverse call launched (j2k_plan_scr16 bits 2, 3)
+    bool scr16_fwd = false;                     // forward_rgba8 of this plan may hand X_1 over as int16 rows (option l0_scr16; the conditions: j2k_planbuild.cpp)
     j2k::TailPlane *d_deep_planes = nullptr;    // dims at level deep_l0
     j2k::DwtJob *d_deep_jobs = nullptr;         // deep workgroups first, then the flat ones
     int ndeep_jobs = 0;

@@ -616,6 +616,27 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
     }
     if (sa) { hipError_t e = hipMalloc(&P->d_scrA, (size_t)sa * esz); if (e != hipSuccess) { j2k_plan_destroy(P); return fail_hip(ctx, e, "hipMalloc scratch A"); } }
     if (sb) { hipError_t e = hipMalloc(&P->d_scrB, (size_t)sb * esz); if (e != hipSuccess) { j2k_plan_destroy(P); return fail_hip(ctx, e, "hipMalloc scratch B"); } }
+    // The 16-bit hand-off of X_1 (option l0_scr16): only where the writer is the packed-RGBA8 workgroup kernel in its default shape (eight
+    // waves, nt stores -- the one instantiation of dwt53_fwd_rgba8_wg16_kernel) and the only reader the deep launch starting at level 1.
+    // Everything else keeps int32 rows: Mallat plans, 9-7, level 0 fused with level 1 (l0_fuse) or merged with the deep launch (mega), frames
+    // with a single-component plane beside the triples (the plane kernels write its prefix), the per-level and LDS-tail launches.  The
+    // planar calls of the same plan (arbitrary int32 planes) and a YCbCr source keep int32 rows in the same buffer: the choice is made per
+    // call (plan_forward_impl), the row slots are the same.  8-bit unsigned samples bound what is stored (J2K_SCR16_BOUND).
+    P->scr16_fwd = (ctx->l0_scr16 & 1) && S.wavelet == W53 && !S.mallat && S.C == 3 && S.mct && S.precision == 8 && S.dc_shift == 128 &&
+                   J2K_SCR16_BOUND + S.dc_shift <= INT16_MAX && P->deep_l0 == 1 && P->d_deep_jobs && P->d_fwd_wg_jobs && P->fwd_wg_waves == 8 &&
+                   !P->d_fwd_wg2_jobs && !P->d_mega_fwd_jobs && !P->fwd[0][0].njobs;      // (and l0_store == 1, read per call as the launch reads it)
+    // The inverse direction (option bit 1): the values are a decoder's, so the format is chosen per stored row at run time (dwt53_deep_inv_body's
+    // vote) and recorded in d_scr16_fmt, one byte per 8 elements of the scratch (rows of X_1 are at least 8 long), rewritten by every call that
+    // uses it.  Only where the one reader of X_1 is the packed-RGBA8 workgroup kernel in its default shape (four waves, everything in registers
+    // -- the one instantiation of dwt53_inv_rgba8_wg16_kernel), per call (plan_inverse_impl): the general level-0 kernel (planar, reduced and
+    // area calls, l0_wg_inv = 0), the plane kernels (a fourth component: no such plane may be in the frame) and the merged launch read int32 rows
+    // and get them from dwt53_deep_inv_kernel as ever.  Batch and shard plans are plans like any other here: same tables, same two launches.
+    if ((ctx->l0_scr16 & 2) && S.wavelet == W53 && !S.mallat && S.C == 3 && S.mct && P->deep_l0 == 1 && P->d_deep_jobs_inv && P->d_inv_wg_jobs &&
+        P->inv_wg_waves == 4 && !P->inv[0][0].njobs && sa) {
+        hipError_t e = hipMalloc((void **)&P->d_scr16_fmt, (size_t)sa / 8 + 16);
+        if (e != hipSuccess) { j2k_plan_destroy(P); return fail_hip(ctx, e, "hipMalloc scratch format table"); }
+        P->scr16_inv = true;
+    }
 
     // ---- code-block jobs: encoder.go:616-673 per tile, top-left addressing (encoder.go:763-795) ----
     // (closed-loop mode, j2k_params.closed_loop: the same order, but band b of resolution r is the Mallat rectangle of level
@@ -918,7 +939,7 @@ extern "C" void j2k_plan_destroy(j2k_plan *P) {
                     P->d_t2_packets, P->d_tile_packet0, P->d_t2_cbs, P->d_t2_poffs, P->d_t2_ptile, P->d_t2_ws, P->d_t2_chains, P->d_t2_body_base, P->d_t2_par, P->d_frame_status,
                     P->d_cl_decoded, P->d_cl_coeff, P->d_cl_coeff_dec, P->d_cl_numbps, P->d_cl_offs, P->d_cl_lens, P->d_host_io, P->d_host_pix,
                     P->d_rate_wj, P->d_rate_ws, P->d_cl_rate, P->d_cl_dense, P->d_cl_lfloors,
-                    P->d_area_blocks, P->d_area_planes, P->d_area_frame};
+                    P->d_area_blocks, P->d_area_planes, P->d_area_frame, P->d_scr16_fmt};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete P;
 }

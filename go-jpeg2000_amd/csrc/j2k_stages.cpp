@@ -33,6 +33,8 @@ int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix
     const int nlevel_launches = (P->deep_l0 >= 0) ? P->deep_l0 : ((P->tail_l0 >= 0) ? P->tail_l0 : S.levels);
     bool fused_l1 = false;             // level 1 ran inside the level-0 launch (packed RGBA8 frames, dwt53_fwd_rgba8_wg2_kernel)
     bool mega = false;                 // level 0 ran its top bands only: the merged launch below takes the rest with the deep levels
+    bool scr16 = false;                // level 0 stored the rows of X_1 as int16 (dwt53_fwd_rgba8_wg16_kernel): the deep launch reads them so
+    P->last_fwd_scr16 = false;
     for (int l = 0; l < nlevel_launches; l++)
     for (int rep_ = 0; rep_ < dev_reps(l == 0 ? 1 : (l == 1 ? 2 : 4)); rep_++) {      // (always once outside dev builds)
         if (l == 1 && fused_l1) continue;
@@ -65,6 +67,8 @@ int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix
                             L.planes1 = P->fwd[0][1].d_planes; L.nxt1 = (int32_t *)P->d_scrB;
                             fused_l1 = true;
                         }
+                        // the rows of X_1 as int16, read by the deep launch below (j2k_plan::scr16_fwd; the YCbCr source keeps int32 rows)
+                        if (P->scr16_fwd && ctx->l0_store == 1 && !pix.ycc.y && !mega && !fused_l1) { L.scr16 = 1; scr16 = true; P->last_fwd_scr16 = true; }
                     }
                 }
                 if (ev1) { L.ev_start = ev0; L.ev_stop = ev1; }
@@ -94,7 +98,7 @@ int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix
         hipEvent_t e0, e1;
         profile_pair(ctx, 1, e0, e1);
         HIPCHK(ctx, launch_dwt53_deep_fwd(ctx->stream, P->d_deep_jobs, P->ndeep_jobs, P->d_deep_planes, P->deep_lds_fwd,
-                                          (const int32_t *)((P->deep_l0 & 1) ? P->d_scrA : P->d_scrB), (int32_t *)d_coeff, e0, e1));
+                                          (const int32_t *)((P->deep_l0 & 1) ? P->d_scrA : P->d_scrB), (int32_t *)d_coeff, e0, e1, scr16 ? 1 : 0));
     }
     for (int rep_ = 0; P->deep_l0 < 0 && P->tail_l0 >= 0 && rep_ < dev_reps(4); rep_++) {
         hipEvent_t e0, e1;
@@ -115,6 +119,9 @@ int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix
     const double dq_step = (P->dequantize && S.quant == Q_ENCODER) ? 1.0 / (double)S.quality : 1.0;
     // (a guarded call keeps level 0 -- the launch that writes the frame -- apart from the deep levels: same results)
     const bool mega = P->d_mega_inv_jobs && pix.triple == 8 && pix_stride > 0 && ctx->l0_wg_inv && S.wavelet == W53 && !guard;
+    // rows of X_1 as int16 where they fit (j2k_plan::scr16_inv): only when the level-0 launch below is dwt53_inv_rgba8_wg16_kernel
+    const bool scr16 = P->scr16_inv && !mega && pix.triple == 8 && pix_stride > 0 && ctx->l0_wg_inv && ctx->l0_inv_wpe == 5 && S.wavelet == W53;
+    P->last_inv_scr16 = scr16;
     for (int rep_ = 0; mega && rep_ < dev_reps(0x100); rep_++) {
         hipEvent_t e0, e1;
         profile_pair(ctx, 3, e0, e1);
@@ -126,7 +133,7 @@ int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix
         hipEvent_t e0, e1;
         profile_pair(ctx, 3, e0, e1);
         HIPCHK(ctx, launch_dwt53_deep_inv(ctx->stream, P->d_deep_jobs_inv, P->ndeep_jobs_inv, P->d_deep_planes, P->deep_lds, (const int32_t *)d_coeff,
-                                          (int32_t *)((P->deep_l0 & 1) ? P->d_scrA : P->d_scrB), e0, e1));
+                                          (int32_t *)((P->deep_l0 & 1) ? P->d_scrA : P->d_scrB), e0, e1, scr16 ? P->d_scr16_fmt : nullptr));
     }
     for (int rep_ = 0; P->deep_l0 < 0 && P->tail_l0 >= 0 && rep_ < dev_reps(0x100); rep_++) {
         hipEvent_t e0, e1;
@@ -152,6 +159,7 @@ int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix
                     // of the inverse level table is the forward one)
                     L.jobs = P->d_inv_wg_jobs; L.njobs = P->inv_wg_njobs; L.wg_waves = P->inv_wg_waves; L.wg_store = ctx->l0_inv_wpe;
                     if (mega) { L.jobs = P->d_inv_top_jobs; L.njobs = P->inv_top_njobs; }   // the bottom bands ran beside the deep levels
+                    if (scr16) L.scr16_fmt = P->d_scr16_fmt;
                 }
                 profile_pair(ctx, l == 0 ? 2 : 3, L.ev_start, L.ev_stop);
                 HIPCHK(ctx, launch_dwt53_inv(ctx->stream, L, (const int32_t *)d_coeff, (const int32_t *)prev, (int32_t *)dst,
@@ -610,6 +618,11 @@ extern "C" int j2k_plan_pixels_fused(const j2k_plan *P, int format, const void *
     if (inverse) return ((S.precision == 8 || S.precision == 16) && pix_fusable(P, S.precision / 8, S.C == 1 ? 1 : 4, d_pix, stride, true, io)) ? 1 : 0;
     if (format < 0 || format >= 6 || kPixComp[format] != S.C) return J2K_ERR_INVALID_ARG;
     return pix_fusable(P, kPixPrec[format] / 8, S.C == 1 ? 1 : 4, d_pix, stride, false, io) ? 1 : 0;
+}
+
+extern "C" int j2k_plan_scr16(const j2k_plan *P) {
+    if (!P) return 0;
+    return (P->scr16_fwd ? 1 : 0) | (P->scr16_inv ? 2 : 0) | (P->last_fwd_scr16 ? 4 : 0) | (P->last_inv_scr16 ? 8 : 0);
 }
 
 extern "C" int j2k_plan_inverse_pixels(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride) {

@@ -387,6 +387,16 @@ class FramePlan:
             self.ctx.check(r)
         return bool(r)
 
+    @property
+    def scr16(self):
+        """does forward_rgba8 of a fused frame hand level 1's input over as 16-bit rows (context option l0_scr16)?"""
+        return bool(self.ctx.L.j2k_plan_scr16(self.h) & 1)
+
+    @property
+    def scr16_state(self):
+        """j2k_plan_scr16: 1 / 2 = the plan allows the 16-bit hand-off forward / inverse, 4 / 8 = its last forward / inverse call took it"""
+        return int(self.ctx.L.j2k_plan_scr16(self.h))
+
     # ---- image.YCbCr / CMYK / Paletted (encoder.go:178-195; j2kgfx.pixels.YCbCr / CMYK / Paletted) ---------------------------
     def _img(self, img):
         for a in img.buffers():

@@ -451,6 +451,12 @@ int j2k_plan_inverse_pixels(j2k_plan *plan, const int32_t *d_coeff, void *d_pix,
 /* 1 when that call (inverse != 0: j2k_plan_inverse_pixels, format ignored) would take the fused
  * kernels for these pixels, 0 when it would stage; < 0 on bad arguments.  Launches nothing. */
 int j2k_plan_pixels_fused(const j2k_plan *plan, int format, const void *d_pix, size_t stride, int inverse);
+/* The 16-bit hand-off of level 1's input between the packed-RGBA8 level-0 launch and the one-launch deeper levels (context
+ * option l0_scr16: bit 0 forward, bit 1 inverse; same results either way).  Bits: 1 = the plan allows it in
+ * j2k_plan_forward_rgba8 / _forward_pixels(J2K_PIX_RGBA8) of a fused frame, 2 = in j2k_plan_inverse_rgba8 / _inverse_pixels
+ * (rows that fit are stored 16-bit, chosen per row in every call), 4 / 8 = the plan's last forward / inverse call launched
+ * the 16-bit kernels.  Launches nothing. */
+int j2k_plan_scr16(const j2k_plan *plan);
 
 /* ---- the default branch of extractImageData (encoder.go:178-195) for the types Go's decoders return ----------------
  * Any other image.Image becomes 3 components at precision 8: r>>8, g>>8, b>>8 of img.At(x, y).RGBA(), then the

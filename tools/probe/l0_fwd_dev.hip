@@ -14,6 +14,7 @@
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 namespace j2k {
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v2i __attribute__((ext_vector_type(2)));
 #include "../../go-jpeg2000_amd/csrc/dwt53_l0pix.inc"
 }
 using namespace j2k;
