@@ -44,7 +44,8 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
                             uint32_t *lens, uint8_t *numbps, uint8_t *work, size_t work_per_job, int *fault, int max_dim,
                             uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint8_t *bigsym = nullptr, const uint64_t *bigsym_off = nullptr,
                             uint32_t *bignsyms = nullptr, uint32_t *rate = nullptr,    // rate: 32 words per job, the rate tables (blocks <= 64 x 64 only)
-                            uint32_t *rawst = nullptr);   // rawst: the raw-MagRef style -- t1_raw_stage_bytes() per job of staging (blocks <= 64 x 64, no rate tables)
+                            uint32_t *rawst = nullptr,    // rawst: the raw-MagRef style -- t1_raw_stage_bytes() per job of staging (blocks <= 64 x 64, no rate tables)
+                            int *forms = nullptr);        // forms (host, two ints): [0] = blocks per wavefront of the MQ chains (0: the one-kernel form), [1] = 1: blocks above 64 x 64 went through symbol lists
 size_t t1_raw_stage_bytes();
 // rate control (rate.hip): plane distortions of every block; the allocation of a byte budget over the blocks' rate / distortion tables
 hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, uint64_t *dist);
@@ -76,7 +77,8 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
                             const uint32_t *lens, const uint8_t *numbps, int32_t *decoded, uint8_t *work,
                             size_t work_per_job, int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput = 0, int skip_planes = 0,
                             const uint8_t *floors = nullptr,    // floors (device, one byte per job): job j stops at max(skip_planes, floors[j])
-                            int raw_magref = 0);                // the bodies are H | MQ | RAW (blocks <= 64 x 64, no floors)
+                            int raw_magref = 0,                 // the bodies are H | MQ | RAW (blocks <= 64 x 64, no floors)
+                            int *big_launches = nullptr);       // (host) launches of t1_decode_big_kernel: 0, 1 or 2
 size_t t1_dec_split_bytes(size_t njobs, bool raw_magref = false);    // raw_magref: with the un-stuffed RAW strings of the style's blocks
 hipError_t launch_mq_encode(hipStream_t s, const uint8_t *ctxs, const uint8_t *decs, size_t n, uint8_t *out, size_t cap, uint32_t *out_len, int *fault);
 hipError_t launch_mq_decode(hipStream_t s, const uint8_t *data, size_t len, const uint8_t *ctxs, size_t n, uint8_t *decs, int *fault);

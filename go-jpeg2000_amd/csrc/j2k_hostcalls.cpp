@@ -289,14 +289,19 @@ extern "C" int j2k_decode_blocks_floors(j2k_ctx *ctx, int coder, const uint8_t *
         // the same choice of decoder as j2k_plan_decode_blocks (the two entry points used to differ), and the same fall-back
         // to the one-launch kernels when the lanes decoder's workspace cannot be had
         const int split_min = ctx->t1_dec_split >= 0 ? ctx->t1_dec_split : (mq_throughput_mode() ? 512 : 12000);
-        bool split = split_min > 0 && (int)nblocks >= split_min && !ctx->t1_dec_general;
+        const bool want_split = split_min > 0 && (int)nblocks >= split_min && !ctx->t1_dec_general;
+        bool split = want_split;
         const size_t gen_bytes = (wpj * nblocks + 255) & ~size_t(255);
         if (split && hipMalloc(&d_work, gen_bytes + 256 + j2k::t1_dec_split_bytes(nblocks)) != hipSuccess) { (void)hipGetLastError(); d_work = nullptr; split = false; }
         if (!split) TRY(hipMalloc(&d_work, gen_bytes + 256));
-        int max_dim = 0;
+        int max_dim = 0, big_launches = 0;
         for (size_t j = 0; j < nblocks; j++) max_dim = std::max(max_dim, std::max(bj[j].w, bj[j].h));
         TRY(launch_t1_decode(ctx->stream, (BlockJob *)d_jobs, (int)nblocks, (uint8_t *)d_bytes, (uint64_t *)d_offs, (uint32_t *)d_lens, (uint8_t *)d_nb,
-                             (int32_t *)d_dec, (uint8_t *)d_work, wpj, max_dim, ctx->t1_dec_general, split ? (uint8_t *)d_work + gen_bytes : nullptr, ctx->t1_dec_lanes, 0, skip_planes, (const uint8_t *)d_floors));
+                             (int32_t *)d_dec, (uint8_t *)d_work, wpj, max_dim, ctx->t1_dec_general, split ? (uint8_t *)d_work + gen_bytes : nullptr, ctx->t1_dec_lanes, 0, skip_planes, (const uint8_t *)d_floors, 0, &big_launches));
+        ctx->mq_forms.dec_split = split ? 1 : 0;
+        ctx->mq_forms.dec_lanes = split ? ctx->t1_dec_lanes : 0;
+        ctx->mq_forms.dec_big = big_launches;
+        ctx->mq_forms.dec_fellback = want_split && !split ? 1 : 0;
     }
     for (size_t j = 0; j < nblocks; j++)
         TRY(hipMemcpyAsync(coeffs + coeff_offs[j], (int32_t *)d_dec + bj[j].out_off, (size_t)blocks[j].w * blocks[j].h * 4, hipMemcpyDeviceToHost, ctx->stream));

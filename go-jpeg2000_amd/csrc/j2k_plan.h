@@ -6,6 +6,12 @@
 #include "../../include/j2kgfx.h"
 #include "j2k_internal.h"
 
+// What the MQ block coder's last launches took (j2k_plan_mq_forms / j2k_ctx_mq_forms): written where the choices are made, read by nobody else
+struct j2k_mq_record {
+    int enc_k = 0, enc_big2 = 0;                                   // blocks per wavefront of the MQ chains (0: the one-kernel form) / blocks above 64 x 64 through symbol lists
+    int dec_split = 0, dec_lanes = 0, dec_big = 0, dec_fellback = 0;   // plane-stepped path taken, its form / launches of the big-block decoder / the path was wanted and not had
+};
+
 struct j2k_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -62,13 +68,14 @@ struct j2k_ctx {
     int t1_dec_lanes = 2;      // J2K_T1_DEC_LANES: 2 = the plane-stepped decoder as one launch per group of 64 blocks (t1_lanes.inc, PERSIST), 1 = its passes as launches per plane, 0 = the plane-stepped decoder's SigProp / Cleanup as round 2's step kernels (one block per wavefront) instead of t1_lanes.inc
     int t1_dec_split = -1;     // J2K_T1_DEC_SPLIT: MQ decode of frames with at least this many blocks runs plane by plane with the MagRef chains
                                // of 64 blocks per wavefront in lock step (t1.hip); 0: always the one-launch kernels; -1 (default): 512 while
-                               // at least two contexts of this process code with the MQ coder (frames in flight: throughput), else 0 (one
+                               // at least two contexts of this process code with the MQ coder (frames in flight: throughput), else 12 000 (one
                                // frame at a time: latency)
     bool capturing = false;    // between j2k_ctx_capture_begin / _end: the plan calls are recorded into a HIP graph, nothing may allocate or synchronise
     bool fault_armed_before_capture = false;
     bool counted_mq = false;   // this context has built an MQ-coder plan (counted in g_mq_ctxs)
+    j2k_mq_record mq_forms;    // of the last j2k_decode_blocks / _coarse / _floors (the host calls have no plan)
     bool t2_parallel = true;   // J2K_T2_PARALLEL: frame decode of SOP + EPH streams parses a tile's packets side by side from their markers (verified; 0 = the tile chain only)
-    int t1_lanes = 0;          // J2K_T1_LANES: blocks per wavefront of the lane-parallel MQ kernel (0: blocks / 256, at most 32, while at least two contexts code with the MQ coder, else blocks / 2048)
+    int t1_lanes = 0;          // J2K_T1_LANES: blocks per wavefront of the lane-parallel MQ kernel (0: blocks / 256, at most 64, while at least two contexts code with the MQ coder, else blocks / 2048)
     // cached single-plane plans for the host (unit) calls
     std::vector<j2k_plan *> cache;
     // host-call staging buffers (device)
@@ -293,5 +300,6 @@ struct j2k_plan {
     j2k::AreaPlane *d_area_planes = nullptr;
     int32_t *d_area_frame = nullptr;
     bool raw_magref = false;                // j2k_plan_set_raw_magref: MQ block bodies are H | MQ | RAW, the MagRef decisions bypass the MQ coder
+    j2k_mq_record mq_forms;                 // of the plan's last block encode / block decode (j2k_plan_mq_forms)
     bool dequantize = false;                // j2k_plan_set_dequantize: the 9-7 inverse kernels multiply every int32 coefficient by 1.0 / Quality at their load (dwt.go:514-520)
 };

@@ -722,10 +722,13 @@ int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slot
                 bigsym = (uint8_t *)ctx->stage[4] + head;
             }
         }
+        int forms[2] = {0, 0};
         HIPCHK(ctx, launch_t1_encode(ctx->stream, P->d_bjobs, n, d_coeff, d_slots, d_lens, d_numbps, ws, wpj, d_fault, max_dim,
                                      W.stride ? ws + W.off_sym : nullptr, W.stride, (uint32_t *)(ws + W.off_nsyms),
                                      ctx->t1_lanes > 0 ? ctx->t1_lanes : (mq_throughput_mode() ? -1 : 0), bigsym, P->d_bigsym_off, bignsyms, d_rate,
-                                     P->raw_magref ? (uint32_t *)(ws + raw_off) : nullptr));
+                                     P->raw_magref ? (uint32_t *)(ws + raw_off) : nullptr, forms));
+        P->mq_forms.enc_k = forms[0];
+        P->mq_forms.enc_big2 = forms[1];
     }
     return J2K_OK;
 }
@@ -954,6 +957,24 @@ extern "C" int j2k_plan_decode_blocks_floors(j2k_plan *P, const uint8_t *d_strea
     return plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_stream, d_offs, d_lens, d_numbps, d_decoded, nullptr, skip_planes, d_floors);
 }
 
+// What the MQ block coder's last launches took (include/j2kgfx.h); launches nothing
+static void mq_forms_out(const j2k_mq_record &m, int32_t out[8]) {
+    out[0] = g_mq_ctxs.load(std::memory_order_relaxed);
+    out[1] = m.enc_k; out[2] = m.enc_big2;
+    out[3] = m.dec_split; out[4] = m.dec_lanes; out[5] = m.dec_big; out[6] = m.dec_fellback;
+    out[7] = 0;
+}
+extern "C" int j2k_plan_mq_forms(const j2k_plan *P, int32_t out[8]) {
+    if (!P || !out) return J2K_ERR_INVALID_ARG;
+    mq_forms_out(P->mq_forms, out);
+    return J2K_OK;
+}
+extern "C" int j2k_ctx_mq_forms(const j2k_ctx *ctx, int32_t out[8]) {
+    if (!ctx || !out) return J2K_ERR_INVALID_ARG;
+    mq_forms_out(ctx->mq_forms, out);
+    return J2K_OK;
+}
+
 int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
                             const uint8_t *d_numbps, int32_t *d_decoded, const BlockJob *d_placed, int skip_planes, const uint8_t *d_floors) {
     j2k_ctx *ctx = P->ctx;
@@ -980,18 +1001,26 @@ int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const u
         // (one context alone: the one-launch kernels are a 28-30 ms chain while their 8192 wavefront slots hold the frame, the lanes
         //  decoder a 45-50 ms one whatever the frame -- an 8K frame of 27 000 blocks: 86 ms against 51, tools/check_big_mq.py)
         const int split_min = ctx->t1_dec_split >= 0 ? ctx->t1_dec_split : (mq_throughput_mode() ? 512 : 12000);
-        bool split = split_min > 0 && n >= split_min && !ctx->t1_dec_general && !((uintptr_t)d_stream & 15);
+        const bool want_split = split_min > 0 && n >= split_min && !ctx->t1_dec_general;
+        bool split = want_split && !((uintptr_t)d_stream & 15);
         const size_t gen_bytes = (wpj * (size_t)n + 255) & ~size_t(255);
         // The lanes decoder's workspace is T1DS_STRIDE + 3.5 KB of row masks + 16 KB of plane words per block (0.55 GB for an 8K frame of
         // 27 000 blocks); if the device cannot give it, the one-launch kernels decode the frame with gen_bytes alone
-        // rather than the call failing.
+        // rather than the call failing.  Not while a graph is being captured: there the workspace cannot grow because nothing may
+        // allocate, not because the device is full, and a graph recorded with the other decoder would be replayed in its place for good -- the
+        // capture is refused like every other call that has not run once before.
         int r = stage_reserve(ctx, 2, gen_bytes + 256 + (split ? j2k::t1_dec_split_bytes((size_t)n, P->raw_magref) : 0));
-        if (r != J2K_OK && split) { (void)hipGetLastError(); split = false; r = stage_reserve(ctx, 2, gen_bytes + 256); }
+        if (r != J2K_OK && split && !ctx->capturing) { (void)hipGetLastError(); split = false; r = stage_reserve(ctx, 2, gen_bytes + 256); }
         if (r != J2K_OK) return r;
+        int big_launches = 0;
         HIPCHK(ctx, launch_t1_decode(ctx->stream, d_djobs, n, d_stream, d_offs, d_lens, d_numbps, d_decoded,
                                      (uint8_t *)ctx->stage[2], wpj, max_dim, ctx->t1_dec_general,
                                      split ? (uint8_t *)ctx->stage[2] + gen_bytes : nullptr, ctx->t1_dec_lanes, mq_throughput_mode() ? 1 : 0, skip_planes, d_floors,
-                                     P->raw_magref ? 1 : 0));
+                                     P->raw_magref ? 1 : 0, &big_launches));
+        P->mq_forms.dec_split = split ? 1 : 0;
+        P->mq_forms.dec_lanes = split ? ctx->t1_dec_lanes : 0;
+        P->mq_forms.dec_big = big_launches;
+        P->mq_forms.dec_fellback = want_split && !split ? 1 : 0;
     }
     return J2K_OK;
 }

@@ -1971,7 +1971,8 @@ size_t t1_sym_stride(int planes) { return ((size_t)(planes + 2) * 4096 + 1024 + 
 // sym != null: context formation and MQ coding as two kernels through the symbol workspace; otherwise the one-kernel form.
 template <bool PLANES, bool RAWMR>
 static void launch_t1_encode64(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots, uint32_t *lens, uint8_t *numbps, int *fault,
-                               uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint32_t *aux) {
+                               uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint32_t *aux, int *forms) {
+    if (forms) forms[0] = 0;
     if (!(sym && nsyms)) {
         hipLaunchKernelGGL((t1_encode64_kernel<false, PLANES, RAWMR>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
                            (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nullptr, aux);
@@ -1991,6 +1992,7 @@ static void launch_t1_encode64(hipStream_t s, const BlockJob *jobs, int njobs, c
     // throughput setting fills all 64 lanes.
     int K = lanes > 0 ? lanes : (lanes < 0 ? std::min(64, (njobs + 255) / 256) : (njobs + 2047) / 2048);
     K = std::min(64, std::max(1, K));
+    if (forms) forms[0] = K;
     uint32_t *perm = nsyms + njobs;       // njobs + 64 words behind nsyms (t1_workspace in j2k_stages.cpp)
     hipLaunchKernelGGL(t1_order_kernel, dim3(1), dim3(1024), 0, s, jobs, njobs, (const uint8_t *)nullptr, (const uint32_t *)nsyms, 1, perm,
                        (uint32_t *)nullptr, njobs);
@@ -2009,18 +2011,19 @@ static void launch_t1_encode64(hipStream_t s, const BlockJob *jobs, int njobs, c
 hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots,
                             uint32_t *lens, uint8_t *numbps, uint8_t *work, size_t work_per_job, int *fault, int max_dim,
                             uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint8_t *bigsym, const uint64_t *bigsym_off, uint32_t *bignsyms, uint32_t *rate,
-                            uint32_t *rawst) {
+                            uint32_t *rawst, int *forms) {
+    if (forms) forms[0] = forms[1] = 0;
     if (njobs <= 0) return hipSuccess;
     if (rawst) {     // the raw-MagRef style (j2k_plan_set_raw_magref; blocks <= 64 x 64, no rate tables): the RAWMR instantiations, same sequence
-        launch_t1_encode64<false, true>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rawst);
+        launch_t1_encode64<false, true>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rawst, forms);
         return hipGetLastError();
     }
     static int serial_only = -1;   // J2K_T1_SERIAL=1: A/B against the serial kernel
     if (serial_only < 0) serial_only = 0;          // (round 1's A/B switch J2K_T1_SERIAL: gone, the serial kernel only takes what the others leave)
     if (!serial_only) {
         // rate != null (j2k_plan_encode_blocks_planes): the PLANES instantiations of the <= 64 x 64 kernels; the others are launched as before
-        if (rate) launch_t1_encode64<true, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rate);
-        else launch_t1_encode64<false, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, (uint32_t *)nullptr);
+        if (rate) launch_t1_encode64<true, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rate, forms);
+        else launch_t1_encode64<false, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, (uint32_t *)nullptr, forms);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || max_dim <= 64) return e;
         // blocks above 64 x 64, up to 256 x 256 (the reference's default size): wave-parallel context formation (t1_big.inc)
@@ -2046,6 +2049,7 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
                 hipLaunchKernelGGL(t1_encode_big_kernel<true>, dim3(njobs), dim3(256), sizeof(T1Big), s, jobs, njobs, coef, slots, lens, numbps, fault, rot, bigsym, bigsym_off, bignsyms);
                 hipLaunchKernelGGL(t1_mq_big_kernel, dim3(njobs), dim3(rot ? 256 : 64), 0, s, jobs, njobs, slots, lens, fault, rot, (const uint8_t *)bigsym, bigsym_off, (const uint32_t *)bignsyms);
                 marked = bignsyms;
+                if (forms) forms[1] = 1;
             } else {
                 hipLaunchKernelGGL(t1_encode_big_kernel<false>, dim3(njobs), dim3(256), sizeof(T1Big), s, jobs, njobs, coef, slots, lens, numbps, fault, rot, (uint8_t *)nullptr, (const uint64_t *)nullptr, (uint32_t *)nullptr);
             }
@@ -2073,7 +2077,8 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
 // general_only: every block on the general kernel (A/B knob); otherwise blocks up to 64x64 take t1_decode64_kernel
 hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, const uint8_t *numbps, int32_t *decoded, uint8_t *work, size_t work_per_job,
-                            int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput, int skip_planes, const uint8_t *floors, int raw_magref) {
+                            int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput, int skip_planes, const uint8_t *floors, int raw_magref, int *big_launches) {
+    if (big_launches) *big_launches = 0;
     if (njobs <= 0) return hipSuccess;
     if (raw_magref) {
         // the raw-MagRef style (blocks <= 64 x 64, no per-block floors: the setter and the floors calls have refused everything else): the
@@ -2159,6 +2164,7 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
         { const char *en = tuning_env("J2K_T1_BIG_DEC_CLASSES"); if (en) classes = atoi(en); }
         hipLaunchKernelGGL((t1_decode_big_kernel<4, 258>), dim3(njobs), dim3(rot ? 256 : 64), sizeof(T1BigDec<4, 258>), s, jobs, njobs, stream, offs, lens, numbps, decoded, rot, classes ? 0 : 1, skip_planes, floors);
         if (classes) hipLaunchKernelGGL((t1_decode_big_kernel<2, 130>), dim3(njobs), dim3(rot ? 256 : 64), sizeof(T1BigDec<2, 130>), s, jobs, njobs, stream, offs, lens, numbps, decoded, rot, 0, skip_planes, floors);
+        if (big_launches) *big_launches = classes ? 2 : 1;
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || max_dim <= 256) return e;
     }

@@ -57,7 +57,7 @@ SYMBOLS = [
     "j2k_convert_colorspace", "j2k_convert_colorspace_device",
     "j2k_pixels_components", "j2k_pixels_precision", "j2k_extract_image_data", "j2k_create_image",
     "j2k_unpack_pixels", "j2k_pack_pixels", "j2k_plan_forward_rgba8", "j2k_plan_inverse_rgba8",
-    "j2k_plan_forward_pixels", "j2k_plan_inverse_pixels", "j2k_plan_pixels_fused", "j2k_plan_scr16",
+    "j2k_plan_forward_pixels", "j2k_plan_inverse_pixels", "j2k_plan_pixels_fused", "j2k_plan_scr16", "j2k_plan_mq_forms", "j2k_ctx_mq_forms",
     "j2k_image_validate", "j2k_image_to_rgba8", "j2k_extract_image_planar", "j2k_plan_forward_image", "j2k_plan_image_fused",
     "j2k_plan_encode_frame_image", "j2k_encode_image_host",
     "j2k_tile_part_bound", "j2k_create_tile_header", "j2k_assemble_tiles", "j2k_read_tile_part_header", "j2k_parse_tile_parts",
@@ -139,6 +139,7 @@ def lib():
             "j2k_quantize": (I, [V, DP, S, C.c_double, C.POINTER(C.c_int32)]), "j2k_dequantize": (I, [V, C.POINTER(C.c_int32), S, C.c_double, DP]),
             "j2k_plan_set_dequantize": (I, [V, I]),
             "j2k_plan_set_raw_magref": (I, [V, I]), "j2k_plan_get_raw_magref": (I, [V]), "j2k_plan_scr16": (I, [V]),
+            "j2k_plan_mq_forms": (I, [V, V]), "j2k_ctx_mq_forms": (I, [V, V]),
             "j2k_decode_blocks_coarse": (I, [V, I, V, V, V, V, V, S, I, V, V]),
             "j2k_plan_decode_blocks_coarse": (I, [V, V, V, V, V, I, V]),
             "j2k_plan_decode_frame_pixels_coarse": (I, [V, V, S, V, I, I, I, I, V, S]),

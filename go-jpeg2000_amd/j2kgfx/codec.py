@@ -398,6 +398,15 @@ class FramePlan:
         return int(self.ctx.L.j2k_plan_scr16(self.h))
 
     # ---- image.YCbCr / CMYK / Paletted (encoder.go:178-195; j2kgfx.pixels.YCbCr / CMYK / Paletted) ---------------------------
+    def mq_forms(self):
+        """j2k_plan_mq_forms, (8,) int32: [0] live contexts of this process that have built an MQ plan, [1] blocks per wavefront of the last
+        block encode's MQ chains (0: the one-kernel form), [2] its blocks above 64 x 64 went through symbol lists, [3] the last block decode took
+        the plane-stepped path, [4] in this form (option t1_dec_lanes), [5] launches of the big-block decoder, [6] the path was wanted and not
+        had (stream not 16-byte aligned / no workspace), [7] 0.  Launches nothing."""
+        out = np.zeros(8, dtype=np.int32)
+        self.ctx.check(self.ctx.L.j2k_plan_mq_forms(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def _img(self, img):
         for a in img.buffers():
             if hasattr(a, "data_ptr"):

@@ -66,6 +66,13 @@ class Context:
         """j2k_ctx_set_option: a tuning option of this context (before its plans are made)"""
         self.check(self.L.j2k_ctx_set_option(self.h, name.encode(), int(value)))
 
+    def mq_forms(self):
+        """j2k_ctx_mq_forms: FramePlan.mq_forms() of this context's last entropy.decode_blocks (the host calls have no plan)"""
+        import numpy as np
+        out = np.zeros(8, dtype=np.int32)
+        self.check(self.L.j2k_ctx_mq_forms(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def hold(self, t):
         """Keep `t` alive until the next sync(): kernels queued on the library stream may still read or write it."""
         self._held.append(t)

@@ -457,6 +457,21 @@ int j2k_plan_pixels_fused(const j2k_plan *plan, int format, const void *d_pix, s
  * (rows that fit are stored 16-bit, chosen per row in every call), 4 / 8 = the plan's last forward / inverse call launched
  * the 16-bit kernels.  Launches nothing. */
 int j2k_plan_scr16(const j2k_plan *plan);
+/* Which forms of the MQ block coder the plan's last block encode and block decode took -- the library picks between a latency and a
+ * throughput setting by the number of live contexts of this process that have built an MQ-coder plan (two or more: throughput), and
+ * these calls say what that came to.  They launch nothing and change no launch.
+ *   out[0]  contexts of this process that have built an MQ-coder plan and are still alive (a context counts once), now
+ *   out[1]  blocks per wavefront (K) of the MQ chains of the last block encode; 0 = the one-kernel form ran (or no encode yet)
+ *   out[2]  1 = that encode coded its blocks above 64 x 64 as two kernels through symbol lists
+ *   out[3]  1 = the last block decode took the plane-stepped path, out[4] = its form (context option t1_dec_lanes; 0 otherwise)
+ *   out[5]  launches of the decoder for blocks above 64 x 64 in that decode: 0 (no such block / another kernel took them), 1 or 2
+ *   out[6]  1 = that decode wanted the plane-stepped path and fell back to the one-launch kernels (a stream that is not 16-byte
+ *           aligned, or no room for the path's workspace)
+ *   out[7]  reserved, 0
+ * j2k_ctx_mq_forms: the same record of the context's last j2k_decode_blocks / _coarse / _floors (the host calls have no plan);
+ * out[1] and out[2] are 0. */
+int j2k_plan_mq_forms(const j2k_plan *plan, int32_t out[8]);
+int j2k_ctx_mq_forms(const j2k_ctx *ctx, int32_t out[8]);
 
 /* ---- the default branch of extractImageData (encoder.go:178-195) for the types Go's decoders return ----------------
  * Any other image.Image becomes 3 components at precision 8: r>>8, g>>8, b>>8 of img.At(x, y).RGBA(), then the
