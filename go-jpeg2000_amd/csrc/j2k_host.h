@@ -3,6 +3,9 @@
 // status helpers, the context's staging slots, the plan builder, and the requests, the one encoder / decoder and the two host drivers of the
 // closed-loop frame codec.  Host-side orchestration only: geometry -> device job tables, launches on the
 // context's HIP stream, host <-> device staging.  All arithmetic lives in the .hip kernels; there is no CPU fallback.
+// A plan is made in three steps (j2k_planbuild.cpp: build_plan): build_plan_tables (plan_tables.h / plan_tables.cpp: plain integer code with no HIP
+// in it, run on a CPU under sanitizers by tests/plan_tables_main.cpp) turns the geometry and the context's PlanOptions into every job table and
+// scalar; one list of (device pointer, host vector) pairs uploads the tables -- and frees them in j2k_plan_destroy; the scratch buffers are allocated.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -132,7 +135,7 @@ int check_fault(j2k_ctx *ctx);
 bool profile_pair(j2k_ctx *ctx, int tag, hipEvent_t &e0, hipEvent_t &e1);
 int stage_reserve(j2k_ctx *ctx, int slot, size_t bytes);
 
-// ---- plans (j2k_planbuild.cpp) ----
+// ---- plans (j2k_planbuild.cpp; the tables themselves: plan_tables.h) ----
 static inline int64_t align4(int64_t v) { return (v + 3) & ~int64_t(3); }
 template <typename T>
 static int upload(j2k_ctx *ctx, T **dptr, const std::vector<T> &v) {

@@ -1,26 +1,14 @@
-// j2k_plan.h -- host-side context / plan objects behind the C ABI (include/j2kgfx.h).
-#pragma once
-#include <string>
-#include <vector>
-
-#include "../../include/j2kgfx.h"
-#include "j2k_internal.h"
-
-// What the MQ block coder's last launches took (j2k_plan_mq_forms / j2k_ctx_mq_forms): written where the choices are made, read by nobody else
-struct j2k_mq_record {
-    int enc_k = 0, enc_big2 = 0;                                   // blocks per wavefront of the MQ chains (0: the one-kernel form) / blocks above 64 x 64 through symbol lists
-    int dec_split = 0, dec_lanes = 0, dec_big = 0, dec_fellback = 0;   // plane-stepped path taken, its form / launches of the big-block decoder / the path was wanted and not had
-};
-
-struct j2k_ctx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    std::string last_error;
-    int fuse_compact = 0;      // j2k_plan_encode_stream: encode + compact in ONE kernel (decoupled look-back; J2K_FUSE_COMPACT=1).
-                               // Measured slower than the three kernels it replaces (61.7 vs 58.6 us: the prefix chain crosses XCDs)
+// j2k_plan.h -- host-side context / plan objects behind the C ABI (include/j2kgfx.h).  What a plan derives from its geometry without a device -- its
+// scalars, its tables before they are uploaded -- is in plan_tables.h (no HIP there); here: the options, and what lives on the device.
+// Two parts: j2k::PlanOptions, which needs nothing of HIP and is all that plan_tables.h takes of this file (J2K_PLAN_OPTIONS_ONLY), then the rest.
+#ifndef J2K_PLAN_OPTIONS_H
+#define J2K_PLAN_OPTIONS_H
+namespace j2k {
+// The options of a context that shape its plans' tables (j2k_ctx inherits them; j2k_ctx_set_option and, under J2K_TUNING=1, the environment
+// set them).  The defaults are what the benchmarks measured best.
+struct PlanOptions {
     int fwd_link = 1;          // forward 5-3: bands of one workgroup exchange halo rows through LDS (J2K_FWD_LINK)
     int inv_link = 1;          // same for the inverse kernels (J2K_INV_LINK)
-    int pix_fuse = 1;          // J2K_PIX_FUSE: packed pixels read / written by the level-0 kernels (1: every format; 2: RGBA8 and Gray16 only, as before round 4; 0: always the int32 staging frame)
     bool plane_wg3 = false;    // ... also level 0 of RGB triples of int32 planes (J2K_PLANE_WG3; measured equal to the general kernel on 4K frames: 43 vs 41 us)
     int plane_wg = 4;          // single-component planes (every level > 0, gray level 0) in workgroup form: waves per workgroup (J2K_PLANE_WG: 0 off, 4, 8)
     int l0_fuse = 0;           // forward levels 0 + 1 of RGBA8 frames in one launch: waves per workgroup of the fused bands (J2K_L0_FUSE: 0 off, 8, 16)
@@ -33,14 +21,7 @@ struct j2k_ctx {
     int l0_xcd_group = 16;     // J2K_L0_XCD_GROUP (inverse level-0 table): > 0 = bands go to the XCDs in groups of this many consecutive ones (0: one contiguous chunk of the table per XCD)
     bool l0_xcd = true;        // XCD-aware order of the workgroup jobs (J2K_L0_XCD=0: plane-major order)
     bool ht_alias = true;      // j2k_plan_encode_stream (HT): code each distinct block window once (J2K_HT_ALIAS=0: every job)
-    int ht_enc_waves = 4;      // ... with this many wavefronts per distinct window (J2K_HT_ENC_WAVES: 1 = ht_encode_kernel, 4 = ht_encode_wg_kernel)
-    int ht_dec_front = 3;      // HT block decode, kernels 1 + 2 (J2K_HT_DEC_FRONT: 3 = ht_vlcprep_kernel + ht_walk_kernel, two launches; 1 = ht_front_kernel, the workgroup unstuffs the strings it walks)
-    int ht_dec_lean = 1;       // HT block decode, third kernel (J2K_HT_DEC_LEAN: 1 = ht_decode_lean_kernel, the 64-wide common case written out and everything else out of line; 0 = ht_decode_kernel)
-    int ht_dec_dedup = 1;      // HT block decode (J2K_HT_DEC_DEDUP, with ht_dec_front = 3 and ht_dec_lean = 1 only): 1 = a job whose bytes ht_vlcprep_kernel finds equal to its leader's
-                               // (the plan's candidate table, d_ht_dec_rep) is not decoded; the leader stores its rows to both places.  Equal: in every byte a
-                               // decode path can read.  The walk then takes the jobs in d_ht_walk_order (leaders first).  Measured: docs/KERNEL_NOTES.md 4aa
     int l0_inv_wpe = 5;        // its occupancy variant (J2K_L0_INV_WPE: 5 = all in registers, 26.4 us; 6 = odd row parked in LDS for 6 waves per SIMD, measured slower: 33.6 us)
-    bool l0_wg_inv = true;     // the inverse level 0 to RGBA8 in workgroup form too (J2K_L0_WG_INV=0: the general kernel)
     int l0_store = 1;          // its final-coefficient store flavour (J2K_L0_STORE: 0 plain, 1 nt, 2 sc1, 4 sc1 nt)
     int l0_scr16 = 1;          // J2K_L0_SCR16 (bit 0 forward, bit 1 inverse; 0 ... 3): packed RGBA8 forward, level 0 hands X_1 to the deep launch as int16 rows (dwt53_fwd_rgba8_wg16_kernel ->
                                // dwt53_deep_fwd16_kernel; j2k_plan::scr16_fwd says when; 0 = int32 rows, the kernels as they were).  Measured: level 0
@@ -48,7 +29,6 @@ struct j2k_ctx {
     int band_prows_pix = 3;    // packed-pixel level-0 forward (J2K_BAND_PROWS_PIX)
     int band_prows_97 = 8;     // 9-7 kernels: 7 halo rows per band, so taller bands (J2K_BAND_PROWS_97)
     int band_prows_inv = 0;    // 0: same as band_prows (J2K_BAND_PROWS_INV)
-    int fwd_pf = 0;            // forward 5-3 level kernels: software prefetch of the next pair-row (J2K_FWD_PF)
     int band_prows = 5;        // pair-rows per wavefront band (tunable: J2K_BAND_PROWS)
     int use_tail = 1;          // J2K_TAIL=0: every level as its own launch (A/B)
     int mega = 0;              // J2K_MEGA: packed-RGBA8 frames: the deep levels and the level-0 bands independent of them in ONE launch per direction
@@ -62,6 +42,41 @@ struct j2k_ctx {
     int xcd_map = 0;           // J2K_XCD_MAP=0: plain job order (A/B)
     int cpl0 = 0;              // J2K_CPL0: force columns-per-lane of the level-0 5-3 kernels (tuning)
     int force_novec = 0;       // J2K_FORCE_NOVEC=1: always take the scalar-access kernels (testing)
+};
+}  // namespace j2k
+#endif
+
+#if !defined(J2K_PLAN_OPTIONS_ONLY) && !defined(J2K_PLAN_H)
+#define J2K_PLAN_H
+#include <string>
+#include <vector>
+
+#include "../../include/j2kgfx.h"
+#include "j2k_internal.h"
+#include "plan_tables.h"
+
+// What the MQ block coder's last launches took (j2k_plan_mq_forms / j2k_ctx_mq_forms): written where the choices are made, read by nobody else
+struct j2k_mq_record {
+    int enc_k = 0, enc_big2 = 0;                                   // blocks per wavefront of the MQ chains (0: the one-kernel form) / blocks above 64 x 64 through symbol lists
+    int dec_split = 0, dec_lanes = 0, dec_big = 0, dec_fellback = 0;   // plane-stepped path taken, its form / launches of the big-block decoder / the path was wanted and not had
+};
+
+// (the options that shape a plan's tables: j2k::PlanOptions above)
+struct j2k_ctx : j2k::PlanOptions {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    std::string last_error;
+    int fuse_compact = 0;      // j2k_plan_encode_stream: encode + compact in ONE kernel (decoupled look-back; J2K_FUSE_COMPACT=1).
+                               // Measured slower than the three kernels it replaces (61.7 vs 58.6 us: the prefix chain crosses XCDs)
+    int pix_fuse = 1;          // J2K_PIX_FUSE: packed pixels read / written by the level-0 kernels (1: every format; 2: RGBA8 and Gray16 only, as before round 4; 0: always the int32 staging frame)
+    int ht_enc_waves = 4;      // ... with this many wavefronts per distinct window (J2K_HT_ENC_WAVES: 1 = ht_encode_kernel, 4 = ht_encode_wg_kernel)
+    int ht_dec_front = 3;      // HT block decode, kernels 1 + 2 (J2K_HT_DEC_FRONT: 3 = ht_vlcprep_kernel + ht_walk_kernel, two launches; 1 = ht_front_kernel, the workgroup unstuffs the strings it walks)
+    int ht_dec_lean = 1;       // HT block decode, third kernel (J2K_HT_DEC_LEAN: 1 = ht_decode_lean_kernel, the 64-wide common case written out and everything else out of line; 0 = ht_decode_kernel)
+    int ht_dec_dedup = 1;      // HT block decode (J2K_HT_DEC_DEDUP, with ht_dec_front = 3 and ht_dec_lean = 1 only): 1 = a job whose bytes ht_vlcprep_kernel finds equal to its leader's
+                               // (the plan's candidate table, d_ht_dec_rep) is not decoded; the leader stores its rows to both places.  Equal: in every byte a
+                               // decode path can read.  The walk then takes the jobs in d_ht_walk_order (leaders first).  Measured: docs/KERNEL_NOTES.md 4aa
+    bool l0_wg_inv = true;     // the inverse level 0 to RGBA8 in workgroup form too (J2K_L0_WG_INV=0: the general kernel)
+    int fwd_pf = 0;            // forward 5-3 level kernels: software prefetch of the next pair-row (J2K_FWD_PF)
     int t1_split = 1;          // J2K_T1_SPLIT=0: T1 encoder as one kernel (contexts + MQ chain on lane 0) instead of two
     long t1_sym_mb = 8192;     // J2K_T1_SYM_MB: cap of the T1 symbol workspace; blocks with more bit planes than fit take the one-kernel path
     int t1_dec_general = 0;    // J2K_T1_DEC_GENERAL=1: every block on the general T1 decode kernel (A/B against t1_decode64_kernel)
@@ -91,68 +106,18 @@ struct j2k_ctx {
 
 namespace j2k {
 
-enum Wavelet { W53 = 0, W97 = 1 };
-enum QuantMode {               // how the 9-7 path turns f64 coefficients into int32
-    Q_NONE = 0,                // keep f64 (dwt.Forward97... unit calls)
-    Q_ENCODER = 1,             // int32(v/step +- 0.5), step = 1/quality (encoder.go:265-276)
-    Q_TCD = 2                  // int32(v +- 0.5) (tcd.go:520-532)
-};
-
-// Internal, richer form of j2k_params.
-struct PlanSpec {
-    int W = 0, H = 0, C = 1;
-    int tile_w = 0, tile_h = 0;
-    int levels = 1;            // DWT levels actually run
-    int wavelet = W53;
-    int precision = 8;         // component precision of the plan (pixel pack / unpack)
-    int dc_shift = 0;          // value subtracted on the way in (encoder.go:218-220)
-    int dc_shift_inv = 0;      // value added on the way out: 0 for signed components (decoder.go:344-348), else dc_shift
-    int mct = 0;               // fused RCT (W53) / ICT (W97) on comps 0-2 when C>=3
-    int quant = Q_NONE;
-    int quality = 100;
-    int num_res_jobs = 6;      // resolutions for the encodeTile job enumeration
-    int cb_w = 64, cb_h = 64;
-    int coder = J2K_CODER_MQ;
-    int frame_h = 0;           // rows of one frame of a batch (j2k_params.frame_rows; = H for a single frame)
-    int tile_first = 0, tile_count = 0;
-    bool frame_is_f64 = false; // unit 9-7 calls: source/destination "frame" is f64
-    bool closed_loop = false;  // j2k_params.closed_loop: code-block windows = the Mallat rectangles of the plane (they partition it)
-    bool mallat = false;       // j2k_params.closed_loop == J2K_CLOSED_LOOP_MALLAT: level l runs on the rectangle [0, w_l) x [0, h_l) of the plane, so those windows are its sub-bands
-    bool operator==(const PlanSpec &o) const;
-};
-
-struct Group {                 // one launch unit: a single component or an MCT triple of one tile
-    int tile;                  // shard-local tile index
-    int comp0, nc;
-    int x0, y0, w, h;
-    int64_t coef_off[3];       // element offsets into the coefficient buffer
-    int64_t scrA_off[3], scrB_off[3];
-};
-
-struct LevelTab {
+struct LevelTab : LevelInfo {
     DwtPlane *d_planes = nullptr;
     DwtJob *d_jobs = nullptr;
-    int njobs = 0, nplanes = 0;
-    int cpl = 2, vec = 0, ncomp = 1;
-    int64_t alg_bytes = 0;
-    // single-component planes in workgroup form (dwt53_plane_wg.inc): one entry per (plane, 512-column strip, band of
-    // pwaves - 1 pair-rows); empty when a plane of the level breaks the geometry contract
-    DwtJob *d_pjobs = nullptr;
-    int pnjobs = 0, pwaves = 0, pmulti = 0;
-    bool p_pix_only = false;   // the table serves packed-pixel sources only (level 0 of RGB triples: RGBA64); int32 planes keep the general kernels
-    bool mallat = false;       // a level of a Mallat plan: the MAL instantiation of the general kernels (LevelLaunch::mallat)
+    DwtJob *d_pjobs = nullptr; // the workgroup form's table (LevelInfo::pnjobs)
 };
 
-// A Mallat plan decoded `reduce` resolutions down (j2k_plan_*_reduced): LL_reduce is the frame, W_r x H_r = ceil(W / 2^reduce) x ceil(H / 2^reduce),
-// tile (x0, y0) at (x0 >> reduce, y0 >> reduce)
-struct ReducedTab {
+// the tables of one `reduce` of a Mallat plan (ReducedInfo, plan_tables.h), made at its first use
+struct ReducedTab : ReducedInfo {
     bool built = false;
-    int Wr = 0, Hr = 0;
     LevelTab inv[2];           // the launch of level `reduce`, the final one ([0] single components, [1] MCT triples): out_off / out_stride address the reduced frame
     LLPlane *d_ll = nullptr;   // reduce == levels: no level runs (mct.hip mallat_ll_kernel)
-    int nll = 0, ll_samples = 0;
     // the code-block jobs of the resolutions <= num_resolutions - 1 - reduce, in job order, and their share of the frame's block tables
-    int njobs = 0, max_block_h = 0;
     int *d_ids = nullptr;
     BlockJob *d_bjobs = nullptr, *d_djobs = nullptr, *d_placed = nullptr;   // windows / dense decoded blocks (the plan's offsets) / HT: the windows as destinations
     uint64_t *d_offs = nullptr; uint32_t *d_lens = nullptr; uint8_t *d_numbps = nullptr;
@@ -176,42 +141,22 @@ struct LayerTab {
 
 }  // namespace j2k
 
-struct j2k_plan {
+// The geometry's scalars and host-side lists are j2k::PlanScalars (plan_tables.h), as build_plan_tables derived them; here: the device tables made
+// of its vectors (plan_device_tables in j2k_planbuild.cpp pairs each with its vector: upload and free walk that one list), and whatever the other files make at first use
+struct j2k_plan : j2k::PlanScalars {
     j2k_ctx *ctx = nullptr;
     j2k::PlanSpec spec;
-    int tiles_x = 1, tiles_y = 1, tile_first = 0, tile_count = 1;
-    std::vector<j2k::Group> groups;
-    std::vector<int64_t> plane_desc;        // 7 x int64 per tile-component
-    int64_t coeff_elems = 0, scrA_elems = 0, scrB_elems = 0;
     // [cls][level]: cls 0 = single-component groups, cls 1 = MCT triples
     std::vector<j2k::LevelTab> fwd[2], inv[2];
     void *d_scrA = nullptr, *d_scrB = nullptr;   // int32 (5-3) or f64 (9-7) prefixes
-    // fused LDS tail (5-3): levels tail_l0 .. levels-1 in one launch per direction; -1 = not used
-    int tail_l0 = -1;
-    j2k::TailPlane *d_tail = nullptr;
-    int ntail = 0;
-    size_t tail_lds_fwd = 0, tail_lds_inv = 0;
-    // every level below level 0 in one launch per direction (dwt53_deep.inc): levels deep_l0 .. levels-1; -1 = not used
-    int deep_l0 = -1;
-    bool scr16_inv = false;                     // inverse_rgba8 of this plan may: rows of X_1 that fit int16 are stored so, d_scr16_fmt[(element offset of the row) >> 3] = 1 says which
-    uint8_t *d_scr16_fmt = nullptr;
+    j2k::TailPlane *d_tail = nullptr;           // fused LDS tail (5-3): levels tail_l0 .. levels-1 in one launch per direction
+    uint8_t *d_scr16_fmt = nullptr;             // scr16_inv: d_scr16_fmt[(element offset of a row of X_1 in scratch A) >> 3] = 1 where the row is stored as int16
     bool last_fwd_scr16 = false, last_inv_scr16 = false;   // what the plan's last forward / inverse call launched (j2k_plan_scr16 bits 2, 3)
-    bool scr16_fwd = false;                     // forward_rgba8 of this plan may hand X_1 over as int16 rows (option l0_scr16; the conditions: j2k_planbuild.cpp)
     j2k::TailPlane *d_deep_planes = nullptr;    // dims at level deep_l0
     j2k::DwtJob *d_deep_jobs = nullptr;         // deep workgroups first, then the flat ones
-    int ndeep_jobs = 0;
-    size_t deep_lds = 0, deep_lds_fwd = 0;      // dynamic LDS of the inverse / forward launch
-    std::vector<j2k::DwtJob> deep_jobs_host, deep_jobs_host_inv, flat_jobs_host, flat_jobs_host_inv;
     j2k::DwtJob *d_deep_jobs_inv = nullptr;     // the inverse launch's table (deep / mid jobs own other level-l0 rows than in the forward one)
-    int ndeep_jobs_inv = 0;
     // merged launches for packed RGBA8 frames (dwt53_mega_*_kernel) and the level-0 TOP band tables that go with them
     j2k::DwtJob *d_mega_fwd_jobs = nullptr, *d_mega_inv_jobs = nullptr, *d_fwd_top_jobs = nullptr, *d_inv_top_jobs = nullptr;
-    int mega_fwd_njobs = 0, mega_inv_njobs = 0, fwd_top_njobs = 0, inv_top_njobs = 0;
-    int64_t fwd_top_bytes = 0, inv_top_bytes = 0;        // algorithmic bytes of the top-band launches (16 B per pixel)
-    // code-block jobs
-    std::vector<j2k_block> blocks;          // plane = shard-local tile-component index
-    std::vector<int32_t> block_tile;        // tile of each job
-    std::vector<int32_t> block_res;         // resolution of each job (a packet = the jobs of one tile-component and resolution)
     // closed-loop frame codec (j2k_plan_encode_tile_parts / j2k_plan_decode_tile_parts): tables and workspaces, made at first use
     j2k_t2_dev_packet *d_t2_packets = nullptr;   // one packet per (tile, component, resolution) with blocks, J2K_T2_* flags set
     int *d_tile_packet0 = nullptr;               // first packet of every tile of the shard (+ the packet count)
@@ -228,48 +173,32 @@ struct j2k_plan {
     int32_t *d_cl_decoded = nullptr, *d_cl_coeff = nullptr;   // j2k_plan_*_frame_pixels: decoded blocks, coefficient planes
     int32_t *d_cl_coeff_dec = nullptr;           // HT plans: the frame DECODER's coefficient planes (zeroed once, only the coded rows ever written)
     uint8_t *d_cl_numbps = nullptr; uint64_t *d_cl_offs = nullptr; uint32_t *d_cl_lens = nullptr;
-    int max_block_h = 0;
     void *d_host_io = nullptr, *d_host_pix = nullptr;          // j2k_encode_pixels_host / j2k_decode_pixels_host: tile-parts / pixels on the device
     size_t host_io_bytes = 0, host_pix_bytes = 0;
     int *d_tile_job0 = nullptr;             // first job of each tile of the shard (+ the job count): j2k_plan_assemble_tiles_device
-    uint64_t max_tile_bytes = 0;            // slot bytes of the largest tile (an upper bound of its stream bytes)
-    std::vector<uint64_t> slot_off;         // byte offset of each job's worst-case slot
-    std::vector<uint64_t> dec_off;          // element offset of each job's decoded block
     j2k::BlockJob *d_bjobs = nullptr;       // out_off = slot byte offset (encode)
     j2k::BlockJob *d_djobs = nullptr;       // out_off = decoded element offset (decode)
     j2k::BlockJob *d_djobs_placed = nullptr; // closed-loop HT plans: out_off = the block's window in the coefficient planes, stride = the plane's
-    int64_t bytes_cap = 0, decoded_elems = 0, block_samples = 0;
-    int64_t dwt_bytes = 0, dwt_level0_bytes = 0;
     // device workspaces owned by the plan for j2k_encode_frame
     void *d_frame = nullptr, *d_coeff = nullptr, *d_slots = nullptr, *d_stream = nullptr;
     void *d_lens = nullptr, *d_numbps = nullptr, *d_offs = nullptr;
     // fused encode + compact (j2k_plan_encode_stream): look-back status words, tagged with the launch epoch
     j2k::DwtJob *d_fwd_pix_jobs = nullptr;  // level-0 forward job table of the packed-pixel path (shorter bands)
-    int fwd_pix_njobs = 0;
     j2k::HtUJob *d_ht_ujobs = nullptr; int *d_ht_alias_next = nullptr;   // HT: one entry per distinct window / the job ids sharing each window
     j2k::BlockJob *d_bjobs_alias = nullptr;                  // d_bjobs with every job's slot = the slot of its window's coded job
-    int ht_nunique = 0;
     // HT decode, byte-identical blocks (option ht_dec_dedup): CANDIDATES only -- the prep kernel compares the bytes.  d_ht_dec_rep[j] = the leader of job j (the
     // lowest job with the same window that it may follow; j itself otherwise), d_ht_dec_fol[8 j] = how many jobs follow leader j (at most J2K_HT_DEC_MAX_FOLLOWERS),
     // d_ht_dec_fol[8 j + 1 ..] = their ids.  Both null when no job has a follower (closed-loop plans: the windows partition the plane).
-    std::vector<int32_t> ht_dec_rep;        // the host's copy of d_ht_dec_rep (every HT plan; j2k_plan_get_ht_decode_leaders)
     int32_t *d_ht_dec_rep = nullptr, *d_ht_dec_fol = nullptr;
     // The walk's static order under the same option: slot s of the bit-string scratch (and lane s % 64 of walk workgroup s / 64) belongs to job
     // ht_walk_order[s] -- the ht_walk_nlead jobs that are their own leader first, in ascending job order, the static followers behind them, ascending;
     // d_ht_walk_pos is the inverse (job -> slot).  Uploaded with d_ht_dec_rep; the identity, and null, when no job has a follower.
-    std::vector<int32_t> ht_walk_order;     // the host's copy (every HT plan; j2k_plan_get_ht_decode_walk_order)
     int32_t *d_ht_walk_order = nullptr, *d_ht_walk_pos = nullptr;
-    int ht_walk_nlead = 0;
     j2k::DwtJob *d_fwd97_wg_jobs = nullptr; // 9-7: one job per workgroup = (plane, component, band) of dwt97_fwd_rgb_wg_kernel
-    int fwd97_wg_njobs = 0, fwd97_wg_waves = 0;
     j2k::DwtJob *d_inv97_wg_jobs = nullptr; // 9-7 inverse: one job per workgroup = (plane, band) of dwt97_inv_rgb_wg_kernel
-    int inv97_wg_njobs = 0, inv97_wg_waves = 0;
     j2k::DwtJob *d_fwd_wg2_jobs = nullptr, *d_fwd_wg_rest_jobs = nullptr;   // fused levels 0+1: top-half bands / the remaining bands
-    int fwd_wg2_njobs = 0, fwd_wg2_waves = 0, fwd_wg_rest_njobs = 0;
     j2k::DwtJob *d_fwd_wg_jobs = nullptr;   // the same as one job per WORKGROUP (dwt53_fwd_rgba8_wg_kernel), when every plane qualifies
-    int fwd_wg_njobs = 0, fwd_wg_waves = 0;
     j2k::DwtJob *d_inv_wg_jobs = nullptr;   // the inverse kernel's table (its own waves per workgroup)
-    int inv_wg_njobs = 0, inv_wg_waves = 0;
     uint32_t *d_maglens = nullptr;          // j2k_plan_encode_stream: end of each block's MagSgn bytes (the MEL hole starts there)
     uint32_t *d_mels = nullptr;      // per job: bytes of MEL zero run of an HT block (max(64, 2wh) / 4), built with d_maglens
     const void *last_stream = nullptr, *last_lens = nullptr;   // outputs of the last j2k_plan_encode_stream: what d_maglens / d_toffs describe
@@ -303,3 +232,4 @@ struct j2k_plan {
     j2k_mq_record mq_forms;                 // of the plan's last block encode / block decode (j2k_plan_mq_forms)
     bool dequantize = false;                // j2k_plan_set_dequantize: the 9-7 inverse kernels multiply every int32 coefficient by 1.0 / Quality at their load (dwt.go:514-520)
 };
+#endif  // J2K_PLAN_H
