@@ -8,7 +8,7 @@
 using namespace j2k;
 
 // every refusal of an area call that its plan, `reduce` and rectangle decide (host only)
-static int area_check(const j2k_plan *P, const j2k_rect *area, int reduce, AreaOut &out, const char *who) {
+int area_check(const j2k_plan *P, const j2k_rect *area, int reduce, AreaOut &out, const char *who) {
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
     const std::string w(who);

@@ -140,13 +140,13 @@ extern "C" size_t j2k_plan_frame_bound(const j2k_plan *P) {
 
 // the packets of a frame written where they end up (t2dev.hip: launch_t2_encode_tile_parts).  d_stream + d_offs: the dense block stream, or
 // d_offs == NULL: d_stream is the plan's slot buffer as plan_encode_private_slots left it and every block is gathered from its slot
-static int encode_tile_parts_impl(j2k_plan *P, const uint8_t *d_data, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,
-                                  int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, const uint8_t *d_kept = nullptr, const uint32_t *d_rate = nullptr) {
+int encode_tile_parts_impl(j2k_plan *P, const uint8_t *d_data, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,
+                           int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, const uint8_t *d_kept, const uint32_t *d_rate, int passes) {
     j2k_ctx *ctx = P->ctx;
     const long n = (long)P->blocks.size(), np = P->t2_npackets;
     const int ht = P->spec.coder == J2K_CODER_HT ? 1 : 0;
     uint64_t *d_res = reinterpret_cast<uint64_t *>((uint8_t *)P->d_t2_ws + ((j2k::t2_dev_workspace(np) + 15) & ~size_t(15)));
-    HIPCHK(ctx, j2k::launch_t2_fill_cbs(ctx->stream, n, d_offs, d_lens, d_numbps, 31, ht | 2, P->d_t2_cbs, d_res, d_kept, d_rate));
+    HIPCHK(ctx, j2k::launch_t2_fill_cbs(ctx->stream, n, d_offs, d_lens, d_numbps, 31, ht | 2, P->d_t2_cbs, d_res, d_kept, d_rate, passes));
     HIPCHK(ctx, j2k::launch_t2_encode_tile_parts(ctx->stream, P->d_t2_packets, np, P->d_t2_cbs, (uint64_t)n, d_data, sop, eph, d_out, (uint64_t)cap, P->d_t2_poffs,
                                                  P->d_t2_ws, d_res, P->d_t2_ptile, P->d_tile_packet0, P->tile_count, P->tile_first, d_tile_offs, P->d_frame_status,
                                                  d_offs ? nullptr : (P->d_bjobs_alias ? P->d_bjobs_alias : P->d_bjobs), d_offs ? nullptr : (ht ? P->d_maglens : nullptr), ht, P->t2_body_slices));
@@ -182,24 +182,24 @@ extern "C" int j2k_plan_encode_tile_parts_kept(j2k_plan *P, const uint8_t *d_str
 
 // the tile-part chains and the packet read (t2dec.hip); d_floors (or null): also every block's floor (the _floors calls)
 static int decode_tile_parts_launch(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, uint64_t *d_offs, uint32_t *d_lens,
-                                    uint8_t *d_numbps, uint8_t *d_floors) {
+                                    uint8_t *d_numbps, uint8_t *d_floors, uint8_t *d_pfloors = nullptr) {
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, j2k::launch_t2_tile_chains(ctx->stream, d_cs, (uint64_t)len, d_tile_offs, P->tile_count, P->tile_first, P->d_tile_packet0, P->d_t2_chains));
     // (SOP + EPH streams: a tile's packets side by side, checked against the serial rule and redone by it where a guess was off -- t2dec.hip)
     HIPCHK(ctx, j2k::launch_t2_decode_tiles(ctx->stream, P->d_t2_chains, P->tile_count, P->d_tile_packet0, P->d_t2_packets, P->t2_npackets, P->d_t2_cbs,
                                             (uint64_t)P->blocks.size(), d_cs, (uint64_t)len, sop, eph, P->d_t2_body_base, P->d_frame_status, ctx->t2_parallel ? P->d_t2_par : nullptr,
-                                            P->spec.coder == J2K_CODER_HT ? 1 : 0, 31, d_offs, d_lens, d_numbps, d_floors));
+                                            P->spec.coder == J2K_CODER_HT ? 1 : 0, 31, d_offs, d_lens, d_numbps, d_floors, d_pfloors));
     return J2K_OK;
 }
-static int decode_tile_parts_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
-                                  uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors) {
+int decode_tile_parts_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                           uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors, uint8_t *d_pfloors) {
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (!d_cs || !d_offs || !d_lens || !d_numbps) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int r = cl_prepare(P);
     if (r != J2K_OK) return r;
-    return decode_tile_parts_launch(P, d_cs, len, d_tile_offs, sop, eph, d_offs, d_lens, d_numbps, d_floors);
+    return decode_tile_parts_launch(P, d_cs, len, d_tile_offs, sop, eph, d_offs, d_lens, d_numbps, d_floors, d_pfloors);
 }
 extern "C" int j2k_plan_decode_tile_parts(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
                                           uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps) {
@@ -283,7 +283,7 @@ int cl_workspaces(j2k_plan *P) {
 }
 
 // the rate tables, the cuts and the floors of a frame, one allocation made at the first rate-limited call
-int cl_rate_workspace(j2k_plan *P, ClRate &W) {
+int cl_rate_workspace(j2k_plan *P, ClRate &W, bool passes) {
     j2k_ctx *ctx = P->ctx;
     const size_t n = P->blocks.size(), nr = (n + 255) & ~size_t(255);
     const size_t bytes = nr * 32 * 8 + nr * 32 * 4 + 3 * nr + 256 + 256;
@@ -297,6 +297,17 @@ int cl_rate_workspace(j2k_plan *P, ClRate &W) {
     W.chosen = (uint64_t *)b; b += 256;
     W.kept = b; W.floors = b + nr; W.floors_r = b + 2 * nr;
     W.achieved = (double *)(b + 3 * nr);                             // (nr is a multiple of 256: aligned)
+    W.spmask = nullptr;
+    if (passes) {                                                    // the pass tables: 96 entries per block, and the SigProp masks
+        if (!P->d_cl_prate) {
+            if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the frame codec's workspaces are made at its first call");
+            HIPCHK(ctx, hipMalloc(&P->d_cl_prate, nr * 96 * 8 + nr * 64 * 8 + nr * 96 * 4 + 256));
+        }
+        uint8_t *pb = (uint8_t *)P->d_cl_prate;
+        W.dist = (uint64_t *)pb; pb += nr * 96 * 8;
+        W.spmask = (uint64_t *)pb; pb += nr * 64 * 8;
+        W.rate = (uint32_t *)pb;
+    }
     return J2K_OK;
 }
 
@@ -319,18 +330,27 @@ int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *
     ClRate W{};
     LayerTab *T = nullptr;
     r = cl_prepare(P);
-    if (r == J2K_OK) r = cl_rate_workspace(P, W);
+    if (r == J2K_OK) r = cl_rate_workspace(P, W, q.passes);
     if (r == J2K_OK && q.layered) r = layer_tab(P, q.nlayers, &T);
     if (r == J2K_OK && (!P->d_slots || (T && !T->d_kept))) {
         if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: run the same calls once before j2k_ctx_capture_begin");
         if (!P->d_slots) HIPCHK(ctx, hipMalloc(&P->d_slots, (size_t)P->bytes_cap + 64));
         if (T && !T->d_kept) HIPCHK(ctx, hipMalloc((void **)&T->d_kept, std::max<size_t>(P->blocks.size() * (size_t)q.nlayers, 64)));
     }
-    if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, q.roi, q.roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
+    if (r == J2K_OK && q.passes) r = plan_encode_blocks_passes(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, W.spmask);
+    else if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, q.roi, q.roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
     if (r == J2K_OK) r = rate_upload_weights(P);
     if (r != J2K_OK) return r;
     const int n = (int)P->blocks.size();
     uint8_t *d_kept = T ? T->d_kept : W.kept;
+    if (q.passes) {      // the same stage order on the pass tables: one budget or one target, the kept-prefix stream with pass counts
+        if (q.kind == EncodeRequest::DISTORTION)
+            HIPCHK(ctx, launch_rate_allocate_quality_passes(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.targets[0], P->d_rate_ws, d_kept, W.chosen,
+                                                            q.d_achieved ? q.d_achieved : W.achieved));
+        else
+            HIPCHK(ctx, launch_rate_allocate_passes(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.budgets[0], P->d_rate_ws, d_kept, W.chosen));
+        return encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, d_kept, W.rate, 1);
+    }
     if (q.kind == EncodeRequest::DISTORTION)
         HIPCHK(ctx, launch_rate_allocate_quality(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.targets, q.nlayers, P->d_rate_ws, d_kept, W.chosen,
                                                  q.d_achieved ? q.d_achieved : W.achieved));
@@ -440,6 +460,7 @@ int plan_decode_frame(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64
     const size_t n = P->blocks.size(), nr = (n + 255) & ~size_t(255);
     const uint8_t *d_data = d_cs;
     uint8_t *d_floors = nullptr, *d_floors_r = nullptr;
+    bool pfl = false;                                    // d_floors holds floors in coding passes (a _passes call)
     if (T) {
         if (!P->d_cl_dense || P->cl_dense_bytes < len + 64 || !P->d_cl_lfloors) {
             if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the dense buffer grows with the stream -- run the call once on a stream at least as long before j2k_ctx_capture_begin");
@@ -455,8 +476,10 @@ int plan_decode_frame(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64
             ClRate W{};
             if ((r = cl_rate_workspace(P, W)) != J2K_OK) return r;
             d_floors = W.floors; d_floors_r = W.floors_r;
+            pfl = q.passes;
         }
-        r = decode_tile_parts_launch(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, d_floors);
+        // (the pass floors travel through the area and subset steps as the plane floors do: both only edit one byte per block)
+        r = decode_tile_parts_launch(P, d_cs, len, d_tile_offs, sop, eph, P->d_cl_offs, P->d_cl_lens, P->d_cl_numbps, pfl ? nullptr : d_floors, pfl ? d_floors : nullptr);
     }
     if (r != J2K_OK) return r;
     // (b)
@@ -478,7 +501,8 @@ int plan_decode_frame(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64
         bjobs = R->d_bjobs; djobs = R->d_djobs; placed = R->d_placed; njobs = R->njobs; max_h = R->max_block_h;
         offs = R->d_offs; lens = R->d_lens; numbps = R->d_numbps; floors = d_floors ? d_floors_r : nullptr;
     }
-    r = plan_decode_blocks_jobs(P, djobs, njobs, d_data, offs, lens, numbps, ht ? coeff : P->d_cl_decoded, ht ? placed : nullptr, q.skip_planes, floors);
+    r = plan_decode_blocks_jobs(P, djobs, njobs, d_data, offs, lens, numbps, ht ? coeff : P->d_cl_decoded, ht ? placed : nullptr, q.skip_planes, pfl ? nullptr : floors,
+                                pfl ? floors : nullptr);
     if (r != J2K_OK) return r;
     if (!ht) HIPCHK(ctx, launch_place_blocks(ctx->stream, bjobs, djobs, njobs, max_h, P->d_cl_decoded, coeff));
     // (d)

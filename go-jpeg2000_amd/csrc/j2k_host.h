@@ -48,10 +48,18 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
                             uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint8_t *bigsym = nullptr, const uint64_t *bigsym_off = nullptr,
                             uint32_t *bignsyms = nullptr, uint32_t *rate = nullptr,    // rate: 32 words per job, the rate tables (blocks <= 64 x 64 only)
                             uint32_t *rawst = nullptr,    // rawst: the raw-MagRef style -- t1_raw_stage_bytes() per job of staging (blocks <= 64 x 64, no rate tables)
-                            int *forms = nullptr);        // forms (host, two ints): [0] = blocks per wavefront of the MQ chains (0: the one-kernel form), [1] = 1: blocks above 64 x 64 went through symbol lists
+                            int *forms = nullptr,         // forms (host, two ints): [0] = blocks per wavefront of the MQ chains (0: the one-kernel form), [1] = 1: blocks above 64 x 64 went through symbol lists
+                            uint64_t *spmask = nullptr);  // spmask (with rate): the pass tables -- rate has 96 words per job, spmask 64 row masks per job (blocks <= 64 x 64 only)
 size_t t1_raw_stage_bytes();
 // rate control (rate.hip): plane distortions of every block; the allocation of a byte budget over the blocks' rate / distortion tables
 hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, uint64_t *dist);
+// pass cuts (tests/pass_cases.py): tables of 96 entries per block; spmask: 64 row masks per block (t1.hip's PASSES instantiations)
+hipError_t launch_rate_distortion_passes(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, const uint64_t *spmask,
+                                         uint64_t *dist);
+hipError_t launch_rate_allocate_passes(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+                                       uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen);
+hipError_t launch_rate_allocate_quality_passes(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+                                               double target, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved);
 // region of interest (area.hip, rate.hip): every block's footprint of a rectangle; the distortions with that footprint weighted `gain` times
 hipError_t launch_roi_windows(hipStream_t s, const j2k_block *blocks, int n, const AreaPlane *planes, int x0, int y0, int x1, int y1, int margin, int32_t *win);
 hipError_t launch_rate_distortion_roi(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, const j2k_block *blocks,
@@ -81,7 +89,8 @@ hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, cons
                             size_t work_per_job, int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput = 0, int skip_planes = 0,
                             const uint8_t *floors = nullptr,    // floors (device, one byte per job): job j stops at max(skip_planes, floors[j])
                             int raw_magref = 0,                 // the bodies are H | MQ | RAW (blocks <= 64 x 64, no floors)
-                            int *big_launches = nullptr);       // (host) launches of t1_decode_big_kernel: 0, 1 or 2
+                            int *big_launches = nullptr,        // (host) launches of t1_decode_big_kernel: 0, 1 or 2
+                            const uint8_t *pfloors = nullptr);  // pfloors (device, one byte per job; blocks <= 64 x 64): job j stops max(3 skip_planes, pfloors[j]) coding passes short
 size_t t1_dec_split_bytes(size_t njobs, bool raw_magref = false);    // raw_magref: with the un-stuffed RAW strings of the style's blocks
 hipError_t launch_mq_encode(hipStream_t s, const uint8_t *ctxs, const uint8_t *decs, size_t n, uint8_t *out, size_t cap, uint32_t *out_len, int *fault);
 hipError_t launch_mq_decode(hipStream_t s, const uint8_t *data, size_t len, const uint8_t *ctxs, size_t n, uint8_t *decs, int *fault);
@@ -105,7 +114,8 @@ void t2_read_chain(const void *src, j2k_t2_dec_state &st, int &status, long &don
 size_t t2_par_workspace(long npackets, int ntiles);
 hipError_t launch_t2_decode_tiles(hipStream_t s, void *chains, int ntiles, const int *tile_packet0, const j2k_t2_dev_packet *packets, long npackets, j2k_t2_dev_cb *cbs,
                                   uint64_t ncbs, const uint8_t *data, uint64_t len, int sop, int eph, uint64_t *body_base, int *frame_status, void *ws,
-                                  int ht, int mb, uint64_t *offs, uint32_t *lens, uint8_t *numbps, uint8_t *floors = nullptr);   // floors: t2_block_out's per-block floors (the _floors calls)
+                                  int ht, int mb, uint64_t *offs, uint32_t *lens, uint8_t *numbps, uint8_t *floors = nullptr,    // floors: t2_block_out's per-block floors (the _floors calls)
+                                  uint8_t *pfloors = nullptr);                                                                  // pfloors: the same in coding passes (the _pfloors calls)
 hipError_t launch_t2_blocks(hipStream_t s, long n, const j2k_t2_dev_cb *cbs, int ht, int mb, uint64_t total, uint64_t *offs, uint32_t *lens, uint8_t *numbps, int *status, uint8_t *floors = nullptr);
 hipError_t launch_place_blocks(hipStream_t s, const BlockJob *src_jobs, const BlockJob *dec_jobs, int njobs, int max_h, const int32_t *decoded, int32_t *coeff, int ystep = 1);
 hipError_t launch_select_blocks(hipStream_t s, const int *ids, int m, const uint64_t *offs, const uint32_t *lens, const uint8_t *numbps, uint64_t *offs_r,
@@ -161,8 +171,8 @@ static inline void first_use_alloc(j2k_ctx *ctx, int &r, void **p, size_t bytes,
 // the closed-loop frame codec's tables and workspaces, made at first use (j2k_frame.cpp)
 int cl_prepare(j2k_plan *P);
 int cl_workspaces(j2k_plan *P);
-struct ClRate { uint32_t *rate; uint64_t *dist; uint8_t *kept; uint64_t *chosen; uint8_t *floors, *floors_r; double *achieved; };   // chosen, achieved: 32 words, one per layer
-int cl_rate_workspace(j2k_plan *P, ClRate &W);
+struct ClRate { uint32_t *rate; uint64_t *dist; uint8_t *kept; uint64_t *chosen; uint8_t *floors, *floors_r; double *achieved; uint64_t *spmask; };   // chosen, achieved: 32 words, one per layer
+int cl_rate_workspace(j2k_plan *P, ClRate &W, bool passes = false);    // passes: rate / dist are the 96-entry pass tables (their own allocation), spmask beside them
 int layer_tab(j2k_plan *P, int L, j2k::LayerTab **out);     // the tables of layer count L, made at its first use (j2k_layers.cpp)
 
 // ---- the closed-loop frame codec: one encoder, one decoder (j2k_frame.cpp) ----
@@ -179,6 +189,7 @@ struct EncodeRequest {
     const j2k_rect *roi = nullptr;
     int roi_gain = 1;
     double *d_achieved = nullptr;
+    bool passes = false;      // the blocks are cut at coding-pass ends (the _passes calls: one budget or one target, no layers, no roi)
 };
 // an entry point's arguments -> its request, or the refusal (through fail(), naming `who`), in this order: the plan (rate_check), the layer count,
 // the rectangle and gain (check_roi), the budgets or targets (targets != NULL: DISTORTION), more than one of them without the layered stream
@@ -195,8 +206,10 @@ int plan_encode_frame_cl(j2k_plan *P, const EncodeRequest &q, const std::functio
                          uint64_t *d_tile_offs, uint64_t *d_layer_offs);
 // What a frame decode reads and how far: layers > 0: the first `layers` layers of a layered stream; truncated: a kept-prefix stream (per-block
 // floors); reduce: resolutions left out (Mallat plans); skip_planes: the uniform quality floor; area (or null): only that rectangle.
-struct DecodeRequest { int layers = 0; bool truncated = false; int reduce = 0, skip_planes = 0; const j2k_rect *area = nullptr; };
+// passes (with truncated): the header's pass count is read at pass granularity and every block takes the pass-cut decode kernel.
+struct DecodeRequest { int layers = 0; bool truncated = false; int reduce = 0, skip_planes = 0; const j2k_rect *area = nullptr; bool passes = false; };
 struct AreaOut { int x0, y0, w, h; };      // the rectangle of the reduced frame an area call returns (j2k_area.cpp: area_check)
+int area_check(const j2k_plan *P, const j2k_rect *area, int reduce, AreaOut &out, const char *who);     // every refusal a rectangle and its plan decide (host only)
 // tile-parts -> pixels, THE stage order of every decode form: parse, need set, block decode + placement, inverse transform.  out: area != NULL.
 // The callers have checked the request; refuses a `reduce` the plan does not allow, null d_cs / d_pix, and first use while capturing.
 int plan_decode_frame(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, const DecodeRequest &q, const AreaOut *out, void *d_pix,
@@ -262,7 +275,14 @@ int ensure(j2k_ctx *ctx, void **p, size_t bytes);
 int ensure_sized(j2k_ctx *ctx, void **p, size_t *cur, size_t need);   // a buffer that grows (synchronises when it does; j2k_hostcalls.cpp)
 struct PixIO { int stride = 0, single = 0, triple = 0; j2k::YccSrc ycc{}; };   // ycc.y: a YCbCr image in place of packed RGBA8 (triple 8)
 int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix = PixIO());
-int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate);
+int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate, uint64_t *d_spmask = nullptr);
+// j2k_plan_encode_blocks_passes without its checks (j2k_passes.cpp): the pass tables of every block
+int plan_encode_blocks_passes(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate, uint64_t *d_dist, uint64_t *d_spmask);
+// the packets of a frame written where they end up (j2k_frame.cpp); d_kept + d_rate: every block cut; passes: at coding-pass ends (96-entry tables)
+int encode_tile_parts_impl(j2k_plan *P, const uint8_t *d_data, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps, int sop, int eph, uint8_t *d_out,
+                           size_t cap, uint64_t *d_tile_offs, const uint8_t *d_kept = nullptr, const uint32_t *d_rate = nullptr, int passes = 0);
+int decode_tile_parts_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, uint64_t *d_offs, uint32_t *d_lens,
+                           uint8_t *d_numbps, uint8_t *d_floors, uint8_t *d_pfloors = nullptr);
 int plan_encode_private_slots(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_lens, uint8_t *d_numbps);
 // guard (device, or null): the launches that write d_frame write nothing if *guard != 0 -- the frame decoder's status word
 int plan_inverse_impl(j2k_plan *P, const void *d_coeff, void *d_frame, PixIO pix = PixIO(), const int *guard = nullptr);
@@ -272,7 +292,8 @@ int plan_inverse_pixels_reduced_impl(j2k_plan *P, const int32_t *d_coeff, int re
 // straight into its window of the coefficient planes `d_decoded`, coded rows only.  skip_planes: the quality floor of the _coarse calls (MQ coder;
 // the callers have checked its range and the coder)
 int plan_decode_blocks_jobs(j2k_plan *P, const j2k::BlockJob *d_djobs, int n, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
-                            const uint8_t *d_numbps, int32_t *d_decoded, const j2k::BlockJob *d_placed, int skip_planes = 0, const uint8_t *d_floors = nullptr);
+                            const uint8_t *d_numbps, int32_t *d_decoded, const j2k::BlockJob *d_placed, int skip_planes = 0, const uint8_t *d_floors = nullptr,
+                            const uint8_t *d_pfloors = nullptr);     // d_pfloors (MQ plans the rate calls accept): floors in coding passes, every block on the one-launch kernel
 // the range of skip_planes and the coder it needs: J2K_OK, or the refusal (through fail())
 int check_skip_planes(j2k_ctx *ctx, int coder, int skip_planes, const char *who);
 // the default branch of extractImageData (j2k_image.cpp): d_img's planes on the device; status_word non-null = report a palette index

@@ -91,7 +91,8 @@ hipError_t launch_image_to_rgba8(hipStream_t s, const j2k_image &img, uint32_t *
 
 // Tier-2 packets on device buffers (t2dev.hip)
 hipError_t launch_t2_fill_cbs(hipStream_t s, long n, const uint64_t *offs, const uint32_t *lens, const uint8_t *numbps, int mb, int ht, j2k_t2_dev_cb *cbs, uint64_t *reset = nullptr,
-                              const uint8_t *kept = nullptr, const uint32_t *rate = nullptr);   // kept + rate: blocks cut at bit planes (rate control)
+                              const uint8_t *kept = nullptr, const uint32_t *rate = nullptr,    // kept + rate: blocks cut at bit planes (rate control)
+                              int passes = 0);                                                  // passes: kept counts coding passes, rate has 96 entries per block
 hipError_t launch_t2_encode_tile_parts(hipStream_t s, const j2k_t2_dev_packet *packets, long npackets, const j2k_t2_dev_cb *cbs, uint64_t ncbs, const uint8_t *data,
                                        int sop, int eph, uint8_t *out, uint64_t cap, uint64_t *offs, void *ws, uint64_t *result, const int32_t *ptile,
                                        const int *tile_packet0, int ntiles, int tile_first, uint64_t *tile_offs, int *status, const BlockJob *slot_jobs,

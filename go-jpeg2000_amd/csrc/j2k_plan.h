@@ -218,6 +218,7 @@ struct j2k_plan : j2k::PlanScalars {
     double *d_rate_wj = nullptr;
     bool rate_wj_valid = false;
     void *d_rate_ws = nullptr;              // the allocation kernel's hulls
+    void *d_cl_prate = nullptr;             // the *_passes frame calls: the 96-entry rate and distortion tables and the SigProp masks (cl_rate_workspace)
     void *d_cl_rate = nullptr;              // the *_rate frame calls: rate and distortion tables, kept planes, chosen bytes, floors (cl_rate_workspace)
     std::vector<j2k::LayerTab> layer_tabs;  // quality layers: [L], 1 ... J2K_MAX_LAYERS
     void *d_cl_dense = nullptr;             // j2k_plan_decode_frame_pixels_layers: the gathered codewords (at least the stream's length) ...

@@ -674,7 +674,8 @@ extern "C" int j2k_plan_encode_blocks(j2k_plan *P, const int32_t *d_coeff, uint8
 }
 
 // d_rate != NULL (MQ plans whose blocks are all <= 64 x 64; j2k_rate.cpp has checked): the rate tables too, 32 words per job
-int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate) {
+// d_spmask != NULL (with d_rate): the pass tables in their place, 96 words per job, and the SigProp masks, 64 words of 64 bits per job
+int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate, uint64_t *d_spmask) {
     if (!P || !d_coeff || !d_slots || !d_lens || !d_numbps) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -726,7 +727,7 @@ int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slot
         HIPCHK(ctx, launch_t1_encode(ctx->stream, P->d_bjobs, n, d_coeff, d_slots, d_lens, d_numbps, ws, wpj, d_fault, max_dim,
                                      W.stride ? ws + W.off_sym : nullptr, W.stride, (uint32_t *)(ws + W.off_nsyms),
                                      ctx->t1_lanes > 0 ? ctx->t1_lanes : (mq_throughput_mode() ? -1 : 0), bigsym, P->d_bigsym_off, bignsyms, d_rate,
-                                     P->raw_magref ? (uint32_t *)(ws + raw_off) : nullptr, forms));
+                                     P->raw_magref ? (uint32_t *)(ws + raw_off) : nullptr, forms, d_rate ? d_spmask : nullptr));
         P->mq_forms.enc_k = forms[0];
         P->mq_forms.enc_big2 = forms[1];
     }
@@ -976,9 +977,10 @@ extern "C" int j2k_ctx_mq_forms(const j2k_ctx *ctx, int32_t out[8]) {
 }
 
 int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
-                            const uint8_t *d_numbps, int32_t *d_decoded, const BlockJob *d_placed, int skip_planes, const uint8_t *d_floors) {
+                            const uint8_t *d_numbps, int32_t *d_decoded, const BlockJob *d_placed, int skip_planes, const uint8_t *d_floors, const uint8_t *d_pfloors) {
     j2k_ctx *ctx = P->ctx;
-    if (d_floors) { const int rr = raw_magref_refuse(P, "block decode with per-block floors"); if (rr != J2K_OK) return rr; }
+    if (d_pfloors && P->spec.coder == J2K_CODER_HT) return fail(ctx, J2K_ERR_UNSUPPORTED, "block decode with per-block pass floors: needs the MQ coder");
+    if (d_floors || d_pfloors) { const int rr = raw_magref_refuse(P, "block decode with per-block floors"); if (rr != J2K_OK) return rr; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!n) return J2K_OK;
     if (P->spec.coder == J2K_CODER_HT) {
@@ -1001,7 +1003,7 @@ int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const u
         // (one context alone: the one-launch kernels are a 28-30 ms chain while their 8192 wavefront slots hold the frame, the lanes
         //  decoder a 45-50 ms one whatever the frame -- an 8K frame of 27 000 blocks: 86 ms against 51, tools/check_big_mq.py)
         const int split_min = ctx->t1_dec_split >= 0 ? ctx->t1_dec_split : (mq_throughput_mode() ? 512 : 12000);
-        const bool want_split = split_min > 0 && n >= split_min && !ctx->t1_dec_general;
+        const bool want_split = split_min > 0 && n >= split_min && !ctx->t1_dec_general && !d_pfloors;    // (pass floors: the one-launch kernel for every block)
         bool split = want_split && !((uintptr_t)d_stream & 15);
         const size_t gen_bytes = (wpj * (size_t)n + 255) & ~size_t(255);
         // The lanes decoder's workspace is T1DS_STRIDE + 3.5 KB of row masks + 16 KB of plane words per block (0.55 GB for an 8K frame of
@@ -1016,7 +1018,7 @@ int plan_decode_blocks_jobs(j2k_plan *P, const BlockJob *d_djobs, int n, const u
         HIPCHK(ctx, launch_t1_decode(ctx->stream, d_djobs, n, d_stream, d_offs, d_lens, d_numbps, d_decoded,
                                      (uint8_t *)ctx->stage[2], wpj, max_dim, ctx->t1_dec_general,
                                      split ? (uint8_t *)ctx->stage[2] + gen_bytes : nullptr, ctx->t1_dec_lanes, mq_throughput_mode() ? 1 : 0, skip_planes, d_floors,
-                                     P->raw_magref ? 1 : 0, &big_launches));
+                                     P->raw_magref ? 1 : 0, &big_launches, d_pfloors));
         P->mq_forms.dec_split = split ? 1 : 0;
         P->mq_forms.dec_lanes = split ? ctx->t1_dec_lanes : 0;
         P->mq_forms.dec_big = big_launches;

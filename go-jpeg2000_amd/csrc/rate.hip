@@ -58,6 +58,85 @@ __global__ __launch_bounds__(64) void rate_distortion_kernel(const BlockJob *__r
     if (lane < RATE_STRIDE) dist[(size_t)jid * RATE_STRIDE + (lane <= nb ? nb - lane : lane)] = lane <= nb ? mine : 0;
 }
 
+// ---- pass cuts (tests/pass_cases.py): the distortion at every coding-pass end -------------------------------------------------------------
+// dist[j * 96 + q], q = 3 p - 2 + s: p whole planes and s passes of plane b = nb - p - 1.  With e_k the error of a sample at floor k (above) and
+// t its top bit, only the samples with t == b see plane b's first two passes differently from a whole-plane cut:
+//   s = 0   sum e_{b+1}^2                                   (rate_distortion_sums' floor b + 1)
+//   s = 1   the same, but e_b for the samples of t == b that turned significant in SigProp (spmask); e_{b+1} = |v| for them
+//   s = 2   sum e_b^2, but |v| for the samples of t == b that wait for Cleanup
+// so per floor k three sums: e_k^2 over all samples, and |v|^2 - e_k^2 over the samples of t == k with and without their spmask bit.
+#define RATE_PASS_STRIDE 96
+template <int KMAX>
+__device__ __forceinline__ void rate_distortion_pass_sums(const BlockJob &J, const int32_t *__restrict__ src, const uint64_t *__restrict__ sprow, int lane,
+                                                          uint64_t &all, uint64_t &insp, uint64_t &incl) {
+    uint64_t acc[KMAX + 1], g[KMAX + 1], c[KMAX + 1];
+#pragma unroll
+    for (int k = 0; k <= KMAX; k++) acc[k] = g[k] = c[k] = 0;
+    for (int y = 0; y < J.h; y++) {
+        const uint64_t spm = sprow[y];
+        for (int x = lane; x < J.w; x += 64) {               // (blocks <= 64 x 64: x = lane)
+            const int32_t v = src[(size_t)y * J.stride + x];
+            const uint32_t a = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+            const int t = 31 - __clz((int)a);                // -1 for a = 0: matches no floor
+            const bool sp = (spm >> (x & 63)) & 1;
+            const uint64_t aa = (uint64_t)a * a;
+#pragma unroll
+            for (int k = 0; k <= KMAX; k++) {
+                uint64_t dd = 0;
+                if (k >= 1) {
+                    const uint32_t half = 1u << (k - 1), low = a & (2u * half - 1u);
+                    const uint32_t d = (a >> k) ? (low >= half ? low - half : half - low) : low;
+                    dd = (uint64_t)d * d;
+                }
+                acc[k] += dd;
+                const uint64_t gain = t == k ? aa - dd : 0;
+                g[k] += sp ? gain : 0;
+                c[k] += sp ? 0 : gain;
+            }
+        }
+    }
+    all = insp = incl = 0;
+#pragma unroll
+    for (int k = 0; k <= KMAX; k++) {
+        uint64_t s0 = acc[k], s1 = g[k], s2 = c[k];
+        for (int o = 32; o > 0; o >>= 1) {
+            s0 += (uint64_t)__shfl_xor((unsigned long long)s0, o);
+            s1 += (uint64_t)__shfl_xor((unsigned long long)s1, o);
+            s2 += (uint64_t)__shfl_xor((unsigned long long)s2, o);
+        }
+        if (lane == k) { all = s0; insp = s1; incl = s2; }
+    }
+}
+
+// One wavefront per block, a sibling of rate_distortion_kernel: lane k holds floor k's three sums and writes the cuts that end at that floor.
+__global__ __launch_bounds__(64) void rate_distortion_passes_kernel(const BlockJob *__restrict__ jobs, int njobs, const int32_t *__restrict__ coef,
+                                                                     const uint8_t *__restrict__ numbps, const uint64_t *__restrict__ spmask,
+                                                                     uint64_t *__restrict__ dist) {
+    const int jid = blockIdx.x;
+    if (jid >= njobs) return;
+    const int lane = threadIdx.x;
+    const BlockJob J = jobs[jid];
+    const int nb = min((int)numbps[jid], RATE_STRIDE - 1);
+    uint64_t *D = dist + (size_t)jid * RATE_PASS_STRIDE;
+    const int last = nb > 0 ? 3 * nb - 2 : 0;
+    for (int q = last + lane; q < RATE_PASS_STRIDE; q += 64) D[q] = 0;       // (the last cut itself: floor 0, no error)
+    if (nb == 0 || J.w > 64 || J.h > 64) return;                             // wave-uniform
+    const int32_t *src = coef + J.src_off;
+    const uint64_t *sprow = spmask + (size_t)jid * 64;
+    uint64_t all = 0, insp = 0, incl = 0;
+    if (nb <= 8) rate_distortion_pass_sums<8>(J, src, sprow, lane, all, insp, incl);
+    else if (nb <= 12) rate_distortion_pass_sums<12>(J, src, sprow, lane, all, insp, incl);
+    else if (nb <= 16) rate_distortion_pass_sums<16>(J, src, sprow, lane, all, insp, incl);
+    else rate_distortion_pass_sums<RATE_STRIDE - 1>(J, src, sprow, lane, all, insp, incl);
+    const uint64_t above = (uint64_t)__shfl_down((unsigned long long)all, 1);        // floor lane + 1's sum
+    if (lane >= 1 && lane <= nb) D[lane == nb ? 0 : 3 * (nb - lane) - 2] = all;      // s = 0 at floor `lane` (floor 0: zero, written above)
+    if (lane <= nb - 2) {                                                            // plane b = lane, p = nb - 1 - lane whole planes above it
+        const int p = nb - 1 - lane;
+        D[3 * p - 1] = above - insp;
+        D[3 * p] = all + incl;
+    }
+}
+
 // ---- region of interest: the distortion of the samples that reconstruct a rectangle of the frame counts `gain` times ----------------------
 // tests/roi_cases.py is the definition: D_roi[p] = D[p] + (gain - 1) * D_in[p] (mod 2^64), D_in the same sum over the block's footprint F_j
 // alone (area_walk.h: roi_window).  The footprint is a sub-window of the block, so D_in is rate_distortion_sums on a job of that window.
@@ -100,19 +179,28 @@ __global__ __launch_bounds__(64) void rate_distortion_roi_kernel(const BlockJob 
 // ---- allocation: one workgroup for the frame ----------------------------------------------------------------------------------------------
 // Workspace per block: the planes of its hull points (32 bytes), their incoming slopes (32 doubles), the count.
 #define RATE_WG 1024
+// ST: the table stride -- RATE_STRIDE with a point per bit plane (points = numBPS), RATE_PASS_STRIDE with a point per coding pass
+// (points = 3 numBPS - 2; tests/pass_cases.py).  The workspace is sized for the larger.
 struct RateWs {
-    double *slope;      // [n][32]
-    uint8_t *plane;     // [n][32]
+    double *slope;      // [n][ST]
+    uint8_t *plane;     // [n][ST]
     uint32_t *count;    // [n]
 };
+template <int ST = RATE_STRIDE>
 __host__ __device__ inline RateWs rate_ws(void *ws, size_t n) {
     RateWs W;
     W.slope = reinterpret_cast<double *>(ws);
-    W.count = reinterpret_cast<uint32_t *>(W.slope + n * RATE_STRIDE);
+    W.count = reinterpret_cast<uint32_t *>(W.slope + n * ST);
     W.plane = reinterpret_cast<uint8_t *>(W.count + n);
     return W;
 }
-size_t rate_allocate_workspace(int njobs) { return (size_t)njobs * (RATE_STRIDE * 9 + 4) + 256; }
+size_t rate_allocate_workspace(int njobs) { return (size_t)njobs * (RATE_PASS_STRIDE * 9 + 4) + 256; }
+// the last point of a block's table
+template <int ST>
+__device__ __forceinline__ int rate_points(const uint8_t *__restrict__ numbps, int j) {
+    const int nb = min((int)numbps[j], RATE_STRIDE - 1);
+    return ST == RATE_STRIDE ? nb : max(3 * nb - 2, 0);
+}
 
 // sum over the workgroup, the same value in every thread (integer sums: the order does not matter)
 __device__ __forceinline__ uint64_t wg_sum(uint64_t v, uint64_t *sh) {
@@ -126,14 +214,15 @@ __device__ __forceinline__ uint64_t wg_sum(uint64_t v, uint64_t *sh) {
 }
 
 // hulls: the upper-left convex hull of (rate, distortion) from p = 0, pop while the new point is not less steep (every thread its own blocks)
+template <int ST = RATE_STRIDE>
 __device__ __forceinline__ void rate_hulls(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist, const uint8_t *__restrict__ numbps,
                                            const double *__restrict__ weights, const RateWs &W) {
     for (int j = threadIdx.x; j < njobs; j += RATE_WG) {
-        const uint32_t *R = rate + (size_t)j * RATE_STRIDE;
-        const uint64_t *D = dist + (size_t)j * RATE_STRIDE;
-        double *sl = W.slope + (size_t)j * RATE_STRIDE;
-        uint8_t *pt = W.plane + (size_t)j * RATE_STRIDE;
-        const int nb = min((int)numbps[j], RATE_STRIDE - 1);
+        const uint32_t *R = rate + (size_t)j * ST;
+        const uint64_t *D = dist + (size_t)j * ST;
+        double *sl = W.slope + (size_t)j * ST;
+        uint8_t *pt = W.plane + (size_t)j * ST;
+        const int nb = rate_points<ST>(numbps, j);
         const double w = weights[j];
         int cnt = 1;
         pt[0] = 0; sl[0] = 0.0;
@@ -163,17 +252,19 @@ __device__ __forceinline__ void rate_hulls(int njobs, const uint32_t *__restrict
         W.count[j] = (uint32_t)cnt;
     }
 }
+template <int ST = RATE_STRIDE>
 __device__ __forceinline__ int rate_pick(const RateWs &W, int j, double lam) {
-    const double *sl = W.slope + (size_t)j * RATE_STRIDE;
+    const double *sl = W.slope + (size_t)j * ST;
     const int cnt = (int)W.count[j];
     int i = 0;
     while (i + 1 < cnt && sl[i + 1] >= lam) i++;
-    return W.plane[(size_t)j * RATE_STRIDE + i];
+    return W.plane[(size_t)j * ST + i];
 }
 // The smallest bit pattern of a non-negative double whose choice fits: bisection over the patterns, 64 steps (the patterns above
 // +infinity are NaNs: no slope is >= a NaN, every block is at its start point, whose rate is 0 -- the top of the range always fits).
 // Writes that choice to kept[0 ... njobs) and returns its bytes.  (Each thread reads back only the hulls it built itself: no barrier
 // needed between rate_hulls and the search.)
+template <int ST = RATE_STRIDE>
 __device__ __forceinline__ uint64_t rate_search(int njobs, const uint32_t *__restrict__ rate, const RateWs &W, uint64_t budget, uint64_t *sh,
                                                 uint8_t *__restrict__ kept) {
     const int tid = threadIdx.x;
@@ -182,37 +273,38 @@ __device__ __forceinline__ uint64_t rate_search(int njobs, const uint32_t *__res
         const uint64_t mid = lo + (hi - lo) / 2;
         const double lam = __longlong_as_double((long long)mid);
         uint64_t b = 0;
-        for (int j = tid; j < njobs; j += RATE_WG) b += rate[(size_t)j * RATE_STRIDE + rate_pick(W, j, lam)];
+        for (int j = tid; j < njobs; j += RATE_WG) b += rate[(size_t)j * ST + rate_pick<ST>(W, j, lam)];
         b = wg_sum(b, sh);                               // every thread takes every step: wg_sum has barriers
         if (lo < hi) { if (b <= budget) hi = mid; else lo = mid + 1; }
     }
     const double lam = __longlong_as_double((long long)hi);
     uint64_t b = 0;
     for (int j = tid; j < njobs; j += RATE_WG) {
-        const int p = rate_pick(W, j, lam);
+        const int p = rate_pick<ST>(W, j, lam);
         kept[j] = (uint8_t)p;
-        b += rate[(size_t)j * RATE_STRIDE + p];
+        b += rate[(size_t)j * ST + p];
     }
     return wg_sum(b, sh);
 }
 
+template <int ST = RATE_STRIDE>
 __global__ __launch_bounds__(RATE_WG) void rate_allocate_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
                                                                 const uint8_t *__restrict__ numbps, const double *__restrict__ weights, uint64_t budget,
                                                                 void *__restrict__ ws, uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen) {
     __shared__ uint64_t sh[RATE_WG / 64];
     const int tid = threadIdx.x;
-    const RateWs W = rate_ws(ws, (size_t)njobs);
+    const RateWs W = rate_ws<ST>(ws, (size_t)njobs);
     // nothing to cut?
     uint64_t part = 0;
-    for (int j = tid; j < njobs; j += RATE_WG) part += rate[(size_t)j * RATE_STRIDE + min((int)numbps[j], RATE_STRIDE - 1)];
+    for (int j = tid; j < njobs; j += RATE_WG) part += rate[(size_t)j * ST + rate_points<ST>(numbps, j)];
     const uint64_t total = wg_sum(part, sh);
     if (total <= budget) {
-        for (int j = tid; j < njobs; j += RATE_WG) kept[j] = (uint8_t)min((int)numbps[j], RATE_STRIDE - 1);
+        for (int j = tid; j < njobs; j += RATE_WG) kept[j] = (uint8_t)rate_points<ST>(numbps, j);
         if (tid == 0) *chosen = total;
         return;
     }
-    rate_hulls(njobs, rate, dist, numbps, weights, W);
-    const uint64_t b = rate_search(njobs, rate, W, budget, sh, kept);
+    rate_hulls<ST>(njobs, rate, dist, numbps, weights, W);
+    const uint64_t b = rate_search<ST>(njobs, rate, W, budget, sh, kept);
     if (tid == 0) *chosen = b;
 }
 
@@ -260,6 +352,7 @@ __device__ __forceinline__ double wg_sum_f64(double v, double *sh) {
 // The LARGEST bit pattern of a non-negative double whose choice has S <= target: bisection over the patterns, 64 steps, the midpoint rounded
 // up.  Pattern 0 always fits (lambda = +0.0 takes every hull to its last point, where D = 0), so `lo` is a fitting pattern throughout.
 // Writes that choice to kept[0 ... njobs), its bytes to *bytes (every thread), and returns its S.
+template <int ST = RATE_STRIDE>
 __device__ __forceinline__ double quality_search(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist, const double *__restrict__ weights,
                                                  const RateWs &W, double target, uint64_t *sh, double *shf, uint8_t *__restrict__ kept, uint64_t *bytes) {
     const int tid = threadIdx.x;
@@ -268,7 +361,7 @@ __device__ __forceinline__ double quality_search(int njobs, const uint32_t *__re
         const uint64_t mid = lo + (hi - lo + 1) / 2;
         const double lam = __longlong_as_double((long long)mid);
         double s = 0.0;
-        for (int j = tid; j < njobs; j += RATE_WG) s = s + weights[j] * (double)dist[(size_t)j * RATE_STRIDE + rate_pick(W, j, lam)];
+        for (int j = tid; j < njobs; j += RATE_WG) s = s + weights[j] * (double)dist[(size_t)j * ST + rate_pick<ST>(W, j, lam)];
         s = wg_sum_f64(s, shf);                          // every thread takes every step: wg_sum_f64 has barriers
         if (s <= target) lo = mid; else hi = mid - 1;
     }
@@ -276,16 +369,30 @@ __device__ __forceinline__ double quality_search(int njobs, const uint32_t *__re
     uint64_t b = 0;
     double s = 0.0;
     for (int j = tid; j < njobs; j += RATE_WG) {
-        const int p = rate_pick(W, j, lam);
+        const int p = rate_pick<ST>(W, j, lam);
         kept[j] = (uint8_t)p;
-        b += rate[(size_t)j * RATE_STRIDE + p];
-        s = s + weights[j] * (double)dist[(size_t)j * RATE_STRIDE + p];
+        b += rate[(size_t)j * ST + p];
+        s = s + weights[j] * (double)dist[(size_t)j * ST + p];
     }
     *bytes = wg_sum(b, sh);
     return wg_sum_f64(s, shf);
 }
 
 struct RateTargets { double t[32]; };
+// the one-target form on the pass tables (j2k_plan_rate_allocate_quality_passes): the same search, a point per coding pass
+__global__ __launch_bounds__(RATE_WG) void rate_allocate_quality_passes_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
+                                                                               const uint8_t *__restrict__ numbps, const double *__restrict__ weights,
+                                                                               double target, void *__restrict__ ws, uint8_t *__restrict__ kept,
+                                                                               uint64_t *__restrict__ chosen, double *__restrict__ achieved) {
+    __shared__ uint64_t sh[RATE_WG / 64];
+    __shared__ double shf[RATE_WG / 64];
+    const RateWs W = rate_ws<RATE_PASS_STRIDE>(ws, (size_t)njobs);
+    rate_hulls<RATE_PASS_STRIDE>(njobs, rate, dist, numbps, weights, W);
+    uint64_t b = 0;
+    const double s = quality_search<RATE_PASS_STRIDE>(njobs, rate, dist, weights, W, target, sh, shf, kept, &b);
+    if (threadIdx.x == 0) { *chosen = b; *achieved = s; }
+}
+
 // One workgroup, a sibling of rate_allocate_layers_kernel: layer l is the search for targets.t[l] -- kept[l * njobs + j], chosen[l] (body bytes),
 // achieved[l] (S).  The hulls are built once.  Targets fall with l, "the largest lambda that fits" then makes kept monotone in l.
 __global__ __launch_bounds__(RATE_WG) void rate_allocate_quality_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
@@ -327,7 +434,25 @@ hipError_t launch_rate_distortion_roi(hipStream_t s, const BlockJob *jobs, int n
 
 hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate,const uint64_t *dist, const uint8_t *numbps, const double *weights,
                                 uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen) {
-    hipLaunchKernelGGL(rate_allocate_kernel, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, budget, ws, kept, chosen);
+    hipLaunchKernelGGL(rate_allocate_kernel<RATE_STRIDE>, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, budget, ws, kept, chosen);
+    return hipGetLastError();
+}
+
+// ---- pass cuts: tables of 96 entries per block, kept[j] = a pass index ----
+hipError_t launch_rate_distortion_passes(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, const uint64_t *spmask,
+                                         uint64_t *dist) {
+    if (njobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rate_distortion_passes_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, numbps, spmask, dist);
+    return hipGetLastError();
+}
+hipError_t launch_rate_allocate_passes(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+                                       uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen) {
+    hipLaunchKernelGGL(rate_allocate_kernel<RATE_PASS_STRIDE>, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, budget, ws, kept, chosen);
+    return hipGetLastError();
+}
+hipError_t launch_rate_allocate_quality_passes(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
+                                               double target, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved) {
+    hipLaunchKernelGGL(rate_allocate_quality_passes_kernel, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, target, ws, kept, chosen, achieved);
     return hipGetLastError();
 }
 

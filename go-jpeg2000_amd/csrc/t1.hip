@@ -554,17 +554,27 @@ __device__ __forceinline__ uint32_t t1_raw_pack(uint8_t *out, uint32_t cap, uint
 //                the table holds the symbol index of every plane end (in the padded list) for t1_mq_lanes_kernel<true>, which
 //                replaces each mark by the byte count when its lane passes it.
 #define T1_RATE_STRIDE 32
+// PLANES as a mode: 0 off, T1_RATE_PLANES the tables above, T1_RATE_PASSES (j2k_plan_encode_blocks_passes; tests/pass_cases.py) a table of
+//                T1_PASS_STRIDE entries with one entry per coding-pass end, q = 3 p - 2 + s after s passes of the plane behind p whole ones
+//                (the top plane's SigProp and MagRef passes are empty and have no entry), and spmask[jid * 64 + y] = the samples of row y that
+//                turned significant in a SigProp pass.  Empty passes are common: consecutive marks are often equal.
+#define T1_RATE_PLANES 1
+#define T1_RATE_PASSES 2
+#define T1_PASS_STRIDE 96
 #define T1_RATE_MARGIN 5u   /* bytes past the coder's byte index that hold everything the registers held at a plane end */
 // RAWMR: the raw-MagRef coding style (j2k_plan_set_raw_magref): the MagRef decisions never become symbols -- they go, in coding
 //                order, to the block's raw bit string in `rate` (not a rate table here: PLANES and RAWMR exclude each other), job j at
 //                j * T1_RAWST_WORDS; the MQ codeword starts three bytes into the slot.  SPLIT = false packs the body (t1_raw_pack) itself,
 //                SPLIT = true leaves that to t1_raw_pack_kernel behind the lanes kernel.
-template <bool SPLIT, bool PLANES = false, bool RAWMR = false>
+template <bool SPLIT, int PLANES = 0, bool RAWMR = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void t1_encode64_kernel(const BlockJob *__restrict__ jobs, int njobs, const int32_t *__restrict__ coef,
                                                          uint8_t *__restrict__ slots, uint32_t *__restrict__ lens,
                                                          uint8_t *__restrict__ numbps, int *__restrict__ fault,
                                                          uint8_t *__restrict__ gsym, size_t sym_stride, uint32_t *__restrict__ nsyms,
-                                                         int plane_budget, const uint32_t *__restrict__ only_skipped, uint32_t *__restrict__ rate = nullptr) {
+                                                         int plane_budget, const uint32_t *__restrict__ only_skipped, uint32_t *__restrict__ rate = nullptr,
+                                                         uint64_t *__restrict__ spmask = nullptr) {
+    constexpr bool PASSES = PLANES == T1_RATE_PASSES;
+    constexpr int RSTRIDE = PASSES ? T1_PASS_STRIDE : T1_RATE_STRIDE;
     __shared__ T1Fast F;
     const int jid = blockIdx.x;
     if (jid >= njobs) return;
@@ -576,7 +586,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
         if (SPLIT && lane == 0) nsyms[jid] = 0;
         return;
     }
-    uint32_t *const rrow = PLANES ? rate + (size_t)jid * T1_RATE_STRIDE : nullptr;
+    uint32_t *const rrow = PLANES ? rate + (size_t)jid * RSTRIDE : nullptr;
     const size_t n = (size_t)w * h;
     build_tables(F.T, J.band, lane);
     __syncthreads();
@@ -606,6 +616,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
     }
     if (maxVal == 0) {
         if (lane == 0) { lens[jid] = 0; numbps[jid] = 0; if (SPLIT) nsyms[jid] = 0; }
+        if (PASSES) {
+            rrow[lane] = 0;
+            if (lane + 64 < RSTRIDE) rrow[lane + 64] = 0;
+            spmask[(size_t)jid * 64 + lane] = 0;
+        } else
         if (PLANES && lane < T1_RATE_STRIDE) rrow[lane] = 0;
         return;
     }
@@ -641,6 +656,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
     const uint64_t rowok = (lane < h) ? wmask : 0ull;
     const uint64_t lt = (1ull << lane) - 1;         // columns before this lane's column
     uint64_t S = 0, REF = 0;
+    uint64_t spacc = 0;                             // PASSES: this row's samples that turned significant in a SigProp pass
     uint8_t *out = slots + J.out_off;
     MqEnc e{0x8000, 0, 12, 0, 0, RAWMR ? out + T1_RAW_HDR : out, (long)t1_mqbuf_bytes(n) - (RAWMR ? (long)T1_RAW_HDR : 0), 0};
     T1RawStage rs;
@@ -667,6 +683,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
         __syncthreads();                                      \
     } while (0)
 #define T1F_ROOM() do { if (nsym + T1F_SYM_STEP > T1F_SYM_CAP) T1F_DRAIN(); } while (0)
+// PASSES: the end of a pass inside plane numBPS - bp (not the top one), entry Q of the table
+#define T1F_PASS_MARK(Q)                                      \
+    do {                                                      \
+        if (PASSES && bp < numBPS - 1) {                      \
+            if (SPLIT) { if (lane == 0) rrow[(Q)] = gtotal + nsym; } \
+            else { T1F_DRAIN(); if (lane == 0) rrow[(Q)] = (uint32_t)e.bp + T1_RATE_MARGIN; } \
+        }                                                     \
+    } while (0)
 
     for (int bp = numBPS - 1; bp >= 0; bp--) {
         const uint64_t B = row_masks(bp);
@@ -719,6 +743,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
                 nsym += __popcll(Vis) + __popcll(New);
             }
         }
+        if (PASSES) spacc |= newsig;
+        T1F_PASS_MARK(3 * (numBPS - bp) - 4);
         // =========== magnitude refinement (t1_fast5.go:252-335): members = significant before this plane ===========
         {
             // "a significant neighbour" of every sample of a row, for all rows at once (lanes = rows) instead of per row on the scalar
@@ -754,6 +780,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
             }
         }
         REF |= S;
+        T1F_PASS_MARK(3 * (numBPS - bp) - 3);
         // =========== cleanup (t1_fast5.go:338-876) ===========
         const uint64_t mem = ~Snew & ~vis & rowok;          // coded here; every member whose bit is set becomes significant
         const uint64_t Sc = Snew | (mem & B);
@@ -831,13 +858,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
         }
         S = Sc;
         if (PLANES) {                                       // the end of plane numBPS - bp
-            if (SPLIT) { if (lane == 0) rrow[numBPS - bp] = gtotal + nsym; }
-            else { T1F_DRAIN(); if (lane == 0) rrow[numBPS - bp] = (uint32_t)e.bp + T1_RATE_MARGIN; }
+            const int at = PASSES ? 3 * (numBPS - bp) - 2 : numBPS - bp;
+            if (SPLIT) { if (lane == 0) rrow[at] = gtotal + nsym; }
+            else { T1F_DRAIN(); if (lane == 0) rrow[at] = (uint32_t)e.bp + T1_RATE_MARGIN; }
         }
     }
     T1F_DRAIN();
+#undef T1F_PASS_MARK
 #undef T1F_DRAIN
 #undef T1F_ROOM
+    if (PASSES) spmask[(size_t)jid * 64 + lane] = spacc;
     if (RAWMR) {
         rs.finish(lane);
         if (!SPLIT) {                                       // flush the codeword (t1_fast5.go:878-898), then H | MQ | RAW
@@ -868,7 +898,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
         if (govf) lens[jid] = 0;
         numbps[jid] = (uint8_t)numBPS;
         if (PLANES) {
-            if (govf) { for (int p = 0; p < T1_RATE_STRIDE; p++) rrow[p] = 0; }      // a faulted block: no marks left where byte counts belong
+            if (govf) { for (int p = 0; p < RSTRIDE; p++) rrow[p] = 0; }      // a faulted block: no marks left where byte counts belong
             else rrow[0] = 0;
         }
         return;
@@ -881,7 +911,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
     if (PLANES) {
         const uint32_t len = end > 1 ? (uint32_t)(end - 1) : 0;
         rrow[0] = 0;
-        for (int p = 1; p < T1_RATE_STRIDE; p++) rrow[p] = p < numBPS ? min(rrow[p], len) : len;
+        const int last = PASSES ? 3 * numBPS - 2 : numBPS;
+        for (int p = 1; p < RSTRIDE; p++) rrow[p] = p < last ? min(rrow[p], len) : len;
     }
 }
 
@@ -918,7 +949,7 @@ __device__ __forceinline__ void t1_wave_sync() {       // LDS written by this wa
 // PLANES: `rate` holds every block's plane-end marks (t1_encode64_kernel<true, true>); a lane that has coded the symbols up to its next
 // mark replaces the mark by its byte index + T1_RATE_MARGIN, and after the flush clamps the table to the codeword's length.
 // RAWMR (the raw-MagRef style): the codeword starts three bytes into the slot; lens[] holds its length until t1_raw_pack_kernel has packed the body.
-template <bool PLANES = false, bool RAWMR = false>
+template <int PLANES = 0, bool RAWMR = false>
 __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const BlockJob *__restrict__ jobs, int njobs, int K, const uint8_t *__restrict__ gsym,
                                                          size_t sym_stride, const uint32_t *__restrict__ nsyms, uint8_t *__restrict__ slots,
                                                          uint32_t *__restrict__ lens, int *__restrict__ fault, const uint32_t *__restrict__ perm,
@@ -978,8 +1009,11 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const Bl
         const bool in = i0 < n;
         return make_uint4(in ? v.x : null16.x, in ? v.y : null16.y, in ? v.z : null16.z, in ? v.w : null16.w);
     };
-    uint32_t *const rrow = PLANES ? rate + (size_t)(live ? jid : 0) * T1_RATE_STRIDE : nullptr;
-    const uint32_t nbl = (PLANES && n) ? numbps[jid] : 0u;
+    constexpr bool PASSES = PLANES == T1_RATE_PASSES;
+    constexpr uint32_t RSTRIDE = PASSES ? T1_PASS_STRIDE : T1_RATE_STRIDE;
+    uint32_t *const rrow = PLANES ? rate + (size_t)(live ? jid : 0) * RSTRIDE : nullptr;
+    // the marks of this lane's block: one per plane, or (PASSES) one per pass end, 3 numBPS - 2 of them
+    const uint32_t nbl = (PLANES && n) ? (PASSES ? 3u * numbps[jid] - 2u : (uint32_t)numbps[jid]) : 0u;
     uint32_t pl = 1, mark = nbl ? rrow[1] : 0xFFFFFFFFu;       // the plane whose end comes next, and the symbol count there
     uint4 cur = fetch(0);
     uint32_t idx = (cur.x & 31u) * 64 + lane;
@@ -1030,6 +1064,13 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const Bl
                 }
             }
             idx = idxn;
+            if (PASSES) {
+                while (i0 + (uint32_t)q + 1u == mark) {     // an empty pass ends where the pass before it did: every mark at this count
+                    rrow[pl] = bp + T1_RATE_MARGIN;
+                    pl++;
+                    mark = pl <= nbl ? rrow[pl] : 0xFFFFFFFFu;
+                }
+            } else
             if (PLANES && i0 + (uint32_t)q + 1u == mark) {
                 rrow[pl] = bp + T1_RATE_MARGIN;
                 pl++;
@@ -1052,7 +1093,7 @@ __global__ __launch_bounds__(64 * T1_LANES_WPW) void t1_mq_lanes_kernel(const Bl
     lens[jid] = (RAWMR && ovf) ? 0xFFFFFFFFu : (end > 1 ? (uint32_t)(end - 1) : 0);      // (the style: the mark makes t1_raw_pack_kernel leave lens = 0)
     if (PLANES) {
         const uint32_t len = end > 1 ? end - 1 : 0u;
-        for (uint32_t p = 1; p < T1_RATE_STRIDE; p++) rrow[p] = p < nbl ? min(rrow[p], len) : len;
+        for (uint32_t p = 1; p < RSTRIDE; p++) rrow[p] = p < nbl ? min(rrow[p], len) : len;
     }
 }
 
@@ -1367,8 +1408,9 @@ __device__ __forceinline__ int32_t t1_coarse_finish(int32_t mag, uint32_t mid, b
 // One block, one wavefront; all lanes call this.  Only the MQ decisions and what depends on them run on lane 0.
 // skip: the quality floor (j2k_*_coarse): the planes below it are left undecoded.
 // RAWMR (the raw-MagRef style): MagRef takes its decisions from rd, lane 0's reader of the body's RAW part.
-template <bool RAWMR = false>
-__device__ __forceinline__ void t1_decode_block_wave(T1DecLane &L, int numBPS, int skip, uint8_t *mrctx, int lane, RawRd *rd = nullptr) {
+// PASSCUT (the *_pfloors calls; tests/pass_cases.py): behind the whole planes the first `part` (0 ... 2) passes of plane skip - 1.
+template <bool RAWMR = false, bool PASSCUT = false>
+__device__ __forceinline__ void t1_decode_block_wave(T1DecLane &L, int numBPS, int skip, uint8_t *mrctx, int lane, RawRd *rd = nullptr, int part = 0) {
     for (int bp = numBPS - 1; bp >= skip; bp--) {
         const int32_t bit = bp < 32 ? (int32_t)(1u << bp) : 0;
         t1_dec_sigprop_wave(L, bit, mrctx, mrctx + 64, lane);
@@ -1377,6 +1419,19 @@ __device__ __forceinline__ void t1_decode_block_wave(T1DecLane &L, int numBPS, i
         t1_dec_magref_wave(L, bit, mrctx, lane);
         t1_dec_cleanup_wave(L, bit, mrctx, lane);
     }
+    if (PASSCUT && part > 0 && skip >= 1 && skip <= numBPS && skip <= 32) {
+        const int32_t bit = (int32_t)(1u << (skip - 1));
+        t1_dec_sigprop_wave(L, bit, mrctx, mrctx + 64, lane);
+        if (part > 1) t1_dec_magref_wave(L, bit, mrctx, lane);
+    }
+}
+// The floor of one sample behind a partial plane (the finish loops of the PASSCUT forms need no record of who turned where): after a lone
+// SigProp of plane b a magnitude is exactly 2^b iff the sample turned significant in that pass -- every older one is a multiple of 2^(b+1) and
+// has not been refined; after SigProp + MagRef every non-zero magnitude is complete down to plane b.
+__device__ __forceinline__ uint32_t t1_pass_mid(uint32_t mag, int skip, int part) {
+    int k = skip;
+    if (part == 2 || (part == 1 && (mag & ((2u << (skip - 1)) - 1u)))) k = skip - 1;
+    return t1_coarse_mid(k);
 }
 __device__ __forceinline__ void mq_dec_init(MqDec &d, const uint8_t *data, long len) {   // NewMQDecoder mqc.go:370-399
     d = MqDec{0, 0x8000, 0, -1, len, data};
@@ -1453,13 +1508,21 @@ struct T1Dec64Shared {
 };
 static_assert(sizeof(T1Dec64Shared) <= 5120, "t1_decode64_kernel: LDS per block above 10 granules (32 blocks per CU)");
 // RAWMR: the raw-MagRef style (j2k_plan_set_raw_magref): the body is H | MQ | RAW, the MQ decoder runs on MQ, MagRef reads RAW.
-template <bool RAWMR = false>
+// PASSCUT: `floors` counts coding PASSES left undecoded (j2k_plan_decode_blocks_pfloors): block j stops f = max(3 skip_uniform, floors[j])
+// passes short of its last -- whole planes down to ceil(f / 3), then the first 3 ceil(f / 3) - f passes of the next plane.
+template <bool RAWMR = false, bool PASSCUT = false>
 __global__ __launch_bounds__(64) void t1_decode64_kernel(const BlockJob *__restrict__ jobs, int njobs, const uint8_t *__restrict__ stream,
                                                          const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
                                                          const uint8_t *__restrict__ numbps, int32_t *__restrict__ decoded, int min_bps, int skip_uniform, const uint8_t *__restrict__ floors) {
     __shared__ T1Dec64Shared S;
     if ((int)blockIdx.x >= njobs) return;
-    const int skip_planes = t1_floor_of(skip_uniform, floors, blockIdx.x);       // this block's floor: the call's, or its own if that is higher
+    int skip_planes, part = 0;
+    if (PASSCUT) {
+        const int f = t1_floor_of(3 * skip_uniform, floors, blockIdx.x);
+        skip_planes = (f + 2) / 3;
+        part = 3 * skip_planes - f;
+    } else
+    skip_planes = t1_floor_of(skip_uniform, floors, blockIdx.x);       // this block's floor: the call's, or its own if that is higher
     if ((int)numbps[blockIdx.x] < min_bps) return;                   // the plane-stepped path took this block
     const int lane = threadIdx.x;
     // The block index as a VECTOR value the compiler cannot prove uniform: everything derived from it (block size, loop
@@ -1500,10 +1563,19 @@ __global__ __launch_bounds__(64) void t1_decode64_kernel(const BlockJob *__restr
         if (lane == 0) mq_dec_init(L.d, stream + offs[jid], (long)lens[jid]);
         L.ent = S.ent; L.mq = c_mq94.v; L.zcsc = S.zcsc; L.flags = S.flags; L.data = out; L.w = w; L.h = h; L.stride = stride;
         if (RAWMR) t1_decode_block_wave<true>(L, __shfl((int)numbps[jid], 0), skip_planes + vzero, S.mrctx, lane, &rd);
+        else if (PASSCUT) t1_decode_block_wave<false, true>(L, __shfl((int)numbps[jid], 0), skip_planes + vzero, S.mrctx, lane, nullptr, part);
         else
         t1_decode_block_wave(L, __shfl((int)numbps[jid], 0), skip_planes + vzero, S.mrctx, lane);
     }
     __syncthreads();                                                      // includes the wait for lane 0's stores and atomics
+    if (PASSCUT && part > 0) {
+        for (int i = lane; i < n; i += 64) {
+            const bool neg = (S.flags[(i / w + 1) * stride + T1D_XO + (i % w)] & T1SignNeg) != 0;
+            const int v = __hip_atomic_load(&out[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            out[i] = t1_coarse_finish(v, t1_pass_mid((uint32_t)v, skip_planes, part), neg);
+        }
+        return;
+    }
     const uint32_t mid = t1_coarse_mid(skip_planes);
     for (int i = lane; i < n; i += 64) {                                  // t1.go:1281-1289
         const bool neg = (S.flags[(i / w + 1) * stride + T1D_XO + (i % w)] & T1SignNeg) != 0;
@@ -1969,19 +2041,19 @@ size_t t1_sym_stride(int planes) { return ((size_t)(planes + 2) * 4096 + 1024 + 
 // The launches for blocks up to 64 x 64, one sequence for every instantiation: PLANES (aux = the rate tables), RAWMR (the raw-MagRef style, aux = the
 // staging records; t1_raw_pack_kernel assembles the bodies behind the lanes kernel), or neither (aux = null).
 // sym != null: context formation and MQ coding as two kernels through the symbol workspace; otherwise the one-kernel form.
-template <bool PLANES, bool RAWMR>
+template <int PLANES, bool RAWMR>
 static void launch_t1_encode64(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots, uint32_t *lens, uint8_t *numbps, int *fault,
-                               uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint32_t *aux, int *forms) {
+                               uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint32_t *aux, int *forms, uint64_t *spmask = nullptr) {
     if (forms) forms[0] = 0;
     if (!(sym && nsyms)) {
         hipLaunchKernelGGL((t1_encode64_kernel<false, PLANES, RAWMR>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                           (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nullptr, aux);
+                           (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nullptr, aux, spmask);
         return;
     }
     int planes = (int)((sym_stride - 1024) / 4096) - 2;
     if (planes > 31) planes = 31;
     hipLaunchKernelGGL((t1_encode64_kernel<true, PLANES, RAWMR>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                       sym, sym_stride, nsyms, planes, (const uint32_t *)nullptr, aux);
+                       sym, sym_stride, nsyms, planes, (const uint32_t *)nullptr, aux, spmask);
     // blocks per wavefront: the kernel runs at the latency of one chain whatever K is, so K decides how much of the
     // device a frame's chains occupy while they run.  Measured on a 4K 12-bit frame (7005 blocks): one frame alone
     // 15.8 ms at K = 4, 18.0 at K = 32 (each wavefront waits for its slowest lane); three or more frames in flight
@@ -2002,7 +2074,7 @@ static void launch_t1_encode64(hipStream_t s, const BlockJob *jobs, int njobs, c
     if (RAWMR) hipLaunchKernelGGL(t1_raw_pack_kernel, dim3(njobs), dim3(64), 0, s, jobs, njobs, slots, lens, (const uint32_t *)nsyms, (const uint32_t *)aux, fault);
     if (planes < 31)        // the lists are shorter than the deepest block can be: the blocks marked T1F_SKIPPED take the one-kernel form
         hipLaunchKernelGGL((t1_encode64_kernel<false, PLANES, RAWMR>), dim3(njobs), dim3(64), 0, s, jobs, njobs, coef, slots, lens, numbps, fault,
-                           (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nsyms, aux);
+                           (uint8_t *)nullptr, (size_t)0, (uint32_t *)nullptr, 0, (const uint32_t *)nsyms, aux, spmask);
 }
 
 // max_dim: largest block width or height among the jobs (<= 64: every block takes the wave-parallel kernels).
@@ -2011,19 +2083,21 @@ static void launch_t1_encode64(hipStream_t s, const BlockJob *jobs, int njobs, c
 hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, uint8_t *slots,
                             uint32_t *lens, uint8_t *numbps, uint8_t *work, size_t work_per_job, int *fault, int max_dim,
                             uint8_t *sym, size_t sym_stride, uint32_t *nsyms, int lanes, uint8_t *bigsym, const uint64_t *bigsym_off, uint32_t *bignsyms, uint32_t *rate,
-                            uint32_t *rawst, int *forms) {
+                            uint32_t *rawst, int *forms, uint64_t *spmask) {
     if (forms) forms[0] = forms[1] = 0;
     if (njobs <= 0) return hipSuccess;
     if (rawst) {     // the raw-MagRef style (j2k_plan_set_raw_magref; blocks <= 64 x 64, no rate tables): the RAWMR instantiations, same sequence
-        launch_t1_encode64<false, true>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rawst, forms);
+        launch_t1_encode64<0, true>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rawst, forms);
         return hipGetLastError();
     }
     static int serial_only = -1;   // J2K_T1_SERIAL=1: A/B against the serial kernel
     if (serial_only < 0) serial_only = 0;          // (round 1's A/B switch J2K_T1_SERIAL: gone, the serial kernel only takes what the others leave)
     if (!serial_only) {
         // rate != null (j2k_plan_encode_blocks_planes): the PLANES instantiations of the <= 64 x 64 kernels; the others are launched as before
-        if (rate) launch_t1_encode64<true, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rate, forms);
-        else launch_t1_encode64<false, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, (uint32_t *)nullptr, forms);
+        // spmask != null (j2k_plan_encode_blocks_passes): the PASSES instantiations, `rate` with T1_PASS_STRIDE entries per job
+        if (rate && spmask) launch_t1_encode64<T1_RATE_PASSES, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rate, forms, spmask);
+        else if (rate) launch_t1_encode64<T1_RATE_PLANES, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, rate, forms);
+        else launch_t1_encode64<0, false>(s, jobs, njobs, coef, slots, lens, numbps, fault, sym, sym_stride, nsyms, lanes, (uint32_t *)nullptr, forms);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || max_dim <= 64) return e;
         // blocks above 64 x 64, up to 256 x 256 (the reference's default size): wave-parallel context formation (t1_big.inc)
@@ -2077,9 +2151,16 @@ hipError_t launch_t1_encode(hipStream_t s, const BlockJob *jobs, int njobs, cons
 // general_only: every block on the general kernel (A/B knob); otherwise blocks up to 64x64 take t1_decode64_kernel
 hipError_t launch_t1_decode(hipStream_t s, const BlockJob *jobs, int njobs, const uint8_t *stream, const uint64_t *offs,
                             const uint32_t *lens, const uint8_t *numbps, int32_t *decoded, uint8_t *work, size_t work_per_job,
-                            int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput, int skip_planes, const uint8_t *floors, int raw_magref, int *big_launches) {
+                            int max_dim, int general_only, uint8_t *split_ws, int sig_lanes, int throughput, int skip_planes, const uint8_t *floors, int raw_magref, int *big_launches,
+                            const uint8_t *pfloors) {
     if (big_launches) *big_launches = 0;
     if (njobs <= 0) return hipSuccess;
+    if (pfloors) {
+        // floors in coding passes (j2k_plan_decode_blocks_pfloors; blocks <= 64 x 64, plain style: the call has refused everything else): every
+        // block on the one-launch kernel, whose PASSCUT form alone knows the partial plane
+        hipLaunchKernelGGL((t1_decode64_kernel<false, true>), dim3(njobs), dim3(64), 0, s, jobs, njobs, stream, offs, lens, numbps, decoded, 0, skip_planes, pfloors);
+        return hipGetLastError();
+    }
     if (raw_magref) {
         // the raw-MagRef style (blocks <= 64 x 64, no per-block floors: the setter and the floors calls have refused everything else): the
         // plane-stepped lanes path where the plain style would take a plane-stepped path (split_ws; its workspace is t1_dec_split_bytes(njobs,

@@ -699,17 +699,22 @@ __global__ __launch_bounds__(256) void t2_seed_kernel(const T2Chain *__restrict_
 // coder's pass count is 3 * numBPS - 2 (t1_fast5.go:66-70); an HT block carries one pass and the decoder does not use the count,
 // so it is mb - ZeroBitPlanes there (what j2k_plan_t2_fill_cbs wrote).
 __device__ __forceinline__ void t2_block_out(long j, const j2k_t2_dev_cb &cb, bool decoded, int ht, int mb, uint64_t total, uint64_t *__restrict__ offs,
-                                             uint32_t *__restrict__ lens, uint8_t *__restrict__ numbps, int *__restrict__ status, uint8_t *__restrict__ floors = nullptr) {
+                                             uint32_t *__restrict__ lens, uint8_t *__restrict__ numbps, int *__restrict__ status, uint8_t *__restrict__ floors = nullptr,
+                                             uint8_t *__restrict__ pfloors = nullptr) {
     // (a body outside the buffer can only come from a chain that failed half way -- the frame's status says so; nothing is read there)
     const bool has = decoded && cb.included_in_layers == 0 && cb.data_len > 0 && cb.num_passes > 0 && cb.data_off <= total && cb.data_len <= total - cb.data_off;
     int nb = 0;
     if (has) nb = ht ? (mb > cb.zero_bit_planes ? mb - cb.zero_bit_planes : 0) : (cb.num_passes + 2) / 3;
     // floors != NULL (the _floors calls, MQ coder): a block cut at a bit plane says so by carrying fewer passes than its planes need -- the
     // planes it has are its TOP ones: floor = mb - ZeroBitPlanes - coded planes (never below 0), and the decoder runs numbps = coded + floor
+    // pfloors != NULL (the _pfloors calls; tests/pass_cases.py): the count is read at pass granularity -- s = (passes + 2) % 3 passes of the plane
+    // below the coded ones are there too, so the block stops 3 floor - s coding passes short of its last
     int floor = 0;
-    if (floors) {
+    if (floors || pfloors) {
+        const int coded = nb;
         if (has && !ht) { floor = max(mb - (int)cb.zero_bit_planes - nb, 0); nb += floor; }
-        floors[j] = (uint8_t)(nb > 31 ? 0 : floor);
+        if (floors) floors[j] = (uint8_t)(nb > 31 ? 0 : floor);
+        if (pfloors) pfloors[j] = (uint8_t)((nb > 31 || floor == 0 || !has || ht) ? 0 : 3 * floor - (cb.num_passes + 2 - 3 * coded));
     }
     // more bit planes than an int32 coefficient has: no encoder of this library writes that (numBPS <= 31) -- a foreign stream; the block is
     // dropped and the frame's status says why
@@ -729,14 +734,15 @@ __global__ __launch_bounds__(256) void t2_blocks_kernel(long n, const j2k_t2_dev
 // workgroup per packet; a packet its chain did not reach (body_base = ~0) has no data
 __global__ __launch_bounds__(256) void t2_finish_kernel(const j2k_t2_dev_packet *__restrict__ packets, j2k_t2_dev_cb *__restrict__ cbs, uint64_t ncbs,
                                                         const uint64_t *__restrict__ body_base, int ht, int mb, uint64_t total, uint64_t *__restrict__ offs,
-                                                        uint32_t *__restrict__ lens, uint8_t *__restrict__ numbps, int *__restrict__ status, uint8_t *__restrict__ floors) {
+                                                        uint32_t *__restrict__ lens, uint8_t *__restrict__ numbps, int *__restrict__ status, uint8_t *__restrict__ floors,
+                                                        uint8_t *__restrict__ pfloors) {
     const j2k_t2_dev_packet P = packets[blockIdx.x];
     const uint64_t b = body_base[blockIdx.x];
     if (P.ncb < 0 || P.cb0 < 0 || (uint64_t)P.cb0 + (uint64_t)P.ncb > ncbs) return;
     for (int64_t i = threadIdx.x; i < P.ncb; i += 256) {
         j2k_t2_dev_cb cb = cbs[P.cb0 + i];
         if (b != ~0ull && cb.included_in_layers == P.layer && cb.data_len > 0) { cb.data_off += b; cbs[P.cb0 + i].data_off = cb.data_off; }
-        t2_block_out((long)(P.cb0 + i), cb, b != ~0ull, ht, mb, total, offs, lens, numbps, status, floors);
+        t2_block_out((long)(P.cb0 + i), cb, b != ~0ull, ht, mb, total, offs, lens, numbps, status, floors, pfloors);
     }
 }
 
@@ -915,7 +921,7 @@ size_t t2_par_workspace(long npackets, int ntiles) {
 }
 hipError_t launch_t2_decode_tiles(hipStream_t s, void *chains, int ntiles, const int *tile_packet0, const j2k_t2_dev_packet *packets, long npackets,
                                   j2k_t2_dev_cb *cbs, uint64_t ncbs, const uint8_t *data, uint64_t len, int sop, int eph, uint64_t *body_base, int *frame_status, void *ws,
-                                  int ht, int mb, uint64_t *offs, uint32_t *lens, uint8_t *numbps, uint8_t *floors) {
+                                  int ht, int mb, uint64_t *offs, uint32_t *lens, uint8_t *numbps, uint8_t *floors, uint8_t *pfloors) {
     if (ntiles <= 0 || npackets <= 0) return hipSuccess;
     T2Chain *tc = reinterpret_cast<T2Chain *>(chains);
     if (sop && eph && ws) {
@@ -935,7 +941,7 @@ hipError_t launch_t2_decode_tiles(hipStream_t s, void *chains, int ntiles, const
     } else
         hipLaunchKernelGGL(t2_decode_kernel<false>, dim3((unsigned)ntiles), dim3(64), 0, s, tc, packets, npackets, cbs, ncbs, data, sop, eph, 2, body_base, frame_status,
                            (const T2Chain *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (const int *)nullptr, (int64_t)0);
-    hipLaunchKernelGGL(t2_finish_kernel, dim3((unsigned)npackets), dim3(256), 0, s, packets, cbs, ncbs, body_base, ht, mb, len, offs, lens, numbps, frame_status, floors);
+    hipLaunchKernelGGL(t2_finish_kernel, dim3((unsigned)npackets), dim3(256), 0, s, packets, cbs, ncbs, body_base, ht, mb, len, offs, lens, numbps, frame_status, floors, pfloors);
     return hipGetLastError();
 }
 // the generic call's one chain, made on the host

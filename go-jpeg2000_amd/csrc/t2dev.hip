@@ -387,7 +387,7 @@ __global__ __launch_bounds__(64) void t2_body_kernel(const j2k_t2_dev_packet *__
 // 3 * numBPS - 2 coding passes EncodeFast5 ran (t1_fast5.go:66-70; HT: one), ZeroBitPlanes = max(mb - numBPS, 0).
 __global__ __launch_bounds__(256) void t2_fill_cbs_kernel(long n, const uint64_t *__restrict__ offs, const uint32_t *__restrict__ lens,
                                                           const uint8_t *__restrict__ numbps, int mb, int ht, j2k_t2_dev_cb *__restrict__ cbs,
-                                                          uint64_t *__restrict__ reset, const uint8_t *__restrict__ kept, const uint32_t *__restrict__ rate) {
+                                                          uint64_t *__restrict__ reset, const uint8_t *__restrict__ kept, const uint32_t *__restrict__ rate, int passes) {
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j == 0 && reset) { reset[0] = 0; reset[1] = 0; reset[2] = 0; }   // (the packet coder's result words, for the launches behind this one)
     if (j >= n) return;
@@ -395,19 +395,21 @@ __global__ __launch_bounds__(256) void t2_fill_cbs_kernel(long n, const uint64_t
     j2k_t2_dev_cb cb{};
     // kept != NULL (rate control, MQ blocks): the block is cut after its first kept[j] bit planes -- the prefix rate[j * 32 + kept[j]] of its bytes,
     // the 3 p - 2 passes of those planes, ZeroBitPlanes as before (so that the decoder can tell the planes cut from the planes never there)
-    const int p = kept ? min((int)kept[j], nb) : nb;
-    const uint32_t len = kept ? min(rate[j * 32 + p], lens[j]) : lens[j];
+    // passes (j2k_plan_encode_tile_parts_kept_passes; tests/pass_cases.py): kept[j] is a PASS count q <= 3 nb - 2 and `rate` has 96 entries per block
+    // -- the prefix rate[j * 96 + q], q passes
+    const int p = kept ? min((int)kept[j], passes ? max(3 * min(nb, 31) - 2, 0) : nb) : nb;
+    const uint32_t len = kept ? min(rate[j * (passes ? 96 : 32) + p], lens[j]) : lens[j];
     cb.included_in_layers = ((ht & 2) && len == 0) ? 1 : 0;         // closed-loop mode (bit 1): a block without data is in no layer, and says so
     cb.zero_bit_planes = mb > nb ? mb - nb : 0;
-    cb.num_passes = (p == 0 || len == 0) ? 0 : ((ht & 1) ? 1 : 3 * p - 2);
+    cb.num_passes = (p == 0 || len == 0) ? 0 : ((ht & 1) ? 1 : (passes ? p : 3 * p - 2));
     cb.data_len = len;
     cb.data_off = offs ? offs[j] : 0;                              // (no stream: the bytes are gathered from the coding slots)
     cbs[j] = cb;
 }
 
-hipError_t launch_t2_fill_cbs(hipStream_t s, long n, const uint64_t *offs, const uint32_t *lens, const uint8_t *numbps, int mb, int ht, j2k_t2_dev_cb *cbs, uint64_t *reset, const uint8_t *kept, const uint32_t *rate) {
+hipError_t launch_t2_fill_cbs(hipStream_t s, long n, const uint64_t *offs, const uint32_t *lens, const uint8_t *numbps, int mb, int ht, j2k_t2_dev_cb *cbs, uint64_t *reset, const uint8_t *kept, const uint32_t *rate, int passes) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(t2_fill_cbs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, offs, lens, numbps, mb, ht, cbs, reset, kept, rate);
+    hipLaunchKernelGGL(t2_fill_cbs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, offs, lens, numbps, mb, ht, cbs, reset, kept, rate, passes);
     return hipGetLastError();
 }
 

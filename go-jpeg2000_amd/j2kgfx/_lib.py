@@ -77,6 +77,9 @@ SYMBOLS = [
     "j2k_plan_area_shape", "j2k_plan_area_blocks", "j2k_plan_decode_frame_pixels_area", "j2k_decode_pixels_host_area",
     "j2k_plan_roi_windows", "j2k_plan_encode_blocks_planes_roi", "j2k_plan_encode_frame_pixels_roi", "j2k_encode_pixels_host_roi",
     "j2k_plan_psnr_distortion", "j2k_plan_rate_allocate_quality", "j2k_plan_encode_frame_pixels_quality", "j2k_encode_pixels_host_quality", "j2k_pixels_sse",
+    "j2k_plan_encode_blocks_passes", "j2k_plan_rate_allocate_passes", "j2k_plan_rate_allocate_quality_passes", "j2k_plan_encode_tile_parts_kept_passes",
+    "j2k_plan_decode_tile_parts_pfloors", "j2k_plan_decode_blocks_pfloors", "j2k_plan_encode_frame_pixels_passes", "j2k_plan_decode_frame_pixels_passes",
+    "j2k_encode_pixels_host_passes", "j2k_decode_pixels_host_passes",
     "j2k_pipe_create", "j2k_pipe_destroy", "j2k_pipe_submit_encode", "j2k_pipe_submit_decode", "j2k_pipe_wait", "j2k_pipe_poll", "j2k_pipe_drain",
     "j2k_host_alloc", "j2k_host_free",
     "j2k_plan_pack_bound", "j2k_plan_pack_stream", "j2k_plan_unpack_stream", "j2k_plan_unpack_streams",
@@ -178,6 +181,16 @@ def lib():
             "j2k_plan_encode_frame_pixels_quality": (I, [V, I, V, S, I, I, DP, I, C.POINTER(Rect), I, V, S, V, V, V]),
             "j2k_encode_pixels_host_quality": (I, [V, I, V, S, I, I, DP, I, C.POINTER(Rect), I, V, S, C.POINTER(S), V, V, V, V, V]),
             "j2k_pixels_sse": (I, [V, I, V, S, V, S, I, I, V]),
+            "j2k_plan_encode_blocks_passes": (I, [V, V, V, V, V, V, V, V]),
+            "j2k_plan_rate_allocate_passes": (I, [V, V, V, V, C.c_int64, V, V]),
+            "j2k_plan_rate_allocate_quality_passes": (I, [V, V, V, V, C.c_double, V, V, V]),
+            "j2k_plan_encode_tile_parts_kept_passes": (I, [V, V, V, V, V, V, V, I, I, V, S, V]),
+            "j2k_plan_decode_tile_parts_pfloors": (I, [V, V, S, V, I, I, V, V, V, V]),
+            "j2k_plan_decode_blocks_pfloors": (I, [V, V, V, V, V, I, V, V]),
+            "j2k_plan_encode_frame_pixels_passes": (I, [V, I, V, S, I, I, C.c_int64, DP, V, S, V, V]),
+            "j2k_plan_decode_frame_pixels_passes": (I, [V, V, S, V, I, I, I, I, C.POINTER(Rect), V, S]),
+            "j2k_encode_pixels_host_passes": (I, [V, I, V, S, I, I, C.c_int64, DP, V, S, C.POINTER(S), V, V, V, V]),
+            "j2k_decode_pixels_host_passes": (I, [V, V, S, I, I, I, I, C.POINTER(Rect), V, S]),
             "j2k_pipe_create": (I, [V, I, C.POINTER(V)]), "j2k_pipe_destroy": (None, [V]),
             "j2k_pipe_submit_encode": (I, [V, I, V, S, I, I, V, S, V, V, V, C.POINTER(C.c_uint64)]),
             "j2k_pipe_submit_decode": (I, [V, V, S, I, I, V, S, C.POINTER(C.c_uint64)]),

@@ -229,8 +229,10 @@ class FramePlan:
         return pix
 
     @_stage
-    def encode_blocks(self, coeff, slots=None, lens=None, numbps=None, planes=False, roi=None, roi_gain=16):
-        """planes=True (closed-loop MQ plans, blocks <= 64 x 64): also the rate and distortion tables of every block, int32 / int64
+    def encode_blocks(self, coeff, slots=None, lens=None, numbps=None, planes=False, roi=None, roi_gain=16, pass_cuts=False):
+        """pass_cuts=True (the plans planes=True takes): the tables at coding-pass granularity, int32 / int64 [blocks, 96], and the SigProp masks,
+        int64 [blocks, 64] (j2k_plan_encode_blocks_passes) -- returns (slots, lens, numbps, rate, dist, spmask).
+        planes=True (closed-loop MQ plans, blocks <= 64 x 64): also the rate and distortion tables of every block, int32 / int64
         [blocks, 32] holding uint32 / uint64 values (j2k_plan_encode_blocks_planes) -- returns (slots, lens, numbps, rate, dist).
         roi=(x0, y0, x1, y1) with planes=True (Mallat plans): the distortion of the samples that reconstruct that rectangle counts roi_gain
         (1 ... 65535) times in dist; everything else is identical (j2k_plan_encode_blocks_planes_roi)"""
@@ -241,6 +243,15 @@ class FramePlan:
         slots = slots if slots is not None else self.empty(self.info.bytes_cap, t.uint8)
         lens = lens if lens is not None else self.empty(n, t.int32)
         numbps = numbps if numbps is not None else self.empty(n, t.uint8)
+        if pass_cuts:
+            if roi is not None:
+                raise ValueError("encode_blocks: pass_cuts together with roi= -- not built")
+            rate = t.zeros((max(n, 1), 96), dtype=t.int32, device=self.device)
+            dist = t.zeros((max(n, 1), 96), dtype=t.int64, device=self.device)
+            spmask = t.zeros((max(n, 1), 64), dtype=t.int64, device=self.device)
+            self.ctx.check(self.ctx.L.j2k_plan_encode_blocks_passes(self.h, self._p(coeff), self._p(slots), self._p(lens), self._p(numbps), self._p(rate),
+                                                                    self._p(dist), self._p(spmask)))
+            return slots, lens, numbps, rate, dist, spmask
         if planes:
             rate = t.zeros((max(n, 1), 32), dtype=t.int32, device=self.device)
             dist = t.zeros((max(n, 1), 32), dtype=t.int64, device=self.device)
@@ -257,13 +268,18 @@ class FramePlan:
         return slots, lens, numbps
 
     @_stage
-    def rate_allocate(self, rate, dist, numbps, max_body_bytes, kept=None, chosen=None):
-        """the planes to keep of every block so that the code-block BODY bytes are at most max_body_bytes (packet and tile-part headers
+    def rate_allocate(self, rate, dist, numbps, max_body_bytes, kept=None, chosen=None, pass_cuts=False):
+        """pass_cuts=True: rate / dist are the 96-entry tables of encode_blocks(pass_cuts=True), kept[j] is a pass count (j2k_plan_rate_allocate_passes).
+        the planes to keep of every block so that the code-block BODY bytes are at most max_body_bytes (packet and tile-part headers
         come on top): returns (kept uint8 [blocks], chosen int64 [1] = the body bytes of that choice)  (j2k_plan_rate_allocate)"""
         t = _torch()
         n = int(self.info.blocks)
         kept = kept if kept is not None else self.empty(n, t.uint8)
         chosen = chosen if chosen is not None else t.zeros(1, dtype=t.int64, device=self.device)
+        if pass_cuts:
+            self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_passes(self.h, self._p(rate), self._p(dist), self._p(numbps), C.c_int64(int(max_body_bytes)),
+                                                                    self._p(kept), self._p(chosen)))
+            return kept, chosen
         self.ctx.check(self.ctx.L.j2k_plan_rate_allocate(self.h, self._p(rate), self._p(dist), self._p(numbps), C.c_int64(int(max_body_bytes)),
                                                          self._p(kept), self._p(chosen)))
         return kept, chosen
@@ -315,8 +331,10 @@ class FramePlan:
         return [float(t) for t in layer_distortion], True
 
     @_stage
-    def rate_allocate_quality(self, rate, dist, numbps, targets, kept=None, chosen=None, achieved=None):
-        """the planes to keep of every block so that the weighted distortion sum_j w_j * dist[j, kept_j] (float64, in the fixed order of
+    def rate_allocate_quality(self, rate, dist, numbps, targets, kept=None, chosen=None, achieved=None, pass_cuts=False):
+        """pass_cuts=True: ONE target on the 96-entry tables of encode_blocks(pass_cuts=True), kept[0, j] is a pass count
+        (j2k_plan_rate_allocate_quality_passes).
+        the planes to keep of every block so that the weighted distortion sum_j w_j * dist[j, kept_j] (float64, in the fixed order of
         tests/quality_cases.py) is at most targets[l], in as few body bytes as the hulls allow; targets fall (or stay) layer by layer:
         (kept uint8 [L, blocks], chosen int64 [L] = body bytes, achieved float64 [L] = that sum)  (j2k_plan_rate_allocate_quality)"""
         t = _torch()
@@ -325,6 +343,12 @@ class FramePlan:
         kept = kept if kept is not None else self.empty(max(L, 1) * n, t.uint8)
         chosen = chosen if chosen is not None else t.zeros(max(L, 1), dtype=t.int64, device=self.device)
         achieved = achieved if achieved is not None else t.zeros(max(L, 1), dtype=t.float64, device=self.device)
+        if pass_cuts:
+            if L != 1:
+                raise ValueError("rate_allocate_quality: pass_cuts takes one target (layers with pass cuts: not built)")
+            self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_quality_passes(self.h, self._p(rate), self._p(dist), self._p(numbps), C.c_double(float(arr[0])),
+                                                                            self._p(kept), self._p(chosen), self._p(achieved)))
+            return kept[:n].view(1, n), chosen[:1], achieved[:1]
         self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_quality(self.h, self._p(rate), self._p(dist), self._p(numbps), arr, L, self._p(kept), self._p(chosen),
                                                                  self._p(achieved)))
         return kept[:L * n].view(L, n), chosen[:L], achieved[:L]
@@ -503,12 +527,16 @@ class FramePlan:
         return int(self.ctx.L.j2k_plan_frame_bound(self.h))
 
     @_stage
-    def encode_tile_parts(self, stream, offs, lens, numbps, sop=False, eph=False, out=None, tile_offs=None, kept=None, rate=None, layers=None):
-        """the block coder's outputs -> SOT | SOD | packets per tile, end to end: (out uint8, tile_offs int64[tiles + 1]).  kept + rate
+    def encode_tile_parts(self, stream, offs, lens, numbps, sop=False, eph=False, out=None, tile_offs=None, kept=None, rate=None, layers=None, pass_cuts=False):
+        """pass_cuts=True with kept + rate (rate_allocate(pass_cuts=True), encode_blocks(pass_cuts=True)): every block cut after its first kept[j]
+        coding passes (j2k_plan_encode_tile_parts_kept_passes; not with layers=: ValueError).
+        the block coder's outputs -> SOT | SOD | packets per tile, end to end: (out uint8, tile_offs int64[tiles + 1]).  kept + rate
         (rate_allocate, encode_blocks(planes=True)): every block cut after its first kept[j] bit planes (j2k_plan_encode_tile_parts_kept).
         layers = L with kept [L, blocks] (rate_allocate_layers): the layered stream -> (out, tile_offs, layer_offs int64 [tiles * L])
         (j2k_plan_encode_tile_parts_layers)"""
         t = _torch()
+        if pass_cuts and (layers is not None or kept is None or rate is None):
+            raise ValueError("encode_tile_parts: pass_cuts takes kept= and rate= and no layers= (layers with pass cuts: not built)")
         if layers is not None:
             nt, L = int(self.info.tiles), int(layers)
             out = out if out is not None else self.empty(self.frame_bound_layers(L) or 64, t.uint8)
@@ -521,6 +549,11 @@ class FramePlan:
         out = out if out is not None else self.empty(self.frame_bound(), t.uint8)
         tile_offs = tile_offs if tile_offs is not None else self.empty(int(self.info.tiles) + 1, t.int64)[:int(self.info.tiles) + 1]
         if kept is not None:
+            if pass_cuts:
+                self.ctx.check(self.ctx.L.j2k_plan_encode_tile_parts_kept_passes(self.h, self._p(stream), self._p(offs), self._p(lens), self._p(numbps), self._p(kept),
+                                                                                 self._p(rate), int(bool(sop)), int(bool(eph)), self._p(out),
+                                                                                 C.c_size_t(int(out.numel())), self._p(tile_offs)))
+                return out, tile_offs
             self.ctx.check(self.ctx.L.j2k_plan_encode_tile_parts_kept(self.h, self._p(stream), self._p(offs), self._p(lens), self._p(numbps), self._p(kept), self._p(rate),
                                                                       int(bool(sop)), int(bool(eph)), self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs)))
             return out, tile_offs
@@ -530,8 +563,10 @@ class FramePlan:
 
     @_stage
     def decode_tile_parts(self, cs, length, tile_offs=None, sop=False, eph=False, offs=None, lens=None, numbps=None, floors=None, layers=None, dense=None,
-                          dense_cap=None):
-        """tile-parts cs[:length] -> (offs, lens, numbps) as decode_blocks takes them (offsets into cs).  floors = True or a device uint8
+                          dense_cap=None, pfloors=None):
+        """pfloors = True or a device uint8 [blocks] tensor (the plans rate_allocate takes): the stream's blocks may be cut at coding passes -- returns
+        (offs, lens, numbps, pfloors), pfloors[j] = the passes block j's header leaves undecoded (j2k_plan_decode_tile_parts_pfloors).
+        tile-parts cs[:length] -> (offs, lens, numbps) as decode_blocks takes them (offsets into cs).  floors = True or a device uint8
         [blocks] tensor (MQ plans): also every block's floor, for streams cut at bit planes -- returns (offs, lens, numbps, floors) with
         numbps counted from each block's top plane down to bit 0 (j2k_plan_decode_tile_parts_floors)"""
         t = _torch()
@@ -539,6 +574,13 @@ class FramePlan:
         offs = offs if offs is not None else self.empty(n + 1, t.int64)
         lens = lens if lens is not None else self.empty(n, t.int32)
         numbps = numbps if numbps is not None else self.empty(n, t.uint8)
+        if pfloors is not None and pfloors is not False:
+            if layers is not None or (floors is not None and floors is not False):
+                raise ValueError("decode_tile_parts: pfloors= together with layers= or floors=")
+            pfloors = self.empty(n, t.uint8) if pfloors is True else pfloors
+            self.ctx.check(self.ctx.L.j2k_plan_decode_tile_parts_pfloors(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
+                                                                         int(bool(sop)), int(bool(eph)), self._p(offs), self._p(lens), self._p(numbps), self._p(pfloors)))
+            return offs, lens, numbps, pfloors
         if layers is not None:
             # the first `layers` layers of a layered stream: every block's segments gathered into a dense buffer -- returns (dense, offs, lens,
             # numbps, floors), offsets into dense; decode_blocks(dense, offs, lens, numbps, floors=floors) (j2k_plan_decode_tile_parts_layers).
@@ -602,6 +644,19 @@ class FramePlan:
             return "_rate", C.c_int64(int(max_body_bytes)), 1, False, None
         return "", None, 1, False, None
 
+    def _pass_cut_args(self, who, max_body_bytes, layer_bytes, roi, min_psnr, max_distortion, layer_psnr, layer_distortion, layers=None):
+        """pass_cuts=True of an encode call -> (budget int64, target pointer or None): one of max_body_bytes, min_psnr, max_distortion"""
+        for k, v in (("layer_bytes", layer_bytes), ("layer_psnr", layer_psnr), ("layer_distortion", layer_distortion), ("roi", roi), ("layers", layers)):
+            if v is not None:
+                raise ValueError("%s: pass_cuts together with %s= -- not built" % (who, k))
+        given = [k for k, v in (("max_body_bytes", max_body_bytes), ("min_psnr", min_psnr), ("max_distortion", max_distortion)) if v is not None]
+        if len(given) != 1:
+            raise ValueError("%s: pass_cuts takes one of max_body_bytes=, min_psnr=, max_distortion=" % who)
+        if max_body_bytes is not None:
+            return C.c_int64(int(max_body_bytes)), None
+        T = self.psnr_distortion(min_psnr) if min_psnr is not None else float(max_distortion)
+        return C.c_int64(0), C.byref(C.c_double(T))
+
     @staticmethod
     def _encode_args(form, arr, L, rect, roi_gain):
         """what an encode entry point takes between eph and out"""
@@ -610,8 +665,11 @@ class FramePlan:
 
     @_stage
     def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16,
-                            min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None):
-        """pixels (a Go Pix layout, device uint8 [H, stride]) -> tile-parts: (out uint8, tile_offs int64[tiles + 1]).  max_body_bytes (closed-loop
+                            min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None, pass_cuts=False):
+        """pass_cuts=True with one of max_body_bytes, min_psnr, max_distortion (anything else beside it: ValueError): the same stream with every block
+        cut at a coding-pass end, not only at a bit-plane end -- about three times as many steps per block (j2k_plan_encode_frame_pixels_passes);
+        returns as without it; decode with pass_cuts=True (truncated=True reads the whole planes of it).
+        pixels (a Go Pix layout, device uint8 [H, stride]) -> tile-parts: (out uint8, tile_offs int64[tiles + 1]).  max_body_bytes (closed-loop
         MQ plans): at most that many bytes of code-block bodies -- packet and tile-part headers come on top, tile_offs[-1] says what the frame took
         (j2k_plan_encode_frame_pixels_rate); decode with truncated=True.  layer_bytes = [B_0 <= B_1 <= ...] (the same plans; not together with
         max_body_bytes): ONE stream of len(layer_bytes) quality layers, layer l cut as max_body_bytes = B_l would -> (out, tile_offs, layer_offs
@@ -626,6 +684,15 @@ class FramePlan:
         layered stream.  achieved: the estimate of every layer's choice, <= its target.  An ESTIMATE in the coefficient domain:
         measure the decoded frame with pixels.psnr.  roi= / roi_gain= weigh the rectangle as with a budget (j2k_plan_encode_frame_pixels_quality)"""
         t = _torch()
+        if pass_cuts:
+            budget, target = self._pass_cut_args("encode_frame_pixels", max_body_bytes, layer_bytes, roi, min_psnr, max_distortion, layer_psnr, layer_distortion)
+            out = out if out is not None else self.empty(self.frame_bound(), t.uint8)
+            tile_offs = tile_offs if tile_offs is not None else self.empty(int(self.info.tiles) + 1, t.int64)[:int(self.info.tiles) + 1]
+            achieved = t.zeros(1, dtype=t.float64, device=self.device) if target is not None else None
+            self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_passes(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
+                                                                          budget, target, self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs),
+                                                                          self._p(achieved) if achieved is not None else None))
+            return (out, tile_offs) + ((achieved,) if achieved is not None else ())
         form, arr, L, layered, rect = self._encode_form("encode_frame_pixels", max_body_bytes, layer_bytes, roi, min_psnr, max_distortion, layer_psnr, layer_distortion)
         nt = int(self.info.tiles)
         out = out if out is not None else self.empty((self.frame_bound_layers(L) or 64) if layered else self.frame_bound(), t.uint8)
@@ -654,8 +721,11 @@ class FramePlan:
         return ("_reduced", [int(reduce)]) if reduce else ("", [])
 
     @_stage
-    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None, area=None):
-        """tile-parts cs[:length] -> pixels into pix (device uint8 [H, stride]; reduce > 0, Mallat plans: [H_r, stride], and only the
+    def decode_frame_pixels(self, cs, length, pix, tile_offs=None, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None, area=None,
+                            pass_cuts=False):
+        """pass_cuts=True (implies truncated; not with layers=: ValueError): the stream's blocks may be cut at coding passes
+        (encode_frame_pixels(pass_cuts=True)); reduce, skip_planes and area compose as with truncated=True (j2k_plan_decode_frame_pixels_passes).
+        tile-parts cs[:length] -> pixels into pix (device uint8 [H, stride]; reduce > 0, Mallat plans: [H_r, stride], and only the
         code-blocks of the resolutions it needs are decoded; skip_planes = k > 0, MQ plans: every block decoder stops after bit plane k;
         truncated=True, MQ plans: the stream's blocks may be cut at bit planes (encode_frame_pixels(max_body_bytes=...)) -- every block runs
         from its own top plane down to max(skip_planes, its floor) (j2k_plan_decode_frame_pixels_rate).  Without it a cut stream decodes by
@@ -666,6 +736,13 @@ class FramePlan:
         rect = self._rect(area) if area is not None else None
         if area is not None and (pix.dim() != 2 or int(pix.shape[0]) != self.area_shape(area, reduce)[0]):
             raise _lib.J2KError(_lib.ERR_INVALID_ARG, "decode_frame_pixels: pix is not area_shape(area, reduce) rows")
+        if pass_cuts:
+            if layers is not None:
+                raise ValueError("decode_frame_pixels: pass_cuts together with layers= -- not built")
+            self.ctx.check(self.ctx.L.j2k_plan_decode_frame_pixels_passes(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
+                                                                          int(bool(sop)), int(bool(eph)), int(reduce), int(skip_planes),
+                                                                          C.byref(rect) if rect is not None else None, self._p(pix), C.c_size_t(int(pix.shape[1]))))
+            return pix
         form, args = self._decode_form(reduce, skip_planes, truncated, layers, rect)
         self.ctx.check(getattr(self.ctx.L, "j2k_plan_decode_frame_pixels" + form)(self.h, self._p(cs), C.c_size_t(int(length)), self._p(tile_offs) if tile_offs is not None else None,
                                                                                  int(bool(sop)), int(bool(eph)), *(args + [self._p(pix), C.c_size_t(int(pix.shape[1]))])))
@@ -673,14 +750,33 @@ class FramePlan:
 
     # ---- host memory in, host memory out: the one-call forms (j2k_encode_pixels_host / j2k_decode_pixels_host) -------------------
     def encode_pixels_host(self, fmt, pix, sop=False, eph=False, cap=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16,
-                           min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None):
-        """pix: numpy uint8 [H, stride] (a Go Pix layout) -> dict(bytes, tile_offs, lens, numbps): every tile as a tile-part.  max_body_bytes: as
+                           min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None, pass_cuts=False):
+        """pass_cuts=True: as encode_frame_pixels (j2k_encode_pixels_host_passes); the dict holds achieved float64 [1] when a target was given.
+        pix: numpy uint8 [H, stride] (a Go Pix layout) -> dict(bytes, tile_offs, lens, numbps): every tile as a tile-part.  max_body_bytes: as
         encode_frame_pixels (j2k_encode_pixels_host_rate; lens / numbps are the uncut ones); layer_bytes: as encode_frame_pixels, the dict also
         holds layer_offs uint64 [tiles * L] (j2k_encode_pixels_host_layers); roi, roi_gain with either budget: as encode_frame_pixels
         (j2k_encode_pixels_host_roi); min_psnr / max_distortion / layer_psnr / layer_distortion: as encode_frame_pixels, the dict also holds
         achieved float64 [L] (j2k_encode_pixels_host_quality)"""
         L = self.ctx.L
         n, nt = int(self.info.blocks), int(self.info.tiles)
+        if pass_cuts:
+            budget, target = self._pass_cut_args("encode_pixels_host", max_body_bytes, layer_bytes, roi, min_psnr, max_distortion, layer_psnr, layer_distortion)
+            cap = int(cap) if cap is not None else self.frame_bound() + 64
+            pix = np.ascontiguousarray(pix, dtype=np.uint8)
+            out = np.zeros(max(cap, 1), np.uint8)
+            toffs = np.zeros(nt + 1, np.uint64)
+            lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
+            ach = np.zeros(1, np.float64)
+            olen = C.c_size_t(0)
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+            st = L.j2k_encode_pixels_host_passes(self.h, int(fmt), ptr(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)), budget, target,
+                                                 ptr(out), C.c_size_t(cap), C.byref(olen), ptr(toffs), ptr(lens), ptr(nbps), ptr(ach) if target is not None else None)
+            self.encoded_len = olen.value
+            self.ctx.check(st)
+            res = dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
+            if target is not None:
+                res["achieved"] = ach.copy()
+            return res
         form, arr, nl, layered, rect = self._encode_form("encode_pixels_host", max_body_bytes, layer_bytes, roi, min_psnr, max_distortion, layer_psnr, layer_distortion)
         if cap is None:
             L.j2k_plan_tile_parts_bound.restype = C.c_size_t
@@ -710,8 +806,9 @@ class FramePlan:
             res["layer_offs"] = loffs[:nt * nl].copy()
         return res
 
-    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None, area=None, pix=None):
-        """closed-loop plans: tile-parts (bytes / numpy uint8) -> numpy uint8 pixels of `shape` = (H, stride); reduce > 0: (H_r, stride);
+    def decode_pixels_host(self, cs, shape, sop=False, eph=False, reduce=0, skip_planes=0, truncated=False, layers=None, area=None, pix=None, pass_cuts=False):
+        """pass_cuts=True: as decode_frame_pixels (j2k_decode_pixels_host_passes).
+        closed-loop plans: tile-parts (bytes / numpy uint8) -> numpy uint8 pixels of `shape` = (H, stride); reduce > 0: (H_r, stride);
         skip_planes > 0 (MQ plans), truncated: as decode_frame_pixels; area: as decode_frame_pixels, shape = (h, stride) with h of area_shape
         (j2k_decode_pixels_host_area; pix: a numpy uint8 array of `shape` to write instead of a new one -- a refused call leaves it alone)"""
         cs = np.ascontiguousarray(np.frombuffer(bytes(cs), np.uint8) if not isinstance(cs, np.ndarray) else cs, dtype=np.uint8)
@@ -723,6 +820,13 @@ class FramePlan:
             assert pix.dtype == np.uint8 and pix.shape == tuple(shape) and pix.flags.c_contiguous
         else:
             pix = np.zeros(shape, np.uint8)
+        if pass_cuts:
+            if layers is not None:
+                raise ValueError("decode_pixels_host: pass_cuts together with layers= -- not built")
+            self.ctx.check(self.ctx.L.j2k_decode_pixels_host_passes(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)), int(reduce),
+                                                                    int(skip_planes), C.byref(rect) if rect is not None else None, pix.ctypes.data_as(C.c_void_p),
+                                                                    C.c_size_t(int(shape[1]))))
+            return pix
         form, args = self._decode_form(reduce, skip_planes, truncated, layers, rect)
         self.ctx.check(getattr(self.ctx.L, "j2k_decode_pixels_host" + form)(self.h, cs.ctypes.data_as(C.c_void_p), C.c_size_t(cs.size), int(bool(sop)), int(bool(eph)),
                                                                            *(args + [pix.ctypes.data_as(C.c_void_p), C.c_size_t(int(shape[1]))])))
@@ -791,11 +895,18 @@ class FramePlan:
         return offs, stream
 
     @_stage
-    def decode_blocks(self, stream, offs, lens, numbps, decoded=None, skip_planes=0, floors=None):
-        """skip_planes = k > 0 (MQ plans): every block's decoder stops after bit plane k (j2k_plan_decode_blocks_coarse); floors: device uint8
+    def decode_blocks(self, stream, offs, lens, numbps, decoded=None, skip_planes=0, floors=None, pfloors=None):
+        """pfloors: device uint8 [blocks], block j stops max(3 skip_planes, pfloors[j]) coding passes short of its last (j2k_plan_decode_blocks_pfloors).
+        skip_planes = k > 0 (MQ plans): every block's decoder stops after bit plane k (j2k_plan_decode_blocks_coarse); floors: device uint8
         [blocks], block j stops after plane max(skip_planes, floors[j]) (j2k_plan_decode_blocks_floors)"""
         t = _torch()
         decoded = decoded if decoded is not None else self.empty(self.info.decoded_elems, t.int32)
+        if pfloors is not None:
+            if floors is not None:
+                raise ValueError("decode_blocks: floors= and pfloors= together")
+            self.ctx.check(self.ctx.L.j2k_plan_decode_blocks_pfloors(self.h, self._p(stream), self._p(offs), self._p(lens), self._p(numbps),
+                                                                     int(skip_planes), self._p(pfloors), self._p(decoded)))
+            return decoded
         if floors is not None:
             self.ctx.check(self.ctx.L.j2k_plan_decode_blocks_floors(self.h, self._p(stream), self._p(offs), self._p(lens), self._p(numbps),
                                                                     int(skip_planes), self._p(floors), self._p(decoded)))

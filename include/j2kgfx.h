@@ -841,7 +841,7 @@ int j2k_plan_decode_blocks_floors(j2k_plan *plan, const uint8_t *d_stream, const
  *                                    reduce as there.
  * j2k_encode_pixels_host_rate /      the synchronous host-memory forms (j2k_encode_pixels_host / j2k_decode_pixels_host_coarse); lens and
  * j2k_decode_pixels_host_rate        numbps of the encode are the UNCUT lengths and plane counts.
- * No pass-level truncation, no budget that includes headers; quality layers: the _layers calls below. */
+ * No budget that includes headers; pass-level truncation: the _passes calls further down; quality layers: the _layers calls below. */
 int j2k_plan_encode_tile_parts_kept(j2k_plan *plan, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
                                     const uint8_t *d_numbps, const uint8_t *d_kept, const uint32_t *d_rate, int sop, int eph,
                                     uint8_t *d_out, size_t cap, uint64_t *d_tile_offs);
@@ -882,7 +882,7 @@ int j2k_plan_set_rate_weights(j2k_plan *plan, const double *weights, size_t coun
  *   j2k_plan_encode_frame_pixels_layers / j2k_plan_decode_frame_pixels_layers   the frame calls (decode: layers, reduce and skip_planes together)
  *   j2k_encode_pixels_host_layers / j2k_decode_pixels_host_layers               the synchronous host-memory forms
  *   j2k_tile_parts_keep_layers         HOST ONLY, no device: the stream cut to its first `keep` layers (Psot patched), out_tile_offs[ntiles + 1]
- * No sub-plane truncation, no header bytes in the budgets, no HT, no conformant Part-1 packet headers, no main header that carries L. */
+ * No sub-plane truncation of a layered stream (the _passes calls cut single-layer streams), no header bytes in the budgets, no HT, no conformant Part-1 packet headers, no main header that carries L. */
 #define J2K_MAX_LAYERS 32
 int j2k_plan_rate_allocate_layers(j2k_plan *plan, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps,
                                   const int64_t *layer_bytes, int nlayers, uint8_t *d_kept, uint64_t *d_chosen);
@@ -1040,6 +1040,66 @@ typedef struct j2k_tcd_rect { int32_t x0, y0, x1, y1; } j2k_tcd_rect;
 typedef struct j2k_tcd_band { int32_t comp, res, type, cbx, cby, pad_; j2k_tcd_rect r; uint64_t cb0; } j2k_tcd_band;
 int j2k_tcd_init_tile(const j2k_tcd_header *h, int tile_index, j2k_tcd_rect *tile, j2k_tcd_rect *comps, j2k_tcd_rect *ress,
                       j2k_tcd_band *bands, size_t band_cap, size_t *nbands, j2k_tcd_rect *cbs, size_t cb_cap, size_t *ncbs);
+
+/* Pass-level rate control: the same cuts at CODING-PASS ends, three times as many steps per block (an opt-in form beside the calls above, which
+ * keep their bytes, tables and refusals; definition: tests/pass_cases.py, argument: DESIGN.md 7).  A block of nb = numBPS planes has the cut
+ * points q = 0 ... 3 nb - 2: q = 0 keeps nothing, q >= 1 keeps p = (q + 2) / 3 whole planes from the top and s = (q + 2) % 3 further passes of the
+ * next plane (s = 1: its SigProp pass, s = 2: SigProp and MagRef) -- the packet header's pass count itself; 3 p - 2 is a whole-plane cut.
+ *   d_rate[j * 96 + q]   uint32: bytes of block j's codeword whose decode has every pass up to q right: [0] = 0, [3 nb - 2] = lens[j], non-decreasing,
+ *                        the entries above repeat lens[j]; the coder's byte index at the pass end + 5, capped at the length.
+ *                        d_rate[j * 96 + 3 p - 2] is j2k_plan_encode_blocks_planes' d_rate[j * 32 + p].
+ *   d_dist[j * 96 + q]   uint64: sum (|v| - |w|)^2 in wrapping arithmetic, w = what j2k_plan_decode_blocks_pfloors leaves of v at that cut; 0 at and
+ *                        above 3 nb - 2; [3 p - 2] is the plane table's [p].
+ *   d_spmask[j * 64 + y] uint64: the samples of row y (bit x) that turned significant in a SigProp pass, not in Cleanup; rows >= h are 0.
+ * j2k_plan_encode_blocks_passes            j2k_plan_encode_blocks + the three tables (the same slots, lens and numbps)
+ * j2k_plan_rate_allocate_passes            j2k_plan_rate_allocate on the pass tables: d_kept[j] = the pass count q kept of block j (<= 91)
+ * j2k_plan_rate_allocate_quality_passes    j2k_plan_rate_allocate_quality for ONE target on the pass tables (the same fixed float64 sum order)
+ * j2k_plan_encode_tile_parts_kept_passes   j2k_plan_encode_tile_parts_kept with d_kept[j] = q: body length d_rate[j * 96 + q], q passes in the header,
+ *                                          ZeroBitPlanes = 31 - numBPS as before; q = 0: in no layer.  d_kept[j] = 3 numBPS - 2 everywhere gives
+ *                                          j2k_plan_encode_tile_parts' bytes.
+ * j2k_plan_decode_tile_parts_pfloors       j2k_plan_decode_tile_parts_floors at pass granularity: with p = (passes + 2) / 3, s = (passes + 2) % 3,
+ *                                          floor = max(31 - ZeroBitPlanes - p, 0): d_numbps[j] = p + floor, d_pfloors[j] = the passes left
+ *                                          undecoded = 3 floor - s (0 where floor = 0).
+ * j2k_plan_decode_blocks_pfloors           block j stops f = max(3 skip_planes, d_pfloors[j]) passes short of its last: whole planes down to
+ *                                          ceil(f / 3), then the first 3 ceil(f / 3) - f passes of the next plane; every non-zero sample takes the
+ *                                          midpoint of what ITS last pass left undecoded.  d_pfloors[j] = 3 k is j2k_plan_decode_blocks_floors with
+ *                                          floors[j] = k, bit for bit.  Every block runs on the one-launch kernel (never the plane-stepped forms).
+ * j2k_plan_encode_frame_pixels_passes      the frame encoder with pass cuts: target == NULL: at most max_body_bytes of code-block bodies; else the fewest
+ *                                          bytes whose weighted distortion is <= *target (host memory; d_achieved, device or NULL: what was reached).
+ *                                          A budget that cuts nothing gives j2k_plan_encode_frame_pixels' bytes.
+ * j2k_plan_decode_frame_pixels_passes      the frame decoder for such streams: reduce and skip_planes as the _rate call, area (or NULL) as
+ *                                          j2k_plan_decode_frame_pixels_area -- all three only edit the block tables, so they compose as there.
+ * j2k_encode_pixels_host_passes /          the synchronous host-memory forms; lens / numbps: the UNCUT lengths and plane counts; achieved (or NULL):
+ * j2k_decode_pixels_host_passes            one float64 when a target was given
+ * The older readers on such a stream: j2k_plan_decode_frame_pixels_rate (truncated) reads p whole planes per block and ignores s -- valid, the
+ * bytes of s further passes are a prefix it does not need.
+ * J2K_ERR_UNSUPPORTED: whatever j2k_plan_rate_allocate refuses (HT, no closed loop, batch plans, the raw-MagRef style, blocks above 64 x 64).
+ * J2K_ERR_INVALID_ARG: a negative budget, a target that is negative or not finite.  Both before anything is launched; under capture the "run the call
+ * once before" rule of the _rate calls.  Not built: layers and a region of interest with pass cuts, the pipelined host codec, the plane-stepped
+ * decode forms, batch plans, the HT coder. */
+int j2k_plan_encode_blocks_passes(j2k_plan *plan, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps,
+                                  uint32_t *d_rate, uint64_t *d_dist, uint64_t *d_spmask);
+int j2k_plan_rate_allocate_passes(j2k_plan *plan, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps,
+                                  int64_t max_body_bytes, uint8_t *d_kept, uint64_t *d_chosen);
+int j2k_plan_rate_allocate_quality_passes(j2k_plan *plan, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps,
+                                          double target, uint8_t *d_kept, uint64_t *d_chosen, double *d_achieved);
+int j2k_plan_encode_tile_parts_kept_passes(j2k_plan *plan, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
+                                           const uint8_t *d_numbps, const uint8_t *d_kept, const uint32_t *d_rate, int sop, int eph,
+                                           uint8_t *d_out, size_t cap, uint64_t *d_tile_offs);
+int j2k_plan_decode_tile_parts_pfloors(j2k_plan *plan, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                       uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_pfloors);
+int j2k_plan_decode_blocks_pfloors(j2k_plan *plan, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
+                                   const uint8_t *d_numbps, int skip_planes, const uint8_t *d_pfloors, int32_t *d_decoded);
+int j2k_plan_encode_frame_pixels_passes(j2k_plan *plan, int format, const void *d_pix, size_t stride, int sop, int eph,
+                                        int64_t max_body_bytes, const double *target, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs,
+                                        double *d_achieved);
+int j2k_plan_decode_frame_pixels_passes(j2k_plan *plan, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
+                                        int reduce, int skip_planes, const j2k_rect *area, void *d_pix, size_t stride);
+int j2k_encode_pixels_host_passes(j2k_plan *plan, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes,
+                                  const double *target, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint32_t *lens,
+                                  uint8_t *numbps, double *achieved);
+int j2k_decode_pixels_host_passes(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, int reduce, int skip_planes,
+                                  const j2k_rect *area, void *pix, size_t stride);
 
 #ifdef __cplusplus
 }
