@@ -1,5 +1,6 @@
 """The closed-loop packet readers on streams this library's encoder never writes (j2k_plan_decode_tile_parts_floors: truncated=True;
-j2k_plan_decode_tile_parts_layers: layers=k; j2k_plan_decode_frame_pixels_area on top of either), importable without a GPU:
+j2k_plan_decode_tile_parts_layers: layers=k; j2k_plan_decode_tile_parts_pfloors: pfloors=True / pass_cuts=True, its streams in
+tests/pass_stream_cases.py; j2k_plan_decode_frame_pixels_area on top of each), importable without a GPU:
 tests/test_stream_reader_cases.py checks this file on the CPU, tests/test_gpu_stream_readers.py holds the device against it bit for bit.
 
 Three small geometries (GEOMETRIES), their tables made as layer_cases.golden_tables makes them (codewords by the oracle, R by shortest_rates), a
@@ -13,6 +14,7 @@ import numpy as np
 import closed_loop_ref as ref
 import layer_cases as lc
 import mallat_cases as mc
+import pass_cases as pc
 import rate_cases as rc
 
 # (W, H, components, precision, tile, resolutions), code-block size, seed
@@ -167,7 +169,7 @@ def _tile_chain(stream, at, want_index):
 
 def read_tiles(t2ref, stream, tile_offs, tiles, k, sop, eph, tile_first=0):
     """The first k layers of every tile-part of `stream` (the caller's bytes, cut to the length the device is told) -> one verdict per tile:
-    dict(ok, why, blocks = {block: dict(zbp, passes, segs = [(offset in stream, length)], floor, numbps, dropped)}).  It never raises.  k = 1
+    dict(ok, why, blocks = {block: dict(zbp, passes, segs = [(offset in stream, length)], floor, numbps, pfloor, dropped)}).  It never raises.  k = 1
     on an L = 1 stream is the reader of the truncated format.  The field decoders are layer_cases.read_layers' (oracle/t2ref.py); on every
     stream that one accepts, this one accepts every tile and returns the same records.
 
@@ -190,17 +192,24 @@ def read_tiles(t2ref, stream, tile_offs, tiles, k, sop, eph, tile_first=0):
     length wider than 32 bits cannot be written, and the sum of a block's segments stays below 2^32 for every stream shorter than 128 MiB -- the
     device's test on the sum cannot fire in these tests).  A CONTRIBUTION OF LENGTH 0 -- no writer makes one, the format of DESIGN.md 7 was silent --
     counts as a contribution for the ZeroBitPlanes rule and adds neither a segment nor its passes.  A block without a segment is empty:
-    length 0, numbps = floor = 0.  Otherwise (floor, numbps) = rate_cases.floors_from_header(zbp, sum of passes).
-      5. a block whose floor + coded planes exceeds 31 (only possible with more than 91 passes) is DROPPED: it is empty in the tables, dropped = True,
+    length 0, numbps = floor = pfloor = 0.  Otherwise (floor, numbps) = rate_cases.floors_from_header(zbp, sum of passes).
+      5. a block whose floor + coded planes exceeds 31 (only possible with more than 91 passes) is DROPPED: it is empty in the tables (pfloor = 0 too), dropped = True,
          the frame's status is J2K_ERR_INVALID_ARG, and every other block of the tile and of the frame keeps its record.
+    THE PASS READER (j2k_plan_decode_tile_parts_pfloors) reads the same fields and takes the pass count at its word: with coded = (passes + 2) // 3
+    and s = (passes + 2) % 3 it is (pfloor, numbps) = pass_cases.pfloor_from_header(zbp, passes) -- the same numbps, pfloor = 3 floor - s passes left
+    undecoded.  Two headers no writer of this library makes are settled here:
+      a. floor == 0 with s > 0 -- a header that claims passes below plane 0: pfloor = 0 and numbps = coded; the decoder runs every one of the
+         `coded` planes to its end.
+      b. mb - zbp < coded -- more coded planes than ZeroBitPlanes leaves room for: floor = 0 (never negative), so pfloor = 0 and numbps = coded.
     The frame's status is J2K_OK iff every tile is read and no block is dropped (frame_ok).
 
     INVARIANTS of the device's tables on every input: offs + lens <= the dense buffer (layers) or the stream length (floors); numbps <= 31;
-    floors <= numbps; lens == 0 implies numbps == floors == 0."""
+    floors <= numbps; lens == 0 implies numbps == floors == 0.  The pass reader: pfloors <= max(3 numbps - 3, 0) in the place of floors <= numbps;
+    lens == 0 implies numbps == pfloors == 0."""
     out = []
     at, lost = 0, None
     for t, packets in enumerate(tiles):
-        blocks = {j: dict(zbp=None, passes=0, segs=[], floor=0, numbps=0, dropped=False) for pk in packets for j in pk}
+        blocks = {j: dict(zbp=None, passes=0, segs=[], floor=0, numbps=0, pfloor=0, dropped=False) for pk in packets for j in pk}
         v = dict(ok=False, why=None, blocks=blocks, done=0, zero_len=0)   # done: packets read to their end (layer-major) before a refusal; zero_len: contributions of length 0
         out.append(v)
         if tile_offs is None and lost is not None:
@@ -248,8 +257,10 @@ def read_tiles(t2ref, stream, tile_offs, tiles, k, sop, eph, tile_first=0):
         for s in blocks.values():
             if s["zbp"] is not None and s["segs"]:
                 s["floor"], s["numbps"] = rc.floors_from_header(s["zbp"], s["passes"])
+                s["pfloor"] = pc.pfloor_from_header(s["zbp"], s["passes"])[0]
+                assert pc.pfloor_from_header(s["zbp"], s["passes"])[1] == s["numbps"]
                 if s["numbps"] > 31:
-                    s.update(floor=0, numbps=0, dropped=True)
+                    s.update(floor=0, numbps=0, pfloor=0, dropped=True)
         v["ok"] = True
     return out
 
@@ -258,15 +269,20 @@ def frame_ok(verdicts):
     return all(v["ok"] and not any(s["dropped"] for s in v["blocks"].values()) for v in verdicts)
 
 
-def block_tables(stream, verdicts):
+def block_tables(stream, verdicts, floor="floor"):
     """{block: (codeword bytes, floor, numbps)} of the tiles that were read -- a dropped block is empty"""
     out = {}
     for v in verdicts:
         if v["ok"]:
             for j, s in v["blocks"].items():
                 data = b"" if s["dropped"] else b"".join(bytes(stream[o:o + ln]) for o, ln in s["segs"])
-                out[j] = (data, s["floor"], s["numbps"])
+                out[j] = (data, s[floor], s["numbps"])
     return out
+
+
+def block_tables_pass(stream, verdicts):
+    """the pass reader's: {block: (codeword bytes, pfloor, numbps)}"""
+    return block_tables(stream, verdicts, "pfloor")
 
 
 # ---- damage ---------------------------------------------------------------------------------------------------------------------------------
@@ -308,19 +324,40 @@ def damage(rng, stream, tile_offs, segs, kind):
     return bytes(bad), n, offs
 
 
-# the three readers' damaged copies, all on geometry a: (cut family, layers read, copies)
-READERS = {"layers32": ("L32-mod5", 32), "layers2": ("L2-empty0-tile", 2), "floors": ("L1-random", 1)}
+# the readers' damaged copies, all on geometry a: (cut family, layers read, copies).  pfloors: the pass reader on pass_stream_cases' random pass cuts
+READERS = {"layers32": ("L32-mod5", 32), "layers2": ("L2-empty0-tile", 2), "floors": ("L1-random", 1), "pfloors": ("P-random", 1)}
 COPIES = 120
-DAMAGE_SEED = {"layers32": 7301, "layers2": 7302, "floors": 7303}
+DAMAGE_SEED = {"layers32": 7301, "layers2": 7302, "floors": 7303, "pfloors": 7304}
 
 
 @functools.lru_cache(None)
 def base_stream(geom, fam, marks):
-    """(stream, tile_offs, layer_offs, kept) of a family on a geometry's tables, by layer_cases.compose"""
+    """(stream, tile_offs, layer_offs, kept) of a family on a geometry's tables, by layer_cases.compose; a pass family (P-...: one layer, kept[0] the
+    pass counts) by pass_stream_cases.pass_stream"""
     import t2ref
+    if fam.startswith("P-"):
+        import pass_stream_cases as ps
+        stream, toffs, F = ps.pass_stream(geom, fam, marks)
+        return stream, toffs, toffs[1:], [list(F["qs"])]
     _, tiles, datas, nbs, Rs, _ = tables(geom)
     kept = family(fam, tiles, nbs, Rs)
     return lc.compose(t2ref, tiles, datas, nbs, Rs, kept, marks, marks) + (kept,)
+
+
+def header_shim(t2ref, edits):
+    """oracle/t2ref.py's packet writer with single header fields changed: edits = {number of the CodeBlock call, from 0: (passes added,
+    ZeroBitPlanes added)} -- well-formed streams whose headers claim what the block does not hold"""
+    made = []
+
+    class Shim:
+        PacketEncoder, Precinct = t2ref.PacketEncoder, t2ref.Precinct
+
+        @staticmethod
+        def CodeBlock(data, incl, zbp, npass):
+            dp, dz = edits.get(len(made), (0, 0))
+            made.append(None)
+            return t2ref.CodeBlock(data, incl, zbp + dz, npass + dp)
+    return Shim
 
 
 def compose_passes(t2ref, tiles, datas, nbs, Rs, kept, sop, eph, block, extra):
@@ -330,16 +367,7 @@ def compose_passes(t2ref, tiles, datas, nbs, Rs, kept, sop, eph, block, extra):
     first = lc.segments(Rs[block], [kept[l][block] for l in range(L)])[1]
     assert first < L
     order = [(l, j) for packets in tiles for l in range(L) for pk in packets for j in pk]      # compose's order of CodeBlock calls
-    target, made = order.index((first, block)), []
-
-    class Shim:
-        PacketEncoder, Precinct = t2ref.PacketEncoder, t2ref.Precinct
-
-        @staticmethod
-        def CodeBlock(data, incl, zbp, npass):
-            made.append(None)
-            return t2ref.CodeBlock(data, incl, zbp, npass + (extra if len(made) - 1 == target else 0))
-    return lc.compose(Shim, tiles, datas, nbs, Rs, kept, sop, eph)
+    return lc.compose(header_shim(t2ref, {order.index((first, block)): (extra, 0)}), tiles, datas, nbs, Rs, kept, sop, eph)
 
 
 CRAFTED = 2                     # copies behind the random ones, kind "passes" (compose_passes): random damage did not produce rule 5 in 36000 copies
@@ -367,9 +395,17 @@ def damaged_copies(reader):
     for c in range(CRAFTED):
         marks = bool(c & 1)
         kept = base_stream("a", fam, marks)[3]
-        contributing = [j for j in range(len(nbs)) if lc.segments(Rs[j], [kept[l][j] for l in range(len(kept))])[1] < min(k, len(kept))]
-        block = contributing[(7 + 11 * c) % len(contributing)]
-        bad, offs, _ = compose_passes(t2ref, tiles, datas, nbs, Rs, kept, marks, marks, block, 100)
+        if fam.startswith("P-"):
+            import pass_stream_cases as ps
+            F = dict(ps.pass_family("a", fam))
+            contributing = [j for j in range(len(nbs)) if F["lengths"][j]]
+            block = contributing[(7 + 11 * c) % len(contributing)]
+            F["edits"] = {block: (100, 0)}
+            bad, offs = ps.compose_cut(t2ref, ps.pass_tables("a"), F, marks, marks)
+        else:
+            contributing = [j for j in range(len(nbs)) if lc.segments(Rs[j], [kept[l][j] for l in range(len(kept))])[1] < min(k, len(kept))]
+            block = contributing[(7 + 11 * c) % len(contributing)]
+            bad, offs, _ = compose_passes(t2ref, tiles, datas, nbs, Rs, kept, marks, marks, block, 100)
         verdicts = read_tiles(t2ref, bad, None if marks else offs, tiles, k, marks, marks)
         out.append(dict(it=COPIES + c, kind="passes", marks=marks, stream=bad, n=len(bad), offs=offs, with_offs=not marks, verdicts=verdicts, block=block))
     return out

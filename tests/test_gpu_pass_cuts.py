@@ -4,7 +4,8 @@
               spmask is the model's; R and D keep the definition's invariants, D is the model's, R[3 p - 2] / D[3 p - 2] are the tables of
               encode_blocks(planes=True); every (block, q) has the prefix property with the UNCHANGED oracle decoder at the per-sample floors of
               coarse_pass; decode_blocks(pfloors = 3 nb - 2 - q) is coarse_pass(v, nb, q, sp); pfloors = 3 k is decode_blocks(floors = k);
-              skip_planes and pfloors combine as max(3 skip, pfloor)
+              skip_planes and pfloors combine as max(3 skip, pfloor)  (many blocks a launch with pfloors of their own, and codewords that are
+              no prefix of a known block: tests/test_gpu_pass_streams.py)
   allocation  on a frame's 96-entry tables the device equals rate_cases.allocate / quality_cases.allocate_quality run on them (zero weights too)
   frames      130 x 70 x 3, 8 bit, 5-3 Mallat, cb 16 and 64, with and without tiles, SOP / EPH on and off: the stream is the t2ref composition, the
               pass reader's pixels are the oracle's inverse of the coarse_pass coefficients (also with reduce, skip_planes and an area), the

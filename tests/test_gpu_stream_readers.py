@@ -1,5 +1,5 @@
-"""GPU: the closed-loop packet readers (decode_tile_parts(layers=k) / (floors=True), decode_frame_pixels(layers=k) / (truncated=True) / (area=))
-on streams this library's encoder never writes, against tests/stream_reader_cases.py bit for bit: hand-made cut families on three small
+"""GPU: the closed-loop packet readers (decode_tile_parts(layers=k) / (floors=True) / (pfloors=True), decode_frame_pixels(layers=k) / (truncated=True) /
+(pass_cuts=True) / (area=)) on streams this library's encoder never writes, against tests/stream_reader_cases.py bit for bit: hand-made cut families on three small
 geometries, a table set with 31 bit planes, damaged copies with a verdict per tile, stale state from frame to frame on one plan, and a dense
 buffer that is too small.  One context and one plan per geometry, reused across the cases on purpose: what a frame leaves in the plan's tables
 is part of what is tested.  Every input is one the readers claim to read or to refuse safely."""
@@ -10,6 +10,8 @@ import area_cases as ac
 import coarse_cases as cc
 import layer_cases as lc
 import mallat_cases as mc
+import pass_cases as pc
+import pass_stream_cases as ps
 import stream_reader_cases as sr
 import test_gpu_rate_frames as rf
 
@@ -104,6 +106,13 @@ def _invariants(o, l, nb, fl, size, tag):
     assert ((nb == 0) & (fl == 0))[l == 0].all(), tag
 
 
+def _invariants_pass(o, l, nb, pf, size, tag):
+    """the pass reader's: pfloors <= max(3 numbps - 3, 0) in the place of floors <= numbps"""
+    assert ((o + l) <= np.uint64(size)).all() and (o <= np.uint64(size)).all(), tag
+    assert (nb <= 31).all() and (pf <= np.maximum(3 * nb - 3, 0)).all(), tag
+    assert ((nb == 0) & (pf == 0))[l == 0].all(), tag
+
+
 def _check_tables(tab, src, o, l, nb, fl, tag):
     """every block of `tab` ({block: (codeword, floor, numbps)}) has that entry in the device's tables, its bytes in src at its offset"""
     for j, (data, floor, numbps) in tab.items():
@@ -136,9 +145,10 @@ def _check_placed(plan, placed, ctiles, wins, coeffs, tag):
         assert np.array_equal(got[mask[t_][c_]], exp[t_][c_][mask[t_][c_]]), (tag, t_, c_)
 
 
-def _decode_and_place(plan, src, offs, lens, numbps, floors, sync=True):
-    """decode_blocks + place_blocks; sync: frame_status() (it raises what the calls found) before the caller reads the result"""
-    placed = plan.place_blocks(plan.decode_blocks(src, offs, lens, numbps, floors=floors))
+def _decode_and_place(plan, src, offs, lens, numbps, floors, sync=True, passes=False):
+    """decode_blocks + place_blocks; sync: frame_status() (it raises what the calls found) before the caller reads the result; passes: `floors`
+    counts coding passes (decode_blocks(pfloors=))"""
+    placed = plan.place_blocks(plan.decode_blocks(src, offs, lens, numbps, **({"pfloors": floors} if passes else {"floors": floors})))
     if sync:
         plan.frame_status()
     return placed
@@ -276,8 +286,9 @@ def test_blocks_of_31_planes_through_the_stage_calls(env, fam, marks):
 
 
 # ---- 3. damaged streams -----------------------------------------------------------------------------------------------------------------------------
-def _read_guarded(torch, plan, reader_k, layered, cs, n, d_toffs, marks, dense_bytes):
-    """one stage read with every output inside a guarded tensor -> (status, host tables, the bytes the offsets point into, guards intact)"""
+def _read_guarded(torch, plan, reader_k, layered, cs, n, d_toffs, marks, dense_bytes, passes=False):
+    """one stage read with every output inside a guarded tensor -> (status, host tables, the bytes the offsets point into, guards intact); passes:
+    the pass reader, its pfloors in the place of the floors"""
     nblk = int(plan.info.blocks)
     wo, o = _guarded(torch, plan, nblk + 1, torch.int64, 0x5A5A5A5A5A5A5A5A)
     wl, l = _guarded(torch, plan, nblk, torch.int32, 0x5A5A5A5A)
@@ -286,6 +297,8 @@ def _read_guarded(torch, plan, reader_k, layered, cs, n, d_toffs, marks, dense_b
     if layered:
         wd, dense = _guarded(torch, plan, dense_bytes, torch.uint8, 0xA5)
         plan.decode_tile_parts(cs, n, tile_offs=d_toffs, sop=marks, eph=marks, layers=reader_k, offs=o, lens=l, numbps=nb, floors=fl, dense=dense)
+    elif passes:
+        plan.decode_tile_parts(cs, n, tile_offs=d_toffs, sop=marks, eph=marks, offs=o, lens=l, numbps=nb, pfloors=fl)
     else:
         plan.decode_tile_parts(cs, n, tile_offs=d_toffs, sop=marks, eph=marks, offs=o, lens=l, numbps=nb, floors=fl)
     st = _status(plan)
@@ -300,29 +313,31 @@ def _read_guarded(torch, plan, reader_k, layered, cs, n, d_toffs, marks, dense_b
 @pytest.mark.parametrize("reader", sorted(sr.READERS))
 def test_damaged_streams(env, reader):
     """the status is the yardstick's verdict, the tables of every tile it reads are the yardstick's (beside refused tiles too), the invariants hold
-    on everything, nothing is written outside the outputs, and a refused stream leaves the caller's pixels alone"""
+    on everything, nothing is written outside the outputs, and a refused stream leaves the caller's pixels alone.  pfloors: the pass reader; its
+    body-damaged codewords go through decode_blocks(pfloors=) -- the PASSCUT decoder and t1_pass_mid on codewords that are no prefix of a known
+    block -- and must be pass_stream_cases.decode_passes of the same bytes"""
     from j2kgfx import _lib
     torch, orc, ctx, get_plan = env
     plan = get_plan("a")
     fam, k = sr.READERS[reader]
-    layered = reader != "floors"
+    layered, passcut = reader not in ("floors", "pfloors"), reader == "pfloors"
     g = sr.GEOMETRIES["a"]
     W, H, Cn, prec, tile, nres = g["case"]
     _, tiles, datas, nbs, Rs, ctiles = sr.tables("a")
     wins = rf._windows(plan, ctiles, Cn)
-    seen = {"ok": 0, "refused": 0, "dropped": 0, "mixed": 0, "body": 0}
+    seen = {"ok": 0, "refused": 0, "dropped": 0, "mixed": 0, "body": 0, "partial": 0}
     for c in sr.damaged_copies(reader):
         tag = (reader, c["it"], c["kind"])
         marks, n, stream = c["marks"], c["n"], c["stream"]
         cs = _in_buffer(torch, plan, stream)
         d_toffs = _dev(torch, plan, np.asarray(c["offs"], dtype=np.uint64), np.uint64) if c["with_offs"] else None
-        st, (ho, hl, hnb, hfl), src, guards, dev = _read_guarded(torch, plan, k, layered, cs, n, d_toffs, marks, len(stream) + 64)
+        st, (ho, hl, hnb, hfl), src, guards, dev = _read_guarded(torch, plan, k, layered, cs, n, d_toffs, marks, len(stream) + 64, passes=passcut)
         verdicts = c["verdicts"]
         good = sr.frame_ok(verdicts)
         assert st == (_lib.OK if good else _lib.ERR_INVALID_ARG), (tag, [v["why"] for v in verdicts])
         assert guards, tag
-        _invariants(ho, hl, hnb, hfl, len(stream) + 64 if layered else n, tag)
-        tab = sr.block_tables(stream[:n], verdicts)
+        (_invariants_pass if passcut else _invariants)(ho, hl, hnb, hfl, len(stream) + 64 if layered else n, tag)
+        tab = (sr.block_tables_pass if passcut else sr.block_tables)(stream[:n], verdicts)
         _check_tables(tab, src if layered else np.frombuffer(stream, np.uint8), ho, hl, hnb, hfl, tag)
         some, every = any(v["ok"] for v in verdicts), all(v["ok"] for v in verdicts)
         seen["ok" if good else "refused"] += 1
@@ -330,12 +345,13 @@ def test_damaged_streams(env, reader):
         seen["dropped"] += int(every and not good)
         if c["kind"] == "body":                                      # the damaged codewords decode as the oracle decodes them
             o, l, nb, fl, dense = dev
-            placed = _decode_and_place(plan, dense if layered else cs, o, l, nb, fl, sync=False)
+            placed = _decode_and_place(plan, dense if layered else cs, o, l, nb, fl, sync=False, passes=passcut)
             assert _status(plan) == _lib.OK, tag
-            _check_placed(plan, placed, ctiles, wins, _block_coeffs(orc, plan, tab), tag)
+            _check_placed(plan, placed, ctiles, wins, ps.expected_coeffs(ps.pass_tables("a"), tab) if passcut else _block_coeffs(orc, plan, tab), tag)
             seen["body"] += 1
+            seen["partial"] += int(passcut and bool(ps.partial_blocks(tab)))
         if not good:                                                 # the frame calls: the same status, with and without area, the pixels untouched
-            kw = dict(layers=k) if layered else dict(truncated=True)
+            kw = dict(layers=k) if layered else (dict(pass_cuts=True) if passcut else dict(truncated=True))
             back = torch.full((H, W), 0x5A, dtype=torch.uint8, device=plan.device)
             plan.decode_frame_pixels(cs, n, back, tile_offs=d_toffs, sop=marks, eph=marks, **kw)
             assert _status(plan) == st and bool((back == 0x5A).all()), tag
@@ -345,18 +361,20 @@ def test_damaged_streams(env, reader):
             assert _status(plan) == st and bool((part == 0x5A).all()), tag
     print("%s: %s" % (reader, seen))
     assert seen["ok"] >= 20 and seen["refused"] >= 20 and seen["dropped"] >= 1 and seen["mixed"] >= 10 and seen["body"] >= 17, seen
+    assert seen["partial"] >= 10 or not passcut, seen
 
 
 # ---- 4. what a frame leaves behind ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("reader", ["layers32", "floors"])
+@pytest.mark.parametrize("reader", ["layers32", "floors", "pfloors"])
 def test_stale_state_on_one_plan(env, reader):
     """busy, cut short inside the first tile's first layer, flat, noise, busy again -- on one plan and one layer count, so every frame meets the
-    entries the one before left in the plan's packet tables"""
+    entries the one before left in the plan's packet tables.  pfloors: the pass reader on a stream of random pass cuts, and between two of its
+    reads a plane-cut stream through floors=True ("planes"): neither reader may find what the other left"""
     import t2ref
     from j2kgfx import _lib
     torch, orc, ctx, get_plan = env
     plan = get_plan("a")
-    layered = reader == "layers32"
+    layered, passcut = reader == "layers32", reader == "pfloors"
     k = 32 if layered else 1
     L = k
     _, tiles, datas, nbs, Rs, _ = sr.tables("a")
@@ -369,6 +387,12 @@ def test_stale_state_on_one_plan(env, reader):
     for marks in MARKS:
         busy, btoffs, bloffs = lc.compose(t2ref, tiles, datas, nbs, Rs, busy_kept, marks, marks)
         flat, ftoffs, floffs = lc.compose(t2ref, tiles, datas, nbs, Rs, flat_kept, marks, marks)
+        if passcut:                                                  # the same shapes of frame, cut at coding passes
+            busy, btoffs, _ = ps.pass_stream("a", "P-random", marks)
+            bloffs = btoffs[1:]
+            flat_cuts = dict(qs=[pc.points(nbs[j]) if j % 7 == 0 else 0 for j in range(n)], lengths=[len(datas[j]) if j % 7 == 0 else 0 for j in range(n)], edits={})
+            flat = ps.compose_cut(t2ref, ps.pass_tables("a"), flat_cuts, marks, marks)[0]
+            planes = sr.base_stream("a", "L1-random", marks)[0]
         cut_n = btoffs[0] + 14 + (bloffs[0] - btoffs[0] - 14) // 2            # inside layer 0 of tile 0
         cut = bytearray(busy)
         cut[6:10] = cut_n.to_bytes(4, "big")                                  # (Psot says so: the chain starts, and runs out of bytes)
@@ -379,17 +403,20 @@ def test_stale_state_on_one_plan(env, reader):
         steps = [("busy", busy, len(busy), None), ("cut", cut, len(cut), None), ("flat", flat, len(flat), None), ("busy", busy, len(busy), None),
                  ("cut", cut, len(cut), btoffs), ("busy", busy, len(busy), btoffs), ("cut", cut, cut_n, None), ("noise", noise, len(noise), None),
                  ("busy", busy, len(busy), None)]
+        if passcut:
+            steps[1:1] = [("planes", planes, len(planes), None), ("busy", busy, len(busy), None)]
         for step, (name, stream, length, offs) in enumerate(steps):
             tag = (reader, marks, step, name)
-            intact = name in ("busy", "flat")
+            intact = name in ("busy", "flat", "planes")
+            passes = passcut and name != "planes"
             verdicts = sr.read_tiles(t2ref, stream[:length], offs, tiles, k, marks, marks)
             assert sr.frame_ok(verdicts) == intact, tag
             cs = _in_buffer(torch, plan, stream)
             d_toffs = _dev(torch, plan, offs, np.int64) if offs is not None else None
-            st, (ho, hl, hnb, hfl), src, guards, dev = _read_guarded(torch, plan, k, layered, cs, length, d_toffs, marks, len(stream) + 64)
+            st, (ho, hl, hnb, hfl), src, guards, dev = _read_guarded(torch, plan, k, layered, cs, length, d_toffs, marks, len(stream) + 64, passes=passes)
             assert st == (_lib.OK if intact else _lib.ERR_INVALID_ARG) and guards, tag
-            _invariants(ho, hl, hnb, hfl, len(stream) + 64 if layered else length, tag)
-            tab = sr.block_tables(stream[:length], verdicts)
+            (_invariants_pass if passes else _invariants)(ho, hl, hnb, hfl, len(stream) + 64 if layered else length, tag)
+            tab = (sr.block_tables_pass if passes else sr.block_tables)(stream[:length], verdicts)
             assert len(tab) == (n if intact else (n - sum(len(pk) for pk in tiles[0]) if offs is not None else 0)), tag
             _check_tables(tab, src if layered else np.frombuffer(stream, np.uint8), ho, hl, hnb, hfl, tag)
             if name == "cut":                                        # no block the chains did not reach carries the busy frame's entry

@@ -158,7 +158,7 @@ def test_damaged_copies_verdict_shares(oracle):
     """the comparison of the GPU test is not vacuous: enough frames accepted, enough refused, a dropped block in a frame otherwise read, frames
     with tiles read beside tiles refused.  The counts are printed (pytest -s) for the pull request's notes."""
     copies = [c for r in sorted(sr.READERS) for c in sr.damaged_copies(r)]
-    assert len(copies) == 3 * (sr.COPIES + sr.CRAFTED) and {c["kind"] for c in copies} == set(sr.KINDS) | {"passes"}
+    assert len(copies) == len(sr.READERS) * (sr.COPIES + sr.CRAFTED) and {c["kind"] for c in copies} == set(sr.KINDS) | {"passes"}
     for c in copies:
         if c["kind"] == "passes":                                    # the crafted ones: everything read, exactly that block dropped
             assert _all_read(c) and _dropped(c) == [c["block"]] and not sr.frame_ok(c["verdicts"])
@@ -176,6 +176,58 @@ def test_damaged_copies_verdict_shares(oracle):
     assert len(over31) >= 1
     assert len(mixed) >= 10
     assert all(not _all_read(c) for c in copies if c["kind"] in ("cut", "noise"))
+
+
+def test_pass_reader_copies_meet_the_vacuity_conditions(oracle):
+    """the pass reader's copies alone, by the yardstick alone: what tests/test_gpu_stream_readers.py::test_damaged_streams[pfloors] counts on the device"""
+    import pass_stream_cases as ps
+    seen = {"ok": 0, "refused": 0, "dropped": 0, "mixed": 0, "body": 0, "partial": 0}
+    for c in sr.damaged_copies("pfloors"):
+        good = sr.frame_ok(c["verdicts"])
+        seen["ok" if good else "refused"] += 1
+        seen["mixed"] += int(any(v["ok"] for v in c["verdicts"]) and not _all_read(c))
+        seen["dropped"] += int(_all_read(c) and not good)
+        tab = sr.block_tables_pass(c["stream"][:c["n"]], c["verdicts"])
+        for j, (data, pfloor, numbps) in tab.items():                 # the invariants the device's tables must keep hold in the yardstick's
+            assert numbps <= 31 and pfloor <= max(3 * numbps - 3, 0) and (data or (numbps, pfloor) == (0, 0)), (c["it"], j)
+        if c["kind"] == "body":
+            seen["body"] += 1
+            seen["partial"] += int(bool(ps.partial_blocks(tab)))
+    print("pfloors: %s" % seen)
+    assert seen["ok"] >= 20 and seen["refused"] >= 20 and seen["dropped"] >= 1 and seen["mixed"] >= 10 and seen["body"] >= 17 and seen["partial"] >= 10, seen
+
+
+def test_pass_record_rules(oracle):
+    """read_tiles' pass-aware record on the two headers no writer makes, and on rule 5"""
+    import pass_cases as pc
+    import pass_stream_cases as ps
+    import t2ref
+    for geom in sorted(sr.GEOMETRIES):
+        T = ps.pass_tables(geom)
+        stream, toffs, F = ps.pass_stream(geom, "P-claims", True)
+        got = sr.read_tiles(t2ref, stream, toffs, T["tiles"], 1, True, True)
+        assert sr.frame_ok(got)
+        blocks = {j: s for v in got for j, s in v["blocks"].items()}
+        kinds = set()
+        for j, kind in F["claims"].items():
+            s, nb = blocks[j], T["nbs"][j]
+            kinds.add(kind)
+            if kind == "passes":                                     # a. s > 0 below plane 0
+                assert s["passes"] in (3 * nb - 1, 3 * nb) and s["zbp"] == 31 - nb
+                assert (s["floor"], s["pfloor"], s["numbps"]) == (0, 0, nb), (geom, j)
+            else:                                                    # b. mb - zbp < coded
+                assert s["passes"] == 3 * nb - 4 and s["zbp"] == 31 - nb + 2 and 31 - s["zbp"] < (s["passes"] + 2) // 3
+                assert (s["floor"], s["pfloor"], s["numbps"]) == (0, 0, nb - 1), (geom, j)
+        assert kinds == {"passes", "zbp"}
+        for j, s in blocks.items():                                  # every other block: the header round trip of pass_cases
+            if j not in F["claims"] and s["segs"]:
+                assert (s["pfloor"], s["numbps"]) == (pc.pfloor_of(T["nbs"][j], F["qs"][j]), T["nbs"][j]), (geom, j)
+            if not s["segs"]:
+                assert (s["floor"], s["pfloor"], s["numbps"]) == (0, 0, 0)
+    for c in sr.damaged_copies("pfloors"):                           # rule 5 on the crafted copies
+        if c["kind"] == "passes":
+            s = [v["blocks"][c["block"]] for v in c["verdicts"] if c["block"] in v["blocks"]][0]
+            assert s["dropped"] and (s["floor"], s["pfloor"], s["numbps"]) == (0, 0, 0) and s["passes"] > 91
 
 
 # ---- j2k_tile_parts_keep_layers -----------------------------------------------------------------------------------------------------------------
