@@ -286,7 +286,10 @@ int cl_workspaces(j2k_plan *P) {
 int cl_rate_workspace(j2k_plan *P, ClRate &W, bool passes) {
     j2k_ctx *ctx = P->ctx;
     const size_t n = P->blocks.size(), nr = (n + 255) & ~size_t(255);
-    const size_t bytes = nr * 32 * 8 + nr * 32 * 4 + 3 * nr + 256 + 256;
+    // (chosen and achieved: [layer][frame] of a batch plan whose frames are allocated alone, 32 x F words each -- sized for the plan's frames whether
+    // or not the setting is on, so that j2k_plan_set_rate_per_frame after the first call finds room)
+    const size_t F = P->spec.frame_h > 0 && P->spec.frame_h < P->spec.H ? (size_t)(P->spec.H / P->spec.frame_h) : 1, lf = 256 * F;
+    const size_t bytes = nr * 32 * 8 + nr * 32 * 4 + 3 * nr + 2 * lf;
     if (!P->d_cl_rate) {
         if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the frame codec's workspaces are made at its first call");
         HIPCHK(ctx, hipMalloc(&P->d_cl_rate, bytes));
@@ -294,7 +297,7 @@ int cl_rate_workspace(j2k_plan *P, ClRate &W, bool passes) {
     uint8_t *b = (uint8_t *)P->d_cl_rate;
     W.dist = (uint64_t *)b; b += nr * 32 * 8;
     W.rate = (uint32_t *)b; b += nr * 32 * 4;
-    W.chosen = (uint64_t *)b; b += 256;
+    W.chosen = (uint64_t *)b; b += lf;
     W.kept = b; W.floors = b + nr; W.floors_r = b + 2 * nr;
     W.achieved = (double *)(b + 3 * nr);                             // (nr is a multiple of 256: aligned)
     W.spmask = nullptr;
@@ -341,23 +344,11 @@ int plan_encode_frame_from_coeff(j2k_plan *P, const int32_t *d_coeff, uint32_t *
     else if (r == J2K_OK) r = plan_encode_blocks_planes_roi(P, d_coeff, (uint8_t *)P->d_slots, d_lens, d_numbps, W.rate, W.dist, q.roi, q.roi_gain);   // (roi == NULL: j2k_plan_encode_blocks_planes)
     if (r == J2K_OK) r = rate_upload_weights(P);
     if (r != J2K_OK) return r;
-    const int n = (int)P->blocks.size();
     uint8_t *d_kept = T ? T->d_kept : W.kept;
-    if (q.passes) {      // the same stage order on the pass tables: one budget or one target, the kept-prefix stream with pass counts
-        if (q.kind == EncodeRequest::DISTORTION)
-            HIPCHK(ctx, launch_rate_allocate_quality_passes(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.targets[0], P->d_rate_ws, d_kept, W.chosen,
-                                                            q.d_achieved ? q.d_achieved : W.achieved));
-        else
-            HIPCHK(ctx, launch_rate_allocate_passes(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.budgets[0], P->d_rate_ws, d_kept, W.chosen));
+    // the one launch that differs between the forms (rate_allocate_launch, j2k_rate.cpp); W.chosen / W.achieved: [layer][frame of the batch]
+    if ((r = rate_allocate_launch(P, q, W.rate, W.dist, d_numbps, d_kept, W.chosen, q.d_achieved ? q.d_achieved : W.achieved)) != J2K_OK) return r;
+    if (q.passes)        // the same stage order on the pass tables: one budget or one target, the kept-prefix stream with pass counts
         return encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, d_kept, W.rate, 1);
-    }
-    if (q.kind == EncodeRequest::DISTORTION)
-        HIPCHK(ctx, launch_rate_allocate_quality(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.targets, q.nlayers, P->d_rate_ws, d_kept, W.chosen,
-                                                 q.d_achieved ? q.d_achieved : W.achieved));
-    else if (q.layered)
-        HIPCHK(ctx, launch_rate_allocate_layers(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.budgets, q.nlayers, P->d_rate_ws, d_kept, W.chosen));      // (W.chosen: 32 words, one per layer)
-    else
-        HIPCHK(ctx, launch_rate_allocate(ctx->stream, n, W.rate, W.dist, d_numbps, P->d_rate_wj, q.budgets[0], P->d_rate_ws, d_kept, W.chosen));
     if (T) return encode_tile_parts_layers_launch(P, *T, q.nlayers, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, d_kept, W.rate, sop, eph, d_out, cap, d_tile_offs, d_layer_offs);
     return encode_tile_parts_impl(P, (const uint8_t *)P->d_slots, nullptr, d_lens, d_numbps, sop, eph, d_out, cap, d_tile_offs, d_kept, W.rate);
 }
@@ -432,6 +423,21 @@ extern "C" int j2k_plan_encode_frame_pixels_quality(j2k_plan *P, int format, con
     const int r = encode_request(P, "j2k_plan_encode_frame_pixels_quality", nullptr, targets, nlayers, d_layer_offs != nullptr, roi != nullptr, roi, roi_gain, d_achieved, q);
     if (r != J2K_OK) return r;
     return encode_frame_pixels(P, format, d_pix, stride, q, sop, eph, d_out, cap, d_tile_offs, d_layer_offs);
+}
+// A budget (frame_bytes) or a target (frame_targets) of its own for every frame of a batch plan with j2k_plan_set_rate_per_frame, exactly one of the
+// two; pass_cuts: at coding-pass ends.  One layer, the kept-prefix stream.  The values are read before the call returns and reach the kernel by
+// value: a captured call replays them.  d_achieved ([frames], may be null): what every frame's choice reached of its target.
+extern "C" int j2k_plan_encode_frame_pixels_rate_frames(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, const int64_t *frame_bytes,
+                                                        const double *frame_targets, int nframes, int pass_cuts, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs,
+                                                        double *d_achieved) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
+    EncodeRequest q;
+    const int r = frame_values_request(P, "j2k_plan_encode_frame_pixels_rate_frames", frame_bytes, frame_targets, nframes, q);
+    if (r != J2K_OK) return r;
+    q.passes = pass_cuts != 0;
+    q.d_achieved = frame_targets ? d_achieved : nullptr;
+    return encode_frame_pixels(P, format, d_pix, stride, q, sop, eph, d_out, cap, d_tile_offs, nullptr);
 }
 
 // ---- the one frame decoder --------------------------------------------------------------------------------------------------------------------

@@ -57,21 +57,31 @@ hipError_t launch_rate_distortion(hipStream_t s, const BlockJob *jobs, int njobs
 hipError_t launch_rate_distortion_passes(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, const uint64_t *spmask,
                                          uint64_t *dist);
 hipError_t launch_rate_allocate_passes(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
-                                       uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen);
+                                       uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen, int nframes = 1, const RateFrame *frames = nullptr,
+                                       const uint64_t *frame_budgets = nullptr);
 hipError_t launch_rate_allocate_quality_passes(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
-                                               double target, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved);
+                                               double target, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved, int nframes = 1,
+                                               const RateFrame *frames = nullptr, const double *frame_targets = nullptr);
 // region of interest (area.hip, rate.hip): every block's footprint of a rectangle; the distortions with that footprint weighted `gain` times
 hipError_t launch_roi_windows(hipStream_t s, const j2k_block *blocks, int n, const AreaPlane *planes, int x0, int y0, int x1, int y1, int margin, int32_t *win);
 hipError_t launch_rate_distortion_roi(hipStream_t s, const BlockJob *jobs, int njobs, const int32_t *coef, const uint8_t *numbps, const j2k_block *blocks,
                                       const AreaPlane *planes, int x0, int y0, int x1, int y1, int margin, uint32_t gain, uint64_t *dist);
 size_t rate_allocate_workspace(int njobs);
+// A batch plan with j2k_plan_set_rate_per_frame: `frames` (device) = the job range of each of its nframes frames, one workgroup per frame, kept
+// [layers][njobs], chosen and achieved [layers][nframes]; frame_budgets / frame_targets (device, or null; one layer): frame f's own value in the
+// place of the scalar.  frames == NULL: one frame of all njobs jobs, as ever.
 hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
-                                uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen);
+                                uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen, int nframes = 1, const RateFrame *frames = nullptr,
+                                const uint64_t *frame_budgets = nullptr);
 hipError_t launch_rate_allocate_layers(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
-                                       const uint64_t *budgets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen);
+                                       const uint64_t *budgets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen, int nframes = 1,
+                                       const RateFrame *frames = nullptr);
+// nframes 64-bit values of the host (budgets, or the bits of float64 targets) into a device table, by value: a captured call replays them
+hipError_t launch_rate_frame_values(hipStream_t s, const uint64_t *values, int nframes, uint64_t *table);
 // the dual (rate.hip): per layer the fewest bytes whose weighted distortion stays within targets[l]; achieved[l] = that distortion
 hipError_t launch_rate_allocate_quality(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
-                                        const double *targets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved);
+                                        const double *targets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved, int nframes = 1,
+                                        const RateFrame *frames = nullptr, const double *frame_targets = nullptr);
 // per-channel sums of squared sample differences of two frames in one Pix layout (pixels.hip)
 size_t pixels_sse_workspace();
 hipError_t launch_pixels_sse(hipStream_t s, const uint8_t *a, size_t stride_a, const uint8_t *b, size_t stride_b, size_t rowbytes, int h, bool wide, int channels,
@@ -171,7 +181,7 @@ static inline void first_use_alloc(j2k_ctx *ctx, int &r, void **p, size_t bytes,
 // the closed-loop frame codec's tables and workspaces, made at first use (j2k_frame.cpp)
 int cl_prepare(j2k_plan *P);
 int cl_workspaces(j2k_plan *P);
-struct ClRate { uint32_t *rate; uint64_t *dist; uint8_t *kept; uint64_t *chosen; uint8_t *floors, *floors_r; double *achieved; uint64_t *spmask; };   // chosen, achieved: 32 words, one per layer
+struct ClRate { uint32_t *rate; uint64_t *dist; uint8_t *kept; uint64_t *chosen; uint8_t *floors, *floors_r; double *achieved; uint64_t *spmask; };   // chosen, achieved: 32 x F words, [layer][frame of the batch]
 int cl_rate_workspace(j2k_plan *P, ClRate &W, bool passes = false);    // passes: rate / dist are the 96-entry pass tables (their own allocation), spmask beside them
 int layer_tab(j2k_plan *P, int L, j2k::LayerTab **out);     // the tables of layer count L, made at its first use (j2k_layers.cpp)
 
@@ -190,6 +200,10 @@ struct EncodeRequest {
     int roi_gain = 1;
     double *d_achieved = nullptr;
     bool passes = false;      // the blocks are cut at coding-pass ends (the _passes calls: one budget or one target, no layers, no roi)
+    // a batch plan with j2k_plan_set_rate_per_frame (rate_frames(P) = F frames): every frame is cut alone under budgets / targets; per_frame (the
+    // _frames calls; one layer, no roi): under ITS entry of frame_values (F budgets, or the bits of F float64 targets) -- d_achieved: F per layer
+    bool per_frame = false;
+    std::vector<uint64_t> frame_values;
 };
 // an entry point's arguments -> its request, or the refusal (through fail(), naming `who`), in this order: the plan (rate_check), the layer count,
 // the rectangle and gain (check_roi), the budgets or targets (targets != NULL: DISTORTION), more than one of them without the layered stream
@@ -256,7 +270,13 @@ int decode_host(j2k_plan *P, const uint8_t *cs, size_t len, size_t pixbytes, voi
 static inline size_t reduced_rows(int H, int reduce) { return reduce > 0 ? (size_t)(((int64_t)H + (((int64_t)1 << reduce) - 1)) >> reduce) : (size_t)H; }
 int rate_check(j2k_plan *P, const char *who);    // what every rate call needs of its plan (j2k_rate.cpp)
 int raw_magref_refuse(const j2k_plan *P, const char *who);    // J2K_ERR_UNSUPPORTED on a plan in the raw-MagRef style (j2k_stages.cpp): the calls that cut bodies or read cut ones
-int rate_upload_weights(j2k_plan *P);            // the per-job weights and the allocation workspace on the device (j2k_rate.cpp)
+int rate_upload_weights(j2k_plan *P);            // the per-job weights, the allocation workspace and (rate_per_frame) the frame ranges on the device (j2k_rate.cpp)
+int rate_frames(const j2k_plan *P);              // F: the frames a rate call allocates separately -- height / frame_rows with j2k_plan_set_rate_per_frame, else 1
+// the one allocation launch of a request on its tables (the frame encoder; the stage calls go through it too): kind, layers, passes, per_frame
+int rate_allocate_launch(j2k_plan *P, const EncodeRequest &q, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, uint8_t *d_kept,
+                         uint64_t *d_chosen, double *d_achieved);
+// the _frames calls' vector: nframes == F, no negative budget / no target that is not finite or is negative -> q.per_frame, q.frame_values
+int frame_values_request(j2k_plan *P, const char *who, const int64_t *frame_bytes, const double *frame_targets, int nframes, EncodeRequest &q);
 int targets_check(j2k_ctx *ctx, const double *targets, int nlayers, const char *who);   // distortion targets: finite, >= 0, none above the one before (j2k_rate.cpp)
 // the plan data of area_blocks_kernel (and of the region-of-interest kernels), uploaded at first use; frame: also the staging frame of a region
 // decode (j2k_area.cpp)

@@ -389,7 +389,7 @@ int pix_format_bytes(int format) {
 
 size_t encode_host_io_bytes(const j2k_plan *P, bool cl_set, int nlayers, size_t bound) {
     const size_t nt = (size_t)P->tile_count, nl = cl_set ? nt * (size_t)nlayers : 0;
-    return ((bound + 64 + 15) & ~size_t(15)) + (cl_set ? nt + 1 + nl + 2 + J2K_MAX_LAYERS : nt + 2) * 8;
+    return ((bound + 64 + 15) & ~size_t(15)) + (cl_set ? nt + 1 + nl + 2 + (size_t)J2K_MAX_LAYERS * (size_t)rate_frames(P) : nt + 2) * 8;      // (achieved: [layer][frame])
 }
 
 int encode_host_launch(j2k_plan *P, const EncodeRequest &request, bool cl_set, size_t bound, int sop, int eph, void *d_io, const std::function<int(int32_t *)> &forward,
@@ -453,7 +453,7 @@ int encode_host(j2k_plan *P, const EncodeRequest &request, bool cl_set, size_t b
     HIPCHK(ctx, hipMemcpyAsync(&offs[io.offs_at], io.d_offs, io.offs_count * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (lens && nb) HIPCHK(ctx, hipMemcpyAsync(lens, io.d_lens, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (numbps && nb) HIPCHK(ctx, hipMemcpyAsync(numbps, io.d_numbps, nb, hipMemcpyDeviceToHost, ctx->stream));
-    if (q.d_achieved && achieved) HIPCHK(ctx, hipMemcpyAsync(achieved, q.d_achieved, (size_t)q.nlayers * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (q.d_achieved && achieved) HIPCHK(ctx, hipMemcpyAsync(achieved, q.d_achieved, (size_t)q.nlayers * (size_t)rate_frames(P) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));      // [layer][frame]
     if (!S.closed_loop && tile_offs) { boffs.resize(nb + 1); if (nb) HIPCHK(ctx, hipMemcpyAsync(boffs.data(), P->d_offs, (nb + 1) * 8, hipMemcpyDeviceToHost, ctx->stream)); }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if ((r = check_fault(ctx)) != J2K_OK) return r;
@@ -504,6 +504,20 @@ extern "C" int j2k_encode_pixels_host_rate(j2k_plan *P, int format, const void *
     q.kind = EncodeRequest::BYTES;
     q.budgets[0] = (uint64_t)max_body_bytes;
     return encode_pixels_host(P, format, pix, stride, q, false, plain_bound(P), sop, eph, out, cap, out_len, tile_offs, nullptr, lens, numbps, nullptr);
+}
+
+// the synchronous host-memory form of j2k_plan_encode_frame_pixels_rate_frames; achieved ([frames], may be null): with frame_targets
+extern "C" int j2k_encode_pixels_host_rate_frames(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *frame_bytes,
+                                                  const double *frame_targets, int nframes, int pass_cuts, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs,
+                                                  uint32_t *lens, uint8_t *numbps, double *achieved) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    EncodeRequest q;
+    int r = host_call_check(P, pix, out_len);
+    if (r == J2K_OK) r = frame_values_request(P, "j2k_encode_pixels_host_rate_frames", frame_bytes, frame_targets, nframes, q);
+    if (r != J2K_OK) return r;
+    q.passes = pass_cuts != 0;
+    return encode_pixels_host(P, format, pix, stride, q, true, j2k_plan_frame_bound(P), sop, eph, out, cap, out_len, tile_offs, nullptr, lens, numbps,
+                              frame_targets ? achieved : nullptr);
 }
 
 // image.YCbCr / CMYK / Paletted in Go memory (encoder.go:178-195): each plane crosses PCIe at its native size -- the bytes the rectangle

@@ -110,15 +110,10 @@ extern "C" size_t j2k_plan_frame_bound_layers(const j2k_plan *P, int nlayers) {
 extern "C" int j2k_plan_rate_allocate_layers(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, const int64_t *layer_bytes,
                                              int nlayers, uint8_t *d_kept, uint64_t *d_chosen) {
     if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen) return J2K_ERR_INVALID_ARG;
-    j2k_ctx *ctx = P->ctx;
     EncodeRequest q;
     int r = encode_request(P, "j2k_plan_rate_allocate_layers", layer_bytes, nullptr, nlayers, true, false, nullptr, 1, nullptr, q);
     if (r != J2K_OK) return r;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    r = rate_upload_weights(P);
-    if (r != J2K_OK) return r;
-    HIPCHK(ctx, launch_rate_allocate_layers(ctx->stream, (int)P->blocks.size(), d_rate, d_dist, d_numbps, P->d_rate_wj, q.budgets, nlayers, P->d_rate_ws, d_kept, d_chosen));
-    return J2K_OK;
+    return rate_allocate_launch(P, q, d_rate, d_dist, d_numbps, d_kept, d_chosen, nullptr);
 }
 
 // the layer table from the cuts, then the packet coder as it is (its kernels write exactly the layered header from these entries: t2_fields,

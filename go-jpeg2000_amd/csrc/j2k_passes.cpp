@@ -32,12 +32,11 @@ extern "C" int j2k_plan_rate_allocate_passes(j2k_plan *P, const uint32_t *d_rate
     int r = rate_check(P, "j2k_plan_rate_allocate_passes");
     if (r != J2K_OK) return r;
     if (max_body_bytes < 0) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_rate_allocate_passes: a negative budget");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    r = rate_upload_weights(P);
-    if (r != J2K_OK) return r;
-    HIPCHK(ctx, launch_rate_allocate_passes(ctx->stream, (int)P->blocks.size(), d_rate, d_dist, d_numbps, P->d_rate_wj, (uint64_t)max_body_bytes, P->d_rate_ws, d_kept,
-                                            d_chosen));
-    return J2K_OK;
+    EncodeRequest q;
+    q.kind = EncodeRequest::BYTES;
+    q.budgets[0] = (uint64_t)max_body_bytes;
+    q.passes = true;
+    return rate_allocate_launch(P, q, d_rate, d_dist, d_numbps, d_kept, d_chosen, nullptr);
 }
 
 extern "C" int j2k_plan_rate_allocate_quality_passes(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, double target,
@@ -47,12 +46,11 @@ extern "C" int j2k_plan_rate_allocate_quality_passes(j2k_plan *P, const uint32_t
     int r = rate_check(P, "j2k_plan_rate_allocate_quality_passes");
     if (r == J2K_OK) r = targets_check(ctx, &target, 1, "j2k_plan_rate_allocate_quality_passes");
     if (r != J2K_OK) return r;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    r = rate_upload_weights(P);
-    if (r != J2K_OK) return r;
-    HIPCHK(ctx, launch_rate_allocate_quality_passes(ctx->stream, (int)P->blocks.size(), d_rate, d_dist, d_numbps, P->d_rate_wj, target, P->d_rate_ws, d_kept, d_chosen,
-                                                    d_achieved));
-    return J2K_OK;
+    EncodeRequest q;
+    q.kind = EncodeRequest::DISTORTION;
+    q.targets[0] = target;
+    q.passes = true;
+    return rate_allocate_launch(P, q, d_rate, d_dist, d_numbps, d_kept, d_chosen, d_achieved);
 }
 
 // j2k_plan_encode_tile_parts_kept with d_kept[j] a pass count q <= 3 numBPS - 2: the block's bytes are the prefix d_rate[j * 96 + q], its header carries q

@@ -218,6 +218,12 @@ struct j2k_plan : j2k::PlanScalars {
     double *d_rate_wj = nullptr;
     bool rate_wj_valid = false;
     void *d_rate_ws = nullptr;              // the allocation kernel's hulls
+    // j2k_plan_set_rate_per_frame: every rate call allocates each frame of a batch alone (tests/frame_rate_cases.py).  d_rate_frames: the job
+    // range of every frame (plan_tables.h: frame_job_ranges), uploaded at the first rate call with the setting on; d_rate_fvals: one 64-bit
+    // value per frame, the budgets or targets of the _frames calls (written on the stream by launch_rate_frame_values)
+    bool rate_per_frame = false;
+    j2k::RateFrame *d_rate_frames = nullptr;
+    uint64_t *d_rate_fvals = nullptr;
     void *d_cl_prate = nullptr;             // the *_passes frame calls: the 96-entry rate and distortion tables and the SigProp masks (cl_rate_workspace)
     void *d_cl_rate = nullptr;              // the *_rate frame calls: rate and distortion tables, kept planes, chosen bytes, floors (cl_rate_workspace)
     std::vector<j2k::LayerTab> layer_tabs;  // quality layers: [L], 1 ... J2K_MAX_LAYERS

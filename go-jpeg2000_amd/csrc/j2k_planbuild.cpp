@@ -124,7 +124,7 @@ extern "C" void j2k_plan_destroy(j2k_plan *P) {
     void *ptrs[] = {P->d_scrA, P->d_scrB, P->d_scr16_fmt, P->d_bigsym_off, P->d_frame, P->d_coeff, P->d_slots, P->d_stream, P->d_lens, P->d_numbps, P->d_offs, P->d_status, P->d_maglens, P->d_mels, P->d_toffs,
                     P->d_t2_packets, P->d_tile_packet0, P->d_t2_cbs, P->d_t2_poffs, P->d_t2_ptile, P->d_t2_ws, P->d_t2_chains, P->d_t2_body_base, P->d_t2_par, P->d_frame_status,
                     P->d_cl_decoded, P->d_cl_coeff, P->d_cl_coeff_dec, P->d_cl_numbps, P->d_cl_offs, P->d_cl_lens, P->d_host_io, P->d_host_pix,
-                    P->d_rate_wj, P->d_rate_ws, P->d_cl_rate, P->d_cl_prate, P->d_cl_dense, P->d_cl_lfloors,
+                    P->d_rate_wj, P->d_rate_ws, P->d_rate_frames, P->d_rate_fvals, P->d_cl_rate, P->d_cl_prate, P->d_cl_dense, P->d_cl_lfloors,
                     P->d_area_blocks, P->d_area_planes, P->d_area_frame};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete P;

@@ -76,12 +76,36 @@ int rate_check(j2k_plan *P, const char *who) {
     const char *why = nullptr;
     if (S.coder != J2K_CODER_MQ) why = "needs the MQ coder (the HT coder's one pass has no planes to cut between)";
     else if (!S.closed_loop) why = "needs a closed-loop plan (only its packets can say where a block was cut)";
-    else if (S.frame_h != S.H) why = "a batch plan (frame_rows): not built";
+    else if (S.frame_h != S.H && !P->rate_per_frame) why = "a batch plan (frame_rows): not built";
     else if (P->raw_magref) why = "the plan codes in the raw-MagRef style (j2k_plan_set_raw_magref): a two-stream body cannot be cut at bit planes";
     else
         for (const j2k_block &b : P->blocks)
             if (b.w > 64 || b.h > 64) { why = "blocks above 64 x 64: not built"; break; }
     if (why) return fail(P->ctx, J2K_ERR_UNSUPPORTED, (std::string(who) + ": " + why).c_str());
+    return J2K_OK;
+}
+
+// ---- batch plans: every frame allocated alone (tests/frame_rate_cases.py) -------------------------------------------------------
+// Plan state in the idiom of j2k_plan_set_raw_magref: the rate calls read it, nothing below them does -- block coding, distortion, packets and
+// readers already work per block or per tile.
+extern "C" int j2k_plan_set_rate_per_frame(j2k_plan *P, int on) {
+    if (!P) return J2K_ERR_INVALID_ARG;
+    j2k_ctx *ctx = P->ctx;
+    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_set_rate_per_frame: plan state cannot change while a graph is being captured");
+    if (on != 0 && on != 1) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_set_rate_per_frame: on is 0 or 1");
+    const PlanSpec &S = P->spec;
+    if (on && S.frame_h > 0 && S.frame_h != S.H && P->tile_count != P->tiles_x * P->tiles_y)
+        return fail(ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_set_rate_per_frame: a shard of a batch plan (tile_first / tile_count): a frame may be partial");
+    P->rate_per_frame = on != 0;
+    return J2K_OK;
+}
+int rate_frames(const j2k_plan *P) {
+    const PlanSpec &S = P->spec;
+    return P->rate_per_frame && S.frame_h > 0 && S.frame_h < S.H ? S.H / S.frame_h : 1;
+}
+extern "C" int j2k_plan_rate_frames(const j2k_plan *P, int32_t *frames) {
+    if (!P || !frames) return J2K_ERR_INVALID_ARG;
+    *frames = rate_frames(P);
     return J2K_OK;
 }
 
@@ -127,6 +151,7 @@ int roi_check(j2k_plan *P, const j2k_rect *roi, int roi_gain, const char *who) {
     const std::string w(who);
     if (!S.mallat) return fail(ctx, J2K_ERR_UNSUPPORTED, (w + ": a region of interest needs a Mallat plan (the prefix layout has no spatial footprint below level 0)").c_str());
     if (P->tile_count != P->tiles_x * P->tiles_y) return fail(ctx, J2K_ERR_UNSUPPORTED, (w + ": a region of interest on a shard plan (tile_first / tile_count)").c_str());
+    if (rate_frames(P) > 1) return fail(ctx, J2K_ERR_UNSUPPORTED, (w + ": a region of interest on a batch plan (the footprint tables know one frame)").c_str());
     if (!roi) return fail(ctx, J2K_ERR_INVALID_ARG, (w + ": no rectangle").c_str());
     if (roi->x0 < 0 || roi->y0 < 0 || roi->x0 >= roi->x1 || roi->y0 >= roi->y1 || roi->x1 > S.W || roi->y1 > S.H)
         return fail(ctx, J2K_ERR_INVALID_ARG, (w + ": the rectangle is inverted, empty or outside the frame").c_str());
@@ -175,21 +200,103 @@ extern "C" int j2k_plan_rate_allocate(j2k_plan *P, const uint32_t *d_rate, const
     int r = rate_check(P, "j2k_plan_rate_allocate");
     if (r != J2K_OK) return r;
     if (max_body_bytes < 0) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_rate_allocate: a negative budget");
+    EncodeRequest q;
+    q.kind = EncodeRequest::BYTES;
+    q.budgets[0] = (uint64_t)max_body_bytes;
+    return rate_allocate_launch(P, q, d_rate, d_dist, d_numbps, d_kept, d_chosen, nullptr);
+}
+
+// The ONE allocation launch of a request (every stage call and the frame encoder end here): the weights, the workspace and -- on a batch plan with
+// j2k_plan_set_rate_per_frame -- the frame ranges on the device, the per-frame values of a _frames call written on the stream, then the kernel its
+// kind, layering and granularity select, F workgroups of it.  F = 1 passes no frame table: the launch is the one it has always been.
+int rate_allocate_launch(j2k_plan *P, const EncodeRequest &q, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, uint8_t *d_kept,
+                         uint64_t *d_chosen, double *d_achieved) {
+    j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    r = rate_upload_weights(P);
+    const int r = rate_upload_weights(P);
     if (r != J2K_OK) return r;
-    HIPCHK(ctx, launch_rate_allocate(ctx->stream, (int)P->blocks.size(), d_rate, d_dist, d_numbps, P->d_rate_wj, (uint64_t)max_body_bytes, P->d_rate_ws, d_kept, d_chosen));
+    const int n = (int)P->blocks.size(), F = rate_frames(P);
+    const RateFrame *frames = F > 1 ? P->d_rate_frames : nullptr;
+    const uint64_t *fv = nullptr;
+    if (q.per_frame && F > 1) {          // (F = 1: the callers have put the one value into budgets[0] / targets[0])
+        HIPCHK(ctx, launch_rate_frame_values(ctx->stream, q.frame_values.data(), F, P->d_rate_fvals));
+        fv = P->d_rate_fvals;
+    }
+    const bool quality = q.kind == EncodeRequest::DISTORTION;
+    if (q.passes && quality)
+        HIPCHK(ctx, launch_rate_allocate_quality_passes(ctx->stream, n, d_rate, d_dist, d_numbps, P->d_rate_wj, q.targets[0], P->d_rate_ws, d_kept, d_chosen, d_achieved, F, frames,
+                                                        reinterpret_cast<const double *>(fv)));
+    else if (q.passes)
+        HIPCHK(ctx, launch_rate_allocate_passes(ctx->stream, n, d_rate, d_dist, d_numbps, P->d_rate_wj, q.budgets[0], P->d_rate_ws, d_kept, d_chosen, F, frames, fv));
+    else if (quality)
+        HIPCHK(ctx, launch_rate_allocate_quality(ctx->stream, n, d_rate, d_dist, d_numbps, P->d_rate_wj, q.targets, q.nlayers, P->d_rate_ws, d_kept, d_chosen, d_achieved, F, frames,
+                                                 reinterpret_cast<const double *>(fv)));
+    else if (q.layered)
+        HIPCHK(ctx, launch_rate_allocate_layers(ctx->stream, n, d_rate, d_dist, d_numbps, P->d_rate_wj, q.budgets, q.nlayers, P->d_rate_ws, d_kept, d_chosen, F, frames));
+    else
+        HIPCHK(ctx, launch_rate_allocate(ctx->stream, n, d_rate, d_dist, d_numbps, P->d_rate_wj, q.budgets[0], P->d_rate_ws, d_kept, d_chosen, F, frames, fv));
     return J2K_OK;
+}
+
+// the vector of a _frames call -> the request: one entry per frame, each checked as the scalar it stands for (the entries belong to different
+// frames: they need not fall or rise).  With F = 1 the one entry IS the scalar: budgets[0] / targets[0], and nothing per frame.
+int frame_values_request(j2k_plan *P, const char *who, const int64_t *frame_bytes, const double *frame_targets, int nframes, EncodeRequest &q) {
+    j2k_ctx *ctx = P->ctx;
+    const std::string w(who);
+    int r = rate_check(P, who);
+    if (r != J2K_OK) return r;
+    if ((frame_bytes != nullptr) == (frame_targets != nullptr)) return fail(ctx, J2K_ERR_INVALID_ARG, (w + ": exactly one of frame_bytes and frame_targets").c_str());
+    const int F = rate_frames(P);
+    if (nframes != F) return fail(ctx, J2K_ERR_INVALID_ARG, (w + ": one entry per frame of the plan (j2k_plan_rate_frames)").c_str());
+    q = EncodeRequest();
+    q.kind = frame_targets ? EncodeRequest::DISTORTION : EncodeRequest::BYTES;
+    q.frame_values.resize((size_t)F);
+    for (int f = 0; f < F; f++) {
+        if (frame_bytes) {
+            if (frame_bytes[f] < 0) return fail(ctx, J2K_ERR_INVALID_ARG, (w + ": a negative budget").c_str());
+            q.frame_values[(size_t)f] = (uint64_t)frame_bytes[f];
+        } else {
+            if (!std::isfinite(frame_targets[f]) || frame_targets[f] < 0.0) return fail(ctx, J2K_ERR_INVALID_ARG, (w + ": a target is a finite distortion >= 0").c_str());
+            memcpy(&q.frame_values[(size_t)f], &frame_targets[f], sizeof(double));
+        }
+    }
+    if (frame_bytes) q.budgets[0] = (uint64_t)frame_bytes[0]; else q.targets[0] = frame_targets[0];
+    q.per_frame = F > 1;
+    return J2K_OK;
+}
+
+// j2k_plan_rate_allocate / _passes with a budget of its own for every frame of the batch
+extern "C" int j2k_plan_rate_allocate_frames(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, const int64_t *frame_bytes, int nframes,
+                                             int pass_cuts, uint8_t *d_kept, uint64_t *d_chosen) {
+    if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen) return J2K_ERR_INVALID_ARG;
+    if (!frame_bytes) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_plan_rate_allocate_frames: no budgets");
+    EncodeRequest q;
+    const int r = frame_values_request(P, "j2k_plan_rate_allocate_frames", frame_bytes, nullptr, nframes, q);
+    if (r != J2K_OK) return r;
+    q.passes = pass_cuts != 0;
+    return rate_allocate_launch(P, q, d_rate, d_dist, d_numbps, d_kept, d_chosen, nullptr);
+}
+// j2k_plan_rate_allocate_quality (one layer) / _quality_passes with a target of its own for every frame
+extern "C" int j2k_plan_rate_allocate_quality_frames(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, const double *frame_targets,
+                                                     int nframes, int pass_cuts, uint8_t *d_kept, uint64_t *d_chosen, double *d_achieved) {
+    if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen || !d_achieved) return J2K_ERR_INVALID_ARG;
+    if (!frame_targets) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_plan_rate_allocate_quality_frames: no targets");
+    EncodeRequest q;
+    const int r = frame_values_request(P, "j2k_plan_rate_allocate_quality_frames", nullptr, frame_targets, nframes, q);
+    if (r != J2K_OK) return r;
+    q.passes = pass_cuts != 0;
+    return rate_allocate_launch(P, q, d_rate, d_dist, d_numbps, d_kept, d_chosen, d_achieved);
 }
 
 // ---- the dual: a distortion target in the place of a byte budget (tests/quality_cases.py) ----------------------------------------
 // T = N * peak^2 * q^2 / 10^(dB / 10): N samples, peak = 2^precision - 1, q = the plan's quality where it quantises (its coefficients are the
-// transform times quality), else 1.  Host only.
+// transform times quality), else 1.  Host only.  N is the samples of ONE frame: on a batch plan with j2k_plan_set_rate_per_frame a target belongs
+// to a frame (W * frame_rows * ncomp), on every other plan it is W * H * ncomp as ever.
 extern "C" int j2k_plan_psnr_distortion(const j2k_plan *P, double db, double *T) {
     if (!P || !T || !std::isfinite(db)) return J2K_ERR_INVALID_ARG;
     const PlanSpec &S = P->spec;
     const double peak = (double)((1u << S.precision) - 1u), q = S.quant != Q_NONE ? (double)S.quality : 1.0;
-    const double t = (double)S.W * (double)S.H * (double)S.C * peak * peak * q * q / std::pow(10.0, db / 10.0);
+    const double t = (double)S.W * (double)(S.H / rate_frames(P)) * (double)S.C * peak * peak * q * q / std::pow(10.0, db / 10.0);
     if (!std::isfinite(t)) return J2K_ERR_INVALID_ARG;
     *T = t;
     return J2K_OK;
@@ -214,12 +321,11 @@ extern "C" int j2k_plan_rate_allocate_quality(j2k_plan *P, const uint32_t *d_rat
     if (nlayers < 1 || nlayers > J2K_MAX_LAYERS) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_rate_allocate_quality: the layer count is 1 ... 32");
     r = targets_check(ctx, targets, nlayers, "j2k_plan_rate_allocate_quality");
     if (r != J2K_OK) return r;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    r = rate_upload_weights(P);
-    if (r != J2K_OK) return r;
-    HIPCHK(ctx, launch_rate_allocate_quality(ctx->stream, (int)P->blocks.size(), d_rate, d_dist, d_numbps, P->d_rate_wj, targets, nlayers, P->d_rate_ws, d_kept, d_chosen,
-                                             d_achieved));
-    return J2K_OK;
+    EncodeRequest q;
+    q.kind = EncodeRequest::DISTORTION;
+    q.nlayers = nlayers; q.layered = true;
+    std::copy(targets, targets + nlayers, q.targets);
+    return rate_allocate_launch(P, q, d_rate, d_dist, d_numbps, d_kept, d_chosen, d_achieved);
 }
 
 int rate_upload_weights(j2k_plan *P) {
@@ -239,6 +345,16 @@ int rate_upload_weights(j2k_plan *P) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));              // an allocation in flight still reads the old weights
         HIPCHK(ctx, hipMemcpy(P->d_rate_wj, wj.data(), wj.size() * sizeof(double), hipMemcpyHostToDevice));
         P->rate_wj_valid = true;
+    }
+    // a batch plan whose frames are allocated alone: their job ranges, and the table the _frames calls' values go through
+    if (rate_frames(P) > 1 && !P->d_rate_frames) {
+        if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: run the same calls once before j2k_ctx_capture_begin");
+        const int F = rate_frames(P);
+        std::vector<RateFrame> fr;
+        if (!frame_job_ranges(P->block_tile, P->tile_count / F, F, fr)) return fail(ctx, J2K_ERR_UNSUPPORTED, "rate_per_frame: the jobs of a frame are not one contiguous range");
+        if (!P->d_rate_fvals) HIPCHK(ctx, hipMalloc((void **)&P->d_rate_fvals, (size_t)F * sizeof(uint64_t)));
+        const int r = upload(ctx, &P->d_rate_frames, fr);
+        if (r != J2K_OK) return r;
     }
     return J2K_OK;
 }

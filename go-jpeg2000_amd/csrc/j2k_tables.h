@@ -78,6 +78,11 @@ struct AreaPlane {
     int32_t pad_[3];
 };
 
+// One frame of a batch plan for the rate allocation (rate.hip, j2k_plan_set_rate_per_frame): its contiguous range of code-block jobs
+struct RateFrame {
+    int32_t first, count;
+};
+
 // |element of X_1| <= J2K_SCR16_BOUND + dc_shift after level 0 of a packed 8-bit frame (derived at st_scr16, dwt53_l0pix.inc)
 #define J2K_SCR16_BOUND (4 * 255 + 3)
 
@@ -89,5 +94,6 @@ J2K_TABLE_LAYOUT(HtUJob, 48, pad_, 44);
 J2K_TABLE_LAYOUT(TailPlane, 32, pad_, 28);
 J2K_TABLE_LAYOUT(LLPlane, 72, pad_, 68);
 J2K_TABLE_LAYOUT(AreaPlane, 32, pad_, 20);
+J2K_TABLE_LAYOUT(RateFrame, 8, count, 4);
 
 }  // namespace j2k

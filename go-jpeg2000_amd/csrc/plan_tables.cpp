@@ -866,3 +866,23 @@ int build_reduced_tables(const PlanOptions &o, const PlanSpec &S, const PlanScal
 }
 
 }  // namespace j2k
+
+// ------------------------------------------------------------------------------
+// frames of a batch as job ranges (the rate allocation of j2k_plan_set_rate_per_frame)
+// ------------------------------------------------------------------------------
+namespace j2k {
+bool frame_job_ranges(const std::vector<int32_t> &block_tile, int tiles_per_frame, int nframes, std::vector<RateFrame> &out) {
+    out.clear();
+    if (tiles_per_frame < 1 || nframes < 1) return false;
+    const size_t n = block_tile.size();
+    size_t j = 0;
+    for (int f = 0; f < nframes; f++) {
+        const int64_t t0 = (int64_t)f * tiles_per_frame, t1 = t0 + tiles_per_frame;
+        const size_t first = j;
+        while (j < n && block_tile[j] >= t0 && block_tile[j] < t1) j++;
+        out.push_back(RateFrame{(int32_t)first, (int32_t)(j - first)});
+    }
+    if (j != n) { out.clear(); return false; }       // a tile out of order or out of range: the jobs of a frame would not be one range
+    return true;
+}
+}  // namespace j2k

@@ -132,6 +132,12 @@ struct PlanTables : PlanScalars {
 // S -> T.  J2K_OK, or J2K_ERR_INVALID_ARG with *why = "bad geometry" / "plane too large"
 int build_plan_tables(const PlanOptions &o, const PlanLimits &lim, const PlanSpec &S, PlanTables &T, const char **why);
 
+// The job range of every frame of a batch for the rate allocation (j2k_plan_set_rate_per_frame; tests/frame_rate_cases.py: frame_ranges): frame f
+// owns the blocks whose tile is in [f * tiles_per_frame, (f + 1) * tiles_per_frame).  block_tile lists the tile of every job and must not fall
+// (block_jobs emits tile by tile), so the ranges are contiguous and in order; false, with `out` empty, if it does, if a tile is outside
+// [0, nframes * tiles_per_frame) or the counts are not positive.  A frame without blocks has count 0 and starts where the next one does.
+bool frame_job_ranges(const std::vector<int32_t> &block_tile, int tiles_per_frame, int nframes, std::vector<RateFrame> &out);
+
 // A Mallat plan decoded `reduce` resolutions down (j2k_plan_*_reduced): LL_reduce is the frame, W_r x H_r = ceil(W / 2^reduce) x ceil(H / 2^reduce),
 // tile (x0, y0) at (x0 >> reduce, y0 >> reduce)
 struct ReducedInfo {

@@ -176,7 +176,14 @@ __global__ __launch_bounds__(64) void rate_distortion_roi_kernel(const BlockJob 
     if (lane < RATE_STRIDE) dist[(size_t)jid * RATE_STRIDE + (lane <= nb ? nb - lane : lane)] = lane <= nb ? mine : 0;
 }
 
-// ---- allocation: one workgroup for the frame ----------------------------------------------------------------------------------------------
+// ---- allocation: one workgroup for a frame ------------------------------------------------------------------------------------------------
+// A launch has F = gridDim.x workgroups; workgroup f allocates frame f of a batch plan (j2k_plan_set_rate_per_frame, tests/frame_rate_cases.py):
+// the contiguous jobs frames[f], under that frame's own budget(s) or target(s).  Every other launch has ONE workgroup and frames == NULL: the
+// frame is all njobs jobs.  Inside a workgroup every index is frame-LOCAL -- the table pointers are moved to the frame's first job, thread t
+// owns the blocks t, t + 1024, ... of ITS frame -- so the float64 sums add in the order the definition fixes for that frame alone and the
+// results are the bits a single-frame plan gives.  Workgroups share nothing: each has its own slice of the hull workspace (sliced by job
+// index), writes kept[l * njobs + j] for its own jobs j and chosen / achieved [l * F + f]; a frame whose full lengths fit returns early while
+// its neighbours search.
 // Workspace per block: the planes of its hull points (32 bytes), their incoming slopes (32 doubles), the count.
 #define RATE_WG 1024
 // ST: the table stride -- RATE_STRIDE with a point per bit plane (points = numBPS), RATE_PASS_STRIDE with a point per coding pass
@@ -195,6 +202,19 @@ __host__ __device__ inline RateWs rate_ws(void *ws, size_t n) {
     return W;
 }
 size_t rate_allocate_workspace(int njobs) { return (size_t)njobs * (RATE_PASS_STRIDE * 9 + 4) + 256; }
+// workgroup blockIdx.x's frame: its first job and its job count (wave-uniform)
+__device__ __forceinline__ RateFrame rate_frame(const RateFrame *__restrict__ frames, int njobs) {
+    return frames ? frames[blockIdx.x] : RateFrame{0, njobs};
+}
+// the workspace of all njobs jobs -> the slice of the frame that starts at job `first`
+template <int ST>
+__device__ __forceinline__ RateWs rate_ws_frame(void *ws, int njobs, int first) {
+    RateWs W = rate_ws<ST>(ws, (size_t)njobs);
+    W.slope += (size_t)first * ST;
+    W.plane += (size_t)first * ST;
+    W.count += first;
+    return W;
+}
 // the last point of a block's table
 template <int ST>
 __device__ __forceinline__ int rate_points(const uint8_t *__restrict__ numbps, int j) {
@@ -290,10 +310,16 @@ __device__ __forceinline__ uint64_t rate_search(int njobs, const uint32_t *__res
 template <int ST = RATE_STRIDE>
 __global__ __launch_bounds__(RATE_WG) void rate_allocate_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
                                                                 const uint8_t *__restrict__ numbps, const double *__restrict__ weights, uint64_t budget,
-                                                                void *__restrict__ ws, uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen) {
+                                                                void *__restrict__ ws, uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen,
+                                                                const RateFrame *__restrict__ frames, const uint64_t *__restrict__ frame_budgets) {
     __shared__ uint64_t sh[RATE_WG / 64];
     const int tid = threadIdx.x;
-    const RateWs W = rate_ws<ST>(ws, (size_t)njobs);
+    const RateFrame fr = rate_frame(frames, njobs);
+    const RateWs W = rate_ws_frame<ST>(ws, njobs, fr.first);
+    if (frame_budgets) budget = frame_budgets[blockIdx.x];                   // (the _frames calls: a budget per frame)
+    rate += (size_t)fr.first * ST; dist += (size_t)fr.first * ST; numbps += fr.first; weights += fr.first; kept += fr.first;
+    chosen += blockIdx.x;
+    njobs = fr.count;
     // nothing to cut?
     uint64_t part = 0;
     for (int j = tid; j < njobs; j += RATE_WG) part += rate[(size_t)j * ST + rate_points<ST>(numbps, j)];
@@ -315,25 +341,31 @@ struct RateBudgets { uint64_t b[32]; };
 __global__ __launch_bounds__(RATE_WG) void rate_allocate_layers_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
                                                                        const uint8_t *__restrict__ numbps, const double *__restrict__ weights,
                                                                        const RateBudgets budgets, int nlayers, void *__restrict__ ws,
-                                                                       uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen) {
+                                                                       uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen,
+                                                                       const RateFrame *__restrict__ frames) {
     __shared__ uint64_t sh[RATE_WG / 64];
     const int tid = threadIdx.x;
-    const RateWs W = rate_ws(ws, (size_t)njobs);
+    const RateFrame fr = rate_frame(frames, njobs);
+    const RateWs W = rate_ws_frame<RATE_STRIDE>(ws, njobs, fr.first);
+    const size_t nall = (size_t)njobs, nfr = gridDim.x;  // kept [l][all jobs], chosen [l][frames]
+    rate += (size_t)fr.first * RATE_STRIDE; dist += (size_t)fr.first * RATE_STRIDE; numbps += fr.first; weights += fr.first; kept += fr.first;
+    chosen += blockIdx.x;
+    njobs = fr.count;
     uint64_t part = 0;
     for (int j = tid; j < njobs; j += RATE_WG) part += rate[(size_t)j * RATE_STRIDE + min((int)numbps[j], RATE_STRIDE - 1)];
     const uint64_t total = wg_sum(part, sh);
     bool have_hulls = false;                             // (uniform over the workgroup: budgets and total are)
     for (int l = 0; l < nlayers; l++) {
         const uint64_t budget = budgets.b[l];
-        uint8_t *kl = kept + (size_t)l * njobs;
+        uint8_t *kl = kept + (size_t)l * nall;
         if (total <= budget) {
             for (int j = tid; j < njobs; j += RATE_WG) kl[j] = (uint8_t)min((int)numbps[j], RATE_STRIDE - 1);
-            if (tid == 0) chosen[l] = total;
+            if (tid == 0) chosen[(size_t)l * nfr] = total;
             continue;
         }
         if (!have_hulls) { rate_hulls(njobs, rate, dist, numbps, weights, W); have_hulls = true; }
         const uint64_t b = rate_search(njobs, rate, W, budget, sh, kl);
-        if (tid == 0) chosen[l] = b;
+        if (tid == 0) chosen[(size_t)l * nfr] = b;
     }
 }
 
@@ -383,14 +415,19 @@ struct RateTargets { double t[32]; };
 __global__ __launch_bounds__(RATE_WG) void rate_allocate_quality_passes_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
                                                                                const uint8_t *__restrict__ numbps, const double *__restrict__ weights,
                                                                                double target, void *__restrict__ ws, uint8_t *__restrict__ kept,
-                                                                               uint64_t *__restrict__ chosen, double *__restrict__ achieved) {
+                                                                               uint64_t *__restrict__ chosen, double *__restrict__ achieved,
+                                                                               const RateFrame *__restrict__ frames, const double *__restrict__ frame_targets) {
     __shared__ uint64_t sh[RATE_WG / 64];
     __shared__ double shf[RATE_WG / 64];
-    const RateWs W = rate_ws<RATE_PASS_STRIDE>(ws, (size_t)njobs);
+    const RateFrame fr = rate_frame(frames, njobs);
+    const RateWs W = rate_ws_frame<RATE_PASS_STRIDE>(ws, njobs, fr.first);
+    if (frame_targets) target = frame_targets[blockIdx.x];                   // (the _frames calls: a target per frame)
+    rate += (size_t)fr.first * RATE_PASS_STRIDE; dist += (size_t)fr.first * RATE_PASS_STRIDE; numbps += fr.first; weights += fr.first; kept += fr.first;
+    njobs = fr.count;
     rate_hulls<RATE_PASS_STRIDE>(njobs, rate, dist, numbps, weights, W);
     uint64_t b = 0;
     const double s = quality_search<RATE_PASS_STRIDE>(njobs, rate, dist, weights, W, target, sh, shf, kept, &b);
-    if (threadIdx.x == 0) { *chosen = b; *achieved = s; }
+    if (threadIdx.x == 0) { chosen[blockIdx.x] = b; achieved[blockIdx.x] = s; }
 }
 
 // One workgroup, a sibling of rate_allocate_layers_kernel: layer l is the search for targets.t[l] -- kept[l * njobs + j], chosen[l] (body bytes),
@@ -398,24 +435,55 @@ __global__ __launch_bounds__(RATE_WG) void rate_allocate_quality_passes_kernel(i
 __global__ __launch_bounds__(RATE_WG) void rate_allocate_quality_kernel(int njobs, const uint32_t *__restrict__ rate, const uint64_t *__restrict__ dist,
                                                                         const uint8_t *__restrict__ numbps, const double *__restrict__ weights,
                                                                         const RateTargets targets, int nlayers, void *__restrict__ ws,
-                                                                        uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen, double *__restrict__ achieved) {
+                                                                        uint8_t *__restrict__ kept, uint64_t *__restrict__ chosen, double *__restrict__ achieved,
+                                                                        const RateFrame *__restrict__ frames, const double *__restrict__ frame_targets) {
     __shared__ uint64_t sh[RATE_WG / 64];
     __shared__ double shf[RATE_WG / 64];
-    const RateWs W = rate_ws(ws, (size_t)njobs);
+    const RateFrame fr = rate_frame(frames, njobs);
+    const RateWs W = rate_ws_frame<RATE_STRIDE>(ws, njobs, fr.first);
+    const size_t nall = (size_t)njobs, nfr = gridDim.x;  // kept [l][all jobs], chosen / achieved [l][frames]
+    rate += (size_t)fr.first * RATE_STRIDE; dist += (size_t)fr.first * RATE_STRIDE; numbps += fr.first; weights += fr.first; kept += fr.first;
+    chosen += blockIdx.x; achieved += blockIdx.x;
+    njobs = fr.count;
     rate_hulls(njobs, rate, dist, numbps, weights, W);
     for (int l = 0; l < nlayers; l++) {
         uint64_t b = 0;
-        const double s = quality_search(njobs, rate, dist, weights, W, targets.t[l], sh, shf, kept + (size_t)l * njobs, &b);
-        if (threadIdx.x == 0) { chosen[l] = b; achieved[l] = s; }
+        const double target = frame_targets ? frame_targets[blockIdx.x] : targets.t[l];      // (the _frames calls: one layer, a target per frame)
+        const double s = quality_search(njobs, rate, dist, weights, W, target, sh, shf, kept + (size_t)l * nall, &b);
+        if (threadIdx.x == 0) { chosen[(size_t)l * nfr] = b; achieved[(size_t)l * nfr] = s; }
     }
 }
 
-// targets: nlayers <= 32 values on the host (a kernel argument); kept: nlayers x njobs bytes; chosen: nlayers x uint64; achieved: nlayers x double
+// One value per frame of a batch (the _frames calls) into the plan's table: the values travel BY VALUE, so a captured call replays with the
+// values it was captured with and the host array may go as soon as the call returns; RATE_FRAME_CHUNK of them per launch, any number of frames.
+#define RATE_FRAME_CHUNK 128
+struct RateFrameValues { uint64_t v[RATE_FRAME_CHUNK]; };
+__global__ __launch_bounds__(RATE_FRAME_CHUNK) void rate_frame_values_kernel(const RateFrameValues vals, int count, uint64_t *__restrict__ table) {
+    if ((int)threadIdx.x < count) table[threadIdx.x] = vals.v[threadIdx.x];
+}
+// values: nframes 64-bit patterns on the host (budgets, or the bits of float64 targets); table: nframes words on the device
+hipError_t launch_rate_frame_values(hipStream_t s, const uint64_t *values, int nframes, uint64_t *table) {
+    for (int at = 0; at < nframes; at += RATE_FRAME_CHUNK) {
+        RateFrameValues V{};
+        const int count = std::min(RATE_FRAME_CHUNK, nframes - at);
+        for (int i = 0; i < count; i++) V.v[i] = values[at + i];
+        hipLaunchKernelGGL(rate_frame_values_kernel, dim3(1), dim3(RATE_FRAME_CHUNK), 0, s, V, count, table + at);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// targets: nlayers <= 32 values on the host (a kernel argument); kept: nlayers x njobs bytes; chosen: nlayers x nframes uint64; achieved: nlayers x
+// nframes double.  frames (device, or null with nframes = 1): the job range of every frame; frame_targets (device, or null): nlayers = 1, frame
+// f's target in the place of targets[0]
 hipError_t launch_rate_allocate_quality(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
-                                        const double *targets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved) {
+                                        const double *targets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved, int nframes,
+                                        const RateFrame *frames, const double *frame_targets) {
     RateTargets T{};
-    for (int l = 0; l < nlayers && l < 32; l++) T.t[l] = targets[l];
-    hipLaunchKernelGGL(rate_allocate_quality_kernel, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, T, std::min(nlayers, 32), ws, kept, chosen, achieved);
+    for (int l = 0; l < nlayers && l < 32; l++) T.t[l] = targets ? targets[l] : 0.0;
+    hipLaunchKernelGGL(rate_allocate_quality_kernel, dim3(frames ? nframes : 1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, T, std::min(nlayers, 32), ws, kept,
+                       chosen, achieved, frames, frame_targets);
     return hipGetLastError();
 }
 
@@ -432,9 +500,12 @@ hipError_t launch_rate_distortion_roi(hipStream_t s, const BlockJob *jobs, int n
     return hipGetLastError();
 }
 
+// frames (device, or null with nframes = 1): the job range of every frame of a batch, one workgroup each, chosen: nframes words; frame_budgets
+// (device, or null): frame f's budget in the place of `budget`
 hipError_t launch_rate_allocate(hipStream_t s, int njobs, const uint32_t *rate,const uint64_t *dist, const uint8_t *numbps, const double *weights,
-                                uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen) {
-    hipLaunchKernelGGL(rate_allocate_kernel<RATE_STRIDE>, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, budget, ws, kept, chosen);
+                                uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen, int nframes, const RateFrame *frames, const uint64_t *frame_budgets) {
+    hipLaunchKernelGGL(rate_allocate_kernel<RATE_STRIDE>, dim3(frames ? nframes : 1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, budget, ws, kept, chosen,
+                       frames, frame_budgets);
     return hipGetLastError();
 }
 
@@ -446,22 +517,26 @@ hipError_t launch_rate_distortion_passes(hipStream_t s, const BlockJob *jobs, in
     return hipGetLastError();
 }
 hipError_t launch_rate_allocate_passes(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
-                                       uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen) {
-    hipLaunchKernelGGL(rate_allocate_kernel<RATE_PASS_STRIDE>, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, budget, ws, kept, chosen);
+                                       uint64_t budget, void *ws, uint8_t *kept, uint64_t *chosen, int nframes, const RateFrame *frames,
+                                       const uint64_t *frame_budgets) {
+    hipLaunchKernelGGL(rate_allocate_kernel<RATE_PASS_STRIDE>, dim3(frames ? nframes : 1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, budget, ws, kept, chosen,
+                       frames, frame_budgets);
     return hipGetLastError();
 }
 hipError_t launch_rate_allocate_quality_passes(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
-                                               double target, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved) {
-    hipLaunchKernelGGL(rate_allocate_quality_passes_kernel, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, target, ws, kept, chosen, achieved);
+                                               double target, void *ws, uint8_t *kept, uint64_t *chosen, double *achieved, int nframes,
+                                               const RateFrame *frames, const double *frame_targets) {
+    hipLaunchKernelGGL(rate_allocate_quality_passes_kernel, dim3(frames ? nframes : 1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, target, ws, kept, chosen,
+                       achieved, frames, frame_targets);
     return hipGetLastError();
 }
 
-// budgets: nlayers <= 32 values on the host (a kernel argument); kept: nlayers x njobs bytes; chosen: nlayers x uint64
+// budgets: nlayers <= 32 values on the host (a kernel argument); kept: nlayers x njobs bytes; chosen: nlayers x nframes uint64
 hipError_t launch_rate_allocate_layers(hipStream_t s, int njobs, const uint32_t *rate, const uint64_t *dist, const uint8_t *numbps, const double *weights,
-                                       const uint64_t *budgets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen) {
+                                       const uint64_t *budgets, int nlayers, void *ws, uint8_t *kept, uint64_t *chosen, int nframes, const RateFrame *frames) {
     RateBudgets B{};
     for (int l = 0; l < nlayers && l < 32; l++) B.b[l] = budgets[l];
-    hipLaunchKernelGGL(rate_allocate_layers_kernel, dim3(1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, B, nlayers, ws, kept, chosen);
+    hipLaunchKernelGGL(rate_allocate_layers_kernel, dim3(frames ? nframes : 1), dim3(RATE_WG), 0, s, njobs, rate, dist, numbps, weights, B, nlayers, ws, kept, chosen, frames);
     return hipGetLastError();
 }
 

@@ -80,6 +80,8 @@ SYMBOLS = [
     "j2k_plan_encode_blocks_passes", "j2k_plan_rate_allocate_passes", "j2k_plan_rate_allocate_quality_passes", "j2k_plan_encode_tile_parts_kept_passes",
     "j2k_plan_decode_tile_parts_pfloors", "j2k_plan_decode_blocks_pfloors", "j2k_plan_encode_frame_pixels_passes", "j2k_plan_decode_frame_pixels_passes",
     "j2k_encode_pixels_host_passes", "j2k_decode_pixels_host_passes",
+    "j2k_plan_set_rate_per_frame", "j2k_plan_rate_frames", "j2k_plan_rate_allocate_frames", "j2k_plan_rate_allocate_quality_frames",
+    "j2k_plan_encode_frame_pixels_rate_frames", "j2k_encode_pixels_host_rate_frames",
     "j2k_pipe_create", "j2k_pipe_destroy", "j2k_pipe_submit_encode", "j2k_pipe_submit_decode", "j2k_pipe_wait", "j2k_pipe_poll", "j2k_pipe_drain",
     "j2k_host_alloc", "j2k_host_free",
     "j2k_plan_pack_bound", "j2k_plan_pack_stream", "j2k_plan_unpack_stream", "j2k_plan_unpack_streams",
@@ -191,6 +193,11 @@ def lib():
             "j2k_plan_decode_frame_pixels_passes": (I, [V, V, S, V, I, I, I, I, C.POINTER(Rect), V, S]),
             "j2k_encode_pixels_host_passes": (I, [V, I, V, S, I, I, C.c_int64, DP, V, S, C.POINTER(S), V, V, V, V]),
             "j2k_decode_pixels_host_passes": (I, [V, V, S, I, I, I, I, C.POINTER(Rect), V, S]),
+            "j2k_plan_set_rate_per_frame": (I, [V, I]), "j2k_plan_rate_frames": (I, [V, C.POINTER(C.c_int32)]),
+            "j2k_plan_rate_allocate_frames": (I, [V, V, V, V, I64P, I, I, V, V]),
+            "j2k_plan_rate_allocate_quality_frames": (I, [V, V, V, V, DP, I, I, V, V, V]),
+            "j2k_plan_encode_frame_pixels_rate_frames": (I, [V, I, V, S, I, I, I64P, DP, I, I, V, S, V, V]),
+            "j2k_encode_pixels_host_rate_frames": (I, [V, I, V, S, I, I, I64P, DP, I, I, V, S, C.POINTER(S), V, V, V, V]),
             "j2k_pipe_create": (I, [V, I, C.POINTER(V)]), "j2k_pipe_destroy": (None, [V]),
             "j2k_pipe_submit_encode": (I, [V, I, V, S, I, I, V, S, V, V, V, C.POINTER(C.c_uint64)]),
             "j2k_pipe_submit_decode": (I, [V, V, S, I, I, V, S, C.POINTER(C.c_uint64)]),

@@ -45,7 +45,8 @@ def _stage(fn):
 class FramePlan:
     def __init__(self, width, height, ncomp, precision=8, lossless=True, quality=0, num_resolutions=6,
                  cb=(64, 64), tile=(0, 0), coder=_lib.CODER_MQ, is_signed=False, tile_first=0, tile_count=0,
-                 ctx=None, track_streams=True, frame_rows=0, closed_loop=False, dequantize=False, mallat=False, raw_magref=False):
+                 ctx=None, track_streams=True, frame_rows=0, closed_loop=False, dequantize=False, mallat=False, raw_magref=False,
+                 rate_per_frame=False):
         self.ctx = ctx or default_context()
         self.track_streams = bool(track_streams)
         self._ext_stream = None
@@ -73,6 +74,8 @@ class FramePlan:
             self.set_dequantize(True)
         if raw_magref:
             self.set_raw_magref(True)
+        if rate_per_frame:
+            self.set_rate_per_frame(True)
 
     def close(self):
         if getattr(self, "h", None):
@@ -268,21 +271,30 @@ class FramePlan:
         return slots, lens, numbps
 
     @_stage
-    def rate_allocate(self, rate, dist, numbps, max_body_bytes, kept=None, chosen=None, pass_cuts=False):
-        """pass_cuts=True: rate / dist are the 96-entry tables of encode_blocks(pass_cuts=True), kept[j] is a pass count (j2k_plan_rate_allocate_passes).
+    def rate_allocate(self, rate, dist, numbps, max_body_bytes=None, kept=None, chosen=None, pass_cuts=False, frame_bytes=None):
+        """frame_bytes=[one budget per frame] in the place of max_body_bytes (batch plans with set_rate_per_frame; a plan of one frame takes [N]):
+        frame f is cut under frame_bytes[f] (j2k_plan_rate_allocate_frames).  chosen: int64 [rate_frames], the body bytes of every frame's choice.
+        pass_cuts=True: rate / dist are the 96-entry tables of encode_blocks(pass_cuts=True), kept[j] is a pass count (j2k_plan_rate_allocate_passes).
         the planes to keep of every block so that the code-block BODY bytes are at most max_body_bytes (packet and tile-part headers
         come on top): returns (kept uint8 [blocks], chosen int64 [1] = the body bytes of that choice)  (j2k_plan_rate_allocate)"""
         t = _torch()
         n = int(self.info.blocks)
         kept = kept if kept is not None else self.empty(n, t.uint8)
-        chosen = chosen if chosen is not None else t.zeros(1, dtype=t.int64, device=self.device)
+        if (max_body_bytes is None) == (frame_bytes is None):
+            raise ValueError("rate_allocate: one of max_body_bytes and frame_bytes=")
+        chosen = self._frame_table("rate_allocate", t, chosen, t.int64, 1)
+        if frame_bytes is not None:
+            arr, F = self._layer_bytes(self._frame_values("rate_allocate: frame_bytes", frame_bytes, int))
+            self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_frames(self.h, self._p(rate), self._p(dist), self._p(numbps), arr, F, int(bool(pass_cuts)),
+                                                                    self._p(kept), self._p(chosen)))
+            return kept, chosen[:F]
         if pass_cuts:
             self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_passes(self.h, self._p(rate), self._p(dist), self._p(numbps), C.c_int64(int(max_body_bytes)),
                                                                     self._p(kept), self._p(chosen)))
-            return kept, chosen
+            return kept, chosen[:self.rate_frames]
         self.ctx.check(self.ctx.L.j2k_plan_rate_allocate(self.h, self._p(rate), self._p(dist), self._p(numbps), C.c_int64(int(max_body_bytes)),
                                                          self._p(kept), self._p(chosen)))
-        return kept, chosen
+        return kept, chosen[:self.rate_frames]
 
     def _layer_bytes(self, layer_bytes):
         b = [int(x) for x in layer_bytes]
@@ -290,19 +302,21 @@ class FramePlan:
 
     @_stage
     def rate_allocate_layers(self, rate, dist, numbps, layer_bytes, kept=None, chosen=None):
-        """rate_allocate for L cumulative budgets in one launch: (kept uint8 [L, blocks], chosen int64 [L])  (j2k_plan_rate_allocate_layers)"""
+        """rate_allocate for L cumulative budgets in one launch: (kept uint8 [L, blocks], chosen int64 [L]; on a batch plan with set_rate_per_frame
+        every frame under the same ladder, chosen [L, rate_frames])  (j2k_plan_rate_allocate_layers)"""
         t = _torch()
         n = int(self.info.blocks)
         arr, L = self._layer_bytes(layer_bytes)
         kept = kept if kept is not None else self.empty(max(L, 1) * n, t.uint8)
-        chosen = chosen if chosen is not None else t.zeros(max(L, 1), dtype=t.int64, device=self.device)
+        chosen = self._frame_table("rate_allocate_layers", t, chosen, t.int64, L)
         self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_layers(self.h, self._p(rate), self._p(dist), self._p(numbps), arr, L, self._p(kept), self._p(chosen)))
-        return kept[:L * n].view(L, n), chosen[:L]
+        return kept[:L * n].view(L, n), self._frame_shape(chosen, L)
 
     # ---- quality targets: the dual of the byte budgets (j2k_*_quality; tests/quality_cases.py is the definition) -------
     def psnr_distortion(self, db):
         """the weighted-distortion target T of a PSNR in dB: width * height * ncomp * peak^2 * q^2 / 10^(dB / 10), peak = 2^precision - 1,
-        q = the plan's quality on a lossy plan, 1 on a lossless one (j2k_plan_psnr_distortion; host only)"""
+        q = the plan's quality on a lossy plan, 1 on a lossless one; on a batch plan with set_rate_per_frame the target of ONE frame
+        (frame_rows in the place of height)  (j2k_plan_psnr_distortion; host only)"""
         T = C.c_double(0.0)
         self.ctx.check(self.ctx.L.j2k_plan_psnr_distortion(self.h, C.c_double(float(db)), C.byref(T)))
         return float(T.value)
@@ -331,27 +345,36 @@ class FramePlan:
         return [float(t) for t in layer_distortion], True
 
     @_stage
-    def rate_allocate_quality(self, rate, dist, numbps, targets, kept=None, chosen=None, achieved=None, pass_cuts=False):
-        """pass_cuts=True: ONE target on the 96-entry tables of encode_blocks(pass_cuts=True), kept[0, j] is a pass count
+    def rate_allocate_quality(self, rate, dist, numbps, targets=None, kept=None, chosen=None, achieved=None, pass_cuts=False, frame_targets=None):
+        """frame_targets=[one target per frame] in the place of targets (batch plans with set_rate_per_frame; one layer): frame f is cut under
+        frame_targets[f] (j2k_plan_rate_allocate_quality_frames).  On such a plan chosen and achieved are [L, rate_frames].
+        pass_cuts=True: ONE target on the 96-entry tables of encode_blocks(pass_cuts=True), kept[0, j] is a pass count
         (j2k_plan_rate_allocate_quality_passes).
         the planes to keep of every block so that the weighted distortion sum_j w_j * dist[j, kept_j] (float64, in the fixed order of
         tests/quality_cases.py) is at most targets[l], in as few body bytes as the hulls allow; targets fall (or stay) layer by layer:
         (kept uint8 [L, blocks], chosen int64 [L] = body bytes, achieved float64 [L] = that sum)  (j2k_plan_rate_allocate_quality)"""
         t = _torch()
         n = int(self.info.blocks)
-        arr, L = self._targets(targets)
+        if (targets is None) == (frame_targets is None):
+            raise ValueError("rate_allocate_quality: one of targets and frame_targets=")
+        arr, L = self._targets(targets) if targets is not None else (None, 1)
         kept = kept if kept is not None else self.empty(max(L, 1) * n, t.uint8)
-        chosen = chosen if chosen is not None else t.zeros(max(L, 1), dtype=t.int64, device=self.device)
-        achieved = achieved if achieved is not None else t.zeros(max(L, 1), dtype=t.float64, device=self.device)
+        chosen = self._frame_table("rate_allocate_quality", t, chosen, t.int64, L)
+        achieved = self._frame_table("rate_allocate_quality", t, achieved, t.float64, L)
+        if frame_targets is not None:
+            arr, F = self._targets(self._frame_values("rate_allocate_quality: frame_targets", frame_targets))
+            self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_quality_frames(self.h, self._p(rate), self._p(dist), self._p(numbps), arr, F, int(bool(pass_cuts)),
+                                                                            self._p(kept), self._p(chosen), self._p(achieved)))
+            return kept[:n].view(1, n), self._frame_shape(chosen, 1), self._frame_shape(achieved, 1)
         if pass_cuts:
             if L != 1:
                 raise ValueError("rate_allocate_quality: pass_cuts takes one target (layers with pass cuts: not built)")
             self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_quality_passes(self.h, self._p(rate), self._p(dist), self._p(numbps), C.c_double(float(arr[0])),
                                                                             self._p(kept), self._p(chosen), self._p(achieved)))
-            return kept[:n].view(1, n), chosen[:1], achieved[:1]
+            return kept[:n].view(1, n), self._frame_shape(chosen, 1), self._frame_shape(achieved, 1)
         self.ctx.check(self.ctx.L.j2k_plan_rate_allocate_quality(self.h, self._p(rate), self._p(dist), self._p(numbps), arr, L, self._p(kept), self._p(chosen),
                                                                  self._p(achieved)))
-        return kept[:L * n].view(L, n), chosen[:L], achieved[:L]
+        return kept[:L * n].view(L, n), self._frame_shape(chosen, L), self._frame_shape(achieved, L)
 
     def frame_bound_layers(self, nlayers):
         return int(self.ctx.L.j2k_plan_frame_bound_layers(self.h, int(nlayers)))
@@ -395,6 +418,48 @@ class FramePlan:
     @property
     def raw_magref(self):
         return bool(self.ctx.L.j2k_plan_get_raw_magref(self.h))
+
+    # ---- batch plans: a budget or a target per frame (j2k_plan_set_rate_per_frame; tests/frame_rate_cases.py is the definition) -------
+    def set_rate_per_frame(self, on=True):
+        """batch plans (frame_rows): every rate, quality, layer and pass call -- which refuse a batch plan without this -- accepts the plan and
+        gives FRAME f THE CUTS IT WOULD GET ALONE: a scalar budget, target or ladder applies to every frame separately.  kept keeps its shape;
+        chosen and achieved gain a frame axis: [F] for the one-layer calls, [L, F] for the layered ones (F = rate_frames; with F = 1 the shapes
+        and every byte are as without the setting).  psnr_distortion (and so min_psnr= / layer_psnr=) is the target of ONE frame.  frame_bytes= /
+        frame_psnr= / frame_distortion= of the encode calls and frame_bytes= / frame_targets= of the allocation calls give every frame its own
+        value.  roi= on such a plan with F > 1 and area= on any batch raise J2K_ERR_UNSUPPORTED; the setter refuses a shard of a batch
+        (j2k_plan_set_rate_per_frame)."""
+        self.ctx.check(self.ctx.L.j2k_plan_set_rate_per_frame(self.h, int(on)))
+
+    @property
+    def rate_frames(self):
+        """F: the frames a rate call allocates separately -- height / frame_rows with set_rate_per_frame on, else 1 (j2k_plan_rate_frames)"""
+        f = C.c_int32(0)
+        self.ctx.check(self.ctx.L.j2k_plan_rate_frames(self.h, C.byref(f)))
+        return int(f.value)
+
+    def _frame_table(self, who, t, given, dtype, layers):
+        """chosen / achieved of an allocation call: `layers` x rate_frames entries (a caller's tensor that is too small: ValueError)"""
+        need = max(int(layers), 1) * self.rate_frames
+        if given is None:
+            return t.zeros(need, dtype=dtype, device=self.device)
+        if int(given.numel()) < need:
+            raise ValueError("%s: a tensor of %d entries for %d layer(s) x %d frame(s)" % (who, int(given.numel()), max(int(layers), 1), self.rate_frames))
+        return given
+
+    def _frame_shape(self, tab, L):
+        """[L x F] entries -> [L] on a plan of one frame (the layout it has always had), else [L, F]"""
+        F = self.rate_frames
+        return tab[:L] if F == 1 else tab[:L * F].view(L, F)
+
+    def _frame_values(self, who, values, kind=float):
+        """one value per frame (a sequence of rate_frames entries; anything else: ValueError)"""
+        try:
+            v = [kind(x) for x in values]
+        except TypeError:
+            raise ValueError("%s: a sequence with one entry per frame" % who)
+        if len(v) != self.rate_frames:
+            raise ValueError("%s: %d entries for the plan's %d frame(s) (rate_frames)" % (who, len(v), self.rate_frames))
+        return v
 
     @_stage
     def forward_pixels(self, fmt, pix, coeff=None):
@@ -657,6 +722,27 @@ class FramePlan:
         T = self.psnr_distortion(min_psnr) if min_psnr is not None else float(max_distortion)
         return C.c_int64(0), C.byref(C.c_double(T))
 
+    def _frame_vector_args(self, who, frame_bytes, frame_psnr, frame_distortion, others):
+        """frame_bytes= / frame_psnr= / frame_distortion= of an encode call -> None without one, else (int64 array or None, float64 array or None, F);
+        `others`: the call's remaining cut arguments by name -- one of them beside a per-frame one is a ValueError"""
+        given = [k for k, v in (("frame_bytes", frame_bytes), ("frame_psnr", frame_psnr), ("frame_distortion", frame_distortion)) if v is not None]
+        if not given:
+            return None
+        if len(given) > 1:
+            raise ValueError("%s: %s together -- one per-frame argument" % (who, " and ".join(given)))
+        for k, v in others:
+            if v is not None:
+                raise ValueError("%s: %s= together with %s= -- a value per frame stands alone" % (who, given[0], k))
+        if frame_bytes is not None:
+            arr, F = self._layer_bytes(self._frame_values("%s: frame_bytes" % who, frame_bytes, int))
+            return arr, None, F
+        if frame_psnr is not None:
+            vals = [self.psnr_distortion(d) for d in self._frame_values("%s: frame_psnr" % who, frame_psnr)]
+        else:
+            vals = self._frame_values("%s: frame_distortion" % who, frame_distortion)
+        arr, F = self._targets(vals)
+        return None, arr, F
+
     @staticmethod
     def _encode_args(form, arr, L, rect, roi_gain):
         """what an encode entry point takes between eph and out"""
@@ -665,8 +751,13 @@ class FramePlan:
 
     @_stage
     def encode_frame_pixels(self, fmt, pix, sop=False, eph=False, out=None, tile_offs=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16,
-                            min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None, pass_cuts=False):
-        """pass_cuts=True with one of max_body_bytes, min_psnr, max_distortion (anything else beside it: ValueError): the same stream with every block
+                            min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None, pass_cuts=False, frame_bytes=None, frame_psnr=None,
+                            frame_distortion=None):
+        """Batch plans with set_rate_per_frame: every budget / target below applies to each frame separately, achieved is [rate_frames] (one layer)
+        or [L, rate_frames].  frame_bytes=[...] / frame_psnr=[...] / frame_distortion=[...] (one of them, nothing else that cuts beside it:
+        ValueError; rate_frames entries; with or without pass_cuts): frame f under ITS value, the kept-prefix stream -> (out, tile_offs) and, with
+        a target, achieved [rate_frames]; on a plan of one frame frame_bytes=[N] is max_body_bytes=N (j2k_plan_encode_frame_pixels_rate_frames).
+        pass_cuts=True with one of max_body_bytes, min_psnr, max_distortion (anything else beside it: ValueError): the same stream with every block
         cut at a coding-pass end, not only at a bit-plane end -- about three times as many steps per block (j2k_plan_encode_frame_pixels_passes);
         returns as without it; decode with pass_cuts=True (truncated=True reads the whole planes of it).
         pixels (a Go Pix layout, device uint8 [H, stride]) -> tile-parts: (out uint8, tile_offs int64[tiles + 1]).  max_body_bytes (closed-loop
@@ -684,11 +775,24 @@ class FramePlan:
         layered stream.  achieved: the estimate of every layer's choice, <= its target.  An ESTIMATE in the coefficient domain:
         measure the decoded frame with pixels.psnr.  roi= / roi_gain= weigh the rectangle as with a budget (j2k_plan_encode_frame_pixels_quality)"""
         t = _torch()
+        fv = self._frame_vector_args("encode_frame_pixels", frame_bytes, frame_psnr, frame_distortion,
+                                     (("max_body_bytes", max_body_bytes), ("layer_bytes", layer_bytes), ("roi", roi), ("min_psnr", min_psnr), ("max_distortion", max_distortion),
+                                      ("layer_psnr", layer_psnr), ("layer_distortion", layer_distortion)))
+        if fv is not None:
+            fb, ft, F = fv
+            out = out if out is not None else self.empty(self.frame_bound(), t.uint8)
+            tile_offs = tile_offs if tile_offs is not None else self.empty(int(self.info.tiles) + 1, t.int64)[:int(self.info.tiles) + 1]
+            achieved = t.zeros(F, dtype=t.float64, device=self.device) if ft is not None else None
+            self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_rate_frames(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
+                                                                               fb, ft, F, int(bool(pass_cuts)), self._p(out), C.c_size_t(int(out.numel())),
+                                                                               self._p(tile_offs), self._p(achieved) if achieved is not None else None))
+            return (out, tile_offs) + ((achieved,) if achieved is not None else ())
+        F = self.rate_frames
         if pass_cuts:
             budget, target = self._pass_cut_args("encode_frame_pixels", max_body_bytes, layer_bytes, roi, min_psnr, max_distortion, layer_psnr, layer_distortion)
             out = out if out is not None else self.empty(self.frame_bound(), t.uint8)
             tile_offs = tile_offs if tile_offs is not None else self.empty(int(self.info.tiles) + 1, t.int64)[:int(self.info.tiles) + 1]
-            achieved = t.zeros(1, dtype=t.float64, device=self.device) if target is not None else None
+            achieved = t.zeros(F, dtype=t.float64, device=self.device) if target is not None else None
             self.ctx.check(self.ctx.L.j2k_plan_encode_frame_pixels_passes(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
                                                                           budget, target, self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs),
                                                                           self._p(achieved) if achieved is not None else None))
@@ -698,7 +802,7 @@ class FramePlan:
         out = out if out is not None else self.empty((self.frame_bound_layers(L) or 64) if layered else self.frame_bound(), t.uint8)
         tile_offs = tile_offs if tile_offs is not None else self.empty(nt + 1, t.int64)[:nt + 1]
         layer_offs = self.empty(nt * max(L, 1), t.int64)[:nt * max(L, 1)] if layered else None
-        achieved = t.zeros(max(L, 1), dtype=t.float64, device=self.device) if form == "_quality" else None
+        achieved = t.zeros(max(L, 1) * F, dtype=t.float64, device=self.device) if form == "_quality" else None
         tail = [self._p(out), C.c_size_t(int(out.numel())), self._p(tile_offs)]
         if form in ("_layers", "_roi", "_quality"):
             tail.append(self._p(layer_offs) if layered else None)
@@ -706,7 +810,9 @@ class FramePlan:
             tail.append(self._p(achieved))
         self.ctx.check(getattr(self.ctx.L, "j2k_plan_encode_frame_pixels" + form)(self.h, int(fmt), self._p(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)),
                                                                                  *(self._encode_args(form, arr, L, rect, roi_gain) + tail)))
-        return (out, tile_offs) + ((layer_offs,) if layered else ()) + ((achieved[:L],) if form == "_quality" else ())
+        if form == "_quality":          # [L] on a plan of one frame as ever; a batch: [F] for the one target, [L, F] for a ladder
+            achieved = achieved[:L] if F == 1 else (achieved[:L * F].view(L, F) if layered else achieved[:F])
+        return (out, tile_offs) + ((layer_offs,) if layered else ()) + ((achieved,) if form == "_quality" else ())
 
     def _decode_form(self, reduce, skip_planes, truncated, layers, area):
         """the decode a call asks for -> (entry-point suffix, what it takes between eph and pix); `area`: a _lib.Rect or None"""
@@ -750,8 +856,11 @@ class FramePlan:
 
     # ---- host memory in, host memory out: the one-call forms (j2k_encode_pixels_host / j2k_decode_pixels_host) -------------------
     def encode_pixels_host(self, fmt, pix, sop=False, eph=False, cap=None, max_body_bytes=None, layer_bytes=None, roi=None, roi_gain=16,
-                           min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None, pass_cuts=False):
-        """pass_cuts=True: as encode_frame_pixels (j2k_encode_pixels_host_passes); the dict holds achieved float64 [1] when a target was given.
+                           min_psnr=None, max_distortion=None, layer_psnr=None, layer_distortion=None, pass_cuts=False, frame_bytes=None, frame_psnr=None,
+                           frame_distortion=None):
+        """Batch plans with set_rate_per_frame, frame_bytes= / frame_psnr= / frame_distortion=: as encode_frame_pixels (j2k_encode_pixels_host_rate_frames);
+        achieved is float64 [rate_frames] for one layer, [L, rate_frames] for a ladder.
+        pass_cuts=True: as encode_frame_pixels (j2k_encode_pixels_host_passes); the dict holds achieved float64 [1] when a target was given.
         pix: numpy uint8 [H, stride] (a Go Pix layout) -> dict(bytes, tile_offs, lens, numbps): every tile as a tile-part.  max_body_bytes: as
         encode_frame_pixels (j2k_encode_pixels_host_rate; lens / numbps are the uncut ones); layer_bytes: as encode_frame_pixels, the dict also
         holds layer_offs uint64 [tiles * L] (j2k_encode_pixels_host_layers); roi, roi_gain with either budget: as encode_frame_pixels
@@ -759,6 +868,29 @@ class FramePlan:
         achieved float64 [L] (j2k_encode_pixels_host_quality)"""
         L = self.ctx.L
         n, nt = int(self.info.blocks), int(self.info.tiles)
+        F = self.rate_frames
+        fv = self._frame_vector_args("encode_pixels_host", frame_bytes, frame_psnr, frame_distortion,
+                                     (("max_body_bytes", max_body_bytes), ("layer_bytes", layer_bytes), ("roi", roi), ("min_psnr", min_psnr), ("max_distortion", max_distortion),
+                                      ("layer_psnr", layer_psnr), ("layer_distortion", layer_distortion)))
+        if fv is not None:
+            fb, ft, F = fv
+            cap = int(cap) if cap is not None else self.frame_bound() + 64
+            pix = np.ascontiguousarray(pix, dtype=np.uint8)
+            out = np.zeros(max(cap, 1), np.uint8)
+            toffs = np.zeros(nt + 1, np.uint64)
+            lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
+            ach = np.zeros(F, np.float64)
+            olen = C.c_size_t(0)
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+            st = L.j2k_encode_pixels_host_rate_frames(self.h, int(fmt), ptr(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)), fb, ft, F,
+                                                      int(bool(pass_cuts)), ptr(out), C.c_size_t(cap), C.byref(olen), ptr(toffs), ptr(lens), ptr(nbps),
+                                                      ptr(ach) if ft is not None else None)
+            self.encoded_len = olen.value
+            self.ctx.check(st)
+            res = dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
+            if ft is not None:
+                res["achieved"] = ach.copy()
+            return res
         if pass_cuts:
             budget, target = self._pass_cut_args("encode_pixels_host", max_body_bytes, layer_bytes, roi, min_psnr, max_distortion, layer_psnr, layer_distortion)
             cap = int(cap) if cap is not None else self.frame_bound() + 64
@@ -766,7 +898,7 @@ class FramePlan:
             out = np.zeros(max(cap, 1), np.uint8)
             toffs = np.zeros(nt + 1, np.uint64)
             lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
-            ach = np.zeros(1, np.float64)
+            ach = np.zeros(F, np.float64)
             olen = C.c_size_t(0)
             ptr = lambda a: a.ctypes.data_as(C.c_void_p)
             st = L.j2k_encode_pixels_host_passes(self.h, int(fmt), ptr(pix), C.c_size_t(int(pix.shape[1])), int(bool(sop)), int(bool(eph)), budget, target,
@@ -788,7 +920,7 @@ class FramePlan:
         out = np.zeros(max(cap, 1), np.uint8)
         toffs = np.zeros(nt + 1, np.uint64); loffs = np.zeros(max(nt * nl, 1), np.uint64)
         lens = np.zeros(max(n, 1), np.uint32); nbps = np.zeros(max(n, 1), np.uint8)
-        ach = np.zeros(max(nl, 1), np.float64)
+        ach = np.zeros(max(nl, 1) * F, np.float64)
         olen = C.c_size_t(0)
         ptr = lambda a: a.ctypes.data_as(C.c_void_p)
         tail = [ptr(out), C.c_size_t(cap), C.byref(olen), ptr(toffs)]
@@ -801,7 +933,7 @@ class FramePlan:
         self.ctx.check(st)
         res = dict(bytes=out[:olen.value].copy(), tile_offs=toffs, lens=lens[:n].copy(), numbps=nbps[:n].copy())
         if form == "_quality":
-            res["achieved"] = ach[:nl].copy()
+            res["achieved"] = ach[:nl].copy() if F == 1 else (ach[:nl * F].reshape(nl, F).copy() if layered else ach[:F].copy())
         if layered:
             res["layer_offs"] = loffs[:nt * nl].copy()
         return res

@@ -1101,6 +1101,51 @@ int j2k_encode_pixels_host_passes(j2k_plan *plan, int format, const void *pix, s
 int j2k_decode_pixels_host_passes(j2k_plan *plan, const uint8_t *cs, size_t len, int sop, int eph, int reduce, int skip_planes,
                                   const j2k_rect *area, void *pix, size_t stride);
 
+/* Rate control on batch plans (j2k_params.frame_rows): a budget or a target PER FRAME.  A batch codes every frame exactly as it would be coded
+ * alone; rate control on it has one meaning: FRAME f GETS THE CUTS IT WOULD GET ALONE UNDER ITS OWN BUDGET.  With F = height / frame_rows frames
+ * and tiles / F tiles per frame, frame f owns the contiguous blocks whose tile is in [f * tiles / F, (f + 1) * tiles / F); the allocation runs the
+ * definitions above (tests/rate_cases.py, layer_cases.py, quality_cases.py, pass_cases.py) on that range alone -- the fixed order of the float64
+ * sum starts again at every frame's first block -- in ONE launch of F workgroups (tests/frame_rate_cases.py is the definition).  The stream
+ * format, the packet writers and every reader are unchanged: they work per tile.
+ *   j2k_plan_set_rate_per_frame        an opt-in plan setting (off by default; the idiom of j2k_plan_set_raw_magref).  OFF: every rate, quality, layer
+ *                                      and pass call refuses a batch plan as ever (J2K_ERR_UNSUPPORTED, "a batch plan (frame_rows): not built").
+ *                                      ON: every one of them accepts it -- the block and allocation stage calls, the kept / layered tile-part
+ *                                      writers, the floors / pfloors / layered readers, the frame encode and decode calls, their host forms,
+ *                                      j2k_tile_parts_keep_layers -- and a scalar budget, target or ladder applies to EVERY FRAME SEPARATELY.
+ *                                      Layouts: d_kept stays [layers][blocks]; d_chosen and d_achieved (and the host forms' achieved) are
+ *                                      [layers][F]: entry l * F + f.  j2k_plan_psnr_distortion gives the target of ONE frame (N = width * frame_rows *
+ *                                      components).  On a plan of one frame the setting changes no byte and no table of any call (F = 1).
+ *                                      Refused: while the context captures, on != 0 / 1: J2K_ERR_INVALID_ARG; a batch plan that is also a shard
+ *                                      (tile_first / tile_count: a frame may be partial): J2K_ERR_UNSUPPORTED.  With F > 1 a region of interest
+ *                                      (roi) is J2K_ERR_UNSUPPORTED (the footprint tables know one frame); area decodes of a batch stay refused.
+ *   j2k_plan_rate_frames               *frames = F with the setting on, 1 with it off
+ * A DIFFERENT budget or target for every frame (a rate controller gives each frame what its buffer allows): host arrays of nframes == F entries,
+ * read before the call returns -- they reach the kernels by value, so a captured call replays the values it was captured with, and no call gains a
+ * host synchronisation.  One layer; pass_cuts != 0: at coding-pass ends (the 96-entry tables).  No limit on F beyond the plan's.
+ *   j2k_plan_rate_allocate_frames          j2k_plan_rate_allocate / _passes, frame f under frame_bytes[f]: d_kept[blocks], d_chosen[F]
+ *   j2k_plan_rate_allocate_quality_frames  j2k_plan_rate_allocate_quality (one layer) / _quality_passes, frame f under frame_targets[f]: d_achieved[F]
+ *   j2k_plan_encode_frame_pixels_rate_frames  the frame encoder: exactly one of frame_bytes and frame_targets non-NULL; d_achieved (device, [F], may be
+ *                                          NULL) is written with frame_targets.  The kept-prefix stream: decode with the _rate / _passes decode calls
+ *   j2k_encode_pixels_host_rate_frames     its synchronous host-memory form; lens / numbps / tile_offs as j2k_encode_pixels_host_rate, achieved [F]
+ * On a plan of a single frame (F = 1, the setting on or off) frame_bytes = {N} is max_body_bytes = N, byte for byte.
+ * Refusals, before anything is launched: nframes != F, a negative budget, a target that is negative or not finite, both or neither of the two
+ * arrays: J2K_ERR_INVALID_ARG (the entries need not fall or rise: they belong to different frames); a batch plan with the setting off, and
+ * whatever else j2k_plan_rate_allocate refuses: J2K_ERR_UNSUPPORTED.  Not built: one budget over all frames of a batch, per-frame ladders
+ * ([F][layers]), roi / area on batches, the pipelined host codec, the HT coder. */
+int j2k_plan_set_rate_per_frame(j2k_plan *plan, int on);
+int j2k_plan_rate_frames(const j2k_plan *plan, int32_t *frames);
+int j2k_plan_rate_allocate_frames(j2k_plan *plan, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps,
+                                  const int64_t *frame_bytes, int nframes, int pass_cuts, uint8_t *d_kept, uint64_t *d_chosen);
+int j2k_plan_rate_allocate_quality_frames(j2k_plan *plan, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps,
+                                          const double *frame_targets, int nframes, int pass_cuts, uint8_t *d_kept, uint64_t *d_chosen,
+                                          double *d_achieved);
+int j2k_plan_encode_frame_pixels_rate_frames(j2k_plan *plan, int format, const void *d_pix, size_t stride, int sop, int eph,
+                                             const int64_t *frame_bytes, const double *frame_targets, int nframes, int pass_cuts,
+                                             uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, double *d_achieved);
+int j2k_encode_pixels_host_rate_frames(j2k_plan *plan, int format, const void *pix, size_t stride, int sop, int eph,
+                                       const int64_t *frame_bytes, const double *frame_targets, int nframes, int pass_cuts, uint8_t *out,
+                                       size_t cap, size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps, double *achieved);
+
 #ifdef __cplusplus
 }
 #endif
