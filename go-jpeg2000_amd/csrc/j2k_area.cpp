@@ -65,6 +65,7 @@ int area_launch(j2k_plan *P, const j2k_rect *area, int reduce, uint8_t *d_need, 
 }
 
 extern "C" int j2k_plan_area_blocks(j2k_plan *P, const j2k_rect *area, int reduce, uint8_t *d_need) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     AreaOut o{};
     int r = area_check(P, area, reduce, o, "j2k_plan_area_blocks");
@@ -77,6 +78,7 @@ extern "C" int j2k_plan_area_blocks(j2k_plan *P, const j2k_rect *area, int reduc
 
 extern "C" int j2k_plan_decode_frame_pixels_area(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int layers, int truncated,
                                                  int reduce, int skip_planes, const j2k_rect *area, void *d_pix, size_t stride) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
@@ -100,6 +102,7 @@ extern "C" int j2k_plan_decode_frame_pixels_area(j2k_plan *P, const uint8_t *d_c
 
 extern "C" int j2k_decode_pixels_host_area(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int layers, int truncated, int reduce, int skip_planes,
                                            const j2k_rect *area, void *pix, size_t stride) {
+    graph_note_plan(P);
     const int c = host_call_check(P, cs, pix);
     if (c != J2K_OK) return c;
     AreaOut o{};

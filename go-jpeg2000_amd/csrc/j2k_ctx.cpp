@@ -127,31 +127,52 @@ extern "C" void j2k_ctx_destroy(j2k_ctx *ctx) {
 // assemble) are recorded instead of run; the graph replays them on the context's stream with the same device pointers.
 // The calls must have run once before (workspaces sized, lazy tables uploaded): nothing may allocate or synchronise while
 // the stream captures.
-struct j2k_graph { j2k_ctx *ctx; hipGraph_t graph; hipGraphExec_t exec; bool arms_fault; };
+//
+// Lifetime (include/j2kgfx.h; the bookkeeping and its argument: graph_guard.h).  The recorded pointers are the callers' buffers, the staging
+// slots the calls reserved and the tables and workspaces of the plans that were called.  The library frees the last two in three places --
+// stage_reserve growing a slot, ensure_sized growing a plan's buffer, j2k_plan_destroy -- and each makes the graphs that recorded the memory
+// stale: j2k_graph_launch refuses them before it launches anything.
+struct j2k_graph { j2k_ctx *ctx; hipGraph_t graph; hipGraphExec_t exec; bool arms_fault; GraphGuard::Snapshot snap; };
 extern "C" int j2k_ctx_capture_begin(j2k_ctx *ctx) {
     if (!ctx || ctx->capturing) return J2K_ERR_INVALID_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->fault_armed_before_capture = ctx->fault_armed;
     HIPCHK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     ctx->capturing = true;
+    ctx->guard.capture_begin();
     return J2K_OK;
 }
 extern "C" int j2k_ctx_capture_end(j2k_ctx *ctx, j2k_graph **out) {
     if (!ctx || !out || !ctx->capturing) return J2K_ERR_INVALID_ARG;
     *out = nullptr;
     ctx->capturing = false;
+    GraphGuard::Snapshot snap = ctx->guard.capture_end();
     hipGraph_t g = nullptr;
     HIPCHK(ctx, hipStreamEndCapture(ctx->stream, &g));
     hipGraphExec_t ex = nullptr;
     hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
     if (e != hipSuccess) { (void)hipGraphDestroy(g); return fail_hip(ctx, e, "hipGraphInstantiate"); }
-    *out = new j2k_graph{ctx, g, ex, ctx->fault_armed};
+    *out = new j2k_graph{ctx, g, ex, ctx->fault_armed, std::move(snap)};
     ctx->fault_armed = ctx->fault_armed_before_capture;      // nothing ran yet
     return J2K_OK;
+}
+extern "C" int j2k_graph_stale(const j2k_graph *G) {
+    if (!G || !G->ctx) return 0;
+    return (int)G->ctx->guard.verdict(G->snap);
 }
 extern "C" int j2k_graph_launch(j2k_graph *G) {
     if (!G || !G->ctx || G->ctx->capturing) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = G->ctx;
+    // host code only, before anything is launched; fault_armed stays as it is
+    switch (ctx->guard.verdict(G->snap)) {
+    case GraphGuard::VALID: break;
+    case GraphGuard::STALE_SLOT:
+        return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_graph_launch: the graph is stale (a): a staging workspace of the context that it recorded was reallocated by a later, larger call -- capture it again");
+    case GraphGuard::STALE_PLAN_BUFFER:
+        return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_graph_launch: the graph is stale (b): a buffer of a plan that it recorded grew with a later call (a longer stream) and was reallocated -- capture it again");
+    case GraphGuard::STALE_PLAN_DESTROYED:
+        return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_graph_launch: the graph is stale (c): a plan that it recorded was destroyed");
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipGraphLaunch(G->exec, ctx->stream));
     if (G->arms_fault) ctx->fault_armed = true;
@@ -260,10 +281,12 @@ bool profile_pair(j2k_ctx *ctx, int tag, hipEvent_t &e0, hipEvent_t &e1) {
 }
 
 int stage_reserve(j2k_ctx *ctx, int slot, size_t bytes) {
+    ctx->guard.slot_used(slot);          // (notes while capturing only) the graph records this slot's address
     if (ctx->stage_bytes[slot] >= bytes) return J2K_OK;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: a workspace would have to grow -- run the same calls once before j2k_ctx_capture_begin");
     if (ctx->stage[slot]) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->guard.slot_reallocated(slot);                  // every graph that recorded the slot is stale from here on
         HIPCHK(ctx, hipFree(ctx->stage[slot]));
         ctx->stage[slot] = nullptr;
         ctx->stage_bytes[slot] = 0;

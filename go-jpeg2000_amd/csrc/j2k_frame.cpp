@@ -62,6 +62,7 @@ extern "C" int j2k_plan_t2_packets(const j2k_plan *P, int layer, j2k_t2_dev_pack
 }
 
 extern "C" int j2k_plan_t2_fill_cbs(j2k_plan *P, int mb, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps, j2k_t2_dev_cb *d_cbs) {
+    graph_note_plan(P);
     if (!P || !d_offs || !d_lens || !d_numbps || !d_cbs) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -155,6 +156,7 @@ int encode_tile_parts_impl(j2k_plan *P, const uint8_t *d_data, const uint64_t *d
 
 extern "C" int j2k_plan_encode_tile_parts(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,
                                           int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (!d_stream || !d_offs || !d_lens || !d_numbps || !d_out || !d_tile_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
@@ -169,6 +171,7 @@ extern "C" int j2k_plan_encode_tile_parts(j2k_plan *P, const uint8_t *d_stream, 
 // as before.  Compaction, bodies, tile-parts, SOP and EPH are unchanged; d_kept[j] = numBPS everywhere gives j2k_plan_encode_tile_parts' bytes.
 extern "C" int j2k_plan_encode_tile_parts_kept(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,
                                                const uint8_t *d_kept, const uint32_t *d_rate, int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (!d_stream || !d_offs || !d_lens || !d_numbps || !d_kept || !d_rate || !d_out || !d_tile_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
@@ -203,6 +206,7 @@ int decode_tile_parts_impl(j2k_plan *P, const uint8_t *d_cs, size_t len, const u
 }
 extern "C" int j2k_plan_decode_tile_parts(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
                                           uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps) {
+    graph_note_plan(P);
     return decode_tile_parts_impl(P, d_cs, len, d_tile_offs, sop, eph, d_offs, d_lens, d_numbps, nullptr);
 }
 // ... for streams whose blocks may be cut at bit planes (j2k_plan_encode_tile_parts_kept): also each block's floor, and numbps counts the planes
@@ -210,6 +214,7 @@ extern "C" int j2k_plan_decode_tile_parts(j2k_plan *P, const uint8_t *d_cs, size
 // j2k_plan_decode_blocks_floors decodes them.  An uncut stream gives floors 0 and j2k_plan_decode_tile_parts' tables.  MQ plans only.
 extern "C" int j2k_plan_decode_tile_parts_floors(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph,
                                                  uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!d_floors) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     if (P->spec.coder != J2K_CODER_MQ) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_decode_tile_parts_floors: per-block floors need the MQ coder");
@@ -218,6 +223,7 @@ extern "C" int j2k_plan_decode_tile_parts_floors(j2k_plan *P, const uint8_t *d_c
 }
 
 extern "C" int j2k_plan_frame_parallel_tiles(j2k_plan *P, long *tiles) {
+    graph_note_plan(P);
     if (!P || !tiles) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
@@ -233,6 +239,7 @@ extern "C" int j2k_plan_frame_parallel_tiles(j2k_plan *P, long *tiles) {
 }
 
 extern "C" int j2k_plan_place_blocks(j2k_plan *P, const int32_t *d_decoded, int32_t *d_coeff) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (!d_decoded || !d_coeff) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
@@ -243,6 +250,7 @@ extern "C" int j2k_plan_place_blocks(j2k_plan *P, const int32_t *d_decoded, int3
 }
 
 extern "C" int j2k_plan_frame_status(j2k_plan *P) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
@@ -370,12 +378,14 @@ static int encode_frame_pixels(j2k_plan *P, int format, const void *d_pix, size_
 }
 extern "C" int j2k_plan_encode_frame_pixels(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, uint8_t *d_out, size_t cap,
                                             uint64_t *d_tile_offs) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     return encode_frame_pixels(P, format, d_pix, stride, EncodeRequest(), sop, eph, d_out, cap, d_tile_offs, nullptr);
 }
 // the same chain from an image.YCbCr / CMYK / Paletted (j2k_image.cpp): a palette index >= npal is the frame status's J2K_ERR_GO_PANIC
 extern "C" int j2k_plan_encode_frame_image(j2k_plan *P, const j2k_image *d_img, int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+    graph_note_plan(P);
     if (!P || !d_img) return J2K_ERR_INVALID_ARG;
     if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     return plan_encode_frame_cl(P, EncodeRequest(), [&](int32_t *d_coeff) { return plan_forward_image_impl(P, d_img, d_coeff, P->d_frame_status); }, sop, eph, d_out, cap,
@@ -385,6 +395,7 @@ extern "C" int j2k_plan_encode_frame_image(j2k_plan *P, const j2k_image *d_img, 
 // frame took).  A budget that cuts nothing gives j2k_plan_encode_frame_pixels' bytes.
 extern "C" int j2k_plan_encode_frame_pixels_rate(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, int64_t max_body_bytes,
                                                  uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     EncodeRequest q;
@@ -394,6 +405,7 @@ extern "C" int j2k_plan_encode_frame_pixels_rate(j2k_plan *P, int format, const 
 }
 extern "C" int j2k_plan_encode_frame_pixels_layers(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
                                                    uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!d_out || !d_tile_offs || !d_layer_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     EncodeRequest q;
@@ -406,6 +418,7 @@ extern "C" int j2k_plan_encode_frame_pixels_layers(j2k_plan *P, int format, cons
 // rectangle and the gain (rate.hip).
 extern "C" int j2k_plan_encode_frame_pixels_roi(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
                                                 const j2k_rect *roi, int roi_gain, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     EncodeRequest q;
@@ -417,6 +430,7 @@ extern "C" int j2k_plan_encode_frame_pixels_roi(j2k_plan *P, int format, const v
 extern "C" int j2k_plan_encode_frame_pixels_quality(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, const double *targets, int nlayers,
                                                     const j2k_rect *roi, int roi_gain, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, uint64_t *d_layer_offs,
                                                     double *d_achieved) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     EncodeRequest q;
@@ -430,6 +444,7 @@ extern "C" int j2k_plan_encode_frame_pixels_quality(j2k_plan *P, int format, con
 extern "C" int j2k_plan_encode_frame_pixels_rate_frames(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, const int64_t *frame_bytes,
                                                         const double *frame_targets, int nframes, int pass_cuts, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs,
                                                         double *d_achieved) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     EncodeRequest q;
@@ -470,7 +485,7 @@ int plan_decode_frame(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64
     if (T) {
         if (!P->d_cl_dense || P->cl_dense_bytes < len + 64 || !P->d_cl_lfloors) {
             if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "capture: the dense buffer grows with the stream -- run the call once on a stream at least as long before j2k_ctx_capture_begin");
-            if ((r = ensure_sized(ctx, &P->d_cl_dense, &P->cl_dense_bytes, len + 64)) != J2K_OK) return r;
+            if ((r = ensure_sized(P, &P->d_cl_dense, &P->cl_dense_bytes, len + 64)) != J2K_OK) return r;
             if (!P->d_cl_lfloors) HIPCHK(ctx, hipMalloc((void **)&P->d_cl_lfloors, 2 * nr + 64));
         }
         d_floors = P->d_cl_lfloors; d_floors_r = P->d_cl_lfloors + nr;
@@ -522,6 +537,7 @@ int plan_decode_frame(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64
 // the device forms of the decode: their own refusals, in their own order (before the first launch), their request, the one decoder
 extern "C" int j2k_plan_decode_frame_pixels(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, void *d_pix,
                                             size_t stride) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     return plan_decode_frame(P, d_cs, len, d_tile_offs, sop, eph, DecodeRequest(), nullptr, d_pix, stride);
 }
@@ -529,6 +545,7 @@ extern "C" int j2k_plan_decode_frame_pixels(j2k_plan *P, const uint8_t *d_cs, si
 // decoder stops after that bit plane)
 extern "C" int j2k_plan_decode_frame_pixels_coarse(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
                                                    int skip_planes, void *d_pix, size_t stride) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     const int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_plan_decode_frame_pixels_coarse");
     if (r != J2K_OK) return r;
@@ -539,6 +556,7 @@ extern "C" int j2k_plan_decode_frame_pixels_coarse(j2k_plan *P, const uint8_t *d
 // ... to a reduced resolution alone (reduce = 0 too asks for a Mallat plan)
 extern "C" int j2k_plan_decode_frame_pixels_reduced(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
                                                     void *d_pix, size_t stride) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     ReducedTab *R = nullptr;
     const int r = plan_reduced(P, reduce, &R);
@@ -549,6 +567,7 @@ extern "C" int j2k_plan_decode_frame_pixels_reduced(j2k_plan *P, const uint8_t *
 // max(skip_planes, its floor from the packet header).  An uncut stream decodes as with the _coarse call.
 extern "C" int j2k_plan_decode_frame_pixels_rate(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
                                                  int skip_planes, void *d_pix, size_t stride) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     int r = check_skip_planes(ctx, P->spec.coder, skip_planes, "j2k_plan_decode_frame_pixels_rate");
@@ -563,6 +582,7 @@ extern "C" int j2k_plan_decode_frame_pixels_rate(j2k_plan *P, const uint8_t *d_c
 // the first `layers` layers of every tile-part of a layered stream
 extern "C" int j2k_plan_decode_frame_pixels_layers(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int layers, int reduce,
                                                    int skip_planes, void *d_pix, size_t stride) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     int r = check_skip_planes(ctx, P->spec.coder, skip_planes, "j2k_plan_decode_frame_pixels_layers");

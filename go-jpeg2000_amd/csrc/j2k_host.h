@@ -154,6 +154,13 @@ bool mq_throughput_mode();
 int check_fault(j2k_ctx *ctx);
 bool profile_pair(j2k_ctx *ctx, int tag, hipEvent_t &e0, hipEvent_t &e1);
 int stage_reserve(j2k_ctx *ctx, int slot, size_t bytes);
+// The first statement of EVERY entry point of the C ABI whose first parameter is `j2k_plan *P` (tests/test_graph_guard.py reads the sources for
+// it): while the plan's context captures, the graph records this plan's tables and workspaces, so the plan is noted for the graph's snapshot
+// (graph_guard.h).  At the entry points and not further in, so that no call family can reach a launch around it; the entry points that take a
+// `const j2k_plan *` are queries and launch nothing.  Costs one test of a bool outside a capture.
+static inline void graph_note_plan(const j2k_plan *P) {
+    if (P && P->ctx && P->ctx->capturing) P->ctx->guard.plan_used(P->serial);
+}
 
 // ---- plans (j2k_planbuild.cpp; the tables themselves: plan_tables.h) ----
 static inline int64_t align4(int64_t v) { return (v + 3) & ~int64_t(3); }
@@ -292,7 +299,7 @@ int plan_encode_blocks_planes_roi(j2k_plan *P, const int32_t *d_coeff, uint8_t *
 struct T1Workspace { size_t off_nsyms, off_sym, stride, total; };
 T1Workspace t1_workspace(const j2k_ctx *ctx, size_t n, size_t wpj);
 int ensure(j2k_ctx *ctx, void **p, size_t bytes);
-int ensure_sized(j2k_ctx *ctx, void **p, size_t *cur, size_t need);   // a buffer that grows (synchronises when it does; j2k_hostcalls.cpp)
+int ensure_sized(j2k_plan *P, void **p, size_t *cur, size_t need);   // a buffer of the plan that grows (synchronises and bumps the plan's generation when it does; j2k_hostcalls.cpp)
 struct PixIO { int stride = 0, single = 0, triple = 0; j2k::YccSrc ycc{}; };   // ycc.y: a YCbCr image in place of packed RGBA8 (triple 8)
 int plan_forward_impl(j2k_plan *P, const void *d_frame, void *d_coeff, PixIO pix = PixIO());
 int plan_encode_blocks_impl(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate, uint64_t *d_spmask = nullptr);

@@ -151,6 +151,8 @@ extern "C" int j2k_encode_blocks(j2k_ctx *ctx, int coder, const int32_t *const *
     if (nblocks == 0) return J2K_OK;
     if (!planes || !plane_w || !plane_h || !blocks || nplanes <= 0) return fail(ctx, J2K_ERR_INVALID_ARG, "NULL argument");
     if (coder != J2K_CODER_MQ && coder != J2K_CODER_HT) return fail(ctx, J2K_ERR_INVALID_ARG, "coder");
+    // (its temporaries are freed before it returns: a graph must never record them)
+    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<int64_t> poff(nplanes);
     int64_t tot = 0;
@@ -251,6 +253,7 @@ extern "C" int j2k_decode_blocks_floors(j2k_ctx *ctx, int coder, const uint8_t *
     if (!offs || !lens || !blocks || !coeffs || !coeff_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "NULL argument");
     if (coder != J2K_CODER_MQ && coder != J2K_CODER_HT) return fail(ctx, J2K_ERR_INVALID_ARG, "coder");
     if (coder == J2K_CODER_MQ && !numbps) return fail(ctx, J2K_ERR_INVALID_ARG, "numbps required for T1.Decode");
+    if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "a synchronising call while the context captures a graph");     // (as j2k_encode_blocks)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     size_t nbytes = 0;
     std::vector<BlockJob> bj(nblocks);
@@ -314,6 +317,7 @@ extern "C" int j2k_decode_blocks_floors(j2k_ctx *ctx, int coder, const uint8_t *
 // ---- whole shard from host planes (encoder.preprocess + encodeTile) ------------------
 extern "C" int j2k_encode_frame(j2k_plan *P, int32_t *const *planes, int32_t *coeff, uint8_t *out, size_t cap,
                                 size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
+    graph_note_plan(P);
     if (!P || !planes) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
@@ -365,9 +369,11 @@ extern "C" int j2k_encode_frame(j2k_plan *P, int32_t *const *planes, int32_t *co
 
 
 // a plan-owned device buffer that grows with what the call needs (the stream is drained before it is replaced)
-int ensure_sized(j2k_ctx *ctx, void **p, size_t *cur, size_t need) {
+// Replacing it makes every graph that recorded a call of this plan stale (graph_guard.h, cause (b)): the plan's generation goes up before the free.
+int ensure_sized(j2k_plan *P, void **p, size_t *cur, size_t need) {
+    j2k_ctx *ctx = P->ctx;
     if (*p && *cur >= need) return J2K_OK;
-    if (*p) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(*p)); *p = nullptr; *cur = 0; }
+    if (*p) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); ctx->guard.plan_buffer_reallocated(P->serial); HIPCHK(ctx, hipFree(*p)); *p = nullptr; *cur = 0; }
     HIPCHK(ctx, hipMalloc(p, std::max<size_t>(need, 64)));
     *cur = std::max<size_t>(need, 64);
     return J2K_OK;
@@ -444,7 +450,7 @@ int encode_host(j2k_plan *P, const EncodeRequest &request, bool cl_set, size_t b
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nb = P->blocks.size(), nt = (size_t)P->tile_count;
     int r;
-    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, encode_host_io_bytes(P, cl_set, request.nlayers, bound))) != J2K_OK) return r;
+    if ((r = ensure_sized(P, &P->d_host_io, &P->host_io_bytes, encode_host_io_bytes(P, cl_set, request.nlayers, bound))) != J2K_OK) return r;
     HostEncodeIO io;
     if ((r = encode_host_launch(P, request, cl_set, bound, sop, eph, P->d_host_io, forward, io)) != J2K_OK) return r;
     const size_t nl = io.nl;
@@ -475,7 +481,7 @@ int encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, 
     const int pb = pix_format_bytes(format);
     if (!pb || stride < (size_t)S.W * pb) return fail(ctx, J2K_ERR_INVALID_ARG, "pixel format / stride");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, (size_t)S.H * stride);
+    const int r = ensure_sized(P, &P->d_host_pix, &P->host_pix_bytes, (size_t)S.H * stride);
     if (r != J2K_OK) return r;
     return encode_host(P, q, cl_set, bound, sop, eph, out, cap, out_len, tile_offs, layer_offs, lens, numbps, achieved, [&](int32_t *d_coeff) {
         HIPCHK(ctx, hipMemcpyAsync(P->d_host_pix, pix, (size_t)S.H * stride, hipMemcpyHostToDevice, ctx->stream));
@@ -486,6 +492,7 @@ size_t plain_bound(const j2k_plan *P) { return P->spec.closed_loop ? j2k_plan_fr
 
 extern "C" int j2k_encode_pixels_host(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, uint8_t *out, size_t cap,
                                       size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
+    graph_note_plan(P);
     const int r = host_call_check(P, pix, out_len);
     if (r != J2K_OK) return r;
     return encode_pixels_host(P, format, pix, stride, EncodeRequest(), false, plain_bound(P), sop, eph, out, cap, out_len, tile_offs, nullptr, lens, numbps, nullptr);
@@ -494,6 +501,7 @@ extern "C" int j2k_encode_pixels_host(j2k_plan *P, int format, const void *pix, 
 // (what else the plan must be, the encoder refuses after the forward transform: MQ coder, no batch, blocks <= 64 x 64)
 extern "C" int j2k_encode_pixels_host_rate(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes, uint8_t *out,
                                            size_t cap, size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (max_body_bytes < 0) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_encode_pixels_host_rate: a negative budget");
     if (!P->spec.closed_loop) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_encode_pixels_host_rate: needs a closed-loop plan");
@@ -510,6 +518,7 @@ extern "C" int j2k_encode_pixels_host_rate(j2k_plan *P, int format, const void *
 extern "C" int j2k_encode_pixels_host_rate_frames(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *frame_bytes,
                                                   const double *frame_targets, int nframes, int pass_cuts, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs,
                                                   uint32_t *lens, uint8_t *numbps, double *achieved) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     EncodeRequest q;
     int r = host_call_check(P, pix, out_len);
@@ -525,6 +534,7 @@ extern "C" int j2k_encode_pixels_host_rate_frames(j2k_plan *P, int format, const
 // level-0 kernel), then j2k_plan_forward_image; a palette index >= npal returns J2K_ERR_GO_PANIC before anything is written.
 extern "C" int j2k_encode_image_host(j2k_plan *P, const j2k_image *img, int sop, int eph, uint8_t *out, size_t cap, size_t *out_len,
                                      uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps) {
+    graph_note_plan(P);
     int r = host_call_check(P, img, out_len);
     if (r != J2K_OK) return r;
     j2k_ctx *ctx = P->ctx;
@@ -538,7 +548,7 @@ extern "C" int j2k_encode_image_host(j2k_plan *P, const j2k_image *img, int sop,
     size_t off[4];
     const size_t total = image_layout(img, need, off);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, total + 64)) != J2K_OK) return r;
+    if ((r = ensure_sized(P, &P->d_host_pix, &P->host_pix_bytes, total + 64)) != J2K_OK) return r;
     return encode_host(P, EncodeRequest(), false, plain_bound(P), sop, eph, out, cap, out_len, tile_offs, nullptr, lens, numbps, nullptr, [&](int32_t *d_coeff) {
         j2k_image d_img;
         const int u = image_upload(ctx, img, need, (uint8_t *)P->d_host_pix, off, &d_img);
@@ -551,8 +561,8 @@ int decode_host(j2k_plan *P, const uint8_t *cs, size_t len, size_t pixbytes, voi
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int r;
-    if ((r = ensure_sized(ctx, &P->d_host_pix, &P->host_pix_bytes, pixbytes)) != J2K_OK) return r;
-    if ((r = ensure_sized(ctx, &P->d_host_io, &P->host_io_bytes, len + 64)) != J2K_OK) return r;
+    if ((r = ensure_sized(P, &P->d_host_pix, &P->host_pix_bytes, pixbytes)) != J2K_OK) return r;
+    if ((r = ensure_sized(P, &P->d_host_io, &P->host_io_bytes, len + 64)) != J2K_OK) return r;
     HIPCHK(ctx, hipMemcpyAsync(P->d_host_io, cs, len, hipMemcpyHostToDevice, ctx->stream));
     if ((r = decode((const uint8_t *)P->d_host_io, P->d_host_pix)) != J2K_OK) return r;
     if (status_first) {
@@ -580,10 +590,12 @@ static int decode_pixels_host_impl(j2k_plan *P, const uint8_t *cs, size_t len, i
     });
 }
 extern "C" int j2k_decode_pixels_host(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, void *pix, size_t stride) {
+    graph_note_plan(P);
     return decode_pixels_host_impl(P, cs, len, sop, eph, -1, pix, stride);
 }
 // ... of a Mallat plan to a reduced resolution: pix holds ceil(H / 2^reduce) rows of `stride` bytes
 extern "C" int j2k_decode_pixels_host_reduced(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, void *pix, size_t stride) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     int32_t wr = 0, hr = 0;
     const int r = j2k_plan_reduced_size(P, reduce, &wr, &hr);     // (J2K_ERR_UNSUPPORTED on any other plan, J2K_ERR_INVALID_ARG for a reduce outside 0 ... levels)
@@ -593,6 +605,7 @@ extern "C" int j2k_decode_pixels_host_reduced(j2k_plan *P, const uint8_t *cs, si
 // ... with both axes (j2k_plan_decode_frame_pixels_coarse): reduce = 0 on any closed-loop plan, reduce > 0 as j2k_decode_pixels_host_reduced
 extern "C" int j2k_decode_pixels_host_coarse(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, int skip_planes, void *pix,
                                              size_t stride) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_decode_pixels_host_coarse");
     int32_t wr = 0, hr = 0;
@@ -603,6 +616,7 @@ extern "C" int j2k_decode_pixels_host_coarse(j2k_plan *P, const uint8_t *cs, siz
 // ... of a stream whose blocks may be cut at bit planes (j2k_plan_decode_frame_pixels_rate)
 extern "C" int j2k_decode_pixels_host_rate(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, int skip_planes, void *pix,
                                            size_t stride) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_decode_pixels_host_rate");
     if (r != J2K_OK) return r;

@@ -174,6 +174,7 @@ int plan_forward_image_impl(j2k_plan *P, const j2k_image *d_img, int32_t *d_coef
 }
 
 extern "C" int j2k_plan_forward_image(j2k_plan *P, const j2k_image *d_img, int32_t *d_coeff) {
+    graph_note_plan(P);
     if (!P || !d_img || !d_coeff) return J2K_ERR_INVALID_ARG;
     return plan_forward_image_impl(P, d_img, d_coeff, nullptr);
 }

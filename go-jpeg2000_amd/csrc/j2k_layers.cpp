@@ -109,6 +109,7 @@ extern "C" size_t j2k_plan_frame_bound_layers(const j2k_plan *P, int nlayers) {
 
 extern "C" int j2k_plan_rate_allocate_layers(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, const int64_t *layer_bytes,
                                              int nlayers, uint8_t *d_kept, uint64_t *d_chosen) {
+    graph_note_plan(P);
     if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen) return J2K_ERR_INVALID_ARG;
     EncodeRequest q;
     int r = encode_request(P, "j2k_plan_rate_allocate_layers", layer_bytes, nullptr, nlayers, true, false, nullptr, 1, nullptr, q);
@@ -134,6 +135,7 @@ int encode_tile_parts_layers_launch(j2k_plan *P, LayerTab &T, int L, const uint8
 extern "C" int j2k_plan_encode_tile_parts_layers(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,
                                                  const uint8_t *d_kept, const uint32_t *d_rate, int nlayers, int sop, int eph, uint8_t *d_out, size_t cap,
                                                  uint64_t *d_tile_offs, uint64_t *d_layer_offs) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (!d_stream || !d_offs || !d_lens || !d_numbps || !d_kept || !d_rate || !d_out || !d_tile_offs || !d_layer_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
@@ -159,6 +161,7 @@ int decode_tile_parts_layers_launch(j2k_plan *P, LayerTab &T, int layers, const 
 
 extern "C" int j2k_plan_decode_tile_parts_layers(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int layers,
                                                  uint8_t *d_dense, size_t dense_cap, uint64_t *d_offs, uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_floors) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (!d_cs || !d_dense || !d_offs || !d_lens || !d_numbps || !d_floors) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
@@ -176,6 +179,7 @@ extern "C" int j2k_plan_decode_tile_parts_layers(j2k_plan *P, const uint8_t *d_c
 // d_host_io holds the larger of the two streams for the forms that can write either (roi, quality: layer_offs == NULL asks for the kept-prefix one)
 extern "C" int j2k_encode_pixels_host_layers(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
                                              uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs, uint32_t *lens, uint8_t *numbps) {
+    graph_note_plan(P);
     EncodeRequest q;
     int r = host_call_check(P, pix, out_len);
     if (r == J2K_OK) r = encode_request(P, "j2k_encode_pixels_host_layers", layer_bytes, nullptr, nlayers, true, false, nullptr, 1, nullptr, q);
@@ -186,6 +190,7 @@ extern "C" int j2k_encode_pixels_host_layers(j2k_plan *P, int format, const void
 extern "C" int j2k_encode_pixels_host_roi(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const int64_t *layer_bytes, int nlayers,
                                           const j2k_rect *roi, int roi_gain, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs,
                                           uint32_t *lens, uint8_t *numbps) {
+    graph_note_plan(P);
     EncodeRequest q;
     int r = host_call_check(P, pix, out_len);
     if (r == J2K_OK) r = encode_request(P, "j2k_encode_pixels_host_roi", layer_bytes, nullptr, nlayers, layer_offs != nullptr, true, roi, roi_gain, nullptr, q);
@@ -197,6 +202,7 @@ extern "C" int j2k_encode_pixels_host_roi(j2k_plan *P, int format, const void *p
 extern "C" int j2k_encode_pixels_host_quality(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, const double *targets, int nlayers,
                                               const j2k_rect *roi, int roi_gain, uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint64_t *layer_offs,
                                               uint32_t *lens, uint8_t *numbps, double *achieved) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!targets) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_encode_pixels_host_quality: no targets");
     EncodeRequest q;
@@ -209,6 +215,7 @@ extern "C" int j2k_encode_pixels_host_quality(j2k_plan *P, int format, const voi
 
 extern "C" int j2k_decode_pixels_host_layers(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int layers, int reduce, int skip_planes, void *pix,
                                              size_t stride) {
+    graph_note_plan(P);
     int r = host_call_check(P, cs, pix);
     if (r != J2K_OK) return r;
     r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_decode_pixels_host_layers");

@@ -19,6 +19,7 @@ int plan_encode_blocks_passes(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_sl
 
 extern "C" int j2k_plan_encode_blocks_passes(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate,
                                              uint64_t *d_dist, uint64_t *d_spmask) {
+    graph_note_plan(P);
     if (!P || !d_coeff || !d_slots || !d_lens || !d_numbps || !d_rate || !d_dist || !d_spmask) return J2K_ERR_INVALID_ARG;
     const int r = rate_check(P, "j2k_plan_encode_blocks_passes");
     if (r != J2K_OK) return r;
@@ -27,6 +28,7 @@ extern "C" int j2k_plan_encode_blocks_passes(j2k_plan *P, const int32_t *d_coeff
 
 extern "C" int j2k_plan_rate_allocate_passes(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, int64_t max_body_bytes,
                                              uint8_t *d_kept, uint64_t *d_chosen) {
+    graph_note_plan(P);
     if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     int r = rate_check(P, "j2k_plan_rate_allocate_passes");
@@ -41,6 +43,7 @@ extern "C" int j2k_plan_rate_allocate_passes(j2k_plan *P, const uint32_t *d_rate
 
 extern "C" int j2k_plan_rate_allocate_quality_passes(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, double target,
                                                      uint8_t *d_kept, uint64_t *d_chosen, double *d_achieved) {
+    graph_note_plan(P);
     if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen || !d_achieved) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     int r = rate_check(P, "j2k_plan_rate_allocate_quality_passes");
@@ -57,6 +60,7 @@ extern "C" int j2k_plan_rate_allocate_quality_passes(j2k_plan *P, const uint32_t
 // passes (none, and no bytes, for q = 0), ZeroBitPlanes as before.  d_kept[j] = 3 numBPS - 2 everywhere gives j2k_plan_encode_tile_parts' bytes.
 extern "C" int j2k_plan_encode_tile_parts_kept_passes(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,
                                                       const uint8_t *d_kept, const uint32_t *d_rate, int sop, int eph, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (!d_stream || !d_offs || !d_lens || !d_numbps || !d_kept || !d_rate || !d_out || !d_tile_offs) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
@@ -72,6 +76,7 @@ extern "C" int j2k_plan_encode_tile_parts_kept_passes(j2k_plan *P, const uint8_t
 // s = (passes + 2) % 3 (0 for an uncut block); d_numbps as that call.  j2k_plan_decode_blocks_pfloors decodes them.
 extern "C" int j2k_plan_decode_tile_parts_pfloors(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, uint64_t *d_offs,
                                                   uint32_t *d_lens, uint8_t *d_numbps, uint8_t *d_pfloors) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!d_pfloors) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     const int r = rate_check(P, "j2k_plan_decode_tile_parts_pfloors");
@@ -83,6 +88,7 @@ extern "C" int j2k_plan_decode_tile_parts_pfloors(j2k_plan *P, const uint8_t *d_
 // 3 ceil(f / 3) - f passes of the next plane; every sample takes the midpoint of what ITS last pass left (tests/pass_cases.py: coarse_pass).
 extern "C" int j2k_plan_decode_blocks_pfloors(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens, const uint8_t *d_numbps,
                                               int skip_planes, const uint8_t *d_pfloors, int32_t *d_decoded) {
+    graph_note_plan(P);
     if (!P || !d_stream || !d_offs || !d_lens || !d_numbps || !d_pfloors || !d_decoded) return J2K_ERR_INVALID_ARG;
     int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_plan_decode_blocks_pfloors");
     if (r == J2K_OK) r = rate_check(P, "j2k_plan_decode_blocks_pfloors");
@@ -101,6 +107,7 @@ static int passes_request(j2k_plan *P, const char *who, int64_t max_body_bytes, 
 
 extern "C" int j2k_plan_encode_frame_pixels_passes(j2k_plan *P, int format, const void *d_pix, size_t stride, int sop, int eph, int64_t max_body_bytes,
                                                    const double *target, uint8_t *d_out, size_t cap, uint64_t *d_tile_offs, double *d_achieved) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (!d_out || !d_tile_offs) return fail(P->ctx, J2K_ERR_INVALID_ARG, "null device pointer");
     EncodeRequest q;
@@ -112,6 +119,7 @@ extern "C" int j2k_plan_encode_frame_pixels_passes(j2k_plan *P, int format, cons
 
 extern "C" int j2k_encode_pixels_host_passes(j2k_plan *P, int format, const void *pix, size_t stride, int sop, int eph, int64_t max_body_bytes, const double *target,
                                              uint8_t *out, size_t cap, size_t *out_len, uint64_t *tile_offs, uint32_t *lens, uint8_t *numbps, double *achieved) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     EncodeRequest q;
     int r = host_call_check(P, pix, out_len);
@@ -123,6 +131,7 @@ extern "C" int j2k_encode_pixels_host_passes(j2k_plan *P, int format, const void
 // j2k_plan_decode_frame_pixels_rate at pass granularity; area (or null): only that rectangle, as j2k_plan_decode_frame_pixels_area returns it
 extern "C" int j2k_plan_decode_frame_pixels_passes(j2k_plan *P, const uint8_t *d_cs, size_t len, const uint64_t *d_tile_offs, int sop, int eph, int reduce,
                                                    int skip_planes, const j2k_rect *area, void *d_pix, size_t stride) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
@@ -145,6 +154,7 @@ extern "C" int j2k_plan_decode_frame_pixels_passes(j2k_plan *P, const uint8_t *d
 
 extern "C" int j2k_decode_pixels_host_passes(j2k_plan *P, const uint8_t *cs, size_t len, int sop, int eph, int reduce, int skip_planes, const j2k_rect *area,
                                              void *pix, size_t stride) {
+    graph_note_plan(P);
     int r = host_call_check(P, cs, pix);
     if (r != J2K_OK) return r;
     AreaOut o{};

@@ -140,6 +140,7 @@ extern "C" void j2k_host_free(void *p) {
 }
 
 extern "C" int j2k_pipe_create(j2k_plan *P, int depth, j2k_pipe **out) {
+    graph_note_plan(P);
     if (!P || !out) return J2K_ERR_INVALID_ARG;
     *out = nullptr;
     j2k_ctx *ctx = P->ctx;

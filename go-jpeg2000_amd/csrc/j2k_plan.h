@@ -54,6 +54,7 @@ struct PlanOptions {
 #include "../../include/j2kgfx.h"
 #include "j2k_internal.h"
 #include "plan_tables.h"
+#include "graph_guard.h"
 
 // What the MQ block coder's last launches took (j2k_plan_mq_forms / j2k_ctx_mq_forms): written where the choices are made, read by nobody else
 struct j2k_mq_record {
@@ -87,6 +88,7 @@ struct j2k_ctx : j2k::PlanOptions {
                                // frame at a time: latency)
     bool capturing = false;    // between j2k_ctx_capture_begin / _end: the plan calls are recorded into a HIP graph, nothing may allocate or synchronise
     bool fault_armed_before_capture = false;
+    j2k::GraphGuard guard;     // which staging slots and plans a capture used, and the generations j2k_graph_launch compares (graph_guard.h)
     bool counted_mq = false;   // this context has built an MQ-coder plan (counted in g_mq_ctxs)
     j2k_mq_record mq_forms;    // of the last j2k_decode_blocks / _coarse / _floors (the host calls have no plan)
     bool t2_parallel = true;   // J2K_T2_PARALLEL: frame decode of SOP + EPH streams parses a tile's packets side by side from their markers (verified; 0 = the tile chain only)
@@ -145,6 +147,7 @@ struct LayerTab {
 // of its vectors (plan_device_tables in j2k_planbuild.cpp pairs each with its vector: upload and free walk that one list), and whatever the other files make at first use
 struct j2k_plan : j2k::PlanScalars {
     j2k_ctx *ctx = nullptr;
+    uint64_t serial = 0;       // of ctx->guard: never reused, so a graph tells this plan from a later one at the same address (graph_guard.h)
     j2k::PlanSpec spec;
     // [cls][level]: cls 0 = single-component groups, cls 1 = MCT triples
     std::vector<j2k::LevelTab> fwd[2], inv[2];

@@ -39,6 +39,7 @@ int build_plan(j2k_ctx *ctx, const PlanSpec &S, j2k_plan **out) {
     if (r != J2K_OK) return fail(ctx, r, why);
     j2k_plan *P = new j2k_plan();
     P->ctx = ctx;
+    P->serial = ctx->guard.plan_created();
     P->spec = S;
     for (int cls = 0; cls < 2; cls++) {
         P->fwd[cls].resize(T.fwd[cls].size()); P->inv[cls].resize(T.inv[cls].size());
@@ -117,6 +118,9 @@ extern "C" int j2k_plan_reduced_size(const j2k_plan *P, int reduce, int32_t *wid
 extern "C" void j2k_plan_destroy(j2k_plan *P) {
     if (!P) return;
     if (P->ctx) { (void)hipSetDevice(P->ctx->device); (void)hipStreamSynchronize(P->ctx->stream); }
+    // every graph that recorded a call of this plan is stale from here on (graph_guard.h, cause (c)): everything below is freed.  The serial is
+    // not given out again, so a plan made later at this address does not bring those graphs back.  (Not graph_note_plan: nothing is recorded.)
+    if (P->ctx) P->ctx->guard.plan_destroyed(P->serial);
     for (ReducedTab &R : P->reduced) free_reduced(R);
     free_layer_tabs(P);
     plan_device_tables(*P, PlanTables(), [](auto *&d, const auto &) { if (d) (void)hipFree(d); d = nullptr; });

@@ -89,6 +89,7 @@ int rate_check(j2k_plan *P, const char *who) {
 // Plan state in the idiom of j2k_plan_set_raw_magref: the rate calls read it, nothing below them does -- block coding, distortion, packets and
 // readers already work per block or per tile.
 extern "C" int j2k_plan_set_rate_per_frame(j2k_plan *P, int on) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_set_rate_per_frame: plan state cannot change while a graph is being captured");
@@ -110,6 +111,7 @@ extern "C" int j2k_plan_rate_frames(const j2k_plan *P, int32_t *frames) {
 }
 
 extern "C" int j2k_plan_get_rate_weights(j2k_plan *P, double *weights, size_t cap, size_t *count) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     plan_rate_weights(P);
     if (count) *count = P->rate_weights.size();
@@ -120,6 +122,7 @@ extern "C" int j2k_plan_get_rate_weights(j2k_plan *P, double *weights, size_t ca
 }
 
 extern "C" int j2k_plan_set_rate_weights(j2k_plan *P, const double *weights, size_t count) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (P->ctx->capturing) return fail(P->ctx, J2K_ERR_INVALID_ARG, "capture: set the weights before j2k_ctx_capture_begin");
     plan_rate_weights(P);
@@ -134,6 +137,7 @@ extern "C" int j2k_plan_set_rate_weights(j2k_plan *P, const double *weights, siz
 
 extern "C" int j2k_plan_encode_blocks_planes(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps,
                                              uint32_t *d_rate, uint64_t *d_dist) {
+    graph_note_plan(P);
     if (!P || !d_coeff || !d_slots || !d_lens || !d_numbps || !d_rate || !d_dist) return J2K_ERR_INVALID_ARG;
     int r = rate_check(P, "j2k_plan_encode_blocks_planes");
     if (r != J2K_OK) return r;
@@ -160,6 +164,7 @@ int roi_check(j2k_plan *P, const j2k_rect *roi, int roi_gain, const char *who) {
 }
 
 extern "C" int j2k_plan_roi_windows(j2k_plan *P, const j2k_rect *roi, int32_t *d_win) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     int r = rate_check(P, "j2k_plan_roi_windows");
@@ -186,6 +191,7 @@ int plan_encode_blocks_planes_roi(j2k_plan *P, const int32_t *d_coeff, uint8_t *
 
 extern "C" int j2k_plan_encode_blocks_planes_roi(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps, uint32_t *d_rate,
                                                  uint64_t *d_dist, const j2k_rect *roi, int roi_gain) {
+    graph_note_plan(P);
     if (!P || !d_coeff || !d_slots || !d_lens || !d_numbps || !d_rate || !d_dist) return J2K_ERR_INVALID_ARG;
     int r = rate_check(P, "j2k_plan_encode_blocks_planes_roi");
     if (r == J2K_OK) r = roi_check(P, roi, roi_gain, "j2k_plan_encode_blocks_planes_roi");
@@ -195,6 +201,7 @@ extern "C" int j2k_plan_encode_blocks_planes_roi(j2k_plan *P, const int32_t *d_c
 
 extern "C" int j2k_plan_rate_allocate(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, int64_t max_body_bytes,
                                       uint8_t *d_kept, uint64_t *d_chosen) {
+    graph_note_plan(P);
     if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     int r = rate_check(P, "j2k_plan_rate_allocate");
@@ -268,6 +275,7 @@ int frame_values_request(j2k_plan *P, const char *who, const int64_t *frame_byte
 // j2k_plan_rate_allocate / _passes with a budget of its own for every frame of the batch
 extern "C" int j2k_plan_rate_allocate_frames(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, const int64_t *frame_bytes, int nframes,
                                              int pass_cuts, uint8_t *d_kept, uint64_t *d_chosen) {
+    graph_note_plan(P);
     if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen) return J2K_ERR_INVALID_ARG;
     if (!frame_bytes) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_plan_rate_allocate_frames: no budgets");
     EncodeRequest q;
@@ -279,6 +287,7 @@ extern "C" int j2k_plan_rate_allocate_frames(j2k_plan *P, const uint32_t *d_rate
 // j2k_plan_rate_allocate_quality (one layer) / _quality_passes with a target of its own for every frame
 extern "C" int j2k_plan_rate_allocate_quality_frames(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, const double *frame_targets,
                                                      int nframes, int pass_cuts, uint8_t *d_kept, uint64_t *d_chosen, double *d_achieved) {
+    graph_note_plan(P);
     if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen || !d_achieved) return J2K_ERR_INVALID_ARG;
     if (!frame_targets) return fail(P->ctx, J2K_ERR_INVALID_ARG, "j2k_plan_rate_allocate_quality_frames: no targets");
     EncodeRequest q;
@@ -314,6 +323,7 @@ int targets_check(j2k_ctx *ctx, const double *targets, int nlayers, const char *
 
 extern "C" int j2k_plan_rate_allocate_quality(j2k_plan *P, const uint32_t *d_rate, const uint64_t *d_dist, const uint8_t *d_numbps, const double *targets, int nlayers,
                                               uint8_t *d_kept, uint64_t *d_chosen, double *d_achieved) {
+    graph_note_plan(P);
     if (!P || !d_rate || !d_dist || !d_numbps || !d_kept || !d_chosen || !d_achieved) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     int r = rate_check(P, "j2k_plan_rate_allocate_quality");

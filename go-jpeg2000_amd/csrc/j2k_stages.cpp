@@ -219,6 +219,7 @@ static int plan_inverse_reduced_impl(j2k_plan *P, const void *d_coeff, int reduc
 }
 
 extern "C" int j2k_plan_inverse_reduced(j2k_plan *P, const int32_t *d_coeff, int reduce, int32_t *d_frame) {
+    graph_note_plan(P);
     if (!P || !d_frame || !d_coeff) return J2K_ERR_INVALID_ARG;
     ReducedTab *R = nullptr;
     int r = plan_reduced(P, reduce, &R);          // (the refusals come first, reduce = 0 included)
@@ -228,10 +229,12 @@ extern "C" int j2k_plan_inverse_reduced(j2k_plan *P, const int32_t *d_coeff, int
 }
 
 extern "C" int j2k_plan_forward(j2k_plan *P, const int32_t *d_frame, int32_t *d_coeff) {
+    graph_note_plan(P);
     if (!P || !d_frame || !d_coeff) return J2K_ERR_INVALID_ARG;
     return plan_forward_impl(P, d_frame, d_coeff);
 }
 extern "C" int j2k_plan_inverse(j2k_plan *P, const int32_t *d_coeff, int32_t *d_frame) {
+    graph_note_plan(P);
     if (!P || !d_frame || !d_coeff) return J2K_ERR_INVALID_ARG;
     return plan_inverse_impl(P, d_coeff, d_frame);
 }
@@ -561,10 +564,12 @@ int plan_inverse_pixels_reduced_impl(j2k_plan *P, const int32_t *d_coeff, int re
     return plan_pack_pixels_reduced(P, *R, reduce, (const int32_t *)ctx->stage[0], d_pix, stride, guard);
 }
 extern "C" int j2k_plan_inverse_pixels_reduced(j2k_plan *P, const int32_t *d_coeff, int reduce, void *d_pix, size_t stride) {
+    graph_note_plan(P);
     return plan_inverse_pixels_reduced_impl(P, d_coeff, reduce, d_pix, stride, nullptr);
 }
 
 extern "C" int j2k_plan_forward_rgba8(j2k_plan *P, const void *d_pix, size_t stride, int32_t *d_coeff) {
+    graph_note_plan(P);
     if (!P || !d_pix || !d_coeff) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
@@ -580,6 +585,7 @@ extern "C" int j2k_plan_forward_rgba8(j2k_plan *P, const void *d_pix, size_t str
 }
 
 extern "C" int j2k_plan_inverse_rgba8(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride) {
+    graph_note_plan(P);
     if (!P || !d_pix || !d_coeff) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
@@ -596,6 +602,7 @@ extern "C" int j2k_plan_inverse_rgba8(j2k_plan *P, const int32_t *d_coeff, void 
 }
 
 extern "C" int j2k_plan_forward_pixels(j2k_plan *P, int format, const void *d_pix, size_t stride, int32_t *d_coeff) {
+    graph_note_plan(P);
     if (!P || !d_pix || !d_coeff) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     const PlanSpec &S = P->spec;
@@ -626,6 +633,7 @@ extern "C" int j2k_plan_scr16(const j2k_plan *P) {
 }
 
 extern "C" int j2k_plan_inverse_pixels(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride) {
+    graph_note_plan(P);
     return plan_inverse_pixels_impl(P, d_coeff, d_pix, stride, nullptr);
 }
 int plan_inverse_pixels_impl(j2k_plan *P, const int32_t *d_coeff, void *d_pix, size_t stride, const int *guard) {
@@ -670,6 +678,7 @@ static size_t t1_work_per_job(const j2k_plan *P) {
 }
 
 extern "C" int j2k_plan_encode_blocks(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_slots, uint32_t *d_lens, uint8_t *d_numbps) {
+    graph_note_plan(P);
     return plan_encode_blocks_impl(P, d_coeff, d_slots, d_lens, d_numbps, nullptr);
 }
 
@@ -765,6 +774,7 @@ int plan_encode_private_slots(j2k_plan *P, const int32_t *d_coeff, uint32_t *d_l
 // slot buffer owned by the context
 extern "C" int j2k_plan_encode_stream(j2k_plan *P, const int32_t *d_coeff, uint8_t *d_stream, uint64_t *d_offs, uint32_t *d_lens,
                                       uint8_t *d_numbps) {
+    graph_note_plan(P);
     if (!P || !d_coeff || !d_stream || !d_offs || !d_lens || !d_numbps) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -821,6 +831,7 @@ extern "C" size_t j2k_plan_tile_parts_bound(const j2k_plan *P) {
 }
 extern "C" int j2k_plan_assemble_tiles_device(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, uint8_t *d_out,
                                               uint64_t *d_out_len) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (!d_stream || !d_offs || !d_out || !d_out_len) return fail(ctx, J2K_ERR_INVALID_ARG, "null device pointer");
@@ -832,6 +843,7 @@ extern "C" int j2k_plan_assemble_tiles_device(j2k_plan *P, const uint8_t *d_stre
 
 extern "C" int j2k_plan_pack_stream(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
                                     const uint8_t *d_numbps, uint8_t *d_pack) {
+    graph_note_plan(P);
     if (!P || !d_stream || !d_offs || !d_lens || !d_numbps || !d_pack) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -856,6 +868,7 @@ extern "C" int j2k_plan_pack_stream(j2k_plan *P, const uint8_t *d_stream, const 
 
 extern "C" int j2k_plan_unpack_streams(j2k_plan *P, int count, const uint8_t *const *d_packs, const size_t *pack_bytes,
                                        uint8_t *const *d_streams, uint64_t *const *d_offs, uint32_t *const *d_lens, uint8_t *const *d_numbps) {
+    graph_note_plan(P);
     if (!P || count < 0 || (count && (!d_packs || !pack_bytes || !d_streams || !d_offs || !d_lens || !d_numbps))) return J2K_ERR_INVALID_ARG;
     for (int i = 0; i < count; i++)
         if (!d_packs[i] || !d_streams[i] || !d_offs[i] || !d_lens[i] || !d_numbps[i]) return J2K_ERR_INVALID_ARG;
@@ -876,10 +889,12 @@ extern "C" int j2k_plan_unpack_streams(j2k_plan *P, int count, const uint8_t *co
 
 extern "C" int j2k_plan_unpack_stream(j2k_plan *P, const uint8_t *d_pack, size_t pack_bytes, uint8_t *d_stream, uint64_t *d_offs,
                                       uint32_t *d_lens, uint8_t *d_numbps) {
+    graph_note_plan(P);
     return j2k_plan_unpack_streams(P, 1, &d_pack, &pack_bytes, &d_stream, &d_offs, &d_lens, &d_numbps);
 }
 
 extern "C" int j2k_plan_compact(j2k_plan *P, const uint8_t *d_slots, const uint32_t *d_lens, uint64_t *d_offs, uint8_t *d_stream) {
+    graph_note_plan(P);
     if (!P || !d_slots || !d_lens || !d_offs || !d_stream) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -891,12 +906,14 @@ extern "C" int j2k_plan_compact(j2k_plan *P, const uint8_t *d_slots, const uint3
 }
 
 extern "C" int j2k_plan_set_decode_coded_rows_only(j2k_plan *P, int on) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     P->dec_coded_rows_only = on != 0;
     return J2K_OK;
 }
 
 extern "C" int j2k_plan_set_dequantize(j2k_plan *P, int on) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     if (P->spec.wavelet != W97 || P->spec.quant != Q_ENCODER) return fail(P->ctx, J2K_ERR_UNSUPPORTED, "j2k_plan_set_dequantize: a lossy plan only");
     P->dequantize = on != 0;
@@ -906,6 +923,7 @@ extern "C" int j2k_plan_set_dequantize(j2k_plan *P, int on) {
 // The raw-MagRef coding style: plan state, like the setters above; the block coder's launches read it, nothing above the block
 // body does.  Built for MQ plans whose blocks are all <= 64 x 64.
 extern "C" int j2k_plan_set_raw_magref(j2k_plan *P, int on) {
+    graph_note_plan(P);
     if (!P) return J2K_ERR_INVALID_ARG;
     j2k_ctx *ctx = P->ctx;
     if (ctx->capturing) return fail(ctx, J2K_ERR_INVALID_ARG, "j2k_plan_set_raw_magref: plan state cannot change while a graph is being captured");
@@ -925,6 +943,7 @@ int raw_magref_refuse(const j2k_plan *P, const char *who) {
 
 extern "C" int j2k_plan_decode_blocks(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
                                       const uint8_t *d_numbps, int32_t *d_decoded) {
+    graph_note_plan(P);
     if (!P || !d_stream || !d_offs || !d_lens || !d_numbps || !d_decoded) return J2K_ERR_INVALID_ARG;
     return plan_decode_blocks_jobs(P, P->d_djobs, (int)P->blocks.size(), d_stream, d_offs, d_lens, d_numbps, d_decoded, nullptr);
 }
@@ -940,6 +959,7 @@ int check_skip_planes(j2k_ctx *ctx, int coder, int skip_planes, const char *who)
 // midpoint of what was left.  skip_planes = 0 is j2k_plan_decode_blocks.
 extern "C" int j2k_plan_decode_blocks_coarse(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
                                              const uint8_t *d_numbps, int skip_planes, int32_t *d_decoded) {
+    graph_note_plan(P);
     if (!P || !d_stream || !d_offs || !d_lens || !d_numbps || !d_decoded) return J2K_ERR_INVALID_ARG;
     const int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_plan_decode_blocks_coarse");
     if (r != J2K_OK) return r;
@@ -950,6 +970,7 @@ extern "C" int j2k_plan_decode_blocks_coarse(j2k_plan *P, const uint8_t *d_strea
 // byte per job, 0 ... 31 -- not checked, a larger value simply leaves the block zeros).  d_floors = NULL is j2k_plan_decode_blocks_coarse.
 extern "C" int j2k_plan_decode_blocks_floors(j2k_plan *P, const uint8_t *d_stream, const uint64_t *d_offs, const uint32_t *d_lens,
                                              const uint8_t *d_numbps, int skip_planes, const uint8_t *d_floors, int32_t *d_decoded) {
+    graph_note_plan(P);
     if (!P || !d_stream || !d_offs || !d_lens || !d_numbps || !d_decoded) return J2K_ERR_INVALID_ARG;
     const int r = check_skip_planes(P->ctx, P->spec.coder, skip_planes, "j2k_plan_decode_blocks_floors");
     if (r != J2K_OK) return r;

@@ -41,7 +41,7 @@ class PlanInfo(C.Structure):
 SYMBOLS = [
     "j2k_ctx_create", "j2k_ctx_destroy", "j2k_ctx_sync", "j2k_ctx_stream", "j2k_ctx_last_error",
     "j2k_status_string", "j2k_version", "j2k_ctx_set_option", "j2k_ctx_profile_enable", "j2k_ctx_profile_read", "j2k_ctx_profile_read_tag",
-    "j2k_ctx_capture_begin", "j2k_ctx_capture_end", "j2k_graph_launch", "j2k_graph_destroy",
+    "j2k_ctx_capture_begin", "j2k_ctx_capture_end", "j2k_graph_launch", "j2k_graph_stale", "j2k_graph_destroy",
     "j2k_dc_level_shift_forward", "j2k_dc_level_shift_inverse", "j2k_forward_rct", "j2k_inverse_rct",
     "j2k_forward_ict", "j2k_inverse_ict",
     "j2k_forward53", "j2k_inverse53", "j2k_forward97", "j2k_inverse97",
@@ -135,7 +135,7 @@ def lib():
             "j2k_ctx_stream": (V, [V]), "j2k_block_bound": (S, [I, I, I]), "j2k_ctx_create": (I, [I, C.POINTER(V)]),
             "j2k_ctx_destroy": (None, [V]), "j2k_ctx_sync": (I, [V]), "j2k_ctx_profile_enable": (I, [V, I]),
             "j2k_ctx_profile_read": (I, [V, I64P, DP]), "j2k_ctx_profile_read_tag": (I, [V, I, I64P, DP]),
-            "j2k_ctx_capture_begin": (I, [V]), "j2k_ctx_capture_end": (I, [V, C.POINTER(V)]), "j2k_graph_launch": (I, [V]),
+            "j2k_ctx_capture_begin": (I, [V]), "j2k_ctx_capture_end": (I, [V, C.POINTER(V)]), "j2k_graph_launch": (I, [V]), "j2k_graph_stale": (I, [V]),
             "j2k_graph_destroy": (None, [V]), "j2k_plan_destroy": (None, [V]), "j2k_comm_get_unique_id": (I, [V]),
             "j2k_comm_load_error": (C.c_char_p, []), "j2k_comm_create": (I, [V, V, I, I, C.POINTER(V)]), "j2k_comm_destroy": (None, [V]),
             "j2k_comm_last_error": (C.c_char_p, [V]), "j2k_comm_stream": (V, [V]),

@@ -155,14 +155,26 @@ class Graph:
         """Replay on the context's stream.  Ordering contract: the replay is ordered behind everything queued so far on torch's
         CURRENT stream of the context's device (e.g. a frame.copy_(new) just before) -- the wait that the stage calls issue
         when they run directly is not part of the recorded graph -- and behind earlier work on the context's own stream.
-        Results are ready after ctx.sync().  Raises once the context or the graph has been closed."""
+        Results are ready after ctx.sync().  Raises once the context or the graph has been closed, and J2KError(ERR_INVALID_ARG) from
+        j2k_graph_launch once the graph is stale (`stale`): nothing is launched then and the context stays usable."""
         if self.h is None or self.ctx.h is None:
             raise _lib.J2KError(_lib.ERR_INVALID_ARG, "graph launch after the graph or its context was closed")
+        if self.stale:           # the C check decides and words the refusal; asked first so that the stream wait below is not queued for nothing
+            self.ctx.check(self.ctx.L.j2k_graph_launch(self.h))
         import torch
         if self.ctx._ext is None:
             self.ctx._ext = torch.cuda.ExternalStream(int(self.ctx.stream), device=torch.device("cuda", self.ctx.device))
         self.ctx._ext.wait_stream(torch.cuda.current_stream(self.ctx.device))
         self.ctx.check(self.ctx.L.j2k_graph_launch(self.h))
+
+    @property
+    def stale(self):
+        """j2k_graph_stale: 0 while the graph may be replayed, else why not (include/j2kgfx.h, "LIFETIME") -- 1: (a) a staging workspace of the
+        context that the capture used was reallocated by a later, larger call; 2: (b) a buffer of a plan it recorded grew (a longer stream);
+        3: (c) a plan it recorded was closed.  A stale graph refuses launch(); run the calls once and capture again."""
+        if self.h is None or self.ctx.h is None:
+            return 0
+        return int(self.ctx.L.j2k_graph_stale(self.h))
 
     def close(self):
         if self.h and self.ctx.h:

@@ -83,11 +83,29 @@ int j2k_ctx_profile_read_tag(j2k_ctx *ctx, int tag, int64_t *launches, double *t
  * instead of run; j2k_graph_launch replays them on the context's stream with the same device pointers (new contents in
  * the same buffers).  The same calls must have run once before the capture (workspaces sized): a call that would have to
  * allocate fails with J2K_ERR_INVALID_ARG and the capture must be ended and discarded.  Synchronous calls (anything in
- * section 1, j2k_ctx_sync, j2k_ctx_profile_read) are not allowed while capturing. */
+ * section 1, j2k_ctx_sync, j2k_ctx_profile_read) are not allowed while capturing.
+ *
+ * LIFETIME.  Besides the caller's own buffers (which the caller keeps alive and in place) a graph records device memory of the library:
+ * the context's staging workspaces that the recorded calls reserved, and the tables and workspaces of the plans whose calls were recorded.
+ * A graph is STALE once, since its capture_end,
+ *   (a) a staging workspace of its context that the capture used was reallocated -- a later call on the SAME CONTEXT, from any of its plans or
+ *       a call that was not captured, needed it larger (a larger frame, more blocks);
+ *   (b) a growable buffer of a plan whose calls the capture recorded was reallocated -- j2k_plan_decode_frame_pixels_layers / _area with layers
+ *       on a longer stream than any before, or a host call (section 1 forms: j2k_encode_pixels_host*, j2k_decode_pixels_host*) of that plan at
+ *       a larger size;
+ *   (c) such a plan was destroyed.
+ * j2k_graph_launch on a stale graph returns J2K_ERR_INVALID_ARG, j2k_ctx_last_error names (a), (b) or (c); nothing is launched and the context
+ * stays usable.  j2k_graph_stale returns 0 for a valid graph and 1 / 2 / 3 for (a) / (b) / (c) (0 for NULL).  j2k_graph_destroy of a stale graph
+ * is legal; after one ordinary (warm) run of the same calls a new capture gives a valid graph again.  Nothing else stales a graph: not the
+ * growth of a workspace the capture did not use, not the growth or the destruction of a plan it did not call, nothing on another context.
+ * Plans are noted at every j2k_plan_* entry point that takes a non-const plan, so no call family relies on the conservative alternative
+ * ("every plan alive at capture_end").  The buffers of a j2k_pipe are never recorded: j2k_pipe_create and both submits refuse while the
+ * context captures.  A graph must be destroyed before its context. */
 typedef struct j2k_graph j2k_graph;
 int j2k_ctx_capture_begin(j2k_ctx *ctx);
 int j2k_ctx_capture_end(j2k_ctx *ctx, j2k_graph **out);
 int j2k_graph_launch(j2k_graph *g);
+int j2k_graph_stale(const j2k_graph *g);
 void j2k_graph_destroy(j2k_graph *g);
 
 /* ==== 1. host calls: one per reference function ============================= */

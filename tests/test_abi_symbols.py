@@ -27,6 +27,7 @@ def test_every_declared_symbol_is_exported(lib):
     L = lib.lib()
     names = declared_functions()
     assert len(names) >= 40
+    assert "j2k_graph_stale" in names and "j2k_graph_launch" in names and "j2k_graph_destroy" in names      # the graph surface: the lifetime query with it
     for n in names:
         assert hasattr(L, n), "libj2kgfx.so does not export %s" % n
     assert sorted(lib.SYMBOLS) == names            # the python binding knows exactly the header's surface
